@@ -28,6 +28,17 @@ ranks of the timed region. `independent_frames` adds the weak-scaling figure (ev
 `--mode frames` is that weak-scaling loop alone; `--mode rows` one frame over N devices from ONE process
 (sf_group_*: strided peer copies).
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline figure needs and no more: it sets up,
+renders the W warm-up frames (and settles the clock, --settle-ms), times the N steps, and prints the line -- `value`,
+`ms_per_step` (the milliseconds one timed step took) and the roofline of those steps. Every other leg named above and
+below takes runs of its own and is behind `--full`: the first render, the fixed-camera loop, the one-frame latency,
+the long loop (`pipeline`), the parity checks of the timed frames, `configs.c4`, `member_shares`, `post` / `d2h` /
+`frameless`, `cpu_baseline`, and on N GPUs `independent_frames` and `gathered_on_rank0`. `--dump-outputs DIR` (plain
+or full) writes what the last timed step computed -- the G-buffer a caller of the path downloads -- as
+DIR/position.npy and DIR/normal.npy (float32 rows x W x 4; rank 0's rows) with the frame rows they hold in
+DIR/rows.npy (float64): every row while the two arrays fit 60 MB, else a fixed seeded sample of rows. The camera path
+is deterministic, so the same arguments give the same frame from run to run and from build to build.
+
 rank 0 prints ONE JSON line. `roofline` prices the dominant kernel against HBM (32 B/ray of G-buffer
 stores); `cpu_baseline` times the reference's own AVX packet path (oracle/_ref,
 compiled from the reference sources) on this host's cores. `configs.c4` is BASELINE configs[3]
@@ -74,6 +85,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the timed steps: first render, fixed camera, latency, the long loop, "
+                         "the parity checks, c4, member shares, post / D2H / frame-less, the CPU baseline, and on N GPUs "
+                         "the weak-scaling and RCCL-gathered legs (the --no-* options below trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame's G-buffer as DIR/position.npy and "
+                         "DIR/normal.npy (float32; DIR/rows.npy lists the frame rows kept, at most 60 MB in all)")
     ap.add_argument("--settle-ms", type=float, default=SETTLE_MS,
                     help="untimed frames beyond --warmup until the GPU has been under load this long (0: off)")
     ap.add_argument("--mode", choices=["dist", "frames", "rows"], default="dist")
@@ -573,6 +591,8 @@ def run_rows(args, torch, ctl, n, kernel):
     slab_bytes = g.slab_bytes()
     gather_bytes = sum(sf.lib().sf_slab_rows(height, band, n, k) for k in range(1, n)) * width * slab_bytes
     same_dev = len(set(devices)) < n
+    if args.dump_outputs:   # the last timed frame, whole in member 0's G-buffer
+        write_dump(args.dump_outputs, take_dump(*g.download(), np.arange(height), width))
     g.close()
     out = {
         "metric": METRIC, "value": round(width * height / t_step / 1e6, 2), "unit": "Mrays/s", "n_gpus": n,
@@ -737,9 +757,36 @@ def check_golden_rows(pos, nrm, golden, rows):
     return len(checked), bad
 
 
+DUMP_MAX_BYTES = 60 * 10 ** 6        # --dump-outputs: position + normal stay below this (the files' limit is 64 MB)
+DUMP_SEED = 1080                     # of the row sample, fixed: two runs or two builds keep the same rows
+
+
+def dump_rows(rows, width):
+    """The frame rows --dump-outputs keeps of `rows` (sorted): all of them while position + normal (32 B/pixel) fit
+    DUMP_MAX_BYTES, else a fixed seeded sample (1080p: 976 of the 1080 rows)."""
+    keep = max(1, DUMP_MAX_BYTES // (BYTES_PER_RAY * width))
+    if len(rows) <= keep:
+        return rows
+    return rows[np.sort(np.random.default_rng(DUMP_SEED).choice(len(rows), size=keep, replace=False))]
+
+
+def take_dump(pos, nrm, rows, width):
+    """Rows `rows` (dump_rows of them) of a downloaded frame, copied out for write_dump."""
+    rows = dump_rows(np.asarray(rows, int), width)
+    return {"position": pos[rows].astype(np.float32, copy=False), "normal": nrm[rows].astype(np.float32, copy=False),
+            "rows": rows.astype(np.float64)}
+
+
+def write_dump(path, dump):
+    """--dump-outputs: DIR/<name>.npy of every array of `dump`."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in dump.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def dist_loop(ctl, torch, dev, width, height, k, steps, warmup, slots, band_rows, nranks, frame_of,
               fixed=False, latency=False, first=False, gather=False, settle_ms=SETTLE_MS, long_steps=0, check=False,
-              batch=1, timing=True):
+              batch=1, timing=True, dump=False):
     """One timed loop of the sf_dist path: `steps` frames (frame_of(i) of the camera path at step i) after
     `warmup`, `slots` in flight, over `nranks` ranks (1: this GPU alone, every rank its own frames); each frame
     is every rank's bands into its own G-buffer (the distributed G-buffer), or with `gather` also assembled on
@@ -751,7 +798,8 @@ def dist_loop(ctl, torch, dev, width, height, k, steps, warmup, slots, band_rows
     `check`: after the timed loop, its last frame's rows (this rank's bands; 12 of them) against the oracle, and
     after the fixed-view loop that frame's rows against the golden digests of the config (when one exists).
     `batch` > 1 (not with `gather`): the loops issue `batch` frames per multi-frame persistent launch (FrameIssuer);
-    the one-frame latency stays one launch per frame."""
+    the one-frame latency stays one launch per frame.
+    `dump`: after the timed loop, its last frame's G-buffer (this rank's rows, dump_rows of them) in out["dump"]."""
     rank = ctl.rank if nranks > 1 else 0
     ids = shard.dist_ids(slots) if nranks > 1 and gather else None
     d = sf.SphereflakeDist(dev.index, width, height, rank=rank, nranks=nranks, slots=slots, ids=ids,
@@ -830,6 +878,10 @@ def dist_loop(ctl, torch, dev, width, height, k, steps, warmup, slots, band_rows
     if st.overflow_tiles:
         raise RuntimeError("traversal overflowed SF_MAX_DEPTH_LIMIT")
     out["stats"] = st
+    if dump and (rank == 0 or not gather):   # the last timed frame as a caller of the path receives it
+        pos, nrm = d.download_slot(d.last_slot())
+        out["dump"] = take_dump(pos, nrm, mine, width)
+        del pos, nrm
     if check and (rank == 0 or not gather):   # the last timed frame, outside the timed region (downloaded now,
         pos, nrm = d.download_slot(d.last_slot())   # checked after the long loop: no idle GPU before that loop)
         rows = mine[np.linspace(0, len(mine) - 1, min(12, len(mine))).astype(int)] if len(mine) else mine
@@ -982,17 +1034,21 @@ def main():
     kernel = sf.SF_KERNEL_WAVE if args.kernel == "wave" else sf.SF_KERNEL_PER_RAY
     if kernel != sf.SF_KERNEL_WAVE and args.mode == "dist":
         raise SystemExit("the per-ray kernel runs in --mode frames only")
-    check = not args.no_check
-    long_steps = args.long_steps or max(4 * args.steps, 200)
+    full = args.full   # every leg beyond the timed steps (a plain run: set-up, warm-up, the timed steps, the line)
+    check = full and not args.no_check
+    long_steps = (args.long_steps or max(4 * args.steps, 200)) if full else 0
+    dump = bool(args.dump_outputs) and rank == 0   # (rank 0 writes its rows of the last timed frame)
 
-    # a tiny render on a throw-away context first: loads the code object, so that `first_render_ms`
-    # below is the first render of a fresh context, not the process's first kernel launch
-    t_load = time.perf_counter()
-    with sf.Sphereflake(64, 64, device=dev.index) as warm:
-        warm.SetCamera(sf.config_camera(64, 64, args.K))
-        warm.Render()
-        warm.Synchronize()
-    module_load_ms = (time.perf_counter() - t_load) * 1e3
+    module_load_ms = None
+    if full:
+        # a tiny render on a throw-away context first: loads the code object, so that `first_render_ms`
+        # below is the first render of a fresh context, not the process's first kernel launch
+        t_load = time.perf_counter()
+        with sf.Sphereflake(64, 64, device=dev.index) as warm:
+            warm.SetCamera(sf.config_camera(64, 64, args.K))
+            warm.Render()
+            warm.Synchronize()
+        module_load_ms = (time.perf_counter() - t_load) * 1e3
 
     if args.mode == "rows":
         run_rows(args, torch, ctl, max(n, args.gpus), kernel)
@@ -1007,23 +1063,29 @@ def main():
     if args.mode == "dist":
         # the frame split over the ranks, each rank's bands into its own HBM (the distributed G-buffer)
         r = dist_loop(ctl, torch, dev, width, height, args.K, args.steps, args.warmup, slots, args.band_rows, n,
-                      lambda i: i, fixed=True, latency=True, first=True, settle_ms=args.settle_ms,
-                      long_steps=long_steps, check=check, batch=batch)
+                      lambda i: i, fixed=full, latency=full, first=full, settle_ms=args.settle_ms,
+                      long_steps=long_steps, check=check, batch=batch, dump=dump)
         rays_step = width * height
     else:   # frames: every rank its own frames (frame i * N + rank), one GPU each, slots in flight
         r = dist_loop(ctl, torch, dev, width, height, args.K, args.steps, args.warmup, slots, args.band_rows, 1,
-                      lambda i: i * n + rank, fixed=True, latency=True, first=True, settle_ms=args.settle_ms,
-                      long_steps=long_steps, check=check, batch=batch)
+                      lambda i: i * n + rank, fixed=full, latency=full, first=full, settle_ms=args.settle_ms,
+                      long_steps=long_steps, check=check, batch=batch, dump=dump)
         rays_step = width * height * n
     d = r["dist"]
     t_step = r["t_step"]
     value = rays_step / t_step / 1e6
     st = r["stats"]
     d.close()
+    dump_n = None
+    if dump:
+        dumped = r.pop("dump")
+        write_dump(args.dump_outputs, dumped)
+        dump_n = len(dumped["rows"])
+        del dumped
 
     # weak-scaling companion of a multi-GPU run: every rank renders its own frames (no gather)
     indep = None
-    if args.mode == "dist" and n > 1:
+    if full and args.mode == "dist" and n > 1:
         bi = frames_per_launch(args.batch, cus, width, height, args.band_rows, 1)
         ri = dist_loop(ctl, torch, dev, width, height, args.K, args.steps, args.warmup,
                        frames_in_flight(args.slots, cus, width, height, args.band_rows, 1, bi), args.band_rows, 1,
@@ -1034,7 +1096,7 @@ def main():
 
     # BASELINE configs[3] (3840x2160, K = 0.22, depth 9) on the same path, all ranks
     c4 = None
-    if not args.no_extras and (width, height, round(args.K, 4)) == (W, H, K):
+    if full and not args.no_extras and (width, height, round(args.K, 4)) == (W, H, K):
         b4 = frames_per_launch(args.batch, cus, 3840, 2160, args.band_rows, nshare)
         r4 = dist_loop(ctl, torch, dev, 3840, 2160, 0.22, 60, 15,
                        frames_in_flight(args.slots, cus, 3840, 2160, args.band_rows, nshare, b4),
@@ -1059,7 +1121,7 @@ def main():
     # N-GPU run itself is `bench.py --gpus N` (value = the distributed frame).
     shares = None
     SHARES_TIMING = os.environ.get("SF_BENCH_SHARES_TIMING", "0") == "1"   # (A/B: the kernel-timing events on)
-    if n == 1 and args.mode == "dist" and not args.no_extras and "pipeline" in r:
+    if full and n == 1 and args.mode == "dist" and not args.no_extras and "pipeline" in r:
         base = r["pipeline"]["steady_frame_ms"]
         shares = {"basis_steady_ms": base, "note": (
             "ONE GPU tracing rank 0's interleaved band share of an N-way split (the member with the most rows), at the "
@@ -1078,7 +1140,7 @@ def main():
                                 "projected_mrays": round(width * height / sp / 1e3, 1)}
 
     post = d2h = prog = None
-    if rank == 0 and n == 1 and not args.no_extras:
+    if full and rank == 0 and n == 1 and not args.no_extras:
         # the consumers of the G-buffer on a plain context: SSAO post-process, D2H into the
         # host GBuffer (PCIe-inclusive, never `value`, §8(f3)), the frame-less mode (§8(f1))
         stream = torch.cuda.Stream(device=dev)
@@ -1151,17 +1213,24 @@ def main():
                        "slots": slots, "frames_per_launch": batch,
                        "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4), "parallelism": par},
             "frame_ms": round(t_step * 1e3, 4),
-            "frame_latency_ms": round(r["latency_ms"], 4),
-            "first_render_ms": round(r["first_render_ms"], 4),
-            "process_first_launch_ms": round(module_load_ms, 3),
-            "fixed_camera": {"value": round(rays_step / r["t_fixed"] / 1e6, 2), "frame_ms": round(r["t_fixed"] * 1e3, 4),
-                             "note": "same timed loop on the unchanging config view"},
+            "full": full,
             "rays_counted": int(st.rays),
             "roofline": roof,
             "valu": pmc_valu(pmc, t_step * 1e3, clock) if n == 1 else None,
             "build": build,
             "ranks": ranks,
         }
+        if full:
+            out["frame_latency_ms"] = round(r["latency_ms"], 4)
+            out["first_render_ms"] = round(r["first_render_ms"], 4)
+            out["process_first_launch_ms"] = round(module_load_ms, 3)
+            out["fixed_camera"] = {"value": round(rays_step / r["t_fixed"] / 1e6, 2),
+                                   "frame_ms": round(r["t_fixed"] * 1e3, 4),
+                                   "note": "same timed loop on the unchanging config view"}
+        if dump:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": ["position", "normal", "rows"],
+                                   "rows": dump_n,
+                                   "note": "the last timed frame's G-buffer rows (float32), rows.npy the frame rows kept"}
         if "pipeline" in r:
             out["pipeline"] = dict(r["pipeline"], note=(
                 "a second loop of long_steps frames from an empty pipeline, timed like the first: steady_frame_ms = "
@@ -1175,7 +1244,7 @@ def main():
                             "note": "outside the timed region; this rank's rows (rank 0's bands on N > 1): the last "
                                     "timed moving frame against the oracle restatement, the last fixed-view frame "
                                     "against the reference-made golden row digests; all ranks combined in bit_exact"}
-        if n > 1 and args.mode == "dist":
+        if full and n > 1 and args.mode == "dist":
             out["independent_frames"] = indep
             if args.rehearse:
                 out["config"]["parallelism"] += f" [rehearsal: {n} ranks on {ndev} GPU(s), no RCCL gather]"
@@ -1185,7 +1254,7 @@ def main():
             out["member_shares"] = shares
         if post is not None:
             out["post"], out["d2h"], out["frameless"] = post, d2h, prog
-        if not args.no_cpu_baseline and n == 1:
+        if full and not args.no_cpu_baseline and n == 1:
             avail, quota = cpu_share()
             thr = args.cpu_threads or (min(avail, quota) if quota else avail)
             try:
@@ -1207,7 +1276,7 @@ def main():
     # error, a hang past --gather-timeout or a gathered frame that differs from the golden frame prints the line
     # with the leg marked failed and exits EXIT_GATHER_FAILED.
     rc = 0 if checks_ok in (None, True) else EXIT_CHECK_FAILED
-    if n > 1 and args.mode == "dist" and not args.rehearse:
+    if full and n > 1 and args.mode == "dist" and not args.rehearse:
         if rank == 0:
             out["gathered_on_rank0"] = {"error": f"not finished within {args.gather_timeout:g} s"}
         wd = Watchdog(args.gather_timeout, (lambda: print(json.dumps(out), flush=True)) if rank == 0 else (lambda: None))

@@ -5,7 +5,7 @@ set -e
 mkdir -p gpurun_out/sweep
 for W in 1 2 4; do
   for L in 9 12; do
-    SF_TRACE_WAVES=$W SF_LEVELS=$L timeout -k 10 120 python bench.py --steps 20 --warmup 5 --no-cpu-baseline \
+    SF_TRACE_WAVES=$W SF_LEVELS=$L timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline \
       > gpurun_out/sweep/w${W}_l${L}.json 2> gpurun_out/sweep/w${W}_l${L}.err
     echo "waves=$W levels=$L $(python3 -c "import json;d=json.loads(open('gpurun_out/sweep/w${W}_l${L}.json').readlines()[-1]);print(d['value'],d['kernel_ms'])")"
   done

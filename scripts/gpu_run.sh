@@ -5,7 +5,7 @@
 # Usage (from the repo root, via gpurun): scripts/gpu_run.sh <tag> <step> [<step> ...]
 #   tests[=<pytest args>]        the -m gpu suite (or the given selection), -x, thread timeouts
 #   smoke                        __graft_entry__.smoke()
-#   bench[=<bench.py args>]      one bench line -> bench_<n>.json
+#   bench[=<bench.py args>]      one bench.py --full line (every leg) -> bench_<n>.json
 #   probe=<script> [args]        python3 scripts/<script> args -> probe_<n>.txt
 #   pmc[=<bench.py args>]        the PMC passes of scripts/prof_pmc.sh + their summary (pmc_summary.txt)
 #   rocprof[=<bench.py args>]    rocprofv3 --kernel-trace --stats of one bench run -> stats/
@@ -31,7 +31,7 @@ for step in "$@"; do
       timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$n.txt 2>&1
       rc=$?; tail -2 $OUT/smoke_$n.txt ;;
     bench)
-      timeout -k 10 400 python -u bench.py $arg > $OUT/bench_$n.json 2> $OUT/bench_$n.err
+      timeout -k 10 400 python -u bench.py --full $arg > $OUT/bench_$n.json 2> $OUT/bench_$n.err
       rc=$?; tail -1 $OUT/bench_$n.json; [ $rc -ne 0 ] && tail -20 $OUT/bench_$n.err ;;
     probe)
       timeout -k 10 400 python3 -u scripts/$arg > $OUT/probe_$n.txt 2>&1
@@ -43,7 +43,7 @@ for step in "$@"; do
       rc=$?; head -30 $OUT/pmc_summary.txt ;;
     rocprof)
       (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- \
-        python3 $R/bench.py $arg > $OUT/stats.log 2>&1)
+        python3 $R/bench.py --full $arg > $OUT/stats.log 2>&1)
       rc=$?; cat $(find $OUT/stats -name "*kernel_stats.csv") 2>/dev/null | head -12 ;;
     *)
       echo "unknown step $name"; rc=2 ;;

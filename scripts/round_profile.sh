@@ -22,10 +22,10 @@ scripts/prof_pmc.sh $TAG/pmc || exit 6
 python3 scripts/pmc_summary.py --json $OUT/pmc_traffic.json --config "1920x1080 K=0.25 moving" $OUT/pmc/*/ > $OUT/pmc_summary.txt
 head -40 $OUT/pmc_summary.txt
 cp -f $OUT/pmc_traffic.json profiles/pmc_traffic.json
-timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 4; }
+timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 4; }
 tail -1 $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-extras > $OUT/stats.log 2>&1 || { tail -20 $OUT/stats.log; exit 5; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-extras > $OUT/stats.log 2>&1 || { tail -20 $OUT/stats.log; exit 5; }
 cat $(find $OUT/stats -name "*kernel_stats.csv") | head -12
 grep '^{' $OUT/stats.log | tail -1 > $OUT/bench_under_rocprof.json
 # timed loop of the default bench: 1 code-object warm-up + 1 first render + 30 warmup + the settle frames,

@@ -8,7 +8,7 @@ tail -2 $O/tests.txt
 for r in 1 2 3; do
   for lib in old new; do
     if [ $lib = old ]; then export SF_LIB=$PWD/scratch_ab/lib_old.so; else unset SF_LIB; fi
-    timeout -k 10 300 python3 -u bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/b_$lib.json 2>/dev/null || exit 1
+    timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/b_$lib.json 2>/dev/null || exit 1
     python3 -c "import json; d=json.loads(open('$O/b_$lib.json').read().strip().splitlines()[-1]); m=d['member_shares']; print('$lib', d['ms_per_step'], ' '.join(f\"{k}: {m[k]['steady_ms']} ({m[k]['speedup']}x)\" for k in ('n2','n4','n8')))" | tee -a $O/ab.txt
   done
 done

@@ -9,12 +9,12 @@ line() {  # line <label> <file>
 }
 for r in 1 2; do
   for cm in 1 0; do
-    SF_STREAM_CUMASK=$cm timeout -k 10 300 python3 -u bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/b20_$cm.json 2> $O/b20_$cm.err || exit 1
+    SF_STREAM_CUMASK=$cm timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/b20_$cm.json 2> $O/b20_$cm.err || exit 1
     line "cumask=$cm 20-step" $O/b20_$cm.json
   done
 done
 for cm in 1 0; do
-  SF_STREAM_CUMASK=$cm timeout -k 10 300 python3 -u bench.py --no-cpu-baseline > $O/b200_$cm.json 2> $O/b200_$cm.err || exit 1
+  SF_STREAM_CUMASK=$cm timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline > $O/b200_$cm.json 2> $O/b200_$cm.err || exit 1
   line "cumask=$cm 200-step" $O/b200_$cm.json
 done
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/pytest_gpu.log 2>&1 || { tail -30 $O/pytest_gpu.log; exit 1; }

@@ -87,6 +87,45 @@ def test_frames_in_flight_by_share(w, h, n, want, monkeypatch):
     assert bench.frames_in_flight(0, 256, w, h, 8, n, batch=8) == 16
 
 
+def test_dump_rows_are_a_fixed_sample_within_the_limit():
+    """--dump-outputs keeps every row of a frame whose position + normal (32 B/pixel) fit 60 MB, else a fixed
+    seeded sample: sorted, distinct, the same on every call."""
+    assert np.array_equal(bench.dump_rows(np.arange(360), 640), np.arange(360))
+    assert np.array_equal(bench.dump_rows(np.arange(976), 1920), np.arange(976))   # 976 x 1920 x 32 B: just fits
+    for h, w in ((1080, 1920), (2160, 3840), (16384, 16384)):
+        rows = bench.dump_rows(np.arange(h), w)
+        assert len(rows) == 60 * 10 ** 6 // (32 * w) < h
+        assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < h
+        assert np.array_equal(rows, bench.dump_rows(np.arange(h), w))
+        assert len(rows) * w * 32 + len(rows) * 8 <= 64 * 10 ** 6
+    mine = bench.owned_rows(1080, 8, 8, 3)   # a rank's bands: all of them fit, kept as they are
+    assert np.array_equal(bench.dump_rows(mine, 1920), mine)
+
+
+def test_dump_files_hold_the_rows_as_float32(tmp_path):
+    rng = np.random.default_rng(5)
+    pos = rng.standard_normal((45, 16, 4)).astype(np.float32)
+    nrm = rng.standard_normal((45, 16, 4)).astype(np.float32)
+    rows = bench.owned_rows(45, 8, 3, 1)
+    out = tmp_path / "a" / "b"   # (made if missing)
+    bench.write_dump(str(out), bench.take_dump(pos, nrm, rows, 16))
+    assert sorted(p.name for p in out.iterdir()) == ["normal.npy", "position.npy", "rows.npy"]
+    got = {n: np.load(out / f"{n}.npy") for n in ("position", "normal", "rows")}
+    assert got["position"].dtype == got["normal"].dtype == np.float32 and got["rows"].dtype == np.float64
+    assert np.array_equal(got["rows"], rows)
+    assert np.array_equal(got["position"].view(np.uint32), pos[rows].view(np.uint32))
+    assert np.array_equal(got["normal"].view(np.uint32), nrm[rows].view(np.uint32))
+
+
+def test_full_and_dump_options_default_off(monkeypatch):
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
 def test_cpu_model_and_vendor_parsed():
     """SURVEY.md §8(d): the CPU baseline states the CPU model; the vendor decides whether its frames can match the
     Intel-measured rsqrtps fixtures (AMD hosts: timing-only, VERDICT r5 #6)."""
