@@ -132,6 +132,42 @@ int sf_render(sf_ctx* ctx, const sf_render_params* params);
 int sf_render_to(sf_ctx* ctx, const sf_render_params* params, float* pos4, float* nrm4,
                  float* min_t, uint32_t* hit_index);
 
+/* --- caller-supplied directions ------------------------------------------- */
+/* The reference traces only the pixels of its pinhole frame (ray generation, Sphereflake.cpp:149-167), and brakes the
+   camera by the nearest sphere among those rays (GetClosestSphereDistance, main.cpp:213) -- moves along directions no
+   pixel covers (main.cpp:214-242) are unguarded, its README's "flying into a sphere". Everything after ray generation
+   depends on the ray's normalised direction, the root transform, the child frames and the LOD constant only
+   (Sphereflake.h:86-226), so any direction can be traced from the view's origin: collision probes, picking and
+   ranging, other camera models (panoramas, fisheye, cube faces) for the same G-buffer consumers.
+   Ray i is the reference's ray with D = Normalize(dirs[i]) (SIMD_AVX.h:170-180: rsqrtps and one Newton step), from the
+   origin, root transform and child frames of sf_set_view / sf_set_setup, with the context's variant and per-ray
+   semantics. It gets exactly what a frame pixel with that direction gets: pos4 (x, y, z, 1), nrm4 likewise, a miss
+   (0, 0, 0, 1); min_t FLT_MAX on a miss; hit_index the low 32 bits of the heap index, 0xffffffff on a miss. A
+   direction that does not normalise to finite numbers (zero, tiny, NaN, infinite) is a miss, as the reference's
+   arithmetic makes it. Results never depend on the order or grouping of the rays. */
+typedef struct sf_dirs_params {
+    uint32_t width, height;   /* rays = width * height, row-major; height == 1: a plain list */
+    uint32_t stride;          /* floats per direction in `dirs`: 3 or 4 (the 4th is ignored) */
+    uint32_t max_depth;       /* levels to provision, as sf_render_params.max_depth (0 = auto: the view's geometric
+                                 bound; groups of rays that need more are re-traced at SF_MAX_DEPTH_LIMIT) */
+    void* stream;             /* NULL = the context stream */
+} sf_dirs_params;
+
+/* Into caller-owned DEVICE buffers, in ray order (`dirs` is a device array too); any output may be NULL, not all
+   four. Asynchronous on the stream, ordered with the context's other calls as sf_render_to is. Stats accumulate as
+   for a render (max depth, closest, rays += width * height; overflow_tiles counts the re-traced groups of 64 rays).
+   SF_ENOVIEW before a view is set; SF_EINVAL for a stride other than 3 or 4, null dirs, all outputs null or more
+   than 2^31 - 1 rays; zero rays: SF_OK, nothing done. A later render is not affected in any way. */
+int sf_trace_dirs_to(sf_ctx* ctx, const sf_dirs_params* params, const float* dirs, float* pos4, float* nrm4,
+                     float* min_t, uint32_t* hit_index);
+/* Into the context's own G-buffer and aux channels (sf_download, sf_post_process, sf_save_image then see a frame
+   of another camera model); width x height must equal the context's frame (SF_EINVAL otherwise). */
+int sf_trace_dirs(sf_ctx* ctx, const sf_dirs_params* params, const float* dirs);
+/* Host convenience for a few rays (picking, collision probes along the move axes of main.cpp:214-242): HOST arrays
+   in (n x 3 floats) and out, synchronous. Outputs may be NULL (not all four). */
+int sf_probe_dirs(sf_ctx* ctx, const float* dirs3, uint32_t n, float* min_t, uint32_t* hit_index, float* pos4,
+                  float* nrm4);
+
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the
    work units of all n frames from one set of tile queues -- a wave whose frame runs dry goes on with the next

@@ -45,6 +45,10 @@ extern "C" __global__ void sf_order_scatter(const uint32_t* cost, uint32_t n, ui
 extern "C" __global__ void sf_fixup_wave(FrameArgs a, const uint32_t* overflow_list, uint32_t* counters,
                                          uint32_t parity);
 extern "C" __global__ void sf_trace_ray(FrameArgs a);
+extern "C" __global__ void sf_trace_dirs_wave(FrameArgs a, const float* dirs, uint32_t stride, uint32_t groups,
+                                              uint32_t* overflow_list, uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_dirs_fixup(FrameArgs a, const float* dirs, uint32_t stride,
+                                               const uint32_t* overflow_list, uint32_t* counters, uint32_t parity);
 extern "C" __global__ void sf_band_unpack(FrameArgs a, const float4* stage, uint32_t stage_rows, uint32_t band_rows,
                                            uint32_t n, uint32_t first, uint32_t members, uint32_t row0);
 extern "C" __global__ void sf_node_table(FrameArgs a, float4* table, uint32_t nodes);
@@ -245,6 +249,14 @@ struct sf_ctx {
     uint32_t* prog_ovf_cnt = nullptr;  // [2] list counts, alternating per batch
     uint32_t prog_par = 0;
     unsigned long long* owner = nullptr;   // per pixel: highest ticket written
+    // caller-supplied directions (sf_trace_dirs_to): the feature's own re-trace list and counters, so a trace of
+    // directions leaves the renders' overflow state, schedule and hints alone
+    uint32_t* dirs_ovf = nullptr;      // flagged groups of one trace (dirs_cap entries)
+    uint32_t dirs_cap = 0;             // groups the list holds
+    uint32_t* dirs_cnt = nullptr;      // [0,1] list counts, alternating per trace; [2] groups re-traced so far
+    uint32_t dirs_par = 0;
+    float* probe_buf = nullptr;        // sf_probe_dirs: device scratch, 3 + 4 + 4 + 1 + 1 words per ray
+    uint32_t probe_cap = 0;            // rays it holds
     bool prog_seeded = false;
     uint32_t prog_seed = 0;
     uint64_t prog_next = 0;            // Sobol counter the device MT stream is positioned at
@@ -411,6 +423,9 @@ static void free_ctx(sf_ctx* c)
     if (c->traced) (void)hipEventDestroy(c->traced);
     if (c->pf_stream) (void)hipStreamDestroy(c->pf_stream);
     (void)hipFree(c->owner);
+    (void)hipFree(c->dirs_ovf);
+    (void)hipFree(c->dirs_cnt);
+    (void)hipFree(c->probe_buf);
     if (c->h_depth) (void)hipHostFree(c->h_depth);
     if (c->h_stats) (void)hipHostFree(c->h_stats);
     (void)hipFree(c->tile_trace);
@@ -753,7 +768,9 @@ static int order_rebuild(sf_ctx* c, hipStream_t s, uint32_t ntiles, uint32_t wav
 // Geometric bound: every sphere lies inside the root's bounding sphere (radius 2 around the root centre), so a
 // depth-d node can pass the LOD test (t < T_d, Sphereflake.h:146) only if |root centre| - 2 < T_d. The deepest such
 // d + 1 levels suffice; a bound that is off only costs a re-trace of the affected tiles (sf_fixup_wave), never results.
-static uint32_t frame_levels(const sf_ctx* c, bool* bounded_out)
+// (geometric_levels: the bound alone -- it speaks of the origin and the root ball only, so it holds for rays of any
+// direction, sf_trace_dirs_to; frame_levels: narrowed by the deepest depth a finished render of the frame saw)
+static uint32_t geometric_levels(const sf_ctx* c, bool* bounded_out)
 {
     uint32_t levels = kDefaultLevels;
     const float rc = std::sqrt(c->root[12] * c->root[12] + c->root[13] * c->root[13] + c->root[14] * c->root[14]);
@@ -765,6 +782,14 @@ static uint32_t frame_levels(const sf_ctx* c, bool* bounded_out)
         levels = dmax + 1u;
         bounded = levels <= SF_MAX_DEPTH_LIMIT;
     }
+    *bounded_out = bounded;
+    return levels;
+}
+
+static uint32_t frame_levels(const sf_ctx* c, bool* bounded_out)
+{
+    bool bounded = false;
+    uint32_t levels = geometric_levels(c, &bounded);
     const int32_t seen = *(volatile int32_t*)c->h_depth;   // max depth of a finished render
     if (seen >= 0 && (uint32_t)seen + 1u < levels) {
         levels = (uint32_t)seen + 1u;
@@ -1011,6 +1036,112 @@ int sf_render_to(sf_ctx* c, const sf_render_params* p, float* pos4, float* nrm4,
 {
     if (p && p->packed && !nrm4) nrm4 = pos4;   // (packed slabs write pos4 only)
     return launch(c, p, pos4, nrm4, min_t, hidx);
+}
+
+// Caller-supplied directions (sf.h; kernels sf_trace_dirs_wave / sf_trace_dirs_fixup). A one-shot grid, one wave per
+// group of 64 rays, with the levels of the geometric bound; flagged groups (more levels needed, or a tie under the
+// front-first order) are re-traced by the fixup launch behind it. Reads and writes none of the renders' state: not
+// the overflow counters' parity, the tile order or costs, the depth hint, the timing ring or the frame-less state.
+int sf_trace_dirs_to(sf_ctx* c, const sf_dirs_params* p, const float* dirs, float* pos4, float* nrm4, float* min_t,
+                     uint32_t* hidx)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (p->stride != 3u && p->stride != 4u) return SF_EINVAL;
+    if (!dirs || (!pos4 && !nrm4 && !min_t && !hidx)) return SF_EINVAL;
+    if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
+    const uint64_t n = (uint64_t)p->width * p->height;
+    if (n == 0) return SF_OK;
+    if (n > 0x7fffffffull) return SF_EINVAL;   // (ray counts are 32-bit in the launch arguments)
+    const bool list = p->height == 1u || p->width == 1u;   // one row or one column: consecutive rays
+    const uint32_t tiles_x = (p->width + 7u) / 8u;
+    const uint32_t groups = list ? (uint32_t)((n + 63u) / 64u) : tiles_x * ((p->height + 7u) / 8u);
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    if (!c->dirs_cnt) {
+        SF_HIP(c, hipMalloc(&c->dirs_cnt, 3 * 4));
+        SF_HIP(c, hipMemsetAsync(c->dirs_cnt, 0, 3 * 4, s));
+    }
+    if (groups > c->dirs_cap) {   // grown on demand; an earlier trace may still write the old list
+        SF_HIP(c, hipStreamSynchronize(s));
+        (void)hipFree(c->dirs_ovf);
+        c->dirs_ovf = nullptr;
+        c->dirs_cap = 0;
+        SF_HIP(c, hipMalloc(&c->dirs_ovf, (size_t)groups * 4));
+        c->dirs_cap = groups;
+    }
+    FrameArgs a = frame_args(c);
+    a.W = list ? (uint32_t)n : p->width;
+    a.H = list ? 1u : p->height;
+    a.tiles_x = tiles_x;
+    bool bounded = false;
+    a.max_depth = p->max_depth ? p->max_depth : geometric_levels(c, &bounded);
+    if (a.max_depth < 4u) a.max_depth = 4u;
+    if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
+    a.emit_aux = 1u;
+    a.pos = pos4;
+    a.nrm = nrm4;
+    a.min_t = min_t;
+    a.hit_index = hidx;
+    const size_t lds = (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4;
+    hipLaunchKernelGGL(sf_trace_dirs_wave, dim3(groups), dim3(64), lds, s, a, dirs, p->stride, groups, c->dirs_ovf,
+                       c->dirs_cnt + c->dirs_par);
+    SF_HIP(c, hipGetLastError());
+    const size_t lds_fix = (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4;
+    const uint32_t fb = groups < SF_PROG_FIXUP_BLOCKS ? groups : SF_PROG_FIXUP_BLOCKS;
+    hipLaunchKernelGGL(sf_trace_dirs_fixup, dim3(fb), dim3(64), lds_fix, s, a, dirs, p->stride,
+                       (const uint32_t*)c->dirs_ovf, c->dirs_cnt, c->dirs_par);
+    SF_HIP(c, hipGetLastError());
+    c->dirs_par ^= 1u;
+    c->rays += (int64_t)n;
+    return SF_OK;
+}
+
+int sf_trace_dirs(sf_ctx* c, const sf_dirs_params* p, const float* dirs)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (p->width != c->W || p->height != c->H) return SF_EINVAL;
+    return sf_trace_dirs_to(c, p, dirs, c->pos, c->nrm, c->min_t, c->hit_index);
+}
+
+int sf_probe_dirs(sf_ctx* c, const float* dirs3, uint32_t n, float* min_t, uint32_t* hidx, float* pos4, float* nrm4)
+{
+    if (!c) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!dirs3 || (!pos4 && !nrm4 && !min_t && !hidx)) return SF_EINVAL;
+    if (n == 0) return SF_OK;
+    if (n > 0x7fffffffu) return SF_EINVAL;
+    DevGuard g(c->device);
+    if (n > c->probe_cap) {
+        if (int rc = ctx_drain(c)) return rc;   // an earlier probe's trace may still use the old scratch
+        (void)hipFree(c->probe_buf);
+        c->probe_buf = nullptr;
+        c->probe_cap = 0;
+        SF_HIP(c, hipMalloc(&c->probe_buf, ((size_t)n * 13 + 3) * 4));
+        c->probe_cap = n;
+    }
+    float* const d_dirs = c->probe_buf;
+    float* const d_pos = d_dirs + (size_t)3 * c->probe_cap + ((4u - (3u * c->probe_cap) % 4u) % 4u);   // (16-B aligned)
+    float* const d_nrm = d_pos + (size_t)4 * c->probe_cap;
+    float* const d_min = d_nrm + (size_t)4 * c->probe_cap;
+    uint32_t* const d_idx = reinterpret_cast<uint32_t*>(d_min + c->probe_cap);
+    if (int rc = ctx_join(c, c->stream)) return rc;
+    SF_HIP(c, hipMemcpyAsync(d_dirs, dirs3, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    sf_dirs_params p;
+    std::memset(&p, 0, sizeof p);
+    p.width = n;
+    p.height = 1;
+    p.stride = 3;
+    if (int rc = sf_trace_dirs_to(c, &p, d_dirs, d_pos, d_nrm, d_min, d_idx)) return rc;
+    if (int rc = sf_synchronize(c)) return rc;
+    if (pos4) SF_HIP(c, hipMemcpy(pos4, d_pos, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (nrm4) SF_HIP(c, hipMemcpy(nrm4, d_nrm, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (min_t) SF_HIP(c, hipMemcpy(min_t, d_min, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (hidx) SF_HIP(c, hipMemcpy(hidx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return SF_OK;
 }
 
 // Multi-frame persistent trace (sf.h; kernel sf_trace_frames1). One launch where every frame's own launch() would be
@@ -1960,6 +2091,11 @@ int sf_get_stats(sf_ctx* c, sf_stats* out)
     out->closest = sf_key_float(st[1]);
     out->rays = c->rays;
     out->overflow_tiles = st[2];
+    if (c->dirs_cnt) {   // plus the groups of direction traces that were re-traced (sf_trace_dirs_to)
+        uint32_t re = 0;
+        SF_HIP(c, hipMemcpy(&re, c->dirs_cnt + 2, 4, hipMemcpyDeviceToHost));
+        out->overflow_tiles += re;
+    }
     return SF_OK;
 }
 

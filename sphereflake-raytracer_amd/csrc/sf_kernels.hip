@@ -2915,6 +2915,137 @@ extern "C" __global__ __launch_bounds__(64) void sf_fixup_wave(FrameArgs a, cons
 }
 
 // ------------------------------------------------------------------------------------------
+// Caller-supplied directions (sf_trace_dirs_to): ray i is the reference's ray with
+// D = Normalize(dirs[i]) (SIMD_AVX.h:170-180) from the view's origin -- everything after ray generation
+// (Sphereflake.cpp:167) is a function of D, the root transform, the child frames and the LOD constant only, so
+// the frame's per-ray traversal (traverse_ray) serves it unchanged. One wave64 per group of rays: an 8x8 tile of
+// the direction image (a.W x a.H, a.tiles_x tiles per row), or 64 consecutive rays of a list (a.H == 1). Outputs
+// in ray order, the frame's pixel layout; any of the four may be NULL.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+template <bool FIXUP>
+__device__ __forceinline__ TileStats trace_dir_group(const FrameArgs& a, const float* __restrict__ dirs, uint32_t stride,
+                                                     float* __restrict__ L, const float4 bcol, uint32_t group,
+                                                     uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const uint32_t lane = threadIdx.x & 63u;
+    // the lane's ray; a lane past the end of the list or off the image edge loads the nearest ray inside (a real
+    // direction for the wave's cone) and traverses as an invalid lane: no load or store beyond the last ray
+    size_t ray;
+    bool valid;
+    uint32_t mid;   // the cone axis lane: the tile's centre pixel (4, 4), or a mid lane of a list
+    if (a.H == 1u) {
+        const size_t i = (size_t)group * 64u + lane;
+        valid = i < a.W;
+        ray = valid ? i : (size_t)a.W - 1u;
+        mid = 32u;
+    } else {
+        const uint32_t ty = group / a.tiles_x, tx = group - ty * a.tiles_x;
+        const uint32_t x = tx * SF_TILE + (lane & 7u), y = ty * SF_TILE + (lane >> 3);
+        valid = x < a.W && y < a.H;
+        ray = (size_t)(y < a.H ? y : a.H - 1u) * a.W + (x < a.W ? x : a.W - 1u);
+        mid = 36u;
+    }
+    const float* const dp = dirs + ray * stride;
+    float dx = dp[0], dy = dp[1], dz = dp[2];
+    normalize3(dx, dy, dz, K->lut);
+    // A direction that does not normalise to three finite numbers (zero, tiny, huge, NaN or infinite input) misses
+    // in the reference: the root's tca = (cx dx + cy dy) + cz dz is then NaN or -inf, which fails tca >= 0
+    // (SIMD_AVX.h:247-258), or +inf, where d2 = -inf passes the bounding test but the near root inf - inf = NaN
+    // fails the LOD test (Sphereflake.h:146) -- the root is never entered. Such a lane is traced as an invalid
+    // lane carrying the axis lane's direction, so the traversal's wave-level arithmetic (the cone, whose min
+    // instructions drop NaNs) only ever sees finite directions; the axis lane is the mid lane, or where that one
+    // is not finite the first lane that is.
+    auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
+    const bool fin = finite(dx) && finite(dy) && finite(dz);
+    const uint64_t finm = wave_ballot(fin);
+    HitState h;
+    h.minT = FLT_MAX;
+    h.cx = h.cy = h.cz = 0.f;
+    h.index = 0xffffffffu;
+    h.depth = -1;
+    h.hit = false;
+    int32_t maxd = -1;
+    uint32_t status = 0u;
+    if (finm != 0ull) {   // (uniform; no finite lane: every ray of the group misses)
+        const uint32_t axl = __builtin_amdgcn_readfirstlane(
+            ((finm >> mid) & 1ull) ? mid : (uint32_t)__builtin_ctzll(finm));
+        const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
+        dx = fin ? dx : ax;
+        dy = fin ? dy : ay;
+        dz = fin ? dz : az;
+        // only the culls' A/B switches of the context's flags reach this traversal; the fixup traces in index order
+        const uint32_t flags = (a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST)) |
+                               (FIXUP ? SF_FLAG_NO_FRONT_FIRST : 0u);
+        traverse_ray<>(K, a.root, L, bcol, levels, dx, dy, dz, valid && fin, h, maxd, status, flags, nullptr, axl);
+    }
+    const bool flagged = status != 0u;   // (uniform) more levels needed, or a tie under the front-first order
+    if (!FIXUP && flagged) {
+        // the fixup kernel re-traces this group at SF_MAX_LEVELS in index order and rewrites its rays
+        const uint32_t slot = wave_fetch_add(overflow_count, 1u);
+        overflow_list[slot] = group;   // uniform value and address
+    }
+    if (valid) {
+        float px, py, pz, nx, ny, nz;
+        shade(dx, dy, dz, h, K->lut, px, py, pz, nx, ny, nz);
+        if (a.pos) reinterpret_cast<float4*>(a.pos)[ray] = make_float4(px, py, pz, 1.0f);
+        if (a.nrm) reinterpret_cast<float4*>(a.nrm)[ray] = make_float4(nx, ny, nz, 1.0f);
+        if (a.min_t) a.min_t[ray] = h.minT;
+        if (a.hit_index) a.hit_index[ray] = h.hit ? h.index : 0xffffffffu;
+    }
+    TileStats st;
+    st.maxd = maxd;
+    st.closest = valid ? h.minT : FLT_MAX;
+    st.overflowed = flagged;
+    return st;
+}
+
+}  // namespace
+
+// One group per one-wave workgroup, dynamic LDS for a.max_depth levels (as sf_trace_wave1).
+extern "C" __global__ __launch_bounds__(64) void sf_trace_dirs_wave(FrameArgs a, const float* dirs, uint32_t stride,
+                                                                    uint32_t groups, uint32_t* overflow_list,
+                                                                    uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    stage_root(lds, a.root);
+    const TileStats st = trace_dir_group<false>(a, dirs, stride, lds, build_column(a.consts), blockIdx.x, a.max_depth,
+                                                overflow_list, overflow_count);
+    publish_stats(a, st.maxd, st.closest, 0u);
+}
+
+// Re-trace of the flagged groups (as sf_fixup_wave): counters[parity] groups of `overflow_list`; zeroes the next
+// trace's counter and adds this trace's to counters[2], the re-traced groups sf_get_stats reports.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_dirs_fixup(FrameArgs a, const float* dirs, uint32_t stride,
+                                                                     const uint32_t* overflow_list, uint32_t* counters,
+                                                                     uint32_t parity)
+{
+    extern __shared__ float lds[];
+    const uint32_t n = counters[parity];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        counters[parity ^ 1u] = 0u;
+        counters[2] += n;
+    }
+    if (blockIdx.x >= n) return;
+    int32_t maxd = -1;
+    float closest = FLT_MAX;
+    uint32_t unresolved = 0u;
+    stage_root(lds, a.root);
+    const float4 bcol = build_column(a.consts);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const TileStats st = trace_dir_group<true>(a, dirs, stride, lds, bcol, overflow_list[i], SF_MAX_LEVELS, nullptr,
+                                                   nullptr);
+        maxd = st.maxd > maxd ? st.maxd : maxd;
+        closest = fminf(closest, st.closest);
+        unresolved += st.overflowed ? 1u : 0u;
+    }
+    publish_stats(a, maxd, closest, unresolved);
+}
+
+// ------------------------------------------------------------------------------------------
 // One thread per ray, private stack (Sphereflake.h:86-226 restated as an explicit DFS).
 // ------------------------------------------------------------------------------------------
 extern "C" __global__ __launch_bounds__(256) void sf_trace_ray(FrameArgs a)

@@ -55,6 +55,11 @@ class sf_render_params(ctypes.Structure):
                 ("stream", ctypes.c_void_p)]
 
 
+class sf_dirs_params(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("stride", ctypes.c_uint32),
+                ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
 class sf_stats(ctypes.Structure):
     _fields_ = [("max_depth", ctypes.c_int32), ("closest", ctypes.c_float),
                 ("rays", ctypes.c_int64), ("overflow_tiles", ctypes.c_int64)]
@@ -86,6 +91,11 @@ SIGNATURES = {
     "sf_render": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_render_params)]),
     "sf_render_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_render_params), ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_dirs_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_dirs_params), ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_dirs": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_dirs_params), ctypes.c_void_p]),
+    "sf_probe_dirs": (ctypes.c_int, [_CTX, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p]),
     "sf_render_frames": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
                                         ctypes.POINTER(sf_render_params)]),
     "sf_slab_rows": (ctypes.c_uint32, [ctypes.c_uint32] * 4),
@@ -419,6 +429,61 @@ def render_frames(flakes, **kw):
         _check(lib().sf_render_frames(arr, len(flakes), ctypes.byref(p)), "sf_render_frames", flakes[0].ctx)
 
 
+_hip = None
+
+
+def _hip_runtime() -> ctypes.CDLL:
+    """The HIP runtime the renderer library itself is linked against (already loaded with it: opened by its
+    SONAME, the same instance). Only trace_dirs' numpy path uses it, for its device scratch."""
+    global _hip
+    if _hip is None:
+        lib()
+        H = ctypes.CDLL("libamdhip64.so.7")
+        H.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        H.hipFree.argtypes = [ctypes.c_void_p]
+        H.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        H.hipSetDevice.argtypes = [ctypes.c_int]
+        H.hipGetDevice.argtypes = [ctypes.POINTER(ctypes.c_int)]
+        _hip = H
+    return _hip
+
+
+class _DeviceScratch:
+    """`nbytes` of device memory on `device` for the length of a with-block; synchronous copies."""
+
+    def __init__(self, device: int, nbytes: int):
+        self.device, self.nbytes, self.ptr = device, nbytes, None
+
+    def _hipcall(self, what, rc):
+        if rc != 0:
+            raise SphereflakeError(SF_EHIP, f"{what} (HIP error {rc})")
+
+    def __enter__(self):
+        H = _hip_runtime()
+        prev = ctypes.c_int(-1)
+        H.hipGetDevice(ctypes.byref(prev))
+        self._hipcall("hipSetDevice", H.hipSetDevice(self.device))
+        p = ctypes.c_void_p()
+        try:
+            self._hipcall("hipMalloc", H.hipMalloc(ctypes.byref(p), self.nbytes))
+        finally:
+            if prev.value >= 0:
+                H.hipSetDevice(prev.value)
+        self.ptr = p.value
+        return self
+
+    def upload(self, offset: int, a: np.ndarray):
+        self._hipcall("hipMemcpy", _hip_runtime().hipMemcpy(self.ptr + offset, a.ctypes.data, a.nbytes, 1))
+
+    def download(self, offset: int, a: np.ndarray):
+        self._hipcall("hipMemcpy", _hip_runtime().hipMemcpy(a.ctypes.data, self.ptr + offset, a.nbytes, 2))
+
+    def __exit__(self, *exc):
+        if self.ptr:
+            _hip_runtime().hipFree(self.ptr)
+            self.ptr = None
+
+
 class Sphereflake:
     """Drop-in for the reference class. Owns a device context (G-buffer in HBM)."""
 
@@ -502,6 +567,101 @@ class Sphereflake:
         _check(lib().sf_render_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(pos_ptr), ctypes.c_void_p(nrm_ptr),
                                   ctypes.c_void_p(min_t_ptr or None), ctypes.c_void_p(index_ptr or None)),
                "sf_render_to", self._ctx)
+
+    # caller-supplied directions (sf_trace_dirs_to / sf_trace_dirs / sf_probe_dirs) ------------
+    def trace_dirs(self, dirs, width=None, height=None, out=None, stride=None, max_depth=0, stream=None):
+        """Trace caller-supplied directions from the current view's origin (sphereflake_amd.dirs has generators).
+
+        dirs: a float32 array of directions, [H, W, 3 | 4] (an image, traced as 8x8 tiles) or [N, 3 | 4] (a list):
+          - a numpy array: uploaded, traced, and the results returned as numpy arrays
+            (pos4 [.., 4], nrm4 [.., 4], min_t [..], hit_index [..]) -- synchronous;
+          - a torch CUDA tensor (contiguous float32), or a device address (int) with width, height (1: a list) and
+            stride given: zero copy, asynchronous; results go to `out`.
+        out: (pos4, nrm4, min_t, hit_index) torch CUDA tensors or device addresses, any of them None / 0 -- or None:
+          an image of the context's frame size is then traced into the context's own G-buffer and aux channels
+          (download(), PostProcess(), save_image() see it), and any other numpy input returns numpy arrays.
+          out="host" returns numpy arrays for a frame-sized numpy image too."""
+        host = isinstance(dirs, np.ndarray)
+        if host:
+            dirs = np.ascontiguousarray(dirs, np.float32)
+        shape = tuple(getattr(dirs, "shape", ()))
+        if shape:
+            if len(shape) not in (2, 3) or shape[-1] not in (3, 4):
+                raise ValueError("dirs must be [H, W, 3 | 4] or [N, 3 | 4]")
+            stride = shape[-1] if stride is None else stride
+            if width is None and height is None:
+                height, width = (shape[0], shape[1]) if len(shape) == 3 else (1, shape[0])
+            elif int(width) * int(height) != int(np.prod(shape[:-1])):
+                raise ValueError("width x height does not match dirs")
+            if not host:
+                if not (dirs.is_cuda and dirs.is_contiguous() and dirs.element_size() == 4
+                        and dirs.dtype.is_floating_point):
+                    raise ValueError("dirs must be a contiguous float32 CUDA tensor")
+        elif width is None or height is None or stride is None:
+            raise ValueError("a device address needs width, height and stride")
+        width, height = int(width), int(height)
+        n = width * height
+        p = sf_dirs_params(width, height, int(stride), int(max_depth), stream)
+        to_ctx = out is None and (width, height) == (self.width, self.height) and height > 1
+        if not host:
+            dptr = dirs.data_ptr() if shape else int(dirs)
+            if to_ctx:
+                with self._mutex:
+                    _check(lib().sf_trace_dirs(self._ctx, ctypes.byref(p), ctypes.c_void_p(dptr)), "sf_trace_dirs",
+                           self._ctx)
+                return None
+            if out is None or isinstance(out, str):
+                raise ValueError("device directions need `out` buffers (or the context's frame size)")
+            if len(out) != 4:
+                raise ValueError("out must be (pos4, nrm4, min_t, hit_index)")
+            addr = [0 if o is None else o.data_ptr() if hasattr(o, "data_ptr") else int(o) for o in out]
+            ptrs = [ctypes.c_void_p(a) if a else None for a in addr]
+            with self._mutex:
+                _check(lib().sf_trace_dirs_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(dptr), *ptrs),
+                       "sf_trace_dirs_to", self._ctx)
+            return None
+        if out is not None and not isinstance(out, str):
+            raise ValueError("host directions return host arrays: out must be None or 'host'")
+        lead = shape[:-1] if len(shape) == 3 else (n,)
+        pos = np.empty(lead + (4,), np.float32)
+        nrm = np.empty(lead + (4,), np.float32)
+        mint = np.empty(lead, np.float32)
+        idx = np.empty(lead, np.uint32)
+        if n == 0:
+            return pos, nrm, mint, idx
+        with _DeviceScratch(self.device, dirs.nbytes + 16 + (0 if to_ctx else n * 40)) as d:
+            d.upload(0, dirs)
+            o0 = (dirs.nbytes + 15) // 16 * 16
+            with self._mutex:
+                if to_ctx:
+                    _check(lib().sf_trace_dirs(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr)), "sf_trace_dirs",
+                           self._ctx)
+                else:
+                    _check(lib().sf_trace_dirs_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr),
+                                                  ctypes.c_void_p(d.ptr + o0), ctypes.c_void_p(d.ptr + o0 + 16 * n),
+                                                  ctypes.c_void_p(d.ptr + o0 + 32 * n),
+                                                  ctypes.c_void_p(d.ptr + o0 + 36 * n)), "sf_trace_dirs_to", self._ctx)
+                # (the scratch is freed on leaving: the trace that reads and writes it must be done)
+                _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
+            if to_ctx:
+                return None
+            for a, off in ((pos, 0), (nrm, 16 * n), (mint, 32 * n), (idx, 36 * n)):
+                d.download(o0 + off, a)
+        return pos, nrm, mint, idx
+
+    def probe(self, dirs):
+        """A few rays from the current view's origin, host arrays in and out (sf_probe_dirs; synchronous): picking,
+        ranging, collision probes. dirs: [N, 3]. Returns (min_t [N], hit_index [N], pos4 [N, 4], nrm4 [N, 4]);
+        a miss has min_t = FLT_MAX and hit_index = 0xffffffff."""
+        d = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
+        n = d.shape[0]
+        mint, idx = np.empty(n, np.float32), np.empty(n, np.uint32)
+        pos, nrm = np.empty((n, 4), np.float32), np.empty((n, 4), np.float32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        with self._mutex:
+            _check(lib().sf_probe_dirs(self._ctx, vp(d), n, vp(mint), vp(idx), vp(pos), vp(nrm)), "sf_probe_dirs",
+                   self._ctx)
+        return mint, idx, pos, nrm
 
     def Synchronize(self):
         _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
