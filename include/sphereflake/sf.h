@@ -168,6 +168,47 @@ int sf_trace_dirs(sf_ctx* ctx, const sf_dirs_params* params, const float* dirs);
 int sf_probe_dirs(sf_ctx* ctx, const float* dirs3, uint32_t n, float* min_t, uint32_t* hit_index, float* pos4,
                   float* nrm4);
 
+/* --- caller-supplied origins and directions -------------------------------- */
+/* The origin enters the reference's ray only through the translation column of the root transform
+   (Sphereflake.cpp:83); everything after ray generation depends on the normalised direction, the root transform, the
+   child frames and the LOD constant only (Sphereflake.h:86-226). So "ray i from origins[i]" has an exact meaning:
+   what the reference returns for that direction after SetView at that origin. Uses: a batch of cameras (stereo
+   pairs, cube-map probes, thumbnails along a path) in one launch; the brake of main.cpp:213 probed from where the
+   camera WILL be (sphereflake_amd/rays.py: look_ahead); picking and ranging from points that are not the camera;
+   secondary rays from hit points.
+   Ray i is the reference's ray with D = Normalize(dirs[i]) (SIMD_AVX.h:170-180) under a root transform whose columns
+   0..2 are the context's current root's (sf_set_view / sf_set_setup) and whose column 3 is that of
+   sf_root_transform(origin), 0 - origin per component; with the context's child frames and variant. Outputs as
+   sf_trace_dirs_to, except: pos4 is relative to the ray's OWN origin (D t, the reference's view space); min_t may be
+   negative where the origin is inside a sphere; an origin that is not three finite numbers is a miss, as the
+   reference's arithmetic makes it (the root's tca is NaN or infinite, SIMD_AVX.h:247-258). Results never depend on
+   the order or grouping of the rays.
+   THE REFERENCE'S QUIRK, reproduced: RaySphereIntersection rejects a sphere whose centre is behind the ray
+   (tca >= 0, SIMD_AVX.h:247-258), also when the origin is inside it, and the root's bounding ball is tested first.
+   A ray that starts on the flake and heads away from the flake's centre therefore sees NOTHING, whatever lies along
+   it (shadow feelers towards a light outside the flake all miss); rays heading inwards behave as expected. This is
+   no occlusion query. */
+typedef struct sf_rays_params {
+    uint32_t width, height;     /* rays = width * height, row-major; height == 1: a plain list (as sf_dirs_params) */
+    uint32_t dir_stride;        /* floats per direction: 3 or 4 */
+    uint32_t origin_stride;     /* floats per origin: 3 or 4 */
+    uint32_t rays_per_origin;   /* ray i starts at origins[i / rays_per_origin]; 0 or 1: one origin per ray */
+    uint32_t max_depth;         /* levels to provision; 0 = auto: 12, flagged groups re-traced at SF_MAX_DEPTH_LIMIT */
+    void* stream;               /* NULL = the context stream */
+} sf_rays_params;
+
+/* Into caller-owned DEVICE buffers, in ray order (`origins` and `dirs` are device arrays too); any output may be NULL,
+   not all four. Asynchronous on the stream, ordered with the context's other calls as sf_render_to is; stats
+   accumulate as for sf_trace_dirs_to. SF_ENOVIEW before a view is set; SF_EINVAL for a stride other than 3 or 4, null
+   origins or dirs, all outputs null or more than 2^31 - 1 rays; zero rays: SF_OK, nothing done. A later render is not
+   affected in any way. (There is no variant into the context's own G-buffer: its consumers assume one origin.) */
+int sf_trace_rays_to(sf_ctx* ctx, const sf_rays_params* params, const float* origins, const float* dirs,
+                     float* pos4, float* nrm4, float* min_t, uint32_t* hit_index);
+/* Host convenience for a few rays (the look-ahead brake beside main.cpp:213-242): HOST arrays in (n x 3 directions,
+   ceil(n / rays_per_origin) x 3 origins) and out, synchronous. Outputs may be NULL (not all four). */
+int sf_probe_rays(sf_ctx* ctx, const float* origins3, const float* dirs3, uint32_t n, uint32_t rays_per_origin,
+                  float* min_t, uint32_t* hit_index, float* pos4, float* nrm4);
+
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the
    work units of all n frames from one set of tile queues -- a wave whose frame runs dry goes on with the next

@@ -151,6 +151,26 @@ public:
                             normals ? &normals[0].x : nullptr));
     }
 
+    // Caller-supplied origins and directions (new; sf_trace_rays_to / sf_probe_rays): ray i is the reference's ray with
+    // D = Normalize(dirs[i]) after SetView at origins[i / rays_per_origin] -- positions are relative to the ray's own
+    // origin, and a sphere whose centre is behind the ray is not seen (SIMD_AVX.h:247-258; sf.h). DEVICE pointers,
+    // asynchronous; any output may be null, not all four.
+    void TraceRays(const sf_rays_params& params, const float* origins, const float* dirs, float* positions4,
+                   float* normals4, float* minT = nullptr, uint32_t* hitIndex = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_rays_to(m_Ctx, &params, origins, dirs, positions4, normals4, minT, hitIndex));
+    }
+    // A few rays, HOST arrays in and out, synchronous: the brake of main.cpp:213 probed from the camera's next
+    // positions. minT is FLT_MAX and hitIndex 0xffffffff on a miss.
+    void ProbeRays(const float* origins3, const float* dirs3, uint32_t n, uint32_t raysPerOrigin, float* minT,
+                   uint32_t* hitIndex = nullptr, sf_vec4* positions = nullptr, sf_vec4* normals = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_probe_rays(m_Ctx, origins3, dirs3, n, raysPerOrigin, minT, hitIndex,
+                            positions ? &positions[0].x : nullptr, normals ? &normals[0].x : nullptr));
+    }
+
     // the device frame, downloaded into the vectors when it is newer than their contents (Refresh)
     const GBuffer& GetGBuffer() const
     {

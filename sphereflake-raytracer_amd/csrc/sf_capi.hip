@@ -49,6 +49,15 @@ extern "C" __global__ void sf_trace_dirs_wave(FrameArgs a, const float* dirs, ui
                                               uint32_t* overflow_list, uint32_t* overflow_count);
 extern "C" __global__ void sf_trace_dirs_fixup(FrameArgs a, const float* dirs, uint32_t stride,
                                                const uint32_t* overflow_list, uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_trace_rays_wave(FrameArgs a, const float* origins, const float* dirs, uint32_t ostride,
+                                              uint32_t dstride, uint32_t rpo, uint32_t mixed_ok, uint32_t groups,
+                                              uint32_t* overflow_list, uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_rays_one(FrameArgs a, const float* origins, const float* dirs, uint32_t ostride,
+                                             uint32_t dstride, uint32_t rpo, uint32_t groups, uint32_t* overflow_list,
+                                             uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_rays_fixup(FrameArgs a, const float* origins, const float* dirs, uint32_t ostride,
+                                               uint32_t dstride, uint32_t rpo, const uint32_t* overflow_list,
+                                               uint32_t* counters, uint32_t parity);
 extern "C" __global__ void sf_band_unpack(FrameArgs a, const float4* stage, uint32_t stage_rows, uint32_t band_rows,
                                            uint32_t n, uint32_t first, uint32_t members, uint32_t row0);
 extern "C" __global__ void sf_node_table(FrameArgs a, float4* table, uint32_t nodes);
@@ -97,6 +106,7 @@ static const uint32_t kLut[2048] = {
 
 namespace {
 
+constexpr uint32_t kRaysFixupBlocks = 1024;   // grid of sf_trace_rays_fixup (grid-stride over the re-trace list)
 constexpr uint32_t kDefaultLevels = 12;   // depths 0..11 expand; every BASELINE camera stays <= 10
 // parallel mt19937 draws (sf_mtjump.cpp, sf_kernels.hip): from this many draws per call, in K <= kMtSegMax
 // segments of >= kMtSegMin draws, each jumped to by a convolution split over SF_MT_PARTS workgroups
@@ -257,6 +267,8 @@ struct sf_ctx {
     uint32_t dirs_par = 0;
     float* probe_buf = nullptr;        // sf_probe_dirs: device scratch, 3 + 4 + 4 + 1 + 1 words per ray
     uint32_t probe_cap = 0;            // rays it holds
+    float* rprobe_buf = nullptr;       // sf_probe_rays: device scratch, 16 words per ray
+    uint32_t rprobe_cap = 0;           // rays it holds
     bool prog_seeded = false;
     uint32_t prog_seed = 0;
     uint64_t prog_next = 0;            // Sobol counter the device MT stream is positioned at
@@ -426,6 +438,7 @@ static void free_ctx(sf_ctx* c)
     (void)hipFree(c->dirs_ovf);
     (void)hipFree(c->dirs_cnt);
     (void)hipFree(c->probe_buf);
+    (void)hipFree(c->rprobe_buf);
     if (c->h_depth) (void)hipHostFree(c->h_depth);
     if (c->h_stats) (void)hipHostFree(c->h_stats);
     (void)hipFree(c->tile_trace);
@@ -1136,6 +1149,122 @@ int sf_probe_dirs(sf_ctx* c, const float* dirs3, uint32_t n, float* min_t, uint3
     p.height = 1;
     p.stride = 3;
     if (int rc = sf_trace_dirs_to(c, &p, d_dirs, d_pos, d_nrm, d_min, d_idx)) return rc;
+    if (int rc = sf_synchronize(c)) return rc;
+    if (pos4) SF_HIP(c, hipMemcpy(pos4, d_pos, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (nrm4) SF_HIP(c, hipMemcpy(nrm4, d_nrm, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (min_t) SF_HIP(c, hipMemcpy(min_t, d_min, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (hidx) SF_HIP(c, hipMemcpy(hidx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return SF_OK;
+}
+
+// Caller-supplied origins and directions (sf.h; kernels sf_trace_rays_wave / sf_trace_rays_fixup). Launched as
+// sf_trace_dirs_to launches, whose re-trace list and counters it shares (the two are ordered on the context like any
+// other pair of its calls). The levels are the default, not the view's geometric bound, which speaks of one origin.
+// Where the grouping proves that every group of 64 rays has one origin (one origin for all rays, or a list whose
+// rays_per_origin is a multiple of 64) the launch leaves out the mixed traversal's per-lane centre stack, which
+// is most of its LDS.
+int sf_trace_rays_to(sf_ctx* c, const sf_rays_params* p, const float* origins, const float* dirs, float* pos4,
+                     float* nrm4, float* min_t, uint32_t* hidx)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (p->dir_stride != 3u && p->dir_stride != 4u) return SF_EINVAL;
+    if (p->origin_stride != 3u && p->origin_stride != 4u) return SF_EINVAL;
+    if (!origins || !dirs || (!pos4 && !nrm4 && !min_t && !hidx)) return SF_EINVAL;
+    if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
+    const uint64_t n = (uint64_t)p->width * p->height;
+    if (n == 0) return SF_OK;
+    if (n > 0x7fffffffull) return SF_EINVAL;   // (ray counts are 32-bit in the launch arguments)
+    const bool list = p->height == 1u || p->width == 1u;   // one row or one column: consecutive rays
+    const uint32_t tiles_x = (p->width + 7u) / 8u;
+    const uint32_t groups = list ? (uint32_t)((n + 63u) / 64u) : tiles_x * ((p->height + 7u) / 8u);
+    const uint32_t rpo = p->rays_per_origin ? p->rays_per_origin : 1u;
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    if (!c->dirs_cnt) {
+        SF_HIP(c, hipMalloc(&c->dirs_cnt, 3 * 4));
+        SF_HIP(c, hipMemsetAsync(c->dirs_cnt, 0, 3 * 4, s));
+    }
+    if (groups > c->dirs_cap) {   // grown on demand; an earlier trace may still write the old list
+        SF_HIP(c, hipStreamSynchronize(s));
+        (void)hipFree(c->dirs_ovf);
+        c->dirs_ovf = nullptr;
+        c->dirs_cap = 0;
+        SF_HIP(c, hipMalloc(&c->dirs_ovf, (size_t)groups * 4));
+        c->dirs_cap = groups;
+    }
+    FrameArgs a = frame_args(c);
+    a.W = list ? (uint32_t)n : p->width;
+    a.H = list ? 1u : p->height;
+    a.tiles_x = tiles_x;
+    a.max_depth = p->max_depth ? p->max_depth : kDefaultLevels;
+    if (a.max_depth < 4u) a.max_depth = 4u;
+    if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
+    a.emit_aux = 1u;
+    a.pos = pos4;
+    a.nrm = nrm4;
+    a.min_t = min_t;
+    a.hit_index = hidx;
+    const bool one_origin_groups = rpo >= n || (list && rpo % 64u == 0u);
+    const uint32_t mixed_ok = (!one_origin_groups || (a.flags & SF_FLAG_FORCE_MIXED)) ? 1u : 0u;
+    const size_t lds = (size_t)(mixed_ok ? SF_LDS_RAYS_FLOATS(a.max_depth) : SF_LDS_WAVE_FLOATS(a.max_depth)) * 4;
+    if (mixed_ok)
+        hipLaunchKernelGGL(sf_trace_rays_wave, dim3(groups), dim3(64), lds, s, a, origins, dirs, p->origin_stride,
+                           p->dir_stride, rpo, mixed_ok, groups, c->dirs_ovf, c->dirs_cnt + c->dirs_par);
+    else
+        hipLaunchKernelGGL(sf_trace_rays_one, dim3(groups), dim3(64), lds, s, a, origins, dirs, p->origin_stride,
+                           p->dir_stride, rpo, groups, c->dirs_ovf, c->dirs_cnt + c->dirs_par);
+    SF_HIP(c, hipGetLastError());
+    // (secondary rays go deep: more re-trace blocks than the direction traces', about what the fixup's LDS lets reside)
+    const size_t lds_fix = (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4;
+    const uint32_t fb = groups < kRaysFixupBlocks ? groups : kRaysFixupBlocks;
+    hipLaunchKernelGGL(sf_trace_rays_fixup, dim3(fb), dim3(64), lds_fix, s, a, origins, dirs, p->origin_stride,
+                       p->dir_stride, rpo, (const uint32_t*)c->dirs_ovf, c->dirs_cnt, c->dirs_par);
+    SF_HIP(c, hipGetLastError());
+    c->dirs_par ^= 1u;
+    c->rays += (int64_t)n;
+    return SF_OK;
+}
+
+int sf_probe_rays(sf_ctx* c, const float* origins3, const float* dirs3, uint32_t n, uint32_t rays_per_origin,
+                  float* min_t, uint32_t* hidx, float* pos4, float* nrm4)
+{
+    if (!c) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!origins3 || !dirs3 || (!pos4 && !nrm4 && !min_t && !hidx)) return SF_EINVAL;
+    if (n == 0) return SF_OK;
+    if (n > 0x7fffffffu) return SF_EINVAL;
+    const uint32_t rpo = rays_per_origin ? rays_per_origin : 1u;
+    const uint32_t norig = (n + rpo - 1u) / rpo;
+    DevGuard g(c->device);
+    if (n > c->rprobe_cap) {
+        if (int rc = ctx_drain(c)) return rc;   // an earlier probe's trace may still use the old scratch
+        (void)hipFree(c->rprobe_buf);
+        c->rprobe_buf = nullptr;
+        c->rprobe_cap = 0;
+        SF_HIP(c, hipMalloc(&c->rprobe_buf, ((size_t)n * 16 + 3) * 4));
+        c->rprobe_cap = n;
+    }
+    // {dirs 3, origins 3 (at most one per ray), pos 4, nrm 4, min_t 1, index 1} words per ray
+    float* const d_dirs = c->rprobe_buf;
+    float* const d_org = d_dirs + (size_t)3 * c->rprobe_cap;
+    float* const d_pos = d_org + (size_t)3 * c->rprobe_cap + ((4u - (6u * c->rprobe_cap) % 4u) % 4u);   // (16-B aligned)
+    float* const d_nrm = d_pos + (size_t)4 * c->rprobe_cap;
+    float* const d_min = d_nrm + (size_t)4 * c->rprobe_cap;
+    uint32_t* const d_idx = reinterpret_cast<uint32_t*>(d_min + c->rprobe_cap);
+    if (int rc = ctx_join(c, c->stream)) return rc;
+    SF_HIP(c, hipMemcpyAsync(d_dirs, dirs3, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    SF_HIP(c, hipMemcpyAsync(d_org, origins3, (size_t)norig * 12, hipMemcpyHostToDevice, c->stream));
+    sf_rays_params p;
+    std::memset(&p, 0, sizeof p);
+    p.width = n;
+    p.height = 1;
+    p.dir_stride = 3;
+    p.origin_stride = 3;
+    p.rays_per_origin = rpo;
+    if (int rc = sf_trace_rays_to(c, &p, d_org, d_dirs, d_pos, d_nrm, d_min, d_idx)) return rc;
     if (int rc = sf_synchronize(c)) return rc;
     if (pos4) SF_HIP(c, hipMemcpy(pos4, d_pos, (size_t)n * 16, hipMemcpyDeviceToHost));
     if (nrm4) SF_HIP(c, hipMemcpy(nrm4, d_nrm, (size_t)n * 16, hipMemcpyDeviceToHost));

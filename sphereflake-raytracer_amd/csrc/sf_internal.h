@@ -45,6 +45,11 @@
 #define SF_LDS_LEVEL (SF_LDS_TABLE + SF_LDS_E + 1)      // (+1: levels stay 16-byte aligned)
 // levels - 1 level images: the deepest provisioned level's table is never read (see traverse)
 #define SF_LDS_WAVE_FLOATS(levels) (SF_LDS_ROOT + SF_LDS_CONE + ((levels) - 1) * SF_LDS_LEVEL)
+// Mixed-origin traversal (sf_trace_rays_to): a level table for each of the `levels` depths a node can be open at
+// (columns and the children's shared centre offsets, in the table layout above), then the per-lane centre stack,
+// [level][component x y z][lane] -- a level's load or store has stride one across the lanes
+#define SF_RAYS_CSTACK (3 * 64)
+#define SF_LDS_RAYS_FLOATS(levels) (SF_LDS_WAVE_FLOATS((levels) + 1) + (levels) * SF_RAYS_CSTACK)
 
 // Persistent-kernel tile queues: SF_QUEUES counters per render parity, one 128-byte line each, after
 // the two overflow counters (u32 words).
@@ -101,6 +106,9 @@
 // row-major units are tile halves (pixel rows 0-3 / 4-7 of tile u / 2): a frame of fewer tiles than wave slots -- a
 // member's share -- then ends on half its heaviest tile's traversal (round 6, A/B: SF_HALVES)
 #define SF_FLAG_HALVES 0x4000u
+// send every group of sf_trace_rays_to through the mixed-origin traversal, also where all its rays share one origin
+// (A/B and tests; results identical)
+#define SF_FLAG_FORCE_MIXED 0x8000u
 
 struct DepthTables {
     float r2_bound[SF_DEPTH_TABLE];   // (2 r_d)^2  bounding sphere (Sphereflake.h:108-110)

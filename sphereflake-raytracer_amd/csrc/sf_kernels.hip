@@ -3046,6 +3046,429 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_dirs_fixup(FrameArgs a
 }
 
 // ------------------------------------------------------------------------------------------
+// Caller-supplied origins and directions (sf_trace_rays_to): ray i is the reference's ray with
+// D = Normalize(dirs[i]) under the root transform whose columns 0..2 are the context's and whose translation is
+// 0 - origin (Sphereflake.cpp:83) -- what the reference returns for that direction after SetView at that origin.
+// The rays of a group are grouped as sf_trace_dirs_wave groups them. A group whose rays share one origin (the same
+// bits) runs the frame's own traversal (traverse_ray) on that origin's root image. A group of several origins runs
+// traverse_mixed below: world = parent * child (SIMD_AVX.h:59-81) splits into the axis columns and the centre offset
+// S = (P0 Tx + P1 Ty) + P2 Tz, which do not depend on the origin, and one addition per ray, centre = parent centre + S
+// (fma(parent centre, 1, S): one rounding) -- so the wave still expands a node once for all its rays, and each lane
+// carries its own centres.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// traverse_mixed's third status bit: a shared axis-column sum was an exact -0. The reference adds parent centre x 0
+// to it, a zero with the sign of the ray's own centre component, so the column's zero sign is then per ray (and can
+// reach a normal's zero sign through n = p - C): the group is traced once per distinct origin instead.
+#define SF_STATUS_ZSIGN 4u
+
+// Index order, no cone, no front-first: the visits are the reference's, the ancestor rule of self_test the only tie
+// to handle. Lbase: root image (its axis columns are read; the centre is per lane: ocx, ocy, ocz) and `levels` level
+// tables, whose plane 0 holds the children's S instead of centres; cstk: the centre stack, `levels` x [3][64].
+__device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ K, float* __restrict__ Lbase,
+                                               float* __restrict__ cstk, const float4 bcol, uint32_t levels, float dx,
+                                               float dy, float dz, float ocx, float ocy, float ocz, bool valid,
+                                               HitState& h, int32_t& maxd, uint32_t& status, uint32_t K_flags)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const TraverseLds L{ Lbase };
+    const bool occl_cull = (K_flags & SF_FLAG_NO_OCCL_CULL) == 0u;
+
+    h.minT = FLT_MAX;
+    h.cx = h.cy = h.cz = 0.f;
+    h.index = 0xffffffffu;
+    h.depth = -1;
+    h.hit = false;
+    uint64_t ancm = 0ull;   // lanes whose current best sphere is an ancestor of the open node
+
+    // ---- root node (depth 0): bounding sphere + LOD, per lane on the lane's own root centre
+    const float occ0 = (ocx * ocx + ocy * ocy) + ocz * ocz;
+    const float4 dt0 = depth_consts(K, 0u);
+    const float tca0 = (ocx * dx + ocy * dy) + ocz * dz;
+    const float d20 = occ0 - tca0 * tca0;
+    const bool ex0 = valid && tca0 >= 0.0f && d20 <= dt0.x && near_root(tca0, d20, dt0.x) < dt0.w;
+    if (!wave_ballot(ex0)) return;
+    maxd = 0;
+    float cull_t = depth_consts(K, 1u).w;
+
+    // this lane's column of the cooperative child build, and where it stores it (as traverse_ray)
+    const uint32_t bi = build_child(lane);
+    const uint32_t bc = lane < 27u ? lane / 9u : 3u;
+    const float b[4] = { bcol.x, bcol.y, bcol.z, bcol.w };
+    const uint32_t slot = bc == 3u ? (lane >= 32u && bi == 8u ? (uint32_t)SF_LDS_TABLE + 3u : bi * 4u)
+                                   : SF_LDS_PLANE + bc * SF_LDS_COLS + bi * 3u;
+
+    // (traverse_ray's self_test in index order: a tie is accepted where the best is an ancestor, else dropped)
+    auto self_test = [&](const float4 pc, float tca, float d2, uint32_t dd, float actv, uint32_t idx, float R2s) {
+        const uint64_t hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);
+        if (hsm) {
+            const float xs = R2s - d2;
+            float ts;
+            if ((wave_ballot(!(xs >= 0x1p-96f)) & hsm) != 0ull) ts = near_root_exact(tca, d2, R2s);
+            else ts = near_root_big(tca, xs);
+            uint64_t accm = hsm & wave_ballot(ts < h.minT);
+            const uint64_t tie = hsm & wave_ballot(ts == h.minT);
+            accm |= tie & ancm;
+            sel_in_place(h.minT, ts, accm);
+            sel_in_place(h.cx, pc.x, accm);
+            sel_in_place(h.cy, pc.y, accm);
+            sel_in_place(h.cz, pc.z, accm);
+            sel_in_place(h.index, idx, accm);
+            uint32_t hd = (uint32_t)h.depth;
+            sel_in_place(hd, dd, accm);
+            h.depth = (int32_t)hd;
+            ancm |= accm;
+        }
+    };
+
+    // (traverse_ray's child_lod)
+    auto child_lod = [&](float tca, float d2, float xs, bool hb, uint64_t hbm, float R2b, float T, float Tfar) -> uint64_t {
+        const uint64_t nearm = wave_ballot(tca < T);
+        const uint64_t farm = wave_ballot(tca * (1.0f - 0x1p-8f) >= Tfar);
+        if ((hbm & ~(nearm | farm)) == 0ull) return hbm & nearm;
+        const float sq = __builtin_amdgcn_sqrtf(xs);
+        const float s_lo = __uint_as_float((uint32_t)max((int32_t)__float_as_uint(sq) - 2, 0));
+        const float s_hi = __uint_as_float(__float_as_uint(sq) + 2u);
+        const float t_hi = tca - s_lo;
+        const float t_lo = tca - s_hi;
+        const uint64_t tinym = wave_ballot(xs < 0x1p-96f);
+        const float thx = sel_mask(t_hi, __builtin_inff(), tinym);
+        const float tlx = sel_mask(t_lo, -__builtin_inff(), tinym);
+        const float th = hb ? thx : __builtin_inff();
+        const float tl = hb ? tlx : __builtin_inff();
+        uint64_t exm = wave_ballot(th < T);
+        const uint64_t undm = wave_ballot(sel_mask(tl, __builtin_inff(), exm) < T);
+        if (undm) {
+            const float te = near_root_exact(tca, d2, R2b);
+            exm |= undm & wave_ballot(te < T);
+        }
+        return exm;
+    };
+
+    // ---- the shared part of the 9 children of the node whose axis columns are at col + j cs, into table tb: their
+    // axis columns (lanes 0..26) and their centre offsets S (the other lanes), the sums of traverse_ray's expand
+    // without its fma of the parent centre (ko: byte offset of the children's depth constants)
+    auto expand = [&](const float* col, uint32_t cs, float* tb, uint32_t ko) {
+        lds_fence();
+        const float3 p0 = *reinterpret_cast<const float3*>(col);
+        const float3 p1 = *reinterpret_cast<const float3*>(col + cs);
+        const float3 p2 = *reinterpret_cast<const float3*>(col + 2u * cs);
+        const float sm = bc == 3u ? depth_word_at(K, ko - (1u << 5), 2u) : 1.0f;   // (4/3) r of the node's depth
+        const float b0 = b[0] * sm, b1 = b[1] * sm, b2 = b[2] * sm;
+        const float x = (p0.x * b0 + p1.x * b1) + p2.x * b2;
+        const float y = (p0.y * b0 + p1.y * b1) + p2.y * b2;
+        const float z = (p0.z * b0 + p1.z * b1) + p2.z * b2;
+        const bool negz = bc != 3u && (__float_as_uint(x) == 0x80000000u || __float_as_uint(y) == 0x80000000u ||
+                                       __float_as_uint(z) == 0x80000000u);
+        if (wave_ballot(negz) != 0ull) status |= SF_STATUS_ZSIGN;
+        *reinterpret_cast<float3*>(tb + slot) = make_float3(x, y, z);
+    };
+
+    uint32_t stk_pc = 0u, stk_ix = 0u;   // VGPR stack, lane k = level k: untested children, idxB
+    float* tcur = L.table(0u);
+    float* const cs = cstk + lane;       // this lane's centre of the open node at depth k: cs[192 k + 64 j]
+    uint32_t kofs = 1u << 5;
+    float R2c = depth_consts_at(K, kofs).x;
+    const uint32_t lv32 = __builtin_amdgcn_readfirstlane(levels << 5);
+    uint32_t d = 0, idxB = 1, C;
+    float actv;
+    uint32_t actbits;
+    {
+        const float av0 = ex0 ? __builtin_inff() : -1.0f;
+        self_test(make_float4(ocx, ocy, ocz, occ0), tca0, d20, 0u, av0, 0u, dt0.y);
+        // per lane: beyond the leaf threshold no child of the node can pass LOD for any ray (sfhost::leaf_threshold),
+        // and a child is only ever tested for its own sphere once entered -- such a lane stops visiting here
+        const uint64_t live = wave_ballot(ex0 && !(occ0 > depth_leaf(K, 0u)));
+        if (live == 0ull) {
+            h.hit = h.depth >= 0;
+            return;
+        }
+        actv = sel_mask(-1.0f, __builtin_inff(), live);
+        actbits = actv > 0.0f ? 1u : 0u;
+        cs[0] = ocx;
+        cs[64] = ocy;
+        cs[128] = ocz;
+        expand(L.root() + 4u, 4u, tcur, kofs);
+        C = 0x1ffu;
+    }
+
+    for (;;) {
+        d = __builtin_amdgcn_readfirstlane(d);
+        if (C) {
+            const uint32_t c = __builtin_ctz(C);
+            __asm__("s_bitset0_b32 %0, %1" : "+s"(C) : "s"(c));
+            const float4 dc = depth_consts_at(K, kofs);
+            lds_fence();
+            const float3 S = *reinterpret_cast<const float3*>(tcur + c * 4u);
+            const float cx = ocx + S.x, cy = ocy + S.y, cz = ocz + S.z;
+            const float cc = (cx * cx + cy * cy) + cz * cz;
+            const float tca = (cx * dx + cy * dy) + cz * dz;
+            const float d2 = cc - tca * tca;
+            const float xs = R2c - d2;
+            const bool hb = __builtin_fminf(__builtin_fminf(tca, xs), actv) >= 0.0f;
+            const uint64_t hbm = wave_ballot(hb);
+            if (hbm == 0ull) continue;
+            const float4 dk = depth_consts_at(K, kofs + 16u);   // depth d + 1's {leaf, cull, far}
+            const uint64_t exm = child_lod(tca, d2, xs, hb, hbm, dc.x, dc.w, dk.z);
+            if (exm == 0ull) continue;
+            if (kofs >= lv32) {   // (d + 1 >= levels) the group is re-traced with more levels: nothing here is kept
+                status |= SF_STATUS_OVERFLOW;
+                break;
+            }
+            if ((int32_t)d + 1 > maxd) {   // Sphereflake.h:157-160
+                maxd = (int32_t)d + 1;
+                cull_t = depth_consts_at(K, kofs + (1u << 5)).w;
+            }
+            // occlusion cull, per lane (see traverse_ray)
+            uint64_t amx = exm;
+            if (occl_cull) {
+                const float v = __builtin_fminf(tca - h.minT, tca - cull_t);
+                amx = exm & ~wave_ballot(v - SF_OCCL_MARGIN * tca > dk.y);
+                if (amx == 0ull) continue;
+            }
+            const float avx = sel_mask(-1.0f, __builtin_inff(), amx);
+            self_test(make_float4(cx, cy, cz, cc), tca, d2, d + 1u, avx, idxB + c, dc.y);
+            const uint64_t live = amx & ~wave_ballot(cc > dk.x);   // (the per-lane leaf cut, as at the root)
+            if (live == 0ull) {
+                ancm &= wave_ballot(h.depth != (int32_t)d + 1);   // the child is finished
+                continue;
+            }
+            // push the open node, open child c
+            stk_pc = writelane_s(C, d, stk_pc);
+            stk_ix = writelane_s(idxB, d, stk_ix);
+            {
+                const uint32_t bit = 2u << d;   // level d + 1
+                uint32_t ab = actbits & ~bit;
+                sel_in_place(ab, ab | bit, live);
+                actbits = ab;
+            }
+            idxB = 9u * (idxB + c) + 1u;
+            d += 1u;
+            actv = sel_mask(-1.0f, __builtin_inff(), live);
+            ocx = cx;
+            ocy = cy;
+            ocz = cz;
+            float* const cl = cs + d * SF_RAYS_CSTACK;
+            cl[0] = cx;
+            cl[64] = cy;
+            cl[128] = cz;
+            const float* const col = tcur + SF_LDS_PLANE + 3u * c;   // the entered child's axis columns
+            tcur += SF_LDS_LEVEL;
+            kofs += 1u << 5;
+            expand(col, SF_LDS_COLS, tcur, kofs);
+            R2c = depth_consts_at(K, kofs).x;
+            C = 0x1ffu;
+            continue;
+        }
+        // ---- the node at depth d is finished: a best sphere at depth d is no longer an ancestor
+        ancm &= wave_ballot(h.depth != (int32_t)d);
+        if (d == 0u) break;
+        d -= 1u;
+        tcur -= SF_LDS_LEVEL;
+        kofs -= 1u << 5;
+        R2c = depth_consts_at(K, kofs).x;
+        C = (uint32_t)__builtin_amdgcn_readlane(stk_pc, d);
+        idxB = (uint32_t)__builtin_amdgcn_readlane(stk_ix, d);
+        actv = ((actbits >> d) & 1u) ? __builtin_inff() : -1.0f;
+        const float* const cl = cs + d * SF_RAYS_CSTACK;
+        ocx = cl[0];
+        ocy = cl[64];
+        ocz = cl[128];
+    }
+    h.hit = h.depth >= 0;
+}
+
+// One group of rays. mixed_ok: the launch provisioned the mixed traversal's LDS (SF_LDS_RAYS_FLOATS); without it a
+// group of several origins is traced once per distinct origin, which is always exact. ONE: the host proved from the
+// grouping that the rays of every group share an origin index (sf_trace_rays_one) -- one pass of the frame's
+// traversal, no test, and no mixed traversal compiled in.
+template <bool FIXUP, bool ONE = false>
+__device__ __forceinline__ TileStats trace_ray_group(const FrameArgs& a, const float* __restrict__ origins,
+                                                     const float* __restrict__ dirs, uint32_t ostride, uint32_t dstride,
+                                                     uint32_t rpo, uint32_t mixed_ok, float* __restrict__ L,
+                                                     const float4 bcol, uint32_t group, uint32_t levels,
+                                                     uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const uint32_t lane = threadIdx.x & 63u;
+    // the lane's ray, clamped into the list or image as in trace_dir_group
+    uint32_t ray;
+    bool valid;
+    uint32_t mid;
+    if (a.H == 1u) {
+        const uint64_t i = (uint64_t)group * 64u + lane;
+        valid = i < a.W;
+        ray = valid ? (uint32_t)i : a.W - 1u;
+        mid = 32u;
+    } else {
+        const uint32_t ty = group / a.tiles_x, tx = group - ty * a.tiles_x;
+        const uint32_t x = tx * SF_TILE + (lane & 7u), y = ty * SF_TILE + (lane >> 3);
+        valid = x < a.W && y < a.H;
+        ray = (y < a.H ? y : a.H - 1u) * a.W + (x < a.W ? x : a.W - 1u);   // (< 2^31 rays)
+        mid = 36u;
+    }
+    const float* const dp = dirs + (size_t)ray * dstride;
+    const float* const op = origins + (size_t)(rpo > 1u ? ray / rpo : ray) * ostride;
+    float dx = dp[0], dy = dp[1], dz = dp[2];
+    // the root transform's translation for this origin (Sphereflake.cpp:83: 0 - origin per component)
+    const float rx = 0.0f - op[0], ry = 0.0f - op[1], rz = 0.0f - op[2];
+    normalize3(dx, dy, dz, K->lut);
+    // a direction that does not normalise to finite numbers is a miss (see trace_dir_group). So is an origin that is
+    // not finite: the root's tca is then NaN, -inf, or +inf with d2 = inf - inf = NaN, and the root is not entered --
+    // traverse_mixed finds that by the reference's own arithmetic per lane, and a group that shares such an origin
+    // leaves traverse_ray at its root test, before the cone.
+    auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
+    const bool fin = finite(dx) && finite(dy) && finite(dz);
+    const bool on = valid && fin;
+    const uint64_t onm = wave_ballot(on);
+    HitState h;
+    h.minT = FLT_MAX;
+    h.cx = h.cy = h.cz = 0.f;
+    h.index = 0xffffffffu;
+    h.depth = -1;
+    h.hit = false;
+    int32_t maxd = -1;
+    uint32_t status = 0u;
+    if (onm != 0ull) {   // (uniform; else every ray of the group misses)
+        const uint32_t f0 = __builtin_amdgcn_readfirstlane((uint32_t)__builtin_ctzll(onm));
+        const bool same = __float_as_uint(rx) == __float_as_uint(readlane_f(rx, f0)) &&
+                          __float_as_uint(ry) == __float_as_uint(readlane_f(ry, f0)) &&
+                          __float_as_uint(rz) == __float_as_uint(readlane_f(rz, f0));
+        const bool mixed = !ONE && ((onm & ~wave_ballot(same)) != 0ull || (a.flags & SF_FLAG_FORCE_MIXED) != 0u);
+        const uint32_t culls = a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST);
+        uint64_t todo = onm;
+        if (!ONE && mixed && mixed_ok != 0u) {
+            float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
+            traverse_mixed(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, maxd, status, culls);
+            if (status & SF_STATUS_ZSIGN) {   // per-ray zero signs: nothing of this pass is kept
+                status = 0u;
+                maxd = -1;
+                h.minT = FLT_MAX;
+                h.cx = h.cy = h.cz = 0.f;
+                h.index = 0xffffffffu;
+                h.depth = -1;
+                h.hit = false;
+            } else {
+                todo = 0ull;
+            }
+        }
+        // ---- one origin at a time: the frame's traversal on that origin's root image, for the lanes that start
+        // there (one pass for a group of one origin). The other lanes carry the axis lane's direction, invalid, so
+        // the cone is the members'.
+        while (todo != 0ull) {
+            const uint32_t l0 = __builtin_amdgcn_readfirstlane((uint32_t)__builtin_ctzll(todo));
+            float r[12];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) r[k] = a.root[k];
+            r[9] = readlane_f(rx, l0);
+            r[10] = readlane_f(ry, l0);
+            r[11] = readlane_f(rz, l0);
+            const bool mine = on && (ONE || (__float_as_uint(rx) == __float_as_uint(r[9]) &&
+                                             __float_as_uint(ry) == __float_as_uint(r[10]) &&
+                                             __float_as_uint(rz) == __float_as_uint(r[11])));
+            const uint64_t m = todo & wave_ballot(mine);   // (holds l0)
+            const bool member = ((m >> lane) & 1ull) != 0ull;
+            const uint32_t axl = __builtin_amdgcn_readfirstlane(((m >> mid) & 1ull) ? mid : l0);
+            const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
+            lds_fence();
+            stage_root(L, r);
+            HitState h1;
+            int32_t md = -1;
+            uint32_t st = 0u;
+            traverse_ray<>(K, r, L, bcol, levels, member ? dx : ax, member ? dy : ay, member ? dz : az, member, h1, md,
+                           st, culls | (FIXUP ? SF_FLAG_NO_FRONT_FIRST : 0u), nullptr, axl);
+            if (member) h = h1;
+            maxd = md > maxd ? md : maxd;
+            status |= st;
+            todo &= ~m;
+            if (ONE) break;
+        }
+    }
+    const bool flagged = status != 0u;   // (uniform) more levels needed, or a tie under the front-first order
+    if (!FIXUP && flagged) {
+        const uint32_t slot = wave_fetch_add(overflow_count, 1u);
+        overflow_list[slot] = group;   // uniform value and address
+    }
+    if (valid) {
+        // (a lane that is not `on` kept the initial miss; its direction may be non-finite and shade ignores it)
+        float px, py, pz, nx, ny, nz;
+        shade(dx, dy, dz, h, K->lut, px, py, pz, nx, ny, nz);
+        if (a.pos) reinterpret_cast<float4*>(a.pos)[ray] = make_float4(px, py, pz, 1.0f);
+        if (a.nrm) reinterpret_cast<float4*>(a.nrm)[ray] = make_float4(nx, ny, nz, 1.0f);
+        if (a.min_t) a.min_t[ray] = h.minT;
+        if (a.hit_index) a.hit_index[ray] = h.hit ? h.index : 0xffffffffu;
+    }
+    TileStats st;
+    st.maxd = maxd;
+    st.closest = valid ? h.minT : FLT_MAX;
+    st.overflowed = flagged;
+    return st;
+}
+
+}  // namespace
+
+// One group per one-wave workgroup; dynamic LDS: SF_LDS_RAYS_FLOATS(a.max_depth) with mixed_ok, else
+// SF_LDS_WAVE_FLOATS(a.max_depth).
+extern "C" __global__ __launch_bounds__(64) void sf_trace_rays_wave(FrameArgs a, const float* origins, const float* dirs,
+                                                                    uint32_t ostride, uint32_t dstride, uint32_t rpo,
+                                                                    uint32_t mixed_ok, uint32_t groups,
+                                                                    uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    stage_root(lds, a.root);
+    const TileStats st = trace_ray_group<false>(a, origins, dirs, ostride, dstride, rpo, mixed_ok, lds,
+                                                build_column(a.consts), blockIdx.x, a.max_depth, overflow_list,
+                                                overflow_count);
+    publish_stats(a, st.maxd, st.closest, 0u);
+}
+
+// The same where the host proved one origin per group (one origin for all rays, or a list whose rays_per_origin is
+// a multiple of 64): dynamic LDS SF_LDS_WAVE_FLOATS(a.max_depth), the launch of sf_trace_dirs_wave plus the origin.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_rays_one(FrameArgs a, const float* origins, const float* dirs,
+                                                                   uint32_t ostride, uint32_t dstride, uint32_t rpo,
+                                                                   uint32_t groups, uint32_t* overflow_list,
+                                                                   uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    const TileStats st = trace_ray_group<false, true>(a, origins, dirs, ostride, dstride, rpo, 0u, lds,
+                                                      build_column(a.consts), blockIdx.x, a.max_depth, overflow_list,
+                                                      overflow_count);
+    publish_stats(a, st.maxd, st.closest, 0u);
+}
+
+// Re-trace of the flagged groups at SF_MAX_LEVELS (as sf_trace_dirs_fixup, whose list and counters it shares).
+extern "C" __global__ __launch_bounds__(64) void sf_trace_rays_fixup(FrameArgs a, const float* origins, const float* dirs,
+                                                                     uint32_t ostride, uint32_t dstride, uint32_t rpo,
+                                                                     const uint32_t* overflow_list, uint32_t* counters,
+                                                                     uint32_t parity)
+{
+    extern __shared__ float lds[];
+    const uint32_t n = counters[parity];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        counters[parity ^ 1u] = 0u;
+        counters[2] += n;
+    }
+    if (blockIdx.x >= n) return;
+    int32_t maxd = -1;
+    float closest = FLT_MAX;
+    uint32_t unresolved = 0u;
+    const float4 bcol = build_column(a.consts);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        lds_fence();
+        stage_root(lds, a.root);   // (a group traced per origin overwrites the root image)
+        const TileStats st = trace_ray_group<true>(a, origins, dirs, ostride, dstride, rpo, 1u, lds, bcol,
+                                                   overflow_list[i], SF_MAX_LEVELS, nullptr, nullptr);
+        maxd = st.maxd > maxd ? st.maxd : maxd;
+        closest = fminf(closest, st.closest);
+        unresolved += st.overflowed ? 1u : 0u;
+    }
+    publish_stats(a, maxd, closest, unresolved);
+}
+
+// ------------------------------------------------------------------------------------------
 // One thread per ray, private stack (Sphereflake.h:86-226 restated as an explicit DFS).
 // ------------------------------------------------------------------------------------------
 extern "C" __global__ __launch_bounds__(256) void sf_trace_ray(FrameArgs a)

@@ -60,6 +60,12 @@ class sf_dirs_params(ctypes.Structure):
                 ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
 
 
+class sf_rays_params(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("dir_stride", ctypes.c_uint32),
+                ("origin_stride", ctypes.c_uint32), ("rays_per_origin", ctypes.c_uint32),
+                ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
 class sf_stats(ctypes.Structure):
     _fields_ = [("max_depth", ctypes.c_int32), ("closest", ctypes.c_float),
                 ("rays", ctypes.c_int64), ("overflow_tiles", ctypes.c_int64)]
@@ -96,6 +102,10 @@ SIGNATURES = {
     "sf_trace_dirs": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_dirs_params), ctypes.c_void_p]),
     "sf_probe_dirs": (ctypes.c_int, [_CTX, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_rays_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_rays_params), ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_probe_rays": (ctypes.c_int, [_CTX, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_render_frames": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
                                         ctypes.POINTER(sf_render_params)]),
     "sf_slab_rows": (ctypes.c_uint32, [ctypes.c_uint32] * 4),
@@ -661,6 +671,108 @@ class Sphereflake:
         with self._mutex:
             _check(lib().sf_probe_dirs(self._ctx, vp(d), n, vp(mint), vp(idx), vp(pos), vp(nrm)), "sf_probe_dirs",
                    self._ctx)
+        return mint, idx, pos, nrm
+
+    # caller-supplied origins and directions (sf_trace_rays_to / sf_probe_rays) ------------------
+    def trace_rays(self, origins, dirs, rays_per_origin=1, out=None, dir_stride=None, origin_stride=None,
+                   max_depth=0, stream=None, width=None, height=None):
+        """Trace ray i from origins[i // rays_per_origin] along dirs[i] (sphereflake_amd.rays has generators): what
+        the reference returns for that direction after SetView at that origin. Positions are relative to the ray's
+        own origin; a sphere whose centre is behind the ray is not seen, even from inside it (sf.h).
+
+        dirs as for trace_dirs: [H, W, 3 | 4] (an image, traced as 8x8 tiles) or [N, 3 | 4] (a list); origins
+        [M, 3 | 4] with M >= ceil(rays / rays_per_origin). Both numpy arrays: uploaded, traced, and the results
+        returned as numpy arrays (pos4, nrm4, min_t, hit_index) -- synchronous (`out` None or "host"). Both torch
+        CUDA tensors (contiguous float32) or device addresses (ints, with width, height and the strides given): zero
+        copy, asynchronous, results go to `out` = (pos4, nrm4, min_t, hit_index) tensors or addresses, any of them
+        None / 0."""
+        host = isinstance(dirs, np.ndarray)
+        if host != isinstance(origins, np.ndarray):
+            raise ValueError("origins and dirs must both be host arrays or both be on the device")
+        if host:
+            dirs = np.ascontiguousarray(dirs, np.float32)
+            origins = np.ascontiguousarray(origins, np.float32)
+        shape = tuple(getattr(dirs, "shape", ()))
+        oshape = tuple(getattr(origins, "shape", ()))
+        if shape:
+            if len(shape) not in (2, 3) or shape[-1] not in (3, 4):
+                raise ValueError("dirs must be [H, W, 3 | 4] or [N, 3 | 4]")
+            dir_stride = shape[-1] if dir_stride is None else dir_stride
+            if width is None and height is None:
+                height, width = (shape[0], shape[1]) if len(shape) == 3 else (1, shape[0])
+            elif int(width) * int(height) != int(np.prod(shape[:-1])):
+                raise ValueError("width x height does not match dirs")
+        elif width is None or height is None or dir_stride is None:
+            raise ValueError("a device address needs width, height and dir_stride")
+        width, height = int(width), int(height)
+        n = width * height
+        rpo = max(int(rays_per_origin), 1)
+        if oshape:
+            if len(oshape) != 2 or oshape[-1] not in (3, 4):
+                raise ValueError("origins must be [M, 3 | 4]")
+            origin_stride = oshape[-1] if origin_stride is None else origin_stride
+            if oshape[0] * rpo < n:
+                raise ValueError("too few origins for the rays")
+        elif origin_stride is None:
+            raise ValueError("a device address needs origin_stride")
+        if not host:
+            for t in (dirs, origins):
+                if hasattr(t, "data_ptr") and not (t.is_cuda and t.is_contiguous() and t.element_size() == 4
+                                                   and t.dtype.is_floating_point):
+                    raise ValueError("origins and dirs must be contiguous float32 CUDA tensors")
+        p = sf_rays_params(width, height, int(dir_stride), int(origin_stride), rpo, int(max_depth), stream)
+        if not host:
+            if out is None or isinstance(out, str) or len(out) != 4:
+                raise ValueError("device rays need out = (pos4, nrm4, min_t, hit_index)")
+            dptr = dirs.data_ptr() if shape else int(dirs)
+            optr = origins.data_ptr() if oshape else int(origins)
+            addr = [0 if o is None else o.data_ptr() if hasattr(o, "data_ptr") else int(o) for o in out]
+            ptrs = [ctypes.c_void_p(a) if a else None for a in addr]
+            with self._mutex:
+                _check(lib().sf_trace_rays_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(optr or None),
+                                              ctypes.c_void_p(dptr or None), *ptrs), "sf_trace_rays_to", self._ctx)
+            return None
+        if out is not None and not isinstance(out, str):
+            raise ValueError("host rays return host arrays: out must be None or 'host'")
+        lead = shape[:-1] if len(shape) == 3 else (n,)
+        pos = np.empty(lead + (4,), np.float32)
+        nrm = np.empty(lead + (4,), np.float32)
+        mint = np.empty(lead, np.float32)
+        idx = np.empty(lead, np.uint32)
+        if n == 0:
+            return pos, nrm, mint, idx
+        od = (dirs.nbytes + 15) // 16 * 16
+        o0 = od + (origins.nbytes + 15) // 16 * 16
+        with _DeviceScratch(self.device, o0 + n * 40) as d:
+            d.upload(0, dirs)
+            d.upload(od, origins)
+            with self._mutex:
+                _check(lib().sf_trace_rays_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr + od),
+                                              ctypes.c_void_p(d.ptr), ctypes.c_void_p(d.ptr + o0),
+                                              ctypes.c_void_p(d.ptr + o0 + 16 * n), ctypes.c_void_p(d.ptr + o0 + 32 * n),
+                                              ctypes.c_void_p(d.ptr + o0 + 36 * n)), "sf_trace_rays_to", self._ctx)
+                # (the scratch is freed on leaving: the trace that reads and writes it must be done)
+                _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
+            for a, off in ((pos, 0), (nrm, 16 * n), (mint, 32 * n), (idx, 36 * n)):
+                d.download(o0 + off, a)
+        return pos, nrm, mint, idx
+
+    def probe_rays(self, origins, dirs, rays_per_origin=1):
+        """A few rays from caller-supplied origins, host arrays in and out (sf_probe_rays; synchronous): the
+        look-ahead brake (rays.look_ahead), picking from points that are not the camera. origins [M, 3], dirs [N, 3],
+        ray i from origins[i // rays_per_origin]. Returns (min_t [N], hit_index [N], pos4 [N, 4], nrm4 [N, 4])."""
+        d = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
+        o = np.ascontiguousarray(np.asarray(origins, np.float32).reshape(-1, 3))
+        n = d.shape[0]
+        rpo = max(int(rays_per_origin), 1)
+        if o.shape[0] * rpo < n:
+            raise ValueError("too few origins for the rays")
+        mint, idx = np.empty(n, np.float32), np.empty(n, np.uint32)
+        pos, nrm = np.empty((n, 4), np.float32), np.empty((n, 4), np.float32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        with self._mutex:
+            _check(lib().sf_probe_rays(self._ctx, vp(o), vp(d), n, rpo, vp(mint), vp(idx), vp(pos), vp(nrm)),
+                   "sf_probe_rays", self._ctx)
         return mint, idx, pos, nrm
 
     def Synchronize(self):
