@@ -21,7 +21,8 @@ typedef struct {
     int max_depth;
     long long tests, interior, culled, ties, fast_bad, band, hits;
     float margin;     /* relative margin (x |c|) */
-    int mode;         /* 1: lb = tca - rho, 2: lb = tca - sqrt(rho^2 - d2); +4: children front to back */
+    int mode;         /* 1: lb = tca - rho, 2: lb = tca - sqrt(rho^2 - d2); +4: children front to back;
+                         +128: no depth condition in the cull (see sim_set_depth_seed) */
     float axis[3];    /* mode & 8: children ordered along this direction (the tile's centre ray) for every lane */
     float seed;       /* mode & 32: cull bound min(minT, seed) */
     float sinT, cosT; /* the tile's cone (mode & 64: per-depth cone statistics of the unique expansions) */
@@ -51,6 +52,12 @@ static int is_ancestor(uint64_t a, uint64_t n)
 }
 
 static float lod_T(float r) { return g_lod_constant * g_lod_constant * r; } /* t < T (approximately: sim only) */
+
+/* Depth seed of the cull's depth condition (the kernel's DepthSeed): a depth taken as already reached, as when the
+ * context's max-depth word holds it from an earlier frame or tile; -1: none (every traversal starts from its own).
+ * mode & 128 drops the depth condition altogether (the statistic is then no longer exact: what the seed may not do). */
+static int g_depth_seed = -1;
+void sim_set_depth_seed(int seed) { g_depth_seed = seed; }
 
 static void intersect_cull(ctrav_t* tv, const float D[3], const float* node_m, hit_t* h, float r, int depth,
                            uint64_t node)
@@ -148,7 +155,8 @@ static void intersect_cull(ctrav_t* tv, const float D[3], const float* node_m, h
                 float a = rho * rho - d2;
                 lb = tca - sqrtf(a > 0.0f ? a : 0.0f) - M;
             }
-            float Tn = lod_T(1.0f / powf(3.0f, (float)(tv->max_depth + 1)));
+            const int md = tv->max_depth > g_depth_seed ? tv->max_depth : g_depth_seed;
+            float Tn = (tv->mode & 128) ? -FLT_MAX : lod_T(1.0f / powf(3.0f, (float)(md + 1)));
             float mb = h->minT; if ((tv->mode & 32) && tv->seed < mb) mb = tv->seed;
             if (lb > mb && lb >= Tn && lb >= 0.0f) {
                 tv->culled++;

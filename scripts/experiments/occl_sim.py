@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Drive occl_sim.c: plain vs occlusion-culling per-ray traversal on a BASELINE setup (CPU, experiment).
-Usage: occl_sim.py [setup=c3] [row_step=4]"""
+Usage: occl_sim.py [setup=c3] [row_step=4] [cone | seed]
+  seed: the depth-seed table (profiles/depth_seed/model.txt): occl_sim.py c3 8 seed (c1, c2 likewise; c4 with 16)"""
 import ctypes
 import os
 import subprocess
@@ -100,6 +101,33 @@ if len(sys.argv) > 3 and sys.argv[3] == "cone":
             print(f"  [2^{k - 8}, 2^{k - 7}): {wn:9d} children, culled {wc / wn:.3f}")
     sys.exit(0)
 print(f"tiles (every {max(1, step // 2)}th tile row): wave expansions (union over the tile) {t0[0]}, per-lane {t0[1]}")
+if len(sys.argv) > 3 and sys.argv[3] == "seed":
+    # The cull's depth condition (lb >= T(maxd + 1), there only for the max-depth statistic) with maxd seeded by a
+    # depth taken as already reached (the kernel's DepthSeed), against today's per-tile start from 0 and against
+    # no depth condition at all (mode + 128: the bound of what a seed can recover; the statistic is then inexact).
+    import json
+    with open(os.path.join(REPO, "tests", "golden", f"frame_{name}.json")) as f:
+        md = json.load(f)["stats"]["max_depth"]
+    margin = 3 * 2.0 ** -10
+
+    def frac(seed, mode=17):
+        L.sim_set_depth_seed(seed)
+        t = tiles(margin, mode)
+        L.sim_set_depth_seed(-1)
+        return t[0] / t0[0]
+
+    L.sim_set_depth_seed(md)
+    m, i, st = run(margin, 1)
+    L.sim_set_depth_seed(-1)
+    ok = np.array_equal(m.view(np.uint32), ref["minT"].view(np.uint32)) and np.array_equal(i, ref["index"])
+    print(f"  sim_rows, seed {md}: minT and index == oracle: {ok}; max depth max(seed, reached {st[:, 0].max()}) = "
+          f"{max(md, st[:, 0].max())} (oracle rows {ref['stats']['max_depth']}, frame {md})")
+    m, i, st = run(margin, 1 | 128)
+    print(f"  sim_rows, depth condition dropped: max depth reached {st[:, 0].max()} (oracle rows {ref['stats']['max_depth']})")
+    today, full, less, drop = frac(-1), frac(md), frac(md - 1), frac(-1, 17 | 128)
+    print(f"  {name} depth {md}: wave expansions / uncut, mode 17 margin 3*2^-10: today {today:.3f}  seed = frame max "
+          f"{full:.3f} ({100 * (full / today - 1):+.1f} %)  seed = max - 1 {less:.3f}  depth condition dropped {drop:.3f}")
+    sys.exit(0)
 for mode, lg in ((17, 7), (17, 8.415), (17, 9)):
     t = tiles(2.0 ** -lg, mode)
     print(f"  mode {mode} margin 2^-{lg}: wave expansions {t[0] / t0[0]:.3f}  per-lane {t[1] / t0[1]:.3f}  non-ancestor ties {t[2]}")

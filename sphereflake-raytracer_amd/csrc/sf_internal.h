@@ -85,6 +85,9 @@
 #define SF_FLAG_PRIO_FLAT 0x80u
 // disable the occlusion cull of the per-ray traversal (A/B only; results identical)
 #define SF_FLAG_NO_OCCL_CULL 0x100u
+// the occlusion cull's depth bound starts at 0 for every tile (A/B only; results identical): by default it starts from
+// the depth the context's max-depth word already holds and the wave's earlier tiles reached (sf_kernels.hip: DepthSeed)
+#define SF_FLAG_NO_DEPTH_SEED 0x10u
 // children in index order only (A/B; results identical): by default the per-ray traversal enters the children
 // nearer than their parent's centre along the tile's cone axis first
 #define SF_FLAG_NO_FRONT_FIRST 0x200u

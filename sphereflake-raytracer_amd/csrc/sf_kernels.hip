@@ -1073,6 +1073,37 @@ __device__ __forceinline__ void traverse(const DeviceConsts* __restrict__ K, con
 // push, no load at the pop). A node keeps on the VGPR stack its untested children (the cone-culled mask,
 // front children first, as before) instead of its pending ones, and its visiting lanes as one bit per level
 // (`actbits`).
+// The depth seed of the occlusion cull (traverse_ray). The max-depth word stats[0] is a running maximum: it is raised
+// only by depths some traversal really reached, and lowered only by a reset, which the host orders after every launch
+// that updates it and completes before the next one. So a depth M read from the word during a launch -- or reached
+// earlier by this wave in the launch, which publishes it to the same word -- is a lower bound of the word's value
+// after the launch, and an occluded subtree that cannot pass LOD deeper than M cannot change that value.
+struct DepthSeed {
+    int32_t own = -1;    // uniform: the deepest node this wave reached so far under the word (-1: none)
+    int32_t word = -1;   // stats_word(): the word as loaded, not yet made uniform -- depth() waits for the load, and
+                         // trace_tile calls it after the unit's ray generation
+    // The seed (uniform, >= 0), or -1 -- every tile on its own, as without the seed -- with the cull or the seed
+    // switched off. (Depths are below 32, SF_MAX_DEPTH_LIMIT; the mask only keeps a corrupt word inside the depth
+    // table, as a smaller seed: the cull reads depth seed + 1's threshold.)
+    __device__ __forceinline__ int32_t depth(uint32_t flags) const
+    {
+        int32_t seed = -1;
+        if ((flags & (SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_DEPTH_SEED)) == 0u) {
+            const int32_t w = __builtin_amdgcn_readfirstlane(word);
+            const int32_t o = __builtin_amdgcn_readfirstlane(own);
+            const int32_t m = o > w ? o : w;
+            seed = (m > 0 ? m : 0) & 31;
+        }
+        return __builtin_amdgcn_readfirstlane(seed);
+    }
+};
+// The word: a relaxed agent-scope vector load of a uniform address (not a scalar load: the scalar cache is not
+// coherent with the atomics that raise the word). A stale value is only a smaller seed.
+__device__ __forceinline__ int32_t stats_word(const FrameArgs& a)
+{
+    return __hip_atomic_load(&a.stats[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Entry-order mask (bits c and 16 + c, see traverse_ray) of the children c of a node whose child 0 has heap index
 // idxB that belong to subtree part q: (idxB + c) mod 4 == q.
 __device__ __forceinline__ uint32_t split_mask(uint32_t q, uint32_t idxB)
@@ -1089,8 +1120,10 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
                                              HitState& h, int32_t& maxd, uint32_t& status, uint32_t K_flags,
                                              uint64_t* phase_sums = nullptr, uint32_t axl = 36u,
                                              uint64_t* tile_counts = nullptr, uint32_t split_q = 0u,
-                                             uint32_t split_depth = 0u)
+                                             uint32_t split_depth = 0u, int32_t seed = -1)
 {
+    // seed (uniform; -1: none; DepthSeed::depth): a depth already counted in the stats word this traversal's maxd is
+    // published to. The occlusion cull's depth bound starts from it.
     const uint32_t lane = threadIdx.x & 63u;
     const TraverseLds L{ Lbase };
     const bool cone_cull = (K_flags & SF_FLAG_NO_CONE_CULL) == 0u;
@@ -1116,9 +1149,8 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
         const bool hb = valid && tca >= 0.0f && d2 <= dt0.x;
         ex0 = hb && near_root(tca, d2, dt0.x) < dt0.w;
     }
-    if (!wave_ballot(ex0)) return;
+    if (!wave_ballot(ex0)) return;   // (maxd stays the caller's -1, whatever the seed: this traversal reached no depth)
     maxd = 0;
-    float cull_t = depth_consts(K, 1u).w;   // uniform: depth maxd + 1's LOD threshold, reloaded when maxd grows
 
     // ---- the wave's ray cone (as in traverse)
     {
@@ -1137,6 +1169,12 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
         }
         if (lane < 5u) L.cone()[lane] = lane == 0u ? ax : lane == 1u ? ay : lane == 2u ? az : lane == 3u ? cosT : sinT;
     }
+
+    // The cull's depth bound starts from the seed: the word maxd is published to holds at least that already, so the
+    // cull below skips every occluded subtree that cannot pass LOD deeper than max(maxd, seed). maxd itself stays the
+    // depth this traversal reached (started from the seed it would be carried through the loops in a VGPR: +7 % VALU).
+    // uniform: depth max(maxd, seed) + 1's LOD threshold, reloaded when maxd grows beyond the seed
+    float cull_t = depth_consts(K, (uint32_t)(seed > 0 ? seed : 0) + 1u).w;
 
     // this lane's column of the cooperative child build (see traverse)
     const uint32_t bi = build_child(lane);
@@ -1351,10 +1389,14 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
             SF_COUNT(3, 1);
             if ((int32_t)d + 1 > maxd) {   // Sphereflake.h:157-160
                 maxd = (int32_t)d + 1;
-                cull_t = depth_consts_at(K, kofs + (1u << 5)).w;
+                if ((int32_t)d + 1 > seed) cull_t = depth_consts_at(K, kofs + (1u << 5)).w;
             }
             // occlusion cull (see traverse): lanes for which no sphere of the child's subtree can be accepted or
-            // pass LOD deeper than the depth already reached do not enter
+            // pass LOD deeper than the depth already reached do not enter. "Already reached" is max(maxd, seed):
+            // the seed is a depth the stats word already holds (the word is a running maximum, only raised by depths
+            // really reached and only lowered by a reset, which is ordered after every launch), so a subtree that
+            // cannot go deeper than it cannot change the word's final value -- and the pixels never depend on this
+            // condition.
             // The fattened radius rho = R (1 + m) + m |c| (see traverse) without |c|: a lane of exm hit the bounding
             // sphere, so |c|^2 = d2 + tca^2 <= R^2 + tca^2 (+ the float test's slack, 2^-9.6 |c|) and
             // |c| <= tca + R (+ 2^-9.6 |c|, whose m multiple is far inside m's safety factor): rho <= R (1 + 2 m) +
@@ -1557,6 +1599,7 @@ __device__ __forceinline__ void write_pixel(const FrameArgs& a, const Tile& t, f
 
 struct TileStats {
     int32_t maxd;       // uniform: deepest expanded node (-1: none)
+    int32_t seed;       // uniform: the depth seed its cull started from (DepthSeed::depth; -1: none)
     float closest;      // per lane: its minT (FLT_MAX for invalid lanes); reduced in publish_stats
     bool overflowed;    // uniform: the tile needs more LDS levels than provisioned
 };
@@ -1672,10 +1715,11 @@ template <bool FIXUP, bool PIPE = false, class Prefetch = NoPrefetch, bool COMPA
 __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __restrict__ L, const float4 bcol, uint32_t tile,
                                                 uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count,
                                                 uint32_t part = 0u, const Prefetch& pre = Prefetch(), uint32_t fl = ~0u,
-                                                uint32_t slot = 0u)
+                                                uint32_t slot = 0u, const DepthSeed seen = DepthSeed())
 {
     // (fl: the launch's flags, with SF_FLAG_REDO_PASS | SF_FLAG_NO_FRONT_FIRST on a re-trace pass; ~0u: flags)
     // (slot: a subtree part unit's split slot -- its position in the unit order / 4)
+    // (seen: the depth seed of the occlusion cull, see DepthSeed; the seed used is returned beside the tile's maxd)
     const uint32_t flags = fl == ~0u ? a.flags : fl;
     const DeviceConsts* __restrict__ K = a.consts;
     const uint32_t lane = threadIdx.x & 63u;
@@ -1688,6 +1732,7 @@ __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __res
     const uint64_t c_start = (!FIXUP && a.tile_cost) ? __builtin_amdgcn_s_memtime() : 0ull;
     float dx, dy, dz;
     ray_dir(a, (float)t.x, (float)t.y, dx, dy, dz, K->lut);
+    const int32_t seed = seen.depth(flags);
 
     HitState h;
     int32_t maxd = -1;
@@ -1701,11 +1746,11 @@ __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __res
         traverse_ray<PIPE, COMPACT, true>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status,
                                           FIXUP ? (flags | SF_FLAG_NO_FRONT_FIRST) : flags,
                                           FIXUP ? nullptr : a.phase_sums, part_axis_lane(sub ? 0u : part), &tile_counts,
-                                          sub ? part - SF_PART_QUARTER0 : 0u, sub ? a.split_depth : 0xffffffffu);
+                                          sub ? part - SF_PART_QUARTER0 : 0u, sub ? a.split_depth : 0xffffffffu, seed);
     else
         traverse_ray<PIPE, COMPACT>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status,
                                     FIXUP ? (flags | SF_FLAG_NO_FRONT_FIRST) : flags,
-                                    FIXUP ? nullptr : a.phase_sums, part_axis_lane(part), &tile_counts);
+                                    FIXUP ? nullptr : a.phase_sums, part_axis_lane(part), &tile_counts, 0u, 0u, seed);
 #else
     traverse<0, PIPE>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status,
                       FIXUP ? (flags | SF_FLAG_NO_FRONT_FIRST) : flags,
@@ -1849,6 +1894,7 @@ __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __res
     // stats: max depth reached, closest sphere distance (Sphereflake.h:157-160, Sphereflake.cpp:197-200)
     TileStats st;
     st.maxd = maxd;
+    st.seed = seed;
     st.closest = t.valid ? h.minT : FLT_MAX;
     st.overflowed = overflowed;
     return st;
@@ -1914,6 +1960,15 @@ __device__ __forceinline__ void publish_stats_in_loop(const FrameArgs& a, int32_
     if (key < cur_k) wave_atomic_smin(a.stats + 1, key);
 }
 
+// A unit went deeper (maxd) than its seed: raise the word at once, so that the other waves' seeds follow within the
+// frame (the first frame after a reset; afterwards the word already holds the frame's depth and no unit gets here).
+// Read before the atomic, as publish_stats_in_loop does. For wave-uniform loops (no lane-0 region).
+__device__ __forceinline__ void publish_depth_early(const FrameArgs& a, int32_t maxd)
+{
+    maxd = __builtin_amdgcn_readfirstlane(maxd);
+    if (maxd > __builtin_amdgcn_readfirstlane(stats_word(a))) wave_atomic_smax(a.stats + 0, maxd);
+}
+
 }  // namespace
 
 // One wave (one 8x8 tile) per workgroup: LDS is the occupancy limit, so the finest granularity packs best.
@@ -1927,7 +1982,8 @@ __device__ __forceinline__ void trace_wave_body(const FrameArgs& a, uint32_t* ov
     if (tile >= a.tiles_x * a.tile_rows) return;
     float* const L = lds + wv * SF_LDS_WAVE_FLOATS(a.max_depth);
     stage_root(L, a.root);
-    const TileStats st = trace_tile<false>(a, L, build_column(a.consts), tile, a.max_depth, overflow_list, overflow_count);
+    const TileStats st = trace_tile<false>(a, L, build_column(a.consts), tile, a.max_depth, overflow_list, overflow_count,
+                                           0u, NoPrefetch(), ~0u, 0u, DepthSeed{ -1, stats_word(a) });
     publish_stats(a, st.maxd, st.closest, 0u);
 }
 
@@ -2003,6 +2059,9 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
         k = __builtin_amdgcn_readfirstlane(k);
     }
     int32_t maxd = -1;
+#ifdef SF_SEED_READ_ONCE
+    int32_t word_once = -1;
+#endif
     float closest = FLT_MAX;   // per lane
     // The first unit of every wave is static: wave w (in dispatch order) takes unit w, so the head of the
     // heavy-first order starts as the waves arrive instead of behind ~900 simultaneous atomics per queue;
@@ -2031,6 +2090,15 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
         const uint32_t g = first;
         const bool again = (g >> 31) != 0u;
         if (!again && g >= nunits) break;
+        // the cull's depth seed (DepthSeed): the word's load is issued per unit, here, ahead of the unit's ray
+        // generation, and waited for after it (trace_tile)
+#ifndef SF_SEED_READ_ONCE
+        const DepthSeed seen{ maxd, stats_word(at) };
+#else   // (A/B build: only the wave's first unit reads the word)
+        if (g == __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + wv))
+            word_once = __builtin_amdgcn_readfirstlane(stats_word(at));
+        const DepthSeed seen{ maxd, word_once };
+#endif
         uint32_t t = g, part = 0u;
         if (again) {
             t = g & SF_UNIT_TILE_MASK;
@@ -2070,7 +2138,7 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
         const TileStats st = trace_tile<false, PIPE, decltype(ticket), COMPACT, SPLIT>(at, L, bcol, t, at.max_depth, at.overflow_list,
                                                                                at.counters + at.parity, part,
                                                ticket, again ? (at.flags | SF_FLAG_NO_FRONT_FIRST | SF_FLAG_REDO_PASS)
-                                                             : at.flags, g >> 2);
+                                                             : at.flags, g >> 2, seen);
         if ((at.flags & SF_FLAG_DIAG_UNITS) && at.tile_trace && (g >> 31) == 0u) {   // diagnostics only (uniform words)
             // (slot g: the unit's position in the order. A re-trace pass -- its ticket word carries bit 31 -- records
             // nothing: its word is no position, and the slot of the unit it repeats already holds that unit's record)
@@ -2080,6 +2148,23 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
             ut[2] = t | (part << SF_UNIT_PART_SHIFT);
         }
         maxd = st.maxd > maxd ? st.maxd : maxd;
+        if (st.seed >= 0 && st.maxd > st.seed) {
+            // the unit went deeper than the word it read and this wave's earlier units: raise the word at once
+            // (rare -- at most once per depth and wave: the arguments once more from the kernarg segment, so that the
+            // stats pointer is not held in registers across the traversal)
+            FrameArgs ap;
+#if defined(__HIP_DEVICE_COMPILE__)
+            {
+                typedef const __attribute__((address_space(4))) FrameArgs* KernargArgs;
+                KernargArgs pa = (KernargArgs)__builtin_amdgcn_kernarg_segment_ptr();
+                __asm__ volatile("" : "+s"(pa));
+                __builtin_memcpy(&ap, (const FrameArgs*)pa, sizeof(FrameArgs));
+            }
+#else
+            ap = a;
+#endif
+            publish_depth_early(ap, st.maxd);
+        }
         closest = fminf(closest, st.closest);
     }
     // the launch arguments again from the kernarg segment, so that none of them is held in a register
@@ -2281,11 +2366,13 @@ __device__ __forceinline__ void trace_frames_body()
             first = retrace ? (0x80000000u | (part << SF_UNIT_PRIO_SHIFT) | t)
                             : gridDim.x + wave_fetch_add(at.counters + SF_QUEUE_WORD(at.parity, k), 1u) * at.queues + k;
         };
+        // the cull's depth seed is per frame, as the stats words are: frame f's word and this wave's maximum in frame f
+        const DepthSeed seen{ (int32_t)__builtin_amdgcn_readlane(stat_d, f), stats_word(at) };
         const TileStats st = trace_tile<false, false, decltype(ticket)>(at, L, bcol, t, at.max_depth, at.overflow_list,
                                                                       at.counters + at.parity, part, ticket,
                                                                       again ? (at.flags | SF_FLAG_NO_FRONT_FIRST |
                                                                                SF_FLAG_REDO_PASS)
-                                                                            : at.flags);
+                                                                            : at.flags, 0u, seen);
         {   // frame cur's stats: the unit's max depth and closest hit into lane cur of the accumulators
             const int32_t ud = __builtin_amdgcn_readfirstlane(st.maxd);
             const int32_t uk = __builtin_amdgcn_readfirstlane(sf_float_key(wave_min(st.closest)));
@@ -2293,6 +2380,11 @@ __device__ __forceinline__ void trace_frames_body()
             const int32_t ok = (int32_t)__builtin_amdgcn_readlane(stat_k, cur);
             stat_d = writelane_s((uint32_t)(ud > od ? ud : od), cur, stat_d);
             stat_k = writelane_s((uint32_t)(uk < ok ? uk : ok), cur, stat_k);
+            if (st.seed >= 0 && ud > st.seed) {   // (rare: the frame's word follows at once, see publish_depth_early)
+                FrameArgs ap;
+                load_frame(ap, cur);
+                publish_depth_early(ap, ud);
+            }
         }
     }
     {   // every frame's stats once (read before the atomics: thousands of waves end together, publish_stats)
@@ -2905,8 +2997,10 @@ extern "C" __global__ __launch_bounds__(64) void sf_fixup_wave(FrameArgs a, cons
     uint32_t unresolved = 0u;
     stage_root(lds, a.root);
     const float4 bcol = build_column(a.consts);
+    // (the cull's depth seed, DepthSeed: the word and this wave's own tiles)
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-        const TileStats st = trace_tile<true>(a, lds, bcol, overflow_list[i], SF_MAX_LEVELS, nullptr, nullptr);
+        const TileStats st = trace_tile<true>(a, lds, bcol, overflow_list[i], SF_MAX_LEVELS, nullptr, nullptr, 0u,
+                                              NoPrefetch(), ~0u, 0u, DepthSeed{ maxd, stats_word(a) });
         maxd = st.maxd > maxd ? st.maxd : maxd;
         closest = fminf(closest, st.closest);
         unresolved += st.overflowed ? 1u : 0u;
