@@ -186,8 +186,9 @@ int sf_probe_dirs(sf_ctx* ctx, const float* dirs3, uint32_t n, float* min_t, uin
    THE REFERENCE'S QUIRK, reproduced: RaySphereIntersection rejects a sphere whose centre is behind the ray
    (tca >= 0, SIMD_AVX.h:247-258), also when the origin is inside it, and the root's bounding ball is tested first.
    A ray that starts on the flake and heads away from the flake's centre therefore sees NOTHING, whatever lies along
-   it (shadow feelers towards a light outside the flake all miss); rays heading inwards behave as expected. This is
-   no occlusion query. */
+   it (shadow feelers that START ON THE FLAKE and head for a light outside it all miss); rays heading inwards behave
+   as expected. This entry point is no occlusion query for rays that start on the flake. Shadows from a point light
+   are traced the other way round, from the light, where the quirk cannot bite: sf_trace_shadow_to below. */
 typedef struct sf_rays_params {
     uint32_t width, height;     /* rays = width * height, row-major; height == 1: a plain list (as sf_dirs_params) */
     uint32_t dir_stride;        /* floats per direction: 3 or 4 */
@@ -208,6 +209,72 @@ int sf_trace_rays_to(sf_ctx* ctx, const sf_rays_params* params, const float* ori
    ceil(n / rays_per_origin) x 3 origins) and out, synchronous. Outputs may be NULL (not all four). */
 int sf_probe_rays(sf_ctx* ctx, const float* origins3, const float* dirs3, uint32_t n, uint32_t rays_per_origin,
                   float* min_t, uint32_t* hit_index, float* pos4, float* nrm4);
+
+/* --- shadows from a point light -------------------------------------------- */
+/* Is the surface point of pixel p lit by a point light at l? No ray has to start on the flake for that (see THE
+   REFERENCE'S QUIRK above): the ray is traced FROM THE LIGHT towards the surface point and its nearest hit compared
+   with the distance to the point. Every such ray starts at l; with l outside the flake's bounding ball (radius 2
+   about the flake's centre, which encloses every sphere and every nested bounding ball) no sphere the ray can meet
+   has its centre behind the ray, so the reference's own arithmetic gives the geometrically right answer. The rays
+   share one origin: the coherent one-origin traversal of sf_trace_rays_to, in an any-hit mode that stops a ray at
+   its first occluder, fused with the read of the position image; one byte per pixel comes out.
+   DEFINITION (exact). Inputs: a position image pos4 (width x height float4, view space, as sf_render writes it), the
+   origin o it is relative to, the light l (world), a relative bias b in [0, 1). All arithmetic is binary32, round to
+   nearest, every operation rounded on its own (no fused multiply-add). For pixel p with P = pos4[p].xyz:
+     1. P == (0, 0, 0) is a miss of the frame (the test of Shaders/post_final.glsl:20): vis[p] = 255, no ray.
+     2. w = o + P per component; d = (w - l) + 0.0f per component (the + 0.0f removes -0).
+     3. len = sqrt((d.x d.x + d.y d.y) + d.z d.z); bound = len (1.0f - b).
+     4. The ray is the reference's ray for Normalize(d) (SIMD_AVX.h:170-180) under the root transform whose columns
+        0..2 are the context's and whose column 3 is 0 - l: sf_trace_rays_to's ray from the single origin l, with the
+        context's child frames and variant.
+     5. With m the min_t of that ray (what sf_trace_rays_to returns): vis[p] = (m < bound) ? 0 : 255.
+     6. A d that does not normalise to finite numbers, or a light that is not finite, misses the root: vis[p] = 255.
+   sphereflake_amd/lights.py (shadow_model) states steps 1-3 on the host.
+   CONSEQUENCES, not engineered away:
+   - THE LEVEL OF DETAIL IS THE LIGHT'S. A node refines while sqrt(t / r) < 70 with t measured FROM THE LIGHT
+     (Sphereflake.h:146), not from the camera: a distant light -- a "directional" one placed far off -- casts coarse
+     shadows, and spheres the camera sees may cast none.
+   - A LIGHT INSIDE THE RADIUS-2 BALL gets the reference's answer, quirk included: spheres whose centre is behind a
+     ray, as seen from the light, do not occlude.
+   - Self-shadow acne is governed by the bias b: the camera's and the light's traversals stop at different levels of
+     detail and round differently, so the sphere a pixel lies on is met at a distance near len, on either side. */
+typedef struct sf_shadow_params {
+    float light[3];           /* l, world space */
+    float bias;               /* b, 0 <= b < 1 (sf_shadow_defaults: 2^-10) */
+    float origin[3];          /* o, with use_origin != 0 */
+    uint32_t use_origin;      /* 0: o is the context's view origin (sf_set_view) */
+    uint32_t width, height;   /* size of the position image; 0, 0: the context's frame size */
+    uint32_t max_depth;       /* levels to provision; 0 = auto: the geometric bound of the LIGHT's position (as
+                                 sf_dirs_params.max_depth for the view's); flagged tiles are re-traced at
+                                 SF_MAX_DEPTH_LIMIT */
+    void* stream;             /* NULL = the context stream */
+} sf_shadow_params;
+
+/* light (0, 0, 0), the default bias, the context's origin and frame size, auto levels, the context stream. */
+int sf_shadow_defaults(const sf_ctx* ctx, sf_shadow_params* params);
+/* pos4: DEVICE position image (NULL = the context's G-buffer; the sizes must then be 0 or the context's); vis: DEVICE
+   output, width * height bytes, row-major as pos4. Asynchronous on the stream, ordered with the context's other
+   calls as sf_trace_dirs_to is. Touches none of the context's statistics (max depth, closest, rays) and none of the
+   renders' state; re-traced tiles count in overflow_tiles as sf_trace_dirs_to's groups do. SF_ENOVIEW before a view
+   is set; SF_EINVAL for a null vis, a bias outside [0, 1) or NaN, max_depth > SF_MAX_DEPTH_LIMIT, sizes that disagree
+   with a NULL pos4, one size zero and the other not, or more than 2^31 - 1 pixels. */
+int sf_trace_shadow_to(sf_ctx* ctx, const sf_shadow_params* params, const float* pos4, uint8_t* vis);
+/* The context's G-buffer into the context's own visibility buffer (W * H bytes, allocated on first use). */
+int sf_trace_shadow(sf_ctx* ctx, const sf_shadow_params* params);
+/* Synchronous D2H of that buffer (W * H bytes); SF_ESTATE before any sf_trace_shadow. */
+int sf_download_shadow(sf_ctx* ctx, uint8_t* vis);
+/* Its device pointer (NULL before any sf_trace_shadow); see sf_device_buffers. */
+int sf_shadow_buffer(sf_ctx* ctx, uint8_t** vis);
+/* Light the RGBA8 image of sf_post_process in place, after it. Per pixel, with P, w and len as above (the same exact
+   arithmetic; the division is correctly rounded) and n = nrm4[p].xyz: a frame miss (P == 0) is left untouched; else
+   e = l - w per component, lam = max(0, ((n.x e.x + n.y e.y) + n.z e.z) / len) (0 where that is NaN),
+   k = ambient + (1 - ambient) (vis[p] ? lam : 0), and each of r, g, b becomes (uint8) min(c k + 0.5f, 255); alpha
+   stays. params: light, origin / use_origin, stream (the image has the context's frame size). NULL pos4 / nrm4 / vis
+   / rgba select the context's G-buffer, visibility buffer and image; SF_ESTATE where a context buffer selected that
+   way was never written (no sf_post_process, no sf_trace_shadow); SF_EINVAL for an ambient outside [0, 1] or NaN.
+   Asynchronous on the stream. sphereflake_amd/lights.py: light_model. */
+int sf_light_image(sf_ctx* ctx, const sf_shadow_params* params, float ambient, const float* pos4, const float* nrm4,
+                   const uint8_t* vis, uint8_t* rgba);
 
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the

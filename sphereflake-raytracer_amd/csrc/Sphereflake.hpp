@@ -171,6 +171,30 @@ public:
                             positions ? &positions[0].x : nullptr, normals ? &normals[0].x : nullptr));
     }
 
+    // Shadows from a point light (new; sf_trace_shadow_to / sf_trace_shadow, sf.h): every pixel's ray is traced FROM
+    // THE LIGHT towards its surface point, so the quirk above cannot bite while the light is outside the flake's
+    // bounding ball; the level of detail is the light's. visibility: one byte per pixel, 255 lit or frame miss, 0
+    // shadowed. DEVICE pointers, asynchronous; positions4 null = this object's own frame.
+    void TraceShadow(const sf_shadow_params& params, const float* positions4, uint8_t* visibility)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_shadow_to(m_Ctx, &params, positions4, visibility));
+    }
+    // ... of this object's own device frame into its own visibility buffer (sf_download_shadow, LightImage)
+    void TraceShadow(const sf_shadow_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_shadow(m_Ctx, &params));
+    }
+    // Lambert term and shadow of that light on the image of an SSAO::Render(), in place (sf_light_image); null pointers
+    // select this object's own frame, visibility buffer and image.
+    void LightImage(const sf_shadow_params& params, float ambient = 0.25f, const float* positions4 = nullptr,
+                    const float* normals4 = nullptr, const uint8_t* visibility = nullptr, uint8_t* rgba = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_image(m_Ctx, &params, ambient, positions4, normals4, visibility, rgba));
+    }
+
     // the device frame, downloaded into the vectors when it is newer than their contents (Refresh)
     const GBuffer& GetGBuffer() const
     {

@@ -58,6 +58,12 @@ extern "C" __global__ void sf_trace_rays_one(FrameArgs a, const float* origins, 
 extern "C" __global__ void sf_trace_rays_fixup(FrameArgs a, const float* origins, const float* dirs, uint32_t ostride,
                                                uint32_t dstride, uint32_t rpo, const uint32_t* overflow_list,
                                                uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_trace_shadow_wave(FrameArgs a, const float* pos4, ShadowArgs sa, uint8_t* vis,
+                                                uint32_t groups, uint32_t* overflow_list, uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_shadow_fixup(FrameArgs a, const float* pos4, ShadowArgs sa, uint8_t* vis,
+                                                 const uint32_t* overflow_list, uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_light_image_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
+                                          const uint8_t* vis, ShadowArgs sa, float ambient, uint8_t* rgba);
 extern "C" __global__ void sf_band_unpack(FrameArgs a, const float4* stage, uint32_t stage_rows, uint32_t band_rows,
                                            uint32_t n, uint32_t first, uint32_t members, uint32_t row0);
 extern "C" __global__ void sf_node_table(FrameArgs a, float4* table, uint32_t nodes);
@@ -108,6 +114,9 @@ namespace {
 
 constexpr uint32_t kRaysFixupBlocks = 1024;   // grid of sf_trace_rays_fixup (grid-stride over the re-trace list)
 constexpr uint32_t kDefaultLevels = 12;   // depths 0..11 expand; every BASELINE camera stays <= 10
+// sf_shadow_defaults' relative bias: the smallest power of two at which no pixel that faces the light by more than
+// 30 degrees is shadowed by its own sphere (scripts/experiments/shadow_bias.py)
+constexpr float kShadowBias = 0x1p-10f;
 // parallel mt19937 draws (sf_mtjump.cpp, sf_kernels.hip): from this many draws per call, in K <= kMtSegMax
 // segments of >= kMtSegMin draws, each jumped to by a convolution split over SF_MT_PARTS workgroups
 constexpr uint32_t kMtParMin = 32768, kMtSegMin = 8192, kMtSegMax = 32;
@@ -344,6 +353,7 @@ struct sf_ctx {
     uint8_t* blur_h = nullptr;         // W x H
     uint8_t* blur_v = nullptr;
     uint8_t* image = nullptr;          // W x H RGBA8
+    uint8_t* shadow = nullptr;         // W x H visibility bytes (sf_trace_shadow): lazily allocated
     int centre_exact = -1;             // sfhost::post_centre_exact(W) && (H), cached
 };
 
@@ -456,6 +466,7 @@ static void free_ctx(sf_ctx* c)
     (void)hipFree(c->blur_h);
     (void)hipFree(c->blur_v);
     (void)hipFree(c->image);
+    (void)hipFree(c->shadow);
     for (int i = 0; i < sf_ctx::kTimed; ++i)
         for (int j = 0; j < 2; ++j)
             if (c->ev[i][j]) (void)hipEventDestroy(c->ev[i][j]);
@@ -783,10 +794,11 @@ static int order_rebuild(sf_ctx* c, hipStream_t s, uint32_t ntiles, uint32_t wav
 // d + 1 levels suffice; a bound that is off only costs a re-trace of the affected tiles (sf_fixup_wave), never results.
 // (geometric_levels: the bound alone -- it speaks of the origin and the root ball only, so it holds for rays of any
 // direction, sf_trace_dirs_to; frame_levels: narrowed by the deepest depth a finished render of the frame saw)
-static uint32_t geometric_levels(const sf_ctx* c, bool* bounded_out)
+// (centre: the root centre relative to the rays' origin -- the view's root translation, or 0 - light for sf_trace_shadow_to)
+static uint32_t geometric_levels(const sf_ctx* c, const float centre[3], bool* bounded_out)
 {
     uint32_t levels = kDefaultLevels;
-    const float rc = std::sqrt(c->root[12] * c->root[12] + c->root[13] * c->root[13] + c->root[14] * c->root[14]);
+    const float rc = std::sqrt(centre[0] * centre[0] + centre[1] * centre[1] + centre[2] * centre[2]);
     const float gap = (rc - 2.0f) * (1.0f - 1e-3f);
     bool bounded = false;
     if (gap > 0.0f) {
@@ -797,6 +809,10 @@ static uint32_t geometric_levels(const sf_ctx* c, bool* bounded_out)
     }
     *bounded_out = bounded;
     return levels;
+}
+static uint32_t geometric_levels(const sf_ctx* c, bool* bounded_out)
+{
+    return geometric_levels(c, c->root + 12, bounded_out);
 }
 
 static uint32_t frame_levels(const sf_ctx* c, bool* bounded_out)
@@ -1270,6 +1286,136 @@ int sf_probe_rays(sf_ctx* c, const float* origins3, const float* dirs3, uint32_t
     if (nrm4) SF_HIP(c, hipMemcpy(nrm4, d_nrm, (size_t)n * 16, hipMemcpyDeviceToHost));
     if (min_t) SF_HIP(c, hipMemcpy(min_t, d_min, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (hidx) SF_HIP(c, hipMemcpy(hidx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return SF_OK;
+}
+
+// Shadows from a point light (sf.h; kernels sf_trace_shadow_wave / sf_trace_shadow_fixup). Launched
+// as sf_trace_dirs_to launches, one wave per 8x8 tile of the position image, with the root transform of the LIGHT (the
+// context's columns, translation 0 - light) and the levels of the light's geometric bound; shares the direction traces'
+// re-trace list and counters. Touches no statistic (not the stats words, not the ray count) and none of the renders'
+// state.
+int sf_shadow_defaults(const sf_ctx* c, sf_shadow_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->bias = kShadowBias;
+    return SF_OK;
+}
+
+// the launch's ShadowArgs from the parameters (the origin the position image is relative to, the light)
+static ShadowArgs shadow_args(const sf_ctx* c, const sf_shadow_params* p)
+{
+    ShadowArgs sa;
+    for (int k = 0; k < 3; ++k) {
+        sa.o[k] = p->use_origin ? p->origin[k] : c->o[k];
+        sa.l[k] = p->light[k];
+    }
+    sa.keep = 1.0f - p->bias;
+    return sa;
+}
+
+int sf_trace_shadow_to(sf_ctx* c, const sf_shadow_params* p, const float* pos4, uint8_t* vis)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!vis) return SF_EINVAL;
+    if (!(p->bias >= 0.0f && p->bias < 1.0f)) return SF_EINVAL;   // (NaN fails both)
+    if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
+    if ((p->width == 0u) != (p->height == 0u)) return SF_EINVAL;
+    const uint32_t W = p->width ? p->width : c->W, H = p->height ? p->height : c->H;
+    if (!pos4 && (W != c->W || H != c->H)) return SF_EINVAL;
+    if ((uint64_t)W * H > 0x7fffffffull) return SF_EINVAL;   // (pixel indices are 32-bit in the kernel)
+    if (!pos4) pos4 = c->pos;
+    const uint32_t tiles_x = (W + 7u) / 8u;
+    const uint32_t groups = tiles_x * ((H + 7u) / 8u);
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    if (!c->dirs_cnt) {
+        SF_HIP(c, hipMalloc(&c->dirs_cnt, 3 * 4));
+        SF_HIP(c, hipMemsetAsync(c->dirs_cnt, 0, 3 * 4, s));
+    }
+    if (groups > c->dirs_cap) {   // grown on demand; an earlier trace may still write the old list
+        SF_HIP(c, hipStreamSynchronize(s));
+        (void)hipFree(c->dirs_ovf);
+        c->dirs_ovf = nullptr;
+        c->dirs_cap = 0;
+        SF_HIP(c, hipMalloc(&c->dirs_ovf, (size_t)groups * 4));
+        c->dirs_cap = groups;
+    }
+    const ShadowArgs sa = shadow_args(c, p);
+    FrameArgs a = frame_args(c);
+    a.W = W;
+    a.H = H;
+    a.tiles_x = tiles_x;
+    const float centre[3] = { 0.0f - sa.l[0], 0.0f - sa.l[1], 0.0f - sa.l[2] };   // (Sphereflake.cpp:83 at the light)
+    for (int k = 0; k < 3; ++k) a.root[9 + k] = centre[k];
+    bool bounded = false;
+    a.max_depth = p->max_depth ? p->max_depth : geometric_levels(c, centre, &bounded);
+    if (a.max_depth < 4u) a.max_depth = 4u;
+    if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
+    a.stats = nullptr;   // (no statistic is touched)
+    const size_t lds = (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4;
+    hipLaunchKernelGGL(sf_trace_shadow_wave, dim3(groups), dim3(64), lds, s, a, pos4, sa, vis, groups, c->dirs_ovf,
+                       c->dirs_cnt + c->dirs_par);
+    SF_HIP(c, hipGetLastError());
+    const size_t lds_fix = (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4;
+    const uint32_t fb = groups < SF_PROG_FIXUP_BLOCKS ? groups : SF_PROG_FIXUP_BLOCKS;
+    hipLaunchKernelGGL(sf_trace_shadow_fixup, dim3(fb), dim3(64), lds_fix, s, a, pos4, sa, vis,
+                       (const uint32_t*)c->dirs_ovf, c->dirs_cnt, c->dirs_par);
+    SF_HIP(c, hipGetLastError());
+    c->dirs_par ^= 1u;
+    return SF_OK;
+}
+
+int sf_trace_shadow(sf_ctx* c, const sf_shadow_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if ((p->width || p->height) && (p->width != c->W || p->height != c->H)) return SF_EINVAL;
+    if (!c->shadow) {
+        DevGuard g(c->device);
+        SF_HIP(c, hipMalloc(&c->shadow, (size_t)c->W * c->H));
+    }
+    return sf_trace_shadow_to(c, p, nullptr, c->shadow);
+}
+
+int sf_download_shadow(sf_ctx* c, uint8_t* vis)
+{
+    if (!c || !vis) return SF_EINVAL;
+    if (!c->shadow) return SF_ESTATE;
+    int rc = sf_synchronize(c);
+    if (rc != SF_OK) return rc;
+    DevGuard g(c->device);
+    SF_HIP(c, hipMemcpy(vis, c->shadow, (size_t)c->W * c->H, hipMemcpyDeviceToHost));
+    return SF_OK;
+}
+
+int sf_shadow_buffer(sf_ctx* c, uint8_t** vis)
+{
+    if (!c || !vis) return SF_EINVAL;
+    *vis = c->shadow;
+    return SF_OK;
+}
+
+int sf_light_image(sf_ctx* c, const sf_shadow_params* p, float ambient, const float* pos4, const float* nrm4,
+                   const uint8_t* vis, uint8_t* rgba)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view && !p->use_origin) return SF_ENOVIEW;
+    if (!(ambient >= 0.0f && ambient <= 1.0f)) return SF_EINVAL;
+    if (!rgba && !c->image) return SF_ESTATE;
+    if (!vis && !c->shadow) return SF_ESTATE;
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
+    hipLaunchKernelGGL(sf_light_image_px, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
+                       nrm4 ? nrm4 : (const float*)c->nrm, vis ? vis : (const uint8_t*)c->shadow, shadow_args(c, p),
+                       ambient, rgba ? rgba : c->image);
+    SF_HIP(c, hipGetLastError());
     return SF_OK;
 }
 

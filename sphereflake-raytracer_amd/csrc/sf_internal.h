@@ -191,6 +191,13 @@ struct FrameArgs {
 };
 #define SF_CLOCK_WAVES 8u             // live shader clock samples per timed render (one per XCD group)
 
+// Point-light shadows (sf_trace_shadow_to, sf_light_image): what the kernels take beside the FrameArgs or images
+struct ShadowArgs {
+    float o[3];                       // the origin the position image is relative to
+    float l[3];                       // the light (world)
+    float keep;                       // 1 - bias (sf_trace_shadow; unused by sf_light_image)
+};
+
 // Multi-frame persistent trace (round 6, sf_render_frames): the frames of one launch, passed by value in the kernel
 // argument segment (copied by the runtime at the launch, so the host may build the next batch at once; 4 KB at most:
 // 11 FrameArgs). Frame f is one slot context's view into that context's G-buffer and stats. All frames share one

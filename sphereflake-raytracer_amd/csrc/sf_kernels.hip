@@ -1114,13 +1114,20 @@ __device__ __forceinline__ uint32_t split_mask(uint32_t q, uint32_t idxB)
 
 // SPLIT: a subtree part unit (SF_FLAG_SUBTREE): of the nodes at depth split_depth, only those whose heap index is
 // split_q mod 4 are entered (their own sphere and their subtree); everything above is traced as for the whole tile.
-template <bool PIPE = false, bool COMPACT = false, bool SPLIT = false>
+// SHADOW: the any-hit mode of sf_trace_shadow. Only the predicate "some visited sphere has
+// ts < bound" is wanted per lane, so h.minT starts at the lane's `bound`, a lane whose self test accepts is finished
+// and leaves the active set for good (actv, every bit of actbits), a tie is not an acceptance and never flags (it is
+// not `<`), the occlusion cull keeps only its distance condition (no max-depth statistic to protect: maxd is not
+// maintained past 0), and the traversal ends when no lane is live. On return h.depth >= 0 (h.hit) marks the finished
+// lanes; the other fields of h are not maintained. The visits are a subset of the closest-hit traversal's and every
+// sphere left out cannot be accepted below `bound`, so h.hit is exactly (the closest hit's min_t < bound).
+template <bool PIPE = false, bool COMPACT = false, bool SPLIT = false, bool SHADOW = false>
 __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K, const float* root, float* __restrict__ Lbase,
                                              const float4 bcol, uint32_t levels, float dx, float dy, float dz, bool valid,
                                              HitState& h, int32_t& maxd, uint32_t& status, uint32_t K_flags,
                                              uint64_t* phase_sums = nullptr, uint32_t axl = 36u,
                                              uint64_t* tile_counts = nullptr, uint32_t split_q = 0u,
-                                             uint32_t split_depth = 0u, int32_t seed = -1)
+                                             uint32_t split_depth = 0u, int32_t seed = -1, float bound = FLT_MAX)
 {
     // seed (uniform; -1: none; DepthSeed::depth): a depth already counted in the stats word this traversal's maxd is
     // published to. The occlusion cull's depth bound starts from it.
@@ -1131,7 +1138,8 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
     const bool front_first = (K_flags & (SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST)) == 0u;
     SF_STAMP_DECL;
 
-    h.minT = FLT_MAX;
+    if constexpr (SHADOW) h.minT = bound;
+    else h.minT = FLT_MAX;
     h.cx = h.cy = h.cz = 0.f;
     h.index = 0xffffffffu;
     h.depth = -1;
@@ -1192,7 +1200,9 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
     // ---- the own sphere of a node entered for the lanes of actv (+inf on them, -1 elsewhere), with its tca and
     // d2 already formed by its child test (the same operations: Sphereflake.h:174-224, SIMD_AVX.h:236-270).
     // Pre-order with the ancestor tie rule (see traverse's self_test).
-    auto self_test = [&](const float4 pc, float tca, float d2, uint32_t dd, float actv, uint32_t idx, float R2s) {
+    // (returns the accepting lanes: the shadow mode's finished lanes)
+    auto self_test = [&](const float4 pc, float tca, float d2, uint32_t dd, float actv, uint32_t idx,
+                         float R2s) -> uint64_t {
         const uint64_t hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);
         if (hsm) {
             const float xs = R2s - d2;
@@ -1202,6 +1212,12 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
             // strictly nearer lanes accept; exact ties (rare) take a branch of their own: a tie is accepted where
             // the best is an ancestor, and one with a non-ancestor flags the tile (front-first order, see traverse)
             uint64_t accm = hsm & wave_ballot(ts < h.minT);
+            if constexpr (SHADOW) {   // (the finished flag only)
+                uint32_t hd = (uint32_t)h.depth;
+                sel_in_place(hd, dd, accm);
+                h.depth = (int32_t)hd;
+                return accm;
+            }
             const uint64_t tie = hsm & wave_ballot(ts == h.minT);
             if (tie != 0ull) {
                 accm |= tie & ancm;
@@ -1216,7 +1232,9 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
             sel_in_place(hd, dd, accm);
             h.depth = (int32_t)hd;
             ancm |= accm;
+            return accm;
         }
+        return 0ull;
     };
 
     // ---- LOD of one child whose bounding sphere the lanes of hbm hit (xs = R2b - d2, depth constants R2b, T, Tfar):
@@ -1335,8 +1353,14 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
         actbits = ex0 ? 1u : 0u;
         const float tca = (pc.x * dx + pc.y * dy) + pc.z * dz;
         const float d2 = pc.w - tca * tca;
-        self_test(pc, tca, d2, 0u, actv, 0u, depth_consts(K, 0u).y);
-        if (!__builtin_amdgcn_readfirstlane((int)(pc.w > depth_leaf(K, 0u))))
+        const uint64_t acc0 = self_test(pc, tca, d2, 0u, actv, 0u, depth_consts(K, 0u).y);
+        bool live = true;   // (uniform)
+        if constexpr (SHADOW) {   // the lanes the root's sphere finished leave; with none left nothing is expanded
+            actv = sel_mask(actv, -1.0f, acc0);
+            sel_in_place(actbits, 0u, acc0);
+            live = wave_ballot(actbits != 0u) != 0ull;
+        }
+        if (live && !__builtin_amdgcn_readfirstlane((int)(pc.w > depth_leaf(K, 0u))))
             C = expand(pc, L.root() + 4u, 4u, 0u, actv, tcur, kofs, readlane_f(tca, axl));
         else SF_COUNT(4, 1);
         if constexpr (SPLIT) {
@@ -1387,7 +1411,7 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
             if (exm == 0ull) continue;
             // ---- child c passed bounding + LOD for the lanes of exm: enter it
             SF_COUNT(3, 1);
-            if ((int32_t)d + 1 > maxd) {   // Sphereflake.h:157-160
+            if (!SHADOW && (int32_t)d + 1 > maxd) {   // Sphereflake.h:157-160
                 maxd = (int32_t)d + 1;
                 if ((int32_t)d + 1 > seed) cull_t = depth_consts_at(K, kofs + (1u << 5)).w;
             }
@@ -1403,16 +1427,28 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
             // m tca = cull_r + m tca per lane, no square root.
             uint64_t amx = exm;
             if (occl_cull) {
-                const float v = __builtin_fminf(tca - h.minT, tca - cull_t);
+                // (shadow mode: the distance condition alone -- no sphere of the subtree nearer than the lane's bound)
+                float v = tca - h.minT;
+                if constexpr (!SHADOW) v = __builtin_fminf(v, tca - cull_t);
                 const uint64_t cm = wave_ballot(v - SF_OCCL_MARGIN * tca > cull_r);
                 amx = exm & ~cm;
                 SF_COUNT(13, 1);
                 SF_COUNT(12, amx == 0ull ? 1 : 0);
                 if (amx == 0ull) continue;
             }
-            const float avx = sel_mask(-1.0f, __builtin_inff(), amx);
-            self_test(pc, tca, d2, d + 1u, avx, idxB + c, dc.y);
+            float avx = sel_mask(-1.0f, __builtin_inff(), amx);
+            const uint64_t acc = self_test(pc, tca, d2, d + 1u, avx, idxB + c, dc.y);
             SF_STAMP(4);
+            if constexpr (SHADOW) {
+                if (acc != 0ull) {   // finished lanes leave the child, the open node and every ancestor
+                    amx &= ~acc;
+                    avx = sel_mask(avx, -1.0f, acc);
+                    actv = sel_mask(actv, -1.0f, acc);
+                    sel_in_place(actbits, 0u, acc);
+                    if (wave_ballot(actbits != 0u) == 0ull) break;   // no lane is live
+                    if (amx == 0ull) continue;
+                }
+            }
             // an inline leaf -- its own sphere only (sfhost::leaf_threshold): |c|^2 beyond depth d + 1's leaf
             // threshold; the centre's w is broadcast, so one compare is the branch (round 5: no per-level leaf mask
             // formed at the expansion and carried through the stack)
@@ -3560,6 +3596,124 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_rays_fixup(FrameArgs a
         unresolved += st.overflowed ? 1u : 0u;
     }
     publish_stats(a, maxd, closest, unresolved);
+}
+
+// ------------------------------------------------------------------------------------------
+// Shadows from a point light (sf_trace_shadow_to). Pixel p of a view-space position image (float4,
+// as the renders write it; origin o) is a frame miss where P == (0, 0, 0) (Shaders/post_final.glsl:20): vis = 255, no
+// ray. Else w = o + P, d = (w - l) + 0, len = sqrt((d.x d.x + d.y d.y) + d.z d.z), bound = len (1 - bias), every
+// operation rounded on its own; the ray is the reference's ray for Normalize(d) under the root transform whose
+// translation is 0 - l (sf_trace_rays_to's ray from the one origin l), and vis = (its min_t < bound) ? 0 : 255. All
+// rays start at the light, so every group takes the one-origin traversal (traverse_ray) on the light's root image,
+// in its shadow mode: any hit below the bound finishes a lane. One wave64 per 8x8 tile of the image (a.W x a.H,
+// a.tiles_x tiles per row), the grouping of sf_trace_dirs_wave; a.root[9..11] is 0 - l.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+template <bool FIXUP>
+__device__ __forceinline__ bool trace_shadow_group(const FrameArgs& a, const float4* __restrict__ pos4,
+                                                   const ShadowArgs& sa, uint8_t* __restrict__ vis,
+                                                   float* __restrict__ L, const float4 bcol, uint32_t group,
+                                                   uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const uint32_t lane = threadIdx.x & 63u;
+    // the lane's pixel; a lane off the image edge loads the nearest pixel inside and traverses as an invalid lane
+    const uint32_t ty = group / a.tiles_x, tx = group - ty * a.tiles_x;
+    const uint32_t x = tx * SF_TILE + (lane & 7u), y = ty * SF_TILE + (lane >> 3);
+    const bool valid = x < a.W && y < a.H;
+    const uint32_t pix = (y < a.H ? y : a.H - 1u) * a.W + (x < a.W ? x : a.W - 1u);   // (< 2^31 pixels)
+    const float4 P = pos4[pix];
+    const bool surface = !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    float dx = __fadd_rn(__fsub_rn(__fadd_rn(sa.o[0], P.x), sa.l[0]), 0.0f);
+    float dy = __fadd_rn(__fsub_rn(__fadd_rn(sa.o[1], P.y), sa.l[1]), 0.0f);
+    float dz = __fadd_rn(__fsub_rn(__fadd_rn(sa.o[2], P.z), sa.l[2]), 0.0f);
+    // (__builtin_sqrtf is the correctly rounded square root under the build's -fhip-fp32-correctly-rounded-divide-sqrt,
+    // as in near_root; __fsqrt_rn compiles to the bare v_sqrt_f32 here, 1 ulp off for some arguments)
+    const float len = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float bound = __fmul_rn(len, sa.keep);
+    normalize3(dx, dy, dz, K->lut);
+    // a d that does not normalise to finite numbers misses (see trace_dir_group); a light that is not finite makes d
+    // so for every pixel, and the root is not entered either (trace_ray_group)
+    auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
+    const bool on = valid && surface && finite(dx) && finite(dy) && finite(dz);
+    const uint64_t onm = wave_ballot(on);
+    HitState h;
+    h.hit = false;
+    uint32_t status = 0u;
+    if (onm != 0ull) {   // (uniform; else no ray of the group is traced)
+        // the cone axis lane as in trace_ray_group: the tile's centre pixel if it is traced, else the first live lane
+        const uint32_t axl = __builtin_amdgcn_readfirstlane(((onm >> 36u) & 1ull) ? 36u : (uint32_t)__builtin_ctzll(onm));
+        const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
+        const uint32_t culls = a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST);
+        int32_t md = -1;
+#ifdef SF_SHADOW_CLOSEST
+        // measurement builds only: the closest-hit traversal and the comparison afterwards (no early exit, no bound
+        // seed) -- what the any-hit mode is measured against
+        traverse_ray<>(K, a.root, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az, on, h, md, status,
+                       culls | (FIXUP ? SF_FLAG_NO_FRONT_FIRST : 0u), nullptr, axl);
+        h.hit = on && h.minT < bound;
+#else
+        // (a tie never flags in the shadow mode, so the re-trace keeps the front-first order)
+        traverse_ray<false, false, false, true>(K, a.root, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az,
+                                                on, h, md, status, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
+#endif
+    }
+    const bool flagged = status != 0u;   // (uniform) more levels needed
+    if (!FIXUP && flagged) {
+        const uint32_t slot = wave_fetch_add(overflow_count, 1u);
+        overflow_list[slot] = group;   // uniform value and address
+    }
+    // ---- the tile's 64 results as a ballot; a whole tile of an image whose rows are 8-byte aligned is written by 8
+    // lanes, one 8-byte row each (bit k of the row's byte of the ballot -> byte k, 255 where lit)
+    const uint64_t litm = ~wave_ballot(h.hit);
+    const bool rows8 = (a.W & 7u) == 0u && (reinterpret_cast<uintptr_t>(vis) & 7u) == 0u &&
+                       tx * SF_TILE + SF_TILE <= a.W && ty * SF_TILE + SF_TILE <= a.H;   // (uniform)
+    if (rows8) {
+        if (lane < 8u) {
+            const uint64_t b = (litm >> (8u * lane)) & 0xffull;
+            const uint64_t s = (b * 0x0101010101010101ull) & 0x8040201008040201ull;   // byte k: bit k of b, in place
+            const uint64_t n = ((s + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;   // byte k: 1 if set
+            *reinterpret_cast<uint64_t*>(vis + (size_t)(ty * SF_TILE + lane) * a.W + tx * SF_TILE) = n * 0xffull;
+        }
+    } else if (valid) {
+        vis[(size_t)y * a.W + x] = h.hit ? (uint8_t)0 : (uint8_t)255;
+    }
+    return flagged;
+}
+
+}  // namespace
+
+// One tile per one-wave workgroup, dynamic LDS for a.max_depth levels (the launch of sf_trace_dirs_wave). Touches none
+// of the context's statistics.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_shadow_wave(FrameArgs a, const float* pos4, ShadowArgs sa,
+                                                                      uint8_t* vis, uint32_t groups,
+                                                                      uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    stage_root(lds, a.root);
+    trace_shadow_group<false>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, build_column(a.consts), blockIdx.x,
+                              a.max_depth, overflow_list, overflow_count);
+}
+
+// Re-trace of the flagged tiles at SF_MAX_LEVELS (as sf_trace_dirs_fixup, whose list and counters it shares).
+extern "C" __global__ __launch_bounds__(64) void sf_trace_shadow_fixup(FrameArgs a, const float* pos4, ShadowArgs sa,
+                                                                       uint8_t* vis, const uint32_t* overflow_list,
+                                                                       uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    const uint32_t n = counters[parity];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        counters[parity ^ 1u] = 0u;
+        counters[2] += n;
+    }
+    if (blockIdx.x >= n) return;
+    stage_root(lds, a.root);
+    const float4 bcol = build_column(a.consts);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x)
+        trace_shadow_group<true>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, bcol, overflow_list[i],
+                                 SF_MAX_LEVELS, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------

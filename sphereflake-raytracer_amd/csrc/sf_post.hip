@@ -339,3 +339,32 @@ extern "C" __global__ void __launch_bounds__(256) sf_post_fused(PostArgs a)
     const float4 p = ld4(a.pos, px);
     final_store(a, px, p, unorm(v));
 }
+
+// Point-light shading of the final image, in place (sf_light_image, sf.h): one thread per pixel.
+// Every operation is rounded on its own (no contraction: the build's -ffp-contract=off, and the _rn forms say so);
+// sphereflake_amd/lights.py (light_model) restates it and the result equals it bit for bit (tests/test_gpu_shadow.py).
+extern "C" __global__ void __launch_bounds__(256) sf_light_image_px(uint32_t W, uint32_t H, const float* pos4,
+                                                                 const float* nrm4, const uint8_t* vis, ShadowArgs sa,
+                                                                 float ambient, uint8_t* rgba)
+{
+    const uint32_t px = blockIdx.x * 256u + threadIdx.x;
+    if (px >= W * H) return;
+    const float4 P = ld4(pos4, px);
+    if (P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) return;   // a miss of the frame (post_final.glsl:20)
+    const float4 n = ld4(nrm4, px);
+    const float wx = __fadd_rn(sa.o[0], P.x), wy = __fadd_rn(sa.o[1], P.y), wz = __fadd_rn(sa.o[2], P.z);
+    const float dx = __fadd_rn(__fsub_rn(wx, sa.l[0]), 0.0f);
+    const float dy = __fadd_rn(__fsub_rn(wy, sa.l[1]), 0.0f);
+    const float dz = __fadd_rn(__fsub_rn(wz, sa.l[2]), 0.0f);
+    // (sqrtf and / are correctly rounded under the build's -fhip-fp32-correctly-rounded-divide-sqrt; __fsqrt_rn is not)
+    const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float ex = __fsub_rn(sa.l[0], wx), ey = __fsub_rn(sa.l[1], wy), ez = __fsub_rn(sa.l[2], wz);
+    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(n.x, ex), __fmul_rn(n.y, ey)), __fmul_rn(n.z, ez));
+    const float lam = fmaxf(0.0f, dot / len);   // (a NaN quotient gives 0)
+    const float k = __fadd_rn(ambient, __fmul_rn(__fsub_rn(1.0f, ambient), vis[px] ? lam : 0.0f));
+    uchar4 c = reinterpret_cast<uchar4*>(rgba)[px];
+    c.x = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.x, k), 0.5f), 255.0f);
+    c.y = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.y, k), 0.5f), 255.0f);
+    c.z = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.z, k), 0.5f), 255.0f);
+    reinterpret_cast<uchar4*>(rgba)[px] = c;
+}

@@ -66,6 +66,12 @@ class sf_rays_params(ctypes.Structure):
                 ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
 
 
+class sf_shadow_params(ctypes.Structure):
+    _fields_ = [("light", ctypes.c_float * 3), ("bias", ctypes.c_float), ("origin", ctypes.c_float * 3),
+                ("use_origin", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
 class sf_stats(ctypes.Structure):
     _fields_ = [("max_depth", ctypes.c_int32), ("closest", ctypes.c_float),
                 ("rays", ctypes.c_int64), ("overflow_tiles", ctypes.c_int64)]
@@ -106,6 +112,13 @@ SIGNATURES = {
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_probe_rays": (ctypes.c_int, [_CTX, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_shadow_defaults": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shadow_params)]),
+    "sf_trace_shadow_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shadow_params), ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_shadow": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shadow_params)]),
+    "sf_download_shadow": (ctypes.c_int, [_CTX, ctypes.c_void_p]),
+    "sf_shadow_buffer": (ctypes.c_int, [_CTX, ctypes.POINTER(ctypes.c_void_p)]),
+    "sf_light_image": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shadow_params), ctypes.c_float, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_render_frames": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
                                         ctypes.POINTER(sf_render_params)]),
     "sf_slab_rows": (ctypes.c_uint32, [ctypes.c_uint32] * 4),
@@ -774,6 +787,101 @@ class Sphereflake:
             _check(lib().sf_probe_rays(self._ctx, vp(o), vp(d), n, rpo, vp(mint), vp(idx), vp(pos), vp(nrm)),
                    "sf_probe_rays", self._ctx)
         return mint, idx, pos, nrm
+
+    # shadows from a point light (sf_trace_shadow_to / sf_trace_shadow / sf_light_image) ----------
+    def shadow_params(self, light, bias=None, origin=None, width=0, height=0, max_depth=0, stream=None):
+        """sf_shadow_defaults, overridden: bias None keeps the library's default."""
+        p = sf_shadow_params()
+        _check(lib().sf_shadow_defaults(self._ctx, ctypes.byref(p)), "sf_shadow_defaults")
+        p.light[:] = [float(x) for x in _f32(light, 3)]
+        if bias is not None:
+            p.bias = float(bias)
+        if origin is not None:
+            p.origin[:] = [float(x) for x in _f32(origin, 3)]
+            p.use_origin = 1
+        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
+        return p
+
+    def trace_shadow(self, light, bias=None, pos=None, out=None, origin=None, max_depth=0, stream=None):
+        """Which pixels of a position image does a point light at `light` (world) reach? 255 = lit or a miss of the
+        frame, 0 = shadowed; the exact definition is in sf.h and sphereflake_amd.lights.shadow_model.
+
+        pos: the view-space position image, relative to `origin` (None: the context's view origin):
+          - None: the context's own G-buffer (after Render()), into the context's visibility buffer
+            (download_shadow() and light_image() see it) or, with `out`, into that buffer -- asynchronous;
+          - a numpy array [H, W, 4]: uploaded, traced, and a numpy [H, W] uint8 returned -- synchronous;
+          - a torch CUDA tensor [H, W, 4] (contiguous float32), or a (device address, width, height) tuple: zero
+            copy, asynchronous; the result goes to `out`.
+        out: a torch CUDA uint8 tensor of H x W elements, or a device address."""
+        if isinstance(pos, np.ndarray):
+            pos = np.ascontiguousarray(pos, np.float32)
+            if pos.ndim != 3 or pos.shape[-1] != 4:
+                raise ValueError("pos must be [H, W, 4]")
+            if out is not None:
+                raise ValueError("a host position image returns a host array: out must be None")
+            H, W = pos.shape[:2]
+            vis = np.empty((H, W), np.uint8)
+            if H * W == 0:
+                return vis
+            p = self.shadow_params(light, bias, origin, W, H, max_depth, stream)
+            with _DeviceScratch(self.device, pos.nbytes + H * W) as d:
+                d.upload(0, pos)
+                with self._mutex:
+                    _check(lib().sf_trace_shadow_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr),
+                                                    ctypes.c_void_p(d.ptr + pos.nbytes)), "sf_trace_shadow_to", self._ctx)
+                    # (the scratch is freed on leaving: the trace that reads and writes it must be done)
+                    _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
+                d.download(pos.nbytes, vis)
+            return vis
+        optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
+        if pos is None:
+            p = self.shadow_params(light, bias, origin, 0, 0, max_depth, stream)
+            with self._mutex:
+                if optr:
+                    _check(lib().sf_trace_shadow_to(self._ctx, ctypes.byref(p), None, ctypes.c_void_p(optr)),
+                           "sf_trace_shadow_to", self._ctx)
+                else:
+                    _check(lib().sf_trace_shadow(self._ctx, ctypes.byref(p)), "sf_trace_shadow", self._ctx)
+            return None
+        if hasattr(pos, "data_ptr"):
+            shape = tuple(pos.shape)
+            if len(shape) != 3 or shape[-1] != 4 or not (pos.is_cuda and pos.is_contiguous() and pos.element_size() == 4
+                                                         and pos.dtype.is_floating_point):
+                raise ValueError("pos must be a contiguous float32 CUDA tensor [H, W, 4]")
+            pptr, W, H = pos.data_ptr(), shape[1], shape[0]
+        else:
+            pptr, W, H = (int(x) for x in pos)
+        if not optr:
+            raise ValueError("a device position image needs an `out` buffer")
+        p = self.shadow_params(light, bias, origin, W, H, max_depth, stream)
+        with self._mutex:
+            _check(lib().sf_trace_shadow_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(pptr), ctypes.c_void_p(optr)),
+                   "sf_trace_shadow_to", self._ctx)
+        return None
+
+    def download_shadow(self) -> np.ndarray:
+        """[H, W] uint8 of the last trace_shadow() into the context's visibility buffer (synchronous)."""
+        vis = np.empty((self.height, self.width), np.uint8)
+        with self._mutex:
+            _check(lib().sf_download_shadow(self._ctx, vis.ctypes.data_as(ctypes.c_void_p)), "sf_download_shadow",
+                   self._ctx)
+        return vis
+
+    def shadow_buffer(self) -> int:
+        """Device address of the context's visibility buffer (0 before any trace_shadow() into it)."""
+        ptr = ctypes.c_void_p()
+        _check(lib().sf_shadow_buffer(self._ctx, ctypes.byref(ptr)), "sf_shadow_buffer")
+        return ptr.value or 0
+
+    def light_image(self, light, ambient=0.25, origin=None, pos_ptr=0, nrm_ptr=0, vis_ptr=0, rgba_ptr=0, stream=None):
+        """Scale the image of PostProcess() in place by ambient + (1 - ambient) x (lit ? Lambert term : 0)
+        (sf_light_image; sphereflake_amd.lights.light_model). Pointers are device addresses, 0 = the context's
+        G-buffer, visibility buffer (trace_shadow()) and image. Asynchronous."""
+        p = self.shadow_params(light, None, origin, 0, 0, 0, stream)
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        with self._mutex:
+            _check(lib().sf_light_image(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
+                                        vp(vis_ptr), vp(rgba_ptr)), "sf_light_image", self._ctx)
 
     def Synchronize(self):
         _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)

@@ -6,7 +6,9 @@ reference normalises a pixel's ray, SIMD_AVX.h:170-180) and carry no -0 componen
 What a secondary ray sees is the reference's answer, quirk included: a sphere whose centre is behind the ray is
 rejected even when the ray starts inside it (``tca >= 0``, SIMD_AVX.h:247-258), and the root's bounding ball is
 tested first -- so a ray that starts on the flake and heads away from the flake's centre sees nothing at all.
-``reflect`` and ``towards`` are for rays that head inwards; they are no occlusion query.
+``reflect`` and ``towards`` are for rays that head inwards; they are no occlusion query. Shadows from a point light
+are traced the other way round, from the light towards the surface point, where the quirk cannot bite:
+``Sphereflake.trace_shadow`` (sphereflake_amd/lights.py, sf_trace_shadow_to).
 """
 from __future__ import annotations
 
