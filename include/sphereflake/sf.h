@@ -276,6 +276,55 @@ int sf_shadow_buffer(sf_ctx* ctx, uint8_t** vis);
 int sf_light_image(sf_ctx* ctx, const sf_shadow_params* params, float ambient, const float* pos4, const float* nrm4,
                    const uint8_t* vis, uint8_t* rgba);
 
+/* --- many lights per pixel: soft shadows, sky light ------------------------- */
+/* Extends sf_trace_shadow_to from one light to n <= SF_SHADOW_LIGHTS_MAX lights in ONE launch: an area light sampled
+   at n points (a penumbra), or n lights placed outside the radius-2 ball as a ray-traced sky occlusion term (the only
+   way to occlusion here: feelers that start on the flake see nothing, THE REFERENCE'S QUIRK above). Each tile's wave
+   loads its positions once and loops over the lights; one 64-bit word per pixel comes out instead of n byte images.
+   DEFINITION OF THE MASK (exact). Bit i (i < n) of mask[p] is 1 iff sf_trace_shadow_to with light = lights[i] and
+   the same bias, origin, sizes and position image writes 255 at p, and 0 iff it writes 0: steps 1-6 of its
+   definition apply per light, unchanged. Bits n..63 are 0. So a miss of the frame (P == 0) has its low n bits all
+   set, and a light that is not finite sets its own bit everywhere and leaves the other lights' bits alone. THE LEVEL
+   OF DETAIL IS EACH LIGHT'S OWN, and a light inside the radius-2 ball gets the reference's answer, as there. */
+#define SF_SHADOW_LIGHTS_MAX 64
+typedef struct sf_shadows_params {
+    const float* lights;      /* HOST, n x 3 floats, world space; read before the call returns */
+    const float* weights;     /* HOST, n floats, or NULL = every weight (float)1 / (float)n; sf_light_image_many only */
+    uint32_t n;               /* 1 .. SF_SHADOW_LIGHTS_MAX */
+    float bias;               /* as sf_shadow_params.bias; one bias for all lights */
+    float origin[3];          /* as sf_shadow_params.origin */
+    uint32_t use_origin;      /* as sf_shadow_params.use_origin */
+    uint32_t width, height;   /* as sf_shadow_params */
+    uint32_t max_depth;       /* 0 = auto: the largest geometric bound over the n lights */
+    void* stream;             /* NULL = the context stream */
+} sf_shadows_params;
+
+/* Zeroed (n = 0, lights NULL: the caller sets both), the default bias of sf_shadow_defaults. */
+int sf_shadows_defaults(const sf_ctx* ctx, sf_shadows_params* params);
+/* As sf_trace_shadow_to (pos4 DEVICE or NULL = the context's G-buffer; asynchronous and ordered as it is; no statistic
+   and none of the renders' state touched; re-traced tiles -- a tile flagged for any light is re-traced once, for all
+   of them -- count in overflow_tiles). mask: DEVICE output, width * height uint64_t, row-major as pos4. Errors as
+   sf_trace_shadow_to's, and SF_EINVAL for n == 0, n > SF_SHADOW_LIGHTS_MAX, a null lights or a null mask. */
+int sf_trace_shadows_to(sf_ctx* ctx, const sf_shadows_params* params, const float* pos4, uint64_t* mask);
+/* The context's G-buffer into the context's own mask buffer (W * H * 8 bytes, allocated on first use); extends
+   sf_trace_shadow. */
+int sf_trace_shadows(sf_ctx* ctx, const sf_shadows_params* params);
+/* Synchronous D2H of that buffer (W * H uint64_t); SF_ESTATE before any sf_trace_shadows. Extends sf_download_shadow. */
+int sf_download_shadow_masks(sf_ctx* ctx, uint64_t* mask);
+/* Its device pointer (NULL before any sf_trace_shadows); extends sf_shadow_buffer. */
+int sf_shadow_mask_buffer(sf_ctx* ctx, uint64_t** mask);
+/* Extends sf_light_image from a product to a SUM over lights (sf_light_image scales in place, so two calls multiply).
+   Exact, binary32, one rounding per operation, no fma: a frame miss is left untouched; else S = 0, then for
+   i = 0 .. n-1 in that order S = S + w_i (bit i of mask[p] ? lam_i : 0) with lam_i exactly sf_light_image's lam for
+   lights[i] (0 where NaN); k = ambient + (1 - ambient) S, and each of r, g, b becomes (uint8) min(c k + 0.5f, 255);
+   alpha stays. S is not clamped: with n = 1 and weight 1 the result is sf_light_image's, byte for byte. params:
+   lights, weights, n, origin / use_origin, stream. NULL pos4 / nrm4 / mask / rgba select the context's G-buffer, mask
+   buffer and image; SF_ESTATE where a context buffer selected that way was never written; SF_EINVAL for an ambient
+   outside [0, 1] or NaN, n or lights as above, or a weight that is negative or NaN. Asynchronous on the stream.
+   sphereflake_amd/lights.py: light_model_many. */
+int sf_light_image_many(sf_ctx* ctx, const sf_shadows_params* params, float ambient, const float* pos4,
+                        const float* nrm4, const uint64_t* mask, uint8_t* rgba);
+
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the
    work units of all n frames from one set of tile queues -- a wave whose frame runs dry goes on with the next

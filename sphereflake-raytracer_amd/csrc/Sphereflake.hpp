@@ -195,6 +195,30 @@ public:
         Check(sf_light_image(m_Ctx, &params, ambient, positions4, normals4, visibility, rgba));
     }
 
+    // Many lights per pixel in one launch (new; sf_trace_shadows_to / sf_trace_shadows, sf.h): an area light's samples
+    // or a sky of lights outside the flake's bounding ball. masks: one uint64_t per pixel, bit i = what TraceShadow
+    // gives for params.lights[i] (1 lit or frame miss, 0 shadowed). DEVICE pointers, asynchronous; positions4 null =
+    // this object's own frame.
+    void TraceShadows(const sf_shadows_params& params, const float* positions4, uint64_t* masks)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_shadows_to(m_Ctx, &params, positions4, masks));
+    }
+    // ... of this object's own device frame into its own mask buffer (sf_download_shadow_masks, LightImageMany)
+    void TraceShadows(const sf_shadows_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_shadows(m_Ctx, &params));
+    }
+    // The weighted sum of those lights' Lambert terms on the image of an SSAO::Render(), in place
+    // (sf_light_image_many); null pointers select this object's own frame, mask buffer and image.
+    void LightImageMany(const sf_shadows_params& params, float ambient = 0.25f, const float* positions4 = nullptr,
+                        const float* normals4 = nullptr, const uint64_t* masks = nullptr, uint8_t* rgba = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_image_many(m_Ctx, &params, ambient, positions4, normals4, masks, rgba));
+    }
+
     // the device frame, downloaded into the vectors when it is newer than their contents (Refresh)
     const GBuffer& GetGBuffer() const
     {

@@ -64,6 +64,12 @@ extern "C" __global__ void sf_trace_shadow_fixup(FrameArgs a, const float* pos4,
                                                  const uint32_t* overflow_list, uint32_t* counters, uint32_t parity);
 extern "C" __global__ void sf_light_image_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
                                           const uint8_t* vis, ShadowArgs sa, float ambient, uint8_t* rgba);
+extern "C" __global__ void sf_trace_shadows_wave(FrameArgs a, const float* pos4, ShadowLights sl, uint64_t* mask,
+                                                 uint32_t groups, uint32_t* overflow_list, uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_shadows_fixup(FrameArgs a, const float* pos4, ShadowLights sl, uint64_t* mask,
+                                                  const uint32_t* overflow_list, uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_light_image_many_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
+                                                  const uint64_t* mask, ShadowLights sl, float ambient, uint8_t* rgba);
 extern "C" __global__ void sf_band_unpack(FrameArgs a, const float4* stage, uint32_t stage_rows, uint32_t band_rows,
                                            uint32_t n, uint32_t first, uint32_t members, uint32_t row0);
 extern "C" __global__ void sf_node_table(FrameArgs a, float4* table, uint32_t nodes);
@@ -354,6 +360,7 @@ struct sf_ctx {
     uint8_t* blur_v = nullptr;
     uint8_t* image = nullptr;          // W x H RGBA8
     uint8_t* shadow = nullptr;         // W x H visibility bytes (sf_trace_shadow): lazily allocated
+    uint64_t* shadow_masks = nullptr;  // W x H visibility masks (sf_trace_shadows): lazily allocated
     int centre_exact = -1;             // sfhost::post_centre_exact(W) && (H), cached
 };
 
@@ -467,6 +474,7 @@ static void free_ctx(sf_ctx* c)
     (void)hipFree(c->blur_v);
     (void)hipFree(c->image);
     (void)hipFree(c->shadow);
+    (void)hipFree(c->shadow_masks);
     for (int i = 0; i < sf_ctx::kTimed; ++i)
         for (int j = 0; j < 2; ++j)
             if (c->ev[i][j]) (void)hipEventDestroy(c->ev[i][j]);
@@ -1415,6 +1423,161 @@ int sf_light_image(sf_ctx* c, const sf_shadow_params* p, float ambient, const fl
     hipLaunchKernelGGL(sf_light_image_px, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
                        nrm4 ? nrm4 : (const float*)c->nrm, vis ? vis : (const uint8_t*)c->shadow, shadow_args(c, p),
                        ambient, rgba ? rgba : c->image);
+    SF_HIP(c, hipGetLastError());
+    return SF_OK;
+}
+
+// Many lights per pixel in one launch (sf.h; kernels sf_trace_shadows_wave / sf_trace_shadows_fixup /
+// sf_light_image_many_px). The launch of sf_trace_shadow_to with the lights by value in the argument
+// segment; the levels are one value for the launch, the largest geometric bound over the lights.
+static_assert(SF_SHADOW_LIGHTS == SF_SHADOW_LIGHTS_MAX, "one mask bit per light");
+static_assert(sizeof(FrameArgs) + sizeof(ShadowLights) + 64 <= 4096, "kernel argument segment");
+
+int sf_shadows_defaults(const sf_ctx* c, sf_shadows_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->bias = kShadowBias;
+    return SF_OK;
+}
+
+// n and the lights' pointer (both calls), the weights (sf_light_image_many)
+static int shadows_check(const sf_shadows_params* p, bool weights)
+{
+    if (p->n == 0u || p->n > SF_SHADOW_LIGHTS_MAX || !p->lights) return SF_EINVAL;
+    if (weights && p->weights)
+        for (uint32_t i = 0; i < p->n; ++i)
+            if (!(p->weights[i] >= 0.0f)) return SF_EINVAL;   // (NaN fails)
+    return SF_OK;
+}
+
+// the launch's ShadowLights from the parameters: read from the caller's host arrays here, before the call returns
+static void shadows_args(const sf_ctx* c, const sf_shadows_params* p, ShadowLights* sl)
+{
+    std::memset(sl, 0, sizeof *sl);
+    for (int k = 0; k < 3; ++k) sl->o[k] = p->use_origin ? p->origin[k] : c->o[k];
+    sl->keep = 1.0f - p->bias;
+    sl->n = p->n;
+    const float even = 1.0f / (float)p->n;
+    for (uint32_t i = 0; i < p->n; ++i) {
+        for (int k = 0; k < 3; ++k) sl->l[i][k] = p->lights[3 * i + k];
+        sl->w[i] = p->weights ? p->weights[i] : even;
+    }
+}
+
+int sf_trace_shadows_to(sf_ctx* c, const sf_shadows_params* p, const float* pos4, uint64_t* mask)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!mask) return SF_EINVAL;
+    if (int rc = shadows_check(p, false)) return rc;
+    if (!(p->bias >= 0.0f && p->bias < 1.0f)) return SF_EINVAL;   // (NaN fails both)
+    if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
+    if ((p->width == 0u) != (p->height == 0u)) return SF_EINVAL;
+    const uint32_t W = p->width ? p->width : c->W, H = p->height ? p->height : c->H;
+    if (!pos4 && (W != c->W || H != c->H)) return SF_EINVAL;
+    if ((uint64_t)W * H > 0x7fffffffull) return SF_EINVAL;   // (pixel indices are 32-bit in the kernel)
+    if (!pos4) pos4 = c->pos;
+    const uint32_t tiles_x = (W + 7u) / 8u;
+    const uint32_t groups = tiles_x * ((H + 7u) / 8u);
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    if (!c->dirs_cnt) {
+        SF_HIP(c, hipMalloc(&c->dirs_cnt, 3 * 4));
+        SF_HIP(c, hipMemsetAsync(c->dirs_cnt, 0, 3 * 4, s));
+    }
+    if (groups > c->dirs_cap) {   // grown on demand; an earlier trace may still write the old list
+        SF_HIP(c, hipStreamSynchronize(s));
+        (void)hipFree(c->dirs_ovf);
+        c->dirs_ovf = nullptr;
+        c->dirs_cap = 0;
+        SF_HIP(c, hipMalloc(&c->dirs_ovf, (size_t)groups * 4));
+        c->dirs_cap = groups;
+    }
+    ShadowLights sl;
+    shadows_args(c, p, &sl);
+    FrameArgs a = frame_args(c);
+    a.W = W;
+    a.H = H;
+    a.tiles_x = tiles_x;
+    for (int k = 0; k < 3; ++k) a.root[9 + k] = 0.0f;   // (the kernel stages each light's own translation)
+    uint32_t levels = p->max_depth;
+    if (!levels)
+        for (uint32_t i = 0; i < sl.n; ++i) {
+            const float centre[3] = { 0.0f - sl.l[i][0], 0.0f - sl.l[i][1], 0.0f - sl.l[i][2] };
+            if (!std::isfinite(centre[0] + centre[1] + centre[2])) continue;   // (traces nothing)
+            bool bounded = false;
+            const uint32_t li = geometric_levels(c, centre, &bounded);
+            if (li > levels) levels = li;
+        }
+    a.max_depth = levels;
+    if (a.max_depth < 4u) a.max_depth = 4u;
+    if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
+    a.stats = nullptr;   // (no statistic is touched)
+    const size_t lds = (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4;
+    hipLaunchKernelGGL(sf_trace_shadows_wave, dim3(groups), dim3(64), lds, s, a, pos4, sl, mask, groups, c->dirs_ovf,
+                       c->dirs_cnt + c->dirs_par);
+    SF_HIP(c, hipGetLastError());
+    const size_t lds_fix = (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4;
+    const uint32_t fb = groups < SF_PROG_FIXUP_BLOCKS ? groups : SF_PROG_FIXUP_BLOCKS;
+    hipLaunchKernelGGL(sf_trace_shadows_fixup, dim3(fb), dim3(64), lds_fix, s, a, pos4, sl, mask,
+                       (const uint32_t*)c->dirs_ovf, c->dirs_cnt, c->dirs_par);
+    SF_HIP(c, hipGetLastError());
+    c->dirs_par ^= 1u;
+    return SF_OK;
+}
+
+int sf_trace_shadows(sf_ctx* c, const sf_shadows_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if ((p->width || p->height) && (p->width != c->W || p->height != c->H)) return SF_EINVAL;
+    if (!c->shadow_masks) {
+        DevGuard g(c->device);
+        SF_HIP(c, hipMalloc(&c->shadow_masks, (size_t)c->W * c->H * 8));
+    }
+    return sf_trace_shadows_to(c, p, nullptr, c->shadow_masks);
+}
+
+int sf_download_shadow_masks(sf_ctx* c, uint64_t* mask)
+{
+    if (!c || !mask) return SF_EINVAL;
+    if (!c->shadow_masks) return SF_ESTATE;
+    int rc = sf_synchronize(c);
+    if (rc != SF_OK) return rc;
+    DevGuard g(c->device);
+    SF_HIP(c, hipMemcpy(mask, c->shadow_masks, (size_t)c->W * c->H * 8, hipMemcpyDeviceToHost));
+    return SF_OK;
+}
+
+int sf_shadow_mask_buffer(sf_ctx* c, uint64_t** mask)
+{
+    if (!c || !mask) return SF_EINVAL;
+    *mask = c->shadow_masks;
+    return SF_OK;
+}
+
+int sf_light_image_many(sf_ctx* c, const sf_shadows_params* p, float ambient, const float* pos4, const float* nrm4,
+                        const uint64_t* mask, uint8_t* rgba)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view && !p->use_origin) return SF_ENOVIEW;
+    if (!(ambient >= 0.0f && ambient <= 1.0f)) return SF_EINVAL;
+    if (int rc = shadows_check(p, true)) return rc;
+    if (!rgba && !c->image) return SF_ESTATE;
+    if (!mask && !c->shadow_masks) return SF_ESTATE;
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    ShadowLights sl;
+    shadows_args(c, p, &sl);
+    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
+    hipLaunchKernelGGL(sf_light_image_many_px, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
+                       nrm4 ? nrm4 : (const float*)c->nrm, mask ? mask : (const uint64_t*)c->shadow_masks, sl, ambient,
+                       rgba ? rgba : c->image);
     SF_HIP(c, hipGetLastError());
     return SF_OK;
 }

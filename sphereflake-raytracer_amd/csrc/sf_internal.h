@@ -198,6 +198,17 @@ struct ShadowArgs {
     float keep;                       // 1 - bias (sf_trace_shadow; unused by sf_light_image)
 };
 
+// Many lights per pixel in one launch (sf_trace_shadows_to, sf_light_image_many): the lights travel by value in the
+// kernel argument segment beside the FrameArgs (1044 B; indexed with a uniform index they are scalar loads)
+#define SF_SHADOW_LIGHTS 64u          // == SF_SHADOW_LIGHTS_MAX (sf.h): one bit of the mask word per light
+struct ShadowLights {
+    float o[3];                       // the origin the position image is relative to
+    float keep;                       // 1 - bias (sf_trace_shadows_to; unused by sf_light_image_many)
+    uint32_t n;                       // lights in use, 1..SF_SHADOW_LIGHTS
+    float l[SF_SHADOW_LIGHTS][3];     // the lights (world)
+    float w[SF_SHADOW_LIGHTS];        // their weights (sf_light_image_many; unused by the trace)
+};
+
 // Multi-frame persistent trace (round 6, sf_render_frames): the frames of one launch, passed by value in the kernel
 // argument segment (copied by the runtime at the launch, so the host may build the next batch at once; 4 KB at most:
 // 11 FrameArgs). Frame f is one slot context's view into that context's G-buffer and stats. All frames share one

@@ -3717,6 +3717,127 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_shadow_fixup(FrameArgs
 }
 
 // ------------------------------------------------------------------------------------------
+// Many lights per pixel in one launch (sf_trace_shadows_to). Bit i of mask[p] is what
+// sf_trace_shadow_wave writes for light i at p (1 = 255, 0 = 0), bits n..63 are 0. The lane's position is loaded once;
+// per light (a uniform index, the lights are scalar loads from the argument segment) d, len and bound are formed as in
+// trace_shadow_group, the root image is restaged with the translation 0 - l_i (as trace_ray_group does per origin)
+// and traverse_ray runs in its shadow mode, unchanged. A tile with no surface pixel traces nothing. The launch's
+// levels are one value for all lights; a tile flagged for any light goes onto the overflow list once and is re-traced
+// for all of them.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// The part of stage_root's image that depends on the light: words 0..2 the translation, word 3 its squared length
+// (the columns stay). Without a branch on the lane, as stage_root_all_lanes: lane l writes word l & 3. (stage_root
+// itself inside the loop over the lights had its 16 lane compares hoisted into 32 SGPRs: occupancy 7.)
+__device__ __forceinline__ void stage_root_translation(float* __restrict__ Lbase, float tx, float ty, float tz)
+{
+    const uint32_t l = threadIdx.x & 3u;
+    const float tcc = (tx * tx + ty * ty) + tz * tz;
+    Lbase[l] = l == 0u ? tx : l == 1u ? ty : l == 2u ? tz : tcc;   // TraverseLds::root()
+}
+
+template <bool FIXUP>
+__device__ __forceinline__ void trace_shadows_group(const FrameArgs& a, const float4* __restrict__ pos4,
+                                                    const ShadowLights& sl, uint64_t* __restrict__ mask,
+                                                    float* __restrict__ L, const float4 bcol, uint32_t group,
+                                                    uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const uint32_t lane = threadIdx.x & 63u;
+    // the lane's pixel, as in trace_shadow_group
+    const uint32_t ty = group / a.tiles_x, tx = group - ty * a.tiles_x;
+    const uint32_t x = tx * SF_TILE + (lane & 7u), y = ty * SF_TILE + (lane >> 3);
+    const bool valid = x < a.W && y < a.H;
+    const uint32_t pix = (y < a.H ? y : a.H - 1u) * a.W + (x < a.W ? x : a.W - 1u);   // (< 2^31 pixels)
+    const float4 P = pos4[pix];
+    const bool surface = valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    const uint32_t n = sl.n;   // (uniform, 1..64)
+    uint64_t shadowed = 0ull;   // bit i: light i does not reach the lane's pixel
+    uint32_t status = 0u;
+    if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss: every light's bit is set)
+        const float wx = __fadd_rn(sl.o[0], P.x), wy = __fadd_rn(sl.o[1], P.y), wz = __fadd_rn(sl.o[2], P.z);
+        const uint32_t culls = a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST);
+        auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
+        lds_fence();
+        stage_root(L, a.root);   // the columns, once per tile; each light restages its translation
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0u; i < n; ++i) {
+            const float lx = sl.l[i][0], ly = sl.l[i][1], lz = sl.l[i][2];
+            float dx = __fadd_rn(__fsub_rn(wx, lx), 0.0f);
+            float dy = __fadd_rn(__fsub_rn(wy, ly), 0.0f);
+            float dz = __fadd_rn(__fsub_rn(wz, lz), 0.0f);
+            // (the correctly rounded square root, see trace_shadow_group)
+            const float len = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+            const float bound = __fmul_rn(len, sl.keep);
+            normalize3(dx, dy, dz, K->lut);
+            // finiteness depends on the light: a light that is not finite leaves no lane on, and its bit stays set
+            const bool on = surface && finite(dx) && finite(dy) && finite(dz);
+            const uint64_t onm = wave_ballot(on);
+            if (onm == 0ull) continue;   // (uniform)
+            const uint32_t axl = __builtin_amdgcn_readfirstlane(((onm >> 36u) & 1ull) ? 36u : (uint32_t)__builtin_ctzll(onm));
+            const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
+            float r[12];   // (traverse_ray reads the translation only; the columns are in the staged image)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) r[k] = 0.0f;
+            r[9] = __fsub_rn(0.0f, lx);   // (Sphereflake.cpp:83 at the light)
+            r[10] = __fsub_rn(0.0f, ly);
+            r[11] = __fsub_rn(0.0f, lz);
+            lds_fence();
+            stage_root_translation(L, r[9], r[10], r[11]);   // (the light before left its own)
+            HitState h;
+            h.hit = false;
+            int32_t md = -1;
+            uint32_t st = 0u;
+            traverse_ray<false, false, false, true>(K, r, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az, on, h,
+                                                    md, st, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
+            status |= st;
+            shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
+        }
+    }
+    if (!FIXUP && status != 0u) {   // (uniform) more levels needed for some light: once on the list
+        const uint32_t slot = wave_fetch_add(overflow_count, 1u);
+        overflow_list[slot] = group;   // uniform value and address
+    }
+    // a tile row is 64 contiguous bytes: one 8-byte vector store per valid lane
+    const uint64_t all = n >= 64u ? ~0ull : (1ull << n) - 1ull;
+    if (valid) mask[(size_t)y * a.W + x] = all & ~shadowed;
+}
+
+}  // namespace
+
+// One tile per one-wave workgroup, dynamic LDS for a.max_depth levels (the launch of sf_trace_shadow_wave). Touches
+// none of the context's statistics.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_wave(FrameArgs a, const float* pos4, ShadowLights sl,
+                                                                       uint64_t* mask, uint32_t groups,
+                                                                       uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    trace_shadows_group<false>(a, reinterpret_cast<const float4*>(pos4), sl, mask, lds, build_column(a.consts),
+                               blockIdx.x, a.max_depth, overflow_list, overflow_count);
+}
+
+// Re-trace of the flagged tiles, for every light, at SF_MAX_LEVELS (as sf_trace_shadow_fixup, whose list and
+// counters it shares).
+extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_fixup(FrameArgs a, const float* pos4, ShadowLights sl,
+                                                                        uint64_t* mask, const uint32_t* overflow_list,
+                                                                        uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    const uint32_t n = counters[parity];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        counters[parity ^ 1u] = 0u;
+        counters[2] += n;
+    }
+    if (blockIdx.x >= n) return;
+    const float4 bcol = build_column(a.consts);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x)
+        trace_shadows_group<true>(a, reinterpret_cast<const float4*>(pos4), sl, mask, lds, bcol, overflow_list[i],
+                                  SF_MAX_LEVELS, nullptr, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
 // One thread per ray, private stack (Sphereflake.h:86-226 restated as an explicit DFS).
 // ------------------------------------------------------------------------------------------
 extern "C" __global__ __launch_bounds__(256) void sf_trace_ray(FrameArgs a)

@@ -368,3 +368,39 @@ extern "C" __global__ void __launch_bounds__(256) sf_light_image_px(uint32_t W, 
     c.z = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.z, k), 0.5f), 255.0f);
     reinterpret_cast<uchar4*>(rgba)[px] = c;
 }
+
+// The same for many lights (sf_light_image_many, sf.h): one thread per pixel, S = sum over the lights
+// in index order of w_i (bit i of mask[p] ? lam_i : 0) with lam_i exactly sf_light_image_px's lam for light i, then
+// k = ambient + (1 - ambient) S (no clamp on S). The lights and weights are scalar loads from the argument segment.
+// sphereflake_amd/lights.py (light_model_many) restates it (tests/test_gpu_shadows.py).
+extern "C" __global__ void __launch_bounds__(256) sf_light_image_many_px(uint32_t W, uint32_t H, const float* pos4,
+                                                                      const float* nrm4, const uint64_t* mask,
+                                                                      ShadowLights sl, float ambient, uint8_t* rgba)
+{
+    const uint32_t px = blockIdx.x * 256u + threadIdx.x;
+    if (px >= W * H) return;
+    const float4 P = ld4(pos4, px);
+    if (P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) return;   // a miss of the frame (post_final.glsl:20)
+    const float4 n = ld4(nrm4, px);
+    const uint64_t m = mask[px];
+    const float wx = __fadd_rn(sl.o[0], P.x), wy = __fadd_rn(sl.o[1], P.y), wz = __fadd_rn(sl.o[2], P.z);
+    float S = 0.0f;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0u; i < sl.n; ++i) {
+        const float lx = sl.l[i][0], ly = sl.l[i][1], lz = sl.l[i][2];
+        const float dx = __fadd_rn(__fsub_rn(wx, lx), 0.0f);
+        const float dy = __fadd_rn(__fsub_rn(wy, ly), 0.0f);
+        const float dz = __fadd_rn(__fsub_rn(wz, lz), 0.0f);
+        const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+        const float ex = __fsub_rn(lx, wx), ey = __fsub_rn(ly, wy), ez = __fsub_rn(lz, wz);
+        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(n.x, ex), __fmul_rn(n.y, ey)), __fmul_rn(n.z, ez));
+        const float lam = fmaxf(0.0f, dot / len);   // (a NaN quotient gives 0)
+        S = __fadd_rn(S, __fmul_rn(sl.w[i], ((m >> i) & 1ull) ? lam : 0.0f));
+    }
+    const float k = __fadd_rn(ambient, __fmul_rn(__fsub_rn(1.0f, ambient), S));
+    uchar4 c = reinterpret_cast<uchar4*>(rgba)[px];
+    c.x = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.x, k), 0.5f), 255.0f);
+    c.y = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.y, k), 0.5f), 255.0f);
+    c.z = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.z, k), 0.5f), 255.0f);
+    reinterpret_cast<uchar4*>(rgba)[px] = c;
+}

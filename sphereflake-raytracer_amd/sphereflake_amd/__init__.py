@@ -72,6 +72,16 @@ class sf_shadow_params(ctypes.Structure):
                 ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
 
 
+SF_SHADOW_LIGHTS_MAX = 64
+
+
+class sf_shadows_params(ctypes.Structure):
+    _fields_ = [("lights", ctypes.POINTER(ctypes.c_float)), ("weights", ctypes.POINTER(ctypes.c_float)),
+                ("n", ctypes.c_uint32), ("bias", ctypes.c_float), ("origin", ctypes.c_float * 3),
+                ("use_origin", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
 class sf_stats(ctypes.Structure):
     _fields_ = [("max_depth", ctypes.c_int32), ("closest", ctypes.c_float),
                 ("rays", ctypes.c_int64), ("overflow_tiles", ctypes.c_int64)]
@@ -119,6 +129,13 @@ SIGNATURES = {
     "sf_shadow_buffer": (ctypes.c_int, [_CTX, ctypes.POINTER(ctypes.c_void_p)]),
     "sf_light_image": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shadow_params), ctypes.c_float, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_shadows_defaults": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shadows_params)]),
+    "sf_trace_shadows_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shadows_params), ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_shadows": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shadows_params)]),
+    "sf_download_shadow_masks": (ctypes.c_int, [_CTX, ctypes.c_void_p]),
+    "sf_shadow_mask_buffer": (ctypes.c_int, [_CTX, ctypes.POINTER(ctypes.c_void_p)]),
+    "sf_light_image_many": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shadows_params), ctypes.c_float, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_render_frames": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
                                         ctypes.POINTER(sf_render_params)]),
     "sf_slab_rows": (ctypes.c_uint32, [ctypes.c_uint32] * 4),
@@ -882,6 +899,119 @@ class Sphereflake:
         with self._mutex:
             _check(lib().sf_light_image(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
                                         vp(vis_ptr), vp(rgba_ptr)), "sf_light_image", self._ctx)
+
+    # many lights per pixel in one launch (sf_trace_shadows_to / sf_trace_shadows / sf_light_image_many) ----------
+    def shadows_params(self, lights, weights=None, bias=None, origin=None, width=0, height=0, max_depth=0, stream=None):
+        """sf_shadows_defaults, overridden: (params, keepalive). lights [n, 3], weights [n] or None; the host arrays
+        the params point into are in `keepalive` and must outlive the call they are passed to."""
+        L = np.ascontiguousarray(np.asarray(lights, np.float32).reshape(-1, 3))
+        n = L.shape[0]
+        if not 1 <= n <= SF_SHADOW_LIGHTS_MAX:
+            raise ValueError(f"1..{SF_SHADOW_LIGHTS_MAX} lights per call, not {n}")
+        p = sf_shadows_params()
+        _check(lib().sf_shadows_defaults(self._ctx, ctypes.byref(p)), "sf_shadows_defaults")
+        p.lights = L.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        wts = None
+        if weights is not None:
+            wts = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+            if wts.shape[0] != n:
+                raise ValueError("one weight per light")
+            p.weights = wts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        p.n = n
+        if bias is not None:
+            p.bias = float(bias)
+        if origin is not None:
+            p.origin[:] = [float(x) for x in _f32(origin, 3)]
+            p.use_origin = 1
+        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
+        return p, (L, wts)
+
+    def trace_shadows(self, lights, bias=None, pos=None, out=None, max_depth=0, origin=None, stream=None):
+        """Which of up to 64 point lights `lights` [n, 3] (world) reach each pixel of a position image, in one launch:
+        a uint64 per pixel, bit i = 1 where trace_shadow(lights[i]) gives 255 (lit, or a miss of the frame), 0 where
+        it gives 0; bits n..63 are 0 (sf.h). `pos` and `out` as trace_shadow's:
+          - None: the context's own G-buffer (after Render()), into the context's mask buffer
+            (download_shadow_masks() and light_image_many() see it) or, with `out`, into that buffer -- asynchronous;
+          - a numpy array [H, W, 4]: uploaded, traced, and a numpy [H, W] uint64 returned -- synchronous;
+          - a torch CUDA tensor [H, W, 4] (contiguous float32), or a (device address, width, height) tuple: zero
+            copy, asynchronous; the result goes to `out`.
+        out: a torch CUDA tensor of H x W 8-byte elements, or a device address (8-byte aligned)."""
+        if isinstance(pos, np.ndarray):
+            pos = np.ascontiguousarray(pos, np.float32)
+            if pos.ndim != 3 or pos.shape[-1] != 4:
+                raise ValueError("pos must be [H, W, 4]")
+            if out is not None:
+                raise ValueError("a host position image returns a host array: out must be None")
+            H, W = pos.shape[:2]
+            mask = np.empty((H, W), np.uint64)
+            p, keep = self.shadows_params(lights, None, bias, origin, W, H, max_depth, stream)
+            if H * W == 0:
+                return mask
+            with _DeviceScratch(self.device, pos.nbytes + mask.nbytes) as d:
+                d.upload(0, pos)
+                with self._mutex:
+                    _check(lib().sf_trace_shadows_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr),
+                                                     ctypes.c_void_p(d.ptr + pos.nbytes)), "sf_trace_shadows_to",
+                           self._ctx)
+                    # (the scratch is freed on leaving: the trace that reads and writes it must be done)
+                    _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
+                d.download(pos.nbytes, mask)
+            del keep
+            return mask
+        optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
+        if pos is None:
+            p, keep = self.shadows_params(lights, None, bias, origin, 0, 0, max_depth, stream)
+            with self._mutex:
+                if optr:
+                    _check(lib().sf_trace_shadows_to(self._ctx, ctypes.byref(p), None, ctypes.c_void_p(optr)),
+                           "sf_trace_shadows_to", self._ctx)
+                else:
+                    _check(lib().sf_trace_shadows(self._ctx, ctypes.byref(p)), "sf_trace_shadows", self._ctx)
+            del keep
+            return None
+        if hasattr(pos, "data_ptr"):
+            shape = tuple(pos.shape)
+            if len(shape) != 3 or shape[-1] != 4 or not (pos.is_cuda and pos.is_contiguous() and pos.element_size() == 4
+                                                         and pos.dtype.is_floating_point):
+                raise ValueError("pos must be a contiguous float32 CUDA tensor [H, W, 4]")
+            pptr, W, H = pos.data_ptr(), shape[1], shape[0]
+        else:
+            pptr, W, H = (int(x) for x in pos)
+        if not optr:
+            raise ValueError("a device position image needs an `out` buffer")
+        p, keep = self.shadows_params(lights, None, bias, origin, W, H, max_depth, stream)
+        with self._mutex:
+            _check(lib().sf_trace_shadows_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(pptr), ctypes.c_void_p(optr)),
+                   "sf_trace_shadows_to", self._ctx)
+        del keep
+        return None
+
+    def download_shadow_masks(self) -> np.ndarray:
+        """[H, W] uint64 of the last trace_shadows() into the context's mask buffer (synchronous)."""
+        mask = np.empty((self.height, self.width), np.uint64)
+        with self._mutex:
+            _check(lib().sf_download_shadow_masks(self._ctx, mask.ctypes.data_as(ctypes.c_void_p)),
+                   "sf_download_shadow_masks", self._ctx)
+        return mask
+
+    def shadow_mask_buffer(self) -> int:
+        """Device address of the context's mask buffer (0 before any trace_shadows() into it)."""
+        ptr = ctypes.c_void_p()
+        _check(lib().sf_shadow_mask_buffer(self._ctx, ctypes.byref(ptr)), "sf_shadow_mask_buffer")
+        return ptr.value or 0
+
+    def light_image_many(self, lights, weights=None, ambient=0.25, origin=None, pos_ptr=0, nrm_ptr=0, mask_ptr=0,
+                         rgba_ptr=0, stream=None):
+        """Scale the image of PostProcess() in place by ambient + (1 - ambient) x sum_i w_i (lit_i ? Lambert_i : 0)
+        over the lights (sf_light_image_many; sphereflake_amd.lights.light_model_many). weights None: 1 / n each.
+        Pointers are device addresses, 0 = the context's G-buffer, mask buffer (trace_shadows()) and image.
+        Asynchronous."""
+        p, keep = self.shadows_params(lights, weights, None, origin, 0, 0, 0, stream)
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        with self._mutex:
+            _check(lib().sf_light_image_many(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
+                                             vp(mask_ptr), vp(rgba_ptr)), "sf_light_image_many", self._ctx)
+        del keep
 
     def Synchronize(self):
         _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)

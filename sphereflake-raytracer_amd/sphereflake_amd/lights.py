@@ -74,3 +74,117 @@ def light_model(rgba, pos4, nrm4, vis, origin, light, ambient=0.25):
     surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
     out[..., :3] = np.where(surface[..., None], rgb.astype(np.uint8), out[..., :3])
     return out
+
+
+# --- many lights per pixel (sf_trace_shadows_to, sf_light_image_many) ---------------------------------------------
+LIGHTS_MAX = 64          # SF_SHADOW_LIGHTS_MAX: one bit of the mask word per light
+_GOLDEN = np.pi * (3.0 - np.sqrt(5.0))   # the golden angle
+
+
+def _count(n):
+    n = int(n)
+    if not 1 <= n <= LIGHTS_MAX:
+        raise ValueError(f"1..{LIGHTS_MAX} lights, not {n}")
+    return n
+
+
+def masks_from_vis(vis_list):
+    """The mask word of trace_shadows from the visibility bytes of trace_shadow, one image per light in the lights'
+    order: bit i = (vis_list[i] != 0), bits len(vis_list)..63 zero. uint64, the images' shape."""
+    n = _count(len(vis_list))
+    mask = np.zeros(np.asarray(vis_list[0]).shape, np.uint64)
+    for i in range(n):
+        mask |= (np.asarray(vis_list[i]) != 0).astype(np.uint64) << np.uint64(i)
+    return mask
+
+
+def vis_from_masks(mask, n):
+    """The inverse: n visibility images (255 / 0) from the mask words."""
+    mask = np.asarray(mask, np.uint64)
+    return [np.where((mask >> np.uint64(i)) & np.uint64(1), 255, 0).astype(np.uint8) for i in range(_count(n))]
+
+
+def light_model_many(rgba, pos4, nrm4, mask, origin, lights, weights=None, ambient=0.25):
+    """What sf_light_image_many makes of the RGBA8 image `rgba` [..., 4]: a new uint8 array. mask [...] are the words
+    of trace_shadows for the same lights [n, 3]; weights [n] (None: float32(1) / float32(n) each).
+
+    A miss pixel stays; else S = 0, then for i = 0 .. n-1 in that order S = S + w_i (bit i ? lam_i : 0) with lam_i
+    exactly light_model's lam for light i, k = ambient + (1 - ambient) S (S is not clamped), and each of r, g, b
+    becomes uint8(min(c k + 0.5, 255)); alpha stays."""
+    a = _F(ambient)
+    if not 0.0 <= float(a) <= 1.0:
+        raise ValueError("ambient must be in [0, 1]")
+    L = np.asarray(lights, _F).reshape(-1, 3)
+    n = _count(L.shape[0])
+    if weights is None:
+        w = np.full(n, _F(1.0) / _F(n), _F)
+    else:
+        w = np.asarray(weights, _F).reshape(-1)
+        if w.shape[0] != n or not (w >= 0).all():
+            raise ValueError("one weight per light, none negative or NaN")
+    out = np.array(rgba, np.uint8, copy=True)
+    P, wpos = _world(pos4, origin)
+    nr = np.asarray(nrm4, _F)[..., :3]
+    mask = np.asarray(mask, np.uint64)
+    S = np.zeros(P.shape[:-1], _F)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for i in range(n):
+            l = L[i]
+            length = _length((wpos - l) + _F(0.0))
+            e = l - wpos
+            dot = (nr[..., 0] * e[..., 0] + nr[..., 1] * e[..., 1]) + nr[..., 2] * e[..., 2]
+            lam = np.fmax(_F(0.0), dot / length)
+            bit = ((mask >> np.uint64(i)) & np.uint64(1)) != 0
+            S = S + w[i] * np.where(bit, lam, _F(0.0)).astype(_F)
+        k = a + (_F(1.0) - a) * S
+        rgb = np.fmin(out[..., :3].astype(_F) * k[..., None] + _F(0.5), _F(255.0))
+    assert S.dtype == _F and rgb.dtype == _F
+    surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
+    out[..., :3] = np.where(surface[..., None], rgb.astype(np.uint8), out[..., :3])
+    return out
+
+
+def disc(centre, radius, n):
+    """n points of a sunflower disc of `radius` about `centre` that faces the flake's centre (the world origin): an
+    area light's samples. In float64 a = -c / |c|, u = normalize(a x (0, 0, 1)), v = a x u, r_i = radius
+    sqrt((i + 0.5) / n), theta_i = i pi (3 - sqrt 5), point c + r_i cos(theta_i) u + r_i sin(theta_i) v; float32
+    [n, 3]. Deterministic. (A centre on the z axis has no such u: ValueError.)"""
+    n = _count(n)
+    c = np.asarray(centre, np.float64).reshape(3)
+    norm = np.linalg.norm(c)
+    if not norm > 0:
+        raise ValueError("the disc's centre must not be the flake's centre")
+    a = -c / norm
+    u = np.cross(a, (0.0, 0.0, 1.0))
+    if not np.linalg.norm(u) > 0:
+        raise ValueError("a disc centred on the z axis has no horizontal direction")
+    u = u / np.linalg.norm(u)
+    v = np.cross(a, u)
+    i = np.arange(n, dtype=np.float64)
+    r = float(radius) * np.sqrt((i + 0.5) / n)
+    th = i * _GOLDEN
+    pts = c + (r * np.cos(th))[:, None] * u + (r * np.sin(th))[:, None] * v
+    return pts.astype(_F)
+
+
+def sky(n, radius=4.0, up=(0.0, 0.0, 1.0)):
+    """n points of a Fibonacci upper hemisphere of `radius` about the flake's centre (the world origin), the pole
+    along `up`: the lights of a ray-traced sky occlusion term (keep radius > 2: outside the flake's bounding ball).
+    In float64 z_i = (i + 0.5) / n along `up`, s_i = sqrt(1 - z_i^2), theta_i = i pi (3 - sqrt 5), point
+    radius (s_i cos(theta_i) e1 + s_i sin(theta_i) e2 + z_i up) with e1, e2 completing `up` to a right-handed
+    frame; float32 [n, 3]. Deterministic."""
+    n = _count(n)
+    w = np.asarray(up, np.float64).reshape(3)
+    if not np.linalg.norm(w) > 0:
+        raise ValueError("up must not be zero")
+    w = w / np.linalg.norm(w)
+    t = np.array((1.0, 0.0, 0.0)) if abs(w[0]) < 0.9 else np.array((0.0, 1.0, 0.0))
+    e1 = t - w * np.dot(t, w)
+    e1 = e1 / np.linalg.norm(e1)
+    e2 = np.cross(w, e1)
+    i = np.arange(n, dtype=np.float64)
+    z = (i + 0.5) / n
+    s = np.sqrt(1.0 - z * z)
+    th = i * _GOLDEN
+    pts = float(radius) * ((s * np.cos(th))[:, None] * e1 + (s * np.sin(th))[:, None] * e2 + z[:, None] * w)
+    return pts.astype(_F)
