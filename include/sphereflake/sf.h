@@ -233,7 +233,8 @@ int sf_probe_rays(sf_ctx* ctx, const float* origins3, const float* dirs3, uint32
    CONSEQUENCES, not engineered away:
    - THE LEVEL OF DETAIL IS THE LIGHT'S. A node refines while sqrt(t / r) < 70 with t measured FROM THE LIGHT
      (Sphereflake.h:146), not from the camera: a distant light -- a "directional" one placed far off -- casts coarse
-     shadows, and spheres the camera sees may cast none.
+     shadows, and spheres the camera sees may cast none. sf_set_shadow_lod below replaces the 70 for the shadow
+     traces; a directional light proper is sf_trace_sun_to.
    - A LIGHT INSIDE THE RADIUS-2 BALL gets the reference's answer, quirk included: spheres whose centre is behind a
      ray, as seen from the light, do not occlude.
    - Self-shadow acne is governed by the bias b: the camera's and the light's traversals stop at different levels of
@@ -324,6 +325,76 @@ int sf_shadow_mask_buffer(sf_ctx* ctx, uint64_t** mask);
    sphereflake_amd/lights.py: light_model_many. */
 int sf_light_image_many(sf_ctx* ctx, const sf_shadows_params* params, float ambient, const float* pos4,
                         const float* nrm4, const uint64_t* mask, uint8_t* rgba);
+
+/* --- the level of detail of the shadow traces -------------------------------- */
+/* THE LEVEL OF DETAIL IS THE LIGHT'S (above) because a shadow ray refines a node while sqrtf(t / r) < C with t measured
+   from the ray's origin and C the variant's constant (70 AVX, 60 SSE). This sets C for the shadow traces -- and for
+   them only: sf_trace_shadow(_to), sf_trace_shadows(_to) and sf_trace_sun(_to). In their definitions "the reference's
+   ray" then reads "the reference's ray with C in place of the variant's constant in sqrtf(t / r) < C || t < 0
+   (Sphereflake.h:146, SSE :129)"; the oracle takes the same constant (sfo_set_lod_constant). C == 0 (the default) means
+   the variant's own, so a context that never calls this traces what it always traced. Renders, sf_trace_dirs_to,
+   sf_trace_rays_to, the frame-less mode and the multi-GPU paths keep the variant's constant whatever is set here.
+   A ray refined with C sees what a viewer (C / C_variant)^2 times nearer would: to give a light at distance D from a
+   surface the detail the camera has at distance t_ref, C = C_variant sqrt(D / t_ref)
+   (sphereflake_amd/lights.py: matched_lod). Synchronous (drains the context, as sf_set_variant does). SF_EINVAL for a
+   NaN, negative or infinite C. A larger C goes deeper: levels beyond SF_MAX_DEPTH_LIMIT are not traced. */
+int sf_set_shadow_lod(sf_ctx* ctx, float lod_constant);
+float sf_get_shadow_lod(const sf_ctx* ctx);   /* the value set (0 = the variant's own); NaN for a null ctx */
+
+/* --- shadows from a directional light ---------------------------------------- */
+/* A sun: every shadow ray is parallel to s, the direction TOWARDS the light (the reference's one directional light is
+   lightDir = (0.7, 0.7, 0.2), Shaders/post_final.glsl:11). A point light placed far off is no substitute: its level
+   of detail falls with its distance, and so does the precision of the light-relative centres. Here pixel p's ray
+   starts at its own origin F, a fixed distance tau up the sun direction from its own surface point, and runs down to
+   it: the mixed-origin traversal of sf_trace_rays_to, in an any-hit mode, fused with the read of the position image.
+   DEFINITION (exact). Inputs: a position image pos4 and its origin o as for sf_trace_shadow_to, s = dir (used AS
+   GIVEN: not normalised here -- sphereflake_amd/lights.py sun_direction normalises), tau = distance, a relative bias b
+   in [0, 1). All arithmetic is binary32, round to nearest, every operation rounded on its own (no fused
+   multiply-add). For pixel p with P = pos4[p].xyz:
+     1. P == (0, 0, 0) is a miss of the frame: vis[p] = 255, no ray.
+     2. w = o + P per component; f = s tau per component; F = w + f per component.
+     3. d = (w - F) + 0.0f per component; len = sqrt((d.x d.x + d.y d.y) + d.z d.z), correctly rounded;
+        bound = len (1.0f - b).
+     4. The ray is sf_trace_rays_to's ray from the origin F with direction Normalize(d): the root transform's columns
+        0..2 are the context's, its column 3 is 0 - F; the context's child frames and variant; the shadow LOD constant
+        (sf_set_shadow_lod).
+     5. With m the min_t of that ray: vis[p] = (m < bound) ? 0 : 255.
+     6. A d that does not normalise to finite numbers, or an F that is not finite (a non-finite or zero dir among
+        them), misses the root: vis[p] = 255.
+   sphereflake_amd/lights.py (sun_model) states steps 1-3 on the host.
+   CONSEQUENCES:
+   - tau >= 4 puts every F outside the flake's bounding ball (radius 2; |w| <= 2 for a surface point and |s| = 1), where
+     THE REFERENCE'S QUIRK cannot bite. A smaller tau gets the reference's answer, quirk included.
+   - THE LEVEL OF DETAIL IS THAT OF A VIEWER AT DISTANCE tau from each surface point -- the same for every pixel, and
+     the caller's choice. sf_set_shadow_lod with matched_lod(tau, t_ref) makes it the camera's at camera distance t_ref
+     (e.g. sf_get_stats' closest).
+   - Self-shadow acne is governed by the bias, as for sf_trace_shadow_to. */
+typedef struct sf_sun_params {
+    float dir[3];             /* s, towards the sun, world space, as given */
+    float distance;           /* tau, finite and > 0 (sf_sun_defaults: 4) */
+    float bias;               /* as sf_shadow_params.bias */
+    float origin[3];          /* as sf_shadow_params.origin */
+    uint32_t use_origin;      /* as sf_shadow_params.use_origin */
+    uint32_t width, height;   /* as sf_shadow_params */
+    uint32_t max_depth;       /* levels to provision; 0 = 12, as sf_rays_params.max_depth (the rays have no common
+                                 origin to bound them from); flagged tiles are re-traced at SF_MAX_DEPTH_LIMIT */
+    void* stream;             /* NULL = the context stream */
+} sf_sun_params;
+
+/* dir (0, 0, 1), distance 4, the default bias of sf_shadow_defaults, the rest zero. */
+int sf_sun_defaults(const sf_ctx* ctx, sf_sun_params* params);
+/* As sf_trace_shadow_to in every respect but the light: pos4 DEVICE or NULL = the context's G-buffer, vis DEVICE
+   width * height bytes, asynchronous on the stream and ordered with the context's other calls, no statistic and none
+   of the renders' state touched, re-traced tiles counted in overflow_tiles. Errors as sf_trace_shadow_to's, and
+   SF_EINVAL for a distance that is not finite and > 0. */
+int sf_trace_sun_to(sf_ctx* ctx, const sf_sun_params* params, const float* pos4, uint8_t* vis);
+/* The context's G-buffer into the context's visibility buffer -- the one sf_trace_shadow writes: sf_download_shadow
+   and sf_shadow_buffer serve both. */
+int sf_trace_sun(sf_ctx* ctx, const sf_sun_params* params);
+/* sf_light_image for a sun: identical but for lam = max(0, (n.x s.x + n.y s.y) + n.z s.z) (0 where that is NaN) --
+   no light position, no division. params: dir, stream. sphereflake_amd/lights.py: light_model_sun. */
+int sf_light_image_sun(sf_ctx* ctx, const sf_sun_params* params, float ambient, const float* pos4, const float* nrm4,
+                       const uint8_t* vis, uint8_t* rgba);
 
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the

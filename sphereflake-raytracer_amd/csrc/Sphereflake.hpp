@@ -219,6 +219,35 @@ public:
         Check(sf_light_image_many(m_Ctx, &params, ambient, positions4, normals4, masks, rgba));
     }
 
+    // The LOD constant of the shadow traces (new; sf_set_shadow_lod, sf.h): TraceShadow, TraceShadows and TraceSun
+    // refine a node while sqrtf(t / r) < lodConstant; 0 = the variant's own (the default). Render() is not affected.
+    void SetShadowLod(float lodConstant)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_set_shadow_lod(m_Ctx, lodConstant));
+    }
+    // Shadows from a directional light (new; sf_trace_sun_to / sf_trace_sun, sf.h): every pixel's ray runs down the
+    // sun direction from params.distance above its own surface point. visibility as TraceShadow's. DEVICE pointers,
+    // asynchronous; positions4 null = this object's own frame.
+    void TraceSun(const sf_sun_params& params, const float* positions4, uint8_t* visibility)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_sun_to(m_Ctx, &params, positions4, visibility));
+    }
+    // ... of this object's own device frame into its own visibility buffer (sf_download_shadow, LightImageSun)
+    void TraceSun(const sf_sun_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_sun(m_Ctx, &params));
+    }
+    // Lambert term and shadow of that sun on the image of an SSAO::Render(), in place (sf_light_image_sun)
+    void LightImageSun(const sf_sun_params& params, float ambient = 0.25f, const float* positions4 = nullptr,
+                       const float* normals4 = nullptr, const uint8_t* visibility = nullptr, uint8_t* rgba = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_image_sun(m_Ctx, &params, ambient, positions4, normals4, visibility, rgba));
+    }
+
     // the device frame, downloaded into the vectors when it is newer than their contents (Refresh)
     const GBuffer& GetGBuffer() const
     {

@@ -70,6 +70,13 @@ extern "C" __global__ void sf_trace_shadows_fixup(FrameArgs a, const float* pos4
                                                   const uint32_t* overflow_list, uint32_t* counters, uint32_t parity);
 extern "C" __global__ void sf_light_image_many_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
                                                   const uint64_t* mask, ShadowLights sl, float ambient, uint8_t* rgba);
+extern "C" __global__ void sf_trace_sun_wave(FrameArgs a, const float* pos4, SunArgs sa, uint8_t* vis, uint32_t groups,
+                                             uint32_t* overflow_list, uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_sun_fixup(FrameArgs a, const float* pos4, SunArgs sa, uint8_t* vis,
+                                              const uint32_t* overflow_list, uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_light_image_sun_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
+                                                 const uint8_t* vis, float sx, float sy, float sz, float ambient,
+                                                 uint8_t* rgba);
 extern "C" __global__ void sf_band_unpack(FrameArgs a, const float4* stage, uint32_t stage_rows, uint32_t band_rows,
                                            uint32_t n, uint32_t first, uint32_t members, uint32_t row0);
 extern "C" __global__ void sf_node_table(FrameArgs a, float4* table, uint32_t nodes);
@@ -197,6 +204,10 @@ struct sf_ctx {
     uint32_t slab_cache_next = 0;
     DeviceConsts* consts = nullptr;
     DeviceConsts host_consts;
+    // the shadow traces' block (sf_set_shadow_lod): the same but for the depth tables' LOD constant
+    DeviceConsts* shadow_consts = nullptr;
+    DeviceConsts host_shadow_consts;
+    float shadow_lod = 0.0f;           // 0: the variant's own constant
     float child[9][16];
     float root[16];
     float o[3], tl[3], tr[3], bl[3];
@@ -424,6 +435,7 @@ static void free_ctx(sf_ctx* c)
     (void)hipFree(c->ovf_list);
     (void)hipFree(c->node_table);
     (void)hipFree(c->consts);
+    (void)hipFree(c->shadow_consts);
     (void)hipFree(c->mt_state);
     (void)hipFree(c->draws);
     (void)hipFree(c->lanes);
@@ -483,32 +495,51 @@ static void free_ctx(sf_ctx* c)
     delete c;
 }
 
-static int upload_consts(sf_ctx* c)
+static float variant_lod(const sf_ctx* c) { return c->variant == SF_VARIANT_SSE ? 60.0f : 70.0f; }
+
+// the context's constant block for the LOD constant `lod_constant`, on the host
+static void fill_consts(const sf_ctx* c, DeviceConsts* h, float lod_constant)
 {
-    std::memcpy(c->host_consts.child, c->child, sizeof c->child);
-    sfhost::depth_tables(&c->host_consts.dt, c->variant == SF_VARIANT_SSE ? 60.0f : 70.0f);
+    std::memcpy(h->child, c->child, sizeof c->child);
+    sfhost::depth_tables(&h->dt, lod_constant);
     for (int d = 0; d < SF_DEPTH_TABLE; ++d) {
-        float* e = c->host_consts.depth8[d];
-        e[0] = c->host_consts.dt.r2_bound[d];
-        e[1] = c->host_consts.dt.r2_self[d];
-        e[2] = c->host_consts.dt.scale[d];
-        e[3] = c->host_consts.dt.lod[d];
-        e[4] = sfhost::leaf_threshold(&c->host_consts.dt, (uint32_t)d);
+        float* e = h->depth8[d];
+        e[0] = h->dt.r2_bound[d];
+        e[1] = h->dt.r2_self[d];
+        e[2] = h->dt.scale[d];
+        e[3] = h->dt.lod[d];
+        e[4] = sfhost::leaf_threshold(&h->dt, (uint32_t)d);
         e[5] = std::nextafter((float)(std::sqrt((double)e[0]) * (1.0 + 2.0 * (double)SF_OCCL_MARGIN)), FLT_MAX);
         e[6] = std::nextafter((float)((double)e[3] + std::sqrt((double)e[0]) * (1.0 + 0x1p-18)), FLT_MAX);
         e[7] = 0.0f;
     }
-    std::memcpy(c->host_consts.lut, kLut, sizeof kLut);
-    sfhost::sobol_matrices(c->host_consts.sobol);
-    c->host_consts.rw = 1.0f / (float)c->W;
-    c->host_consts.rh = 1.0f / (float)c->H;
-    c->host_consts.fast_div = c->fast_div ? 1u : 0u;
-    c->host_consts.tx_magic = 0xffffffffu / ((c->W + 7) / 8);
+    std::memcpy(h->lut, kLut, sizeof kLut);
+    sfhost::sobol_matrices(h->sobol);
+    h->rw = 1.0f / (float)c->W;
+    h->rh = 1.0f / (float)c->H;
+    h->fast_div = c->fast_div ? 1u : 0u;
+    h->tx_magic = 0xffffffffu / ((c->W + 7) / 8);
+}
+
+// The shadow traces' block alone (sf_set_shadow_lod; the child frames and the variant as they stand).
+static int upload_shadow_consts(sf_ctx* c)
+{
+    fill_consts(c, &c->host_shadow_consts, c->shadow_lod > 0.0f ? c->shadow_lod : variant_lod(c));
+    if (int rc_ = ctx_drain(c)) return rc_;   // no kernel of the context may still read the block
+    SF_HIP(c, hipMemcpyAsync(c->shadow_consts, &c->host_shadow_consts, sizeof(DeviceConsts), hipMemcpyHostToDevice,
+                             c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+    return SF_OK;
+}
+
+static int upload_consts(sf_ctx* c)
+{
+    fill_consts(c, &c->host_consts, variant_lod(c));
     if (int rc_ = ctx_drain(c)) return rc_;   // no kernel of the context may still read the block
     ++c->consts_gen;
     SF_HIP(c, hipMemcpyAsync(c->consts, &c->host_consts, sizeof(DeviceConsts), hipMemcpyHostToDevice, c->stream));
     SF_HIP(c, hipStreamSynchronize(c->stream));
-    return SF_OK;
+    return upload_shadow_consts(c);   // (the children or the variant changed: the shadow traces' block follows)
 }
 
 static int reset_stats_dev(sf_ctx* c, int which)
@@ -673,6 +704,7 @@ int sf_create(int device, uint32_t width, uint32_t height, sf_ctx** out)
     if ((e = hipMalloc(&c->chunk_off, nchunks * SF_ORDER_BUCKETS * 4)) != hipSuccess) return fail(e);
     if ((e = hipMemsetAsync(c->chunk_cnt, 0, nchunks * SF_ORDER_BUCKETS * 4, c->stream)) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&c->consts, sizeof(DeviceConsts))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&c->shadow_consts, sizeof(DeviceConsts))) != hipSuccess) return fail(e);
     if ((e = hipHostMalloc(&c->h_depth, 4, hipHostMallocDefault)) != hipSuccess) return fail(e);
     if ((e = hipHostMalloc(&c->h_stats, 16, hipHostMallocDefault)) != hipSuccess) return fail(e);
     *c->h_depth = -1;
@@ -803,7 +835,8 @@ static int order_rebuild(sf_ctx* c, hipStream_t s, uint32_t ntiles, uint32_t wav
 // (geometric_levels: the bound alone -- it speaks of the origin and the root ball only, so it holds for rays of any
 // direction, sf_trace_dirs_to; frame_levels: narrowed by the deepest depth a finished render of the frame saw)
 // (centre: the root centre relative to the rays' origin -- the view's root translation, or 0 - light for sf_trace_shadow_to)
-static uint32_t geometric_levels(const sf_ctx* c, const float centre[3], bool* bounded_out)
+// (dt: the depth tables the trace runs on -- the context's, or the shadow traces' own, sf_set_shadow_lod)
+static uint32_t geometric_levels(const DepthTables& dt, const float centre[3], bool* bounded_out)
 {
     uint32_t levels = kDefaultLevels;
     const float rc = std::sqrt(centre[0] * centre[0] + centre[1] * centre[1] + centre[2] * centre[2]);
@@ -811,7 +844,7 @@ static uint32_t geometric_levels(const sf_ctx* c, const float centre[3], bool* b
     bool bounded = false;
     if (gap > 0.0f) {
         uint32_t dmax = 0;
-        while (dmax + 1u < SF_DEPTH_TABLE && c->host_consts.dt.lod[dmax + 1u] > gap) ++dmax;
+        while (dmax + 1u < SF_DEPTH_TABLE && dt.lod[dmax + 1u] > gap) ++dmax;
         levels = dmax + 1u;
         bounded = levels <= SF_MAX_DEPTH_LIMIT;
     }
@@ -820,7 +853,7 @@ static uint32_t geometric_levels(const sf_ctx* c, const float centre[3], bool* b
 }
 static uint32_t geometric_levels(const sf_ctx* c, bool* bounded_out)
 {
-    return geometric_levels(c, c->root + 12, bounded_out);
+    return geometric_levels(c->host_consts.dt, c->root + 12, bounded_out);
 }
 
 static uint32_t frame_levels(const sf_ctx* c, bool* bounded_out)
@@ -1359,8 +1392,9 @@ int sf_trace_shadow_to(sf_ctx* c, const sf_shadow_params* p, const float* pos4, 
     a.tiles_x = tiles_x;
     const float centre[3] = { 0.0f - sa.l[0], 0.0f - sa.l[1], 0.0f - sa.l[2] };   // (Sphereflake.cpp:83 at the light)
     for (int k = 0; k < 3; ++k) a.root[9 + k] = centre[k];
+    a.consts = c->shadow_consts;   // (sf_set_shadow_lod)
     bool bounded = false;
-    a.max_depth = p->max_depth ? p->max_depth : geometric_levels(c, centre, &bounded);
+    a.max_depth = p->max_depth ? p->max_depth : geometric_levels(c->host_shadow_consts.dt, centre, &bounded);
     if (a.max_depth < 4u) a.max_depth = 4u;
     if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
     a.stats = nullptr;   // (no statistic is touched)
@@ -1503,13 +1537,14 @@ int sf_trace_shadows_to(sf_ctx* c, const sf_shadows_params* p, const float* pos4
     a.H = H;
     a.tiles_x = tiles_x;
     for (int k = 0; k < 3; ++k) a.root[9 + k] = 0.0f;   // (the kernel stages each light's own translation)
+    a.consts = c->shadow_consts;   // (sf_set_shadow_lod)
     uint32_t levels = p->max_depth;
     if (!levels)
         for (uint32_t i = 0; i < sl.n; ++i) {
             const float centre[3] = { 0.0f - sl.l[i][0], 0.0f - sl.l[i][1], 0.0f - sl.l[i][2] };
             if (!std::isfinite(centre[0] + centre[1] + centre[2])) continue;   // (traces nothing)
             bool bounded = false;
-            const uint32_t li = geometric_levels(c, centre, &bounded);
+            const uint32_t li = geometric_levels(c->host_shadow_consts.dt, centre, &bounded);
             if (li > levels) levels = li;
         }
     a.max_depth = levels;
@@ -1578,6 +1613,126 @@ int sf_light_image_many(sf_ctx* c, const sf_shadows_params* p, float ambient, co
     hipLaunchKernelGGL(sf_light_image_many_px, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
                        nrm4 ? nrm4 : (const float*)c->nrm, mask ? mask : (const uint64_t*)c->shadow_masks, sl, ambient,
                        rgba ? rgba : c->image);
+    SF_HIP(c, hipGetLastError());
+    return SF_OK;
+}
+
+// The LOD constant of the shadow traces (sf.h): a second constant block, the context's own but for the
+// depth tables, which sf_trace_shadow_to, sf_trace_shadows_to and sf_trace_sun_to hand their kernels. No kernel knows.
+int sf_set_shadow_lod(sf_ctx* c, float lod_constant)
+{
+    if (!c || !(lod_constant >= 0.0f) || std::isinf(lod_constant)) return SF_EINVAL;   // (NaN fails the compare)
+    if (lod_constant == c->shadow_lod) return SF_OK;
+    DevGuard g(c->device);
+    const float before = c->shadow_lod;
+    c->shadow_lod = lod_constant;
+    const int rc = upload_shadow_consts(c);
+    if (rc != SF_OK) c->shadow_lod = before;
+    return rc;
+}
+
+float sf_get_shadow_lod(const sf_ctx* c) { return c ? c->shadow_lod : NAN; }
+
+// Shadows from a directional light (sf.h; kernels sf_trace_sun_wave / sf_trace_sun_fixup / sf_light_image_sun_px,
+// DESIGN.md §6.13). Launched as sf_trace_shadow_to launches, with the context's own root columns (each lane forms its
+// own translation), the default levels of sf_trace_rays_to and the mixed traversal's LDS; shares the direction traces'
+// re-trace list and counters. Touches no statistic and none of the renders' state.
+int sf_sun_defaults(const sf_ctx* c, sf_sun_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->dir[2] = 1.0f;
+    p->distance = 4.0f;
+    p->bias = kShadowBias;
+    return SF_OK;
+}
+
+int sf_trace_sun_to(sf_ctx* c, const sf_sun_params* p, const float* pos4, uint8_t* vis)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!vis) return SF_EINVAL;
+    if (!(p->bias >= 0.0f && p->bias < 1.0f)) return SF_EINVAL;   // (NaN fails both)
+    if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
+    if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
+    if ((p->width == 0u) != (p->height == 0u)) return SF_EINVAL;
+    const uint32_t W = p->width ? p->width : c->W, H = p->height ? p->height : c->H;
+    if (!pos4 && (W != c->W || H != c->H)) return SF_EINVAL;
+    if ((uint64_t)W * H > 0x7fffffffull) return SF_EINVAL;   // (pixel indices are 32-bit in the kernel)
+    if (!pos4) pos4 = c->pos;
+    const uint32_t tiles_x = (W + 7u) / 8u;
+    const uint32_t groups = tiles_x * ((H + 7u) / 8u);
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    if (!c->dirs_cnt) {
+        SF_HIP(c, hipMalloc(&c->dirs_cnt, 3 * 4));
+        SF_HIP(c, hipMemsetAsync(c->dirs_cnt, 0, 3 * 4, s));
+    }
+    if (groups > c->dirs_cap) {   // grown on demand; an earlier trace may still write the old list
+        SF_HIP(c, hipStreamSynchronize(s));
+        (void)hipFree(c->dirs_ovf);
+        c->dirs_ovf = nullptr;
+        c->dirs_cap = 0;
+        SF_HIP(c, hipMalloc(&c->dirs_ovf, (size_t)groups * 4));
+        c->dirs_cap = groups;
+    }
+    SunArgs sa;
+    for (int k = 0; k < 3; ++k) {
+        sa.o[k] = p->use_origin ? p->origin[k] : c->o[k];
+        sa.f[k] = p->dir[k] * p->distance;   // (one rounding: step 2 of the definition)
+    }
+    sa.keep = 1.0f - p->bias;
+    FrameArgs a = frame_args(c);
+    a.W = W;
+    a.H = H;
+    a.tiles_x = tiles_x;
+    a.consts = c->shadow_consts;   // (sf_set_shadow_lod)
+    a.max_depth = p->max_depth ? p->max_depth : kDefaultLevels;
+    if (a.max_depth < 4u) a.max_depth = 4u;
+    if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
+    a.stats = nullptr;   // (no statistic is touched)
+    const size_t lds = (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4;
+    hipLaunchKernelGGL(sf_trace_sun_wave, dim3(groups), dim3(64), lds, s, a, pos4, sa, vis, groups, c->dirs_ovf,
+                       c->dirs_cnt + c->dirs_par);
+    SF_HIP(c, hipGetLastError());
+    const size_t lds_fix = (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4;
+    const uint32_t fb = groups < kRaysFixupBlocks ? groups : kRaysFixupBlocks;
+    hipLaunchKernelGGL(sf_trace_sun_fixup, dim3(fb), dim3(64), lds_fix, s, a, pos4, sa, vis,
+                       (const uint32_t*)c->dirs_ovf, c->dirs_cnt, c->dirs_par);
+    SF_HIP(c, hipGetLastError());
+    c->dirs_par ^= 1u;
+    return SF_OK;
+}
+
+int sf_trace_sun(sf_ctx* c, const sf_sun_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if ((p->width || p->height) && (p->width != c->W || p->height != c->H)) return SF_EINVAL;
+    if (!c->shadow) {
+        DevGuard g(c->device);
+        SF_HIP(c, hipMalloc(&c->shadow, (size_t)c->W * c->H));
+    }
+    return sf_trace_sun_to(c, p, nullptr, c->shadow);
+}
+
+int sf_light_image_sun(sf_ctx* c, const sf_sun_params* p, float ambient, const float* pos4, const float* nrm4,
+                       const uint8_t* vis, uint8_t* rgba)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!(ambient >= 0.0f && ambient <= 1.0f)) return SF_EINVAL;
+    if (!rgba && !c->image) return SF_ESTATE;
+    if (!vis && !c->shadow) return SF_ESTATE;
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
+    hipLaunchKernelGGL(sf_light_image_sun_px, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
+                       nrm4 ? nrm4 : (const float*)c->nrm, vis ? vis : (const uint8_t*)c->shadow, p->dir[0], p->dir[1],
+                       p->dir[2], ambient, rgba ? rgba : c->image);
     SF_HIP(c, hipGetLastError());
     return SF_OK;
 }

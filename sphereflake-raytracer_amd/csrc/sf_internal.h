@@ -198,6 +198,13 @@ struct ShadowArgs {
     float keep;                       // 1 - bias (sf_trace_shadow; unused by sf_light_image)
 };
 
+// Shadows from a directional light (sf_trace_sun_to): what the kernels take beside the FrameArgs
+struct SunArgs {
+    float o[3];                       // the origin the position image is relative to
+    float f[3];                       // s tau per component: from a surface point to its ray's origin
+    float keep;                       // 1 - bias
+};
+
 // Many lights per pixel in one launch (sf_trace_shadows_to, sf_light_image_many): the lights travel by value in the
 // kernel argument segment beside the FrameArgs (1044 B; indexed with a uniform index they are scalar loads)
 #define SF_SHADOW_LIGHTS 64u          // == SF_SHADOW_LIGHTS_MAX (sf.h): one bit of the mask word per light

@@ -3196,16 +3196,24 @@ namespace {
 // Index order, no cone, no front-first: the visits are the reference's, the ancestor rule of self_test the only tie
 // to handle. Lbase: root image (its axis columns are read; the centre is per lane: ocx, ocy, ocz) and `levels` level
 // tables, whose plane 0 holds the children's S instead of centres; cstk: the centre stack, `levels` x [3][64].
+// ANYHIT: the any-hit mode of sf_trace_sun, traverse_ray's SHADOW mode on per-lane origins: h.minT
+// starts at the lane's `bound`, a lane whose self test accepts (ts < bound; a tie is not `<`) is finished and leaves
+// actv and every bit of actbits, there is no ancestor bookkeeping, the occlusion cull keeps only its distance
+// condition, maxd is not maintained past 0, and the traversal ends when no lane is live. Only h.hit (the finished
+// lanes) is meaningful on return. SF_STATUS_ZSIGN is not raised: a zero's sign cannot reach a comparison (§6.13).
+template <bool ANYHIT = false>
 __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ K, float* __restrict__ Lbase,
                                                float* __restrict__ cstk, const float4 bcol, uint32_t levels, float dx,
                                                float dy, float dz, float ocx, float ocy, float ocz, bool valid,
-                                               HitState& h, int32_t& maxd, uint32_t& status, uint32_t K_flags)
+                                               HitState& h, int32_t& maxd, uint32_t& status, uint32_t K_flags,
+                                               float bound = FLT_MAX)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const TraverseLds L{ Lbase };
     const bool occl_cull = (K_flags & SF_FLAG_NO_OCCL_CULL) == 0u;
 
-    h.minT = FLT_MAX;
+    if constexpr (ANYHIT) h.minT = bound;
+    else h.minT = FLT_MAX;
     h.cx = h.cy = h.cz = 0.f;
     h.index = 0xffffffffu;
     h.depth = -1;
@@ -3230,7 +3238,9 @@ __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ 
                                    : SF_LDS_PLANE + bc * SF_LDS_COLS + bi * 3u;
 
     // (traverse_ray's self_test in index order: a tie is accepted where the best is an ancestor, else dropped)
-    auto self_test = [&](const float4 pc, float tca, float d2, uint32_t dd, float actv, uint32_t idx, float R2s) {
+    // (returns the accepting lanes: the any-hit mode's finished lanes)
+    auto self_test = [&](const float4 pc, float tca, float d2, uint32_t dd, float actv, uint32_t idx,
+                         float R2s) -> uint64_t {
         const uint64_t hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);
         if (hsm) {
             const float xs = R2s - d2;
@@ -3238,6 +3248,12 @@ __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ 
             if ((wave_ballot(!(xs >= 0x1p-96f)) & hsm) != 0ull) ts = near_root_exact(tca, d2, R2s);
             else ts = near_root_big(tca, xs);
             uint64_t accm = hsm & wave_ballot(ts < h.minT);
+            if constexpr (ANYHIT) {   // (the finished flag only)
+                uint32_t hd = (uint32_t)h.depth;
+                sel_in_place(hd, dd, accm);
+                h.depth = (int32_t)hd;
+                return accm;
+            }
             const uint64_t tie = hsm & wave_ballot(ts == h.minT);
             accm |= tie & ancm;
             sel_in_place(h.minT, ts, accm);
@@ -3249,7 +3265,9 @@ __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ 
             sel_in_place(hd, dd, accm);
             h.depth = (int32_t)hd;
             ancm |= accm;
+            return accm;
         }
+        return 0ull;
     };
 
     // (traverse_ray's child_lod)
@@ -3289,9 +3307,11 @@ __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ 
         const float x = (p0.x * b0 + p1.x * b1) + p2.x * b2;
         const float y = (p0.y * b0 + p1.y * b1) + p2.y * b2;
         const float z = (p0.z * b0 + p1.z * b1) + p2.z * b2;
-        const bool negz = bc != 3u && (__float_as_uint(x) == 0x80000000u || __float_as_uint(y) == 0x80000000u ||
-                                       __float_as_uint(z) == 0x80000000u);
-        if (wave_ballot(negz) != 0ull) status |= SF_STATUS_ZSIGN;
+        if constexpr (!ANYHIT) {
+            const bool negz = bc != 3u && (__float_as_uint(x) == 0x80000000u || __float_as_uint(y) == 0x80000000u ||
+                                           __float_as_uint(z) == 0x80000000u);
+            if (wave_ballot(negz) != 0ull) status |= SF_STATUS_ZSIGN;
+        }
         *reinterpret_cast<float3*>(tb + slot) = make_float3(x, y, z);
     };
 
@@ -3306,10 +3326,12 @@ __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ 
     uint32_t actbits;
     {
         const float av0 = ex0 ? __builtin_inff() : -1.0f;
-        self_test(make_float4(ocx, ocy, ocz, occ0), tca0, d20, 0u, av0, 0u, dt0.y);
+        const uint64_t acc0 = self_test(make_float4(ocx, ocy, ocz, occ0), tca0, d20, 0u, av0, 0u, dt0.y);
         // per lane: beyond the leaf threshold no child of the node can pass LOD for any ray (sfhost::leaf_threshold),
         // and a child is only ever tested for its own sphere once entered -- such a lane stops visiting here
-        const uint64_t live = wave_ballot(ex0 && !(occ0 > depth_leaf(K, 0u)));
+        // (any-hit mode: so does a lane the root's own sphere finished)
+        uint64_t live = wave_ballot(ex0 && !(occ0 > depth_leaf(K, 0u)));
+        if constexpr (ANYHIT) live &= ~acc0;
         if (live == 0ull) {
             h.hit = h.depth >= 0;
             return;
@@ -3346,22 +3368,33 @@ __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ 
                 status |= SF_STATUS_OVERFLOW;
                 break;
             }
-            if ((int32_t)d + 1 > maxd) {   // Sphereflake.h:157-160
+            if (!ANYHIT && (int32_t)d + 1 > maxd) {   // Sphereflake.h:157-160
                 maxd = (int32_t)d + 1;
                 cull_t = depth_consts_at(K, kofs + (1u << 5)).w;
             }
             // occlusion cull, per lane (see traverse_ray)
+            // (any-hit mode: the distance condition alone -- no sphere of the subtree nearer than the lane's bound)
             uint64_t amx = exm;
             if (occl_cull) {
-                const float v = __builtin_fminf(tca - h.minT, tca - cull_t);
+                float v = tca - h.minT;
+                if constexpr (!ANYHIT) v = __builtin_fminf(v, tca - cull_t);
                 amx = exm & ~wave_ballot(v - SF_OCCL_MARGIN * tca > dk.y);
                 if (amx == 0ull) continue;
             }
             const float avx = sel_mask(-1.0f, __builtin_inff(), amx);
-            self_test(make_float4(cx, cy, cz, cc), tca, d2, d + 1u, avx, idxB + c, dc.y);
+            const uint64_t acc = self_test(make_float4(cx, cy, cz, cc), tca, d2, d + 1u, avx, idxB + c, dc.y);
+            if constexpr (ANYHIT) {
+                if (acc != 0ull) {   // finished lanes leave the child, the open node and every ancestor
+                    amx &= ~acc;
+                    actv = sel_mask(actv, -1.0f, acc);
+                    sel_in_place(actbits, 0u, acc);
+                    if (wave_ballot(actbits != 0u) == 0ull) break;   // no lane is live
+                    if (amx == 0ull) continue;
+                }
+            }
             const uint64_t live = amx & ~wave_ballot(cc > dk.x);   // (the per-lane leaf cut, as at the root)
             if (live == 0ull) {
-                ancm &= wave_ballot(h.depth != (int32_t)d + 1);   // the child is finished
+                if constexpr (!ANYHIT) ancm &= wave_ballot(h.depth != (int32_t)d + 1);   // the child is finished
                 continue;
             }
             // push the open node, open child c
@@ -3835,6 +3868,112 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_fixup(FrameArg
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x)
         trace_shadows_group<true>(a, reinterpret_cast<const float4*>(pos4), sl, mask, lds, bcol, overflow_list[i],
                                   SF_MAX_LEVELS, nullptr, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// Shadows from a directional light (sf_trace_sun_to). Pixel p of a position image (as
+// sf_trace_shadow_wave reads it) is a frame miss where P == (0, 0, 0): vis = 255, no ray. Else w = o + P,
+// F = w + f with f = s tau (formed by the host: one product per component), d = (w - F) + 0,
+// len = sqrt((d.x d.x + d.y d.y) + d.z d.z), bound = len (1 - bias), every operation rounded on its own; the ray is
+// sf_trace_rays_to's ray from the origin F with direction Normalize(d), and vis = (its min_t < bound) ? 0 : 255. Every
+// lane has its own origin, so the tile takes the mixed-origin traversal (traverse_mixed) in its any-hit mode: the
+// context's axis columns staged once, the lane's own root centre 0 - F. One wave64 per 8x8 tile, the grouping and the
+// row store of sf_trace_shadow_wave.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+template <bool FIXUP>
+__device__ __forceinline__ void trace_sun_group(const FrameArgs& a, const float4* __restrict__ pos4, const SunArgs& sa,
+                                                uint8_t* __restrict__ vis, float* __restrict__ L, const float4 bcol,
+                                                uint32_t group, uint32_t levels, uint32_t* overflow_list,
+                                                uint32_t* overflow_count)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const uint32_t lane = threadIdx.x & 63u;
+    // the lane's pixel; a lane off the image edge loads the nearest pixel inside and traverses as an invalid lane
+    const uint32_t ty = group / a.tiles_x, tx = group - ty * a.tiles_x;
+    const uint32_t x = tx * SF_TILE + (lane & 7u), y = ty * SF_TILE + (lane >> 3);
+    const bool valid = x < a.W && y < a.H;
+    const uint32_t pix = (y < a.H ? y : a.H - 1u) * a.W + (x < a.W ? x : a.W - 1u);   // (< 2^31 pixels)
+    const float4 P = pos4[pix];
+    const bool surface = !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    const float wx = __fadd_rn(sa.o[0], P.x), wy = __fadd_rn(sa.o[1], P.y), wz = __fadd_rn(sa.o[2], P.z);
+    const float Fx = __fadd_rn(wx, sa.f[0]), Fy = __fadd_rn(wy, sa.f[1]), Fz = __fadd_rn(wz, sa.f[2]);
+    float dx = __fadd_rn(__fsub_rn(wx, Fx), 0.0f);
+    float dy = __fadd_rn(__fsub_rn(wy, Fy), 0.0f);
+    float dz = __fadd_rn(__fsub_rn(wz, Fz), 0.0f);
+    // (the correctly rounded square root, see trace_shadow_group)
+    const float len = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float bound = __fmul_rn(len, sa.keep);
+    normalize3(dx, dy, dz, K->lut);
+    // the lane's root centre (Sphereflake.cpp:83 at F)
+    const float rx = __fsub_rn(0.0f, Fx), ry = __fsub_rn(0.0f, Fy), rz = __fsub_rn(0.0f, Fz);
+    // a d that does not normalise to finite numbers misses (see trace_dir_group); an F that is not finite makes d so
+    auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
+    const bool on = valid && surface && finite(dx) && finite(dy) && finite(dz);
+    HitState h;
+    h.hit = false;
+    uint32_t status = 0u;
+    if (wave_ballot(on) != 0ull) {   // (uniform; else no ray of the group is traced)
+        const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;   // (the mixed traversal has no cone and no order)
+        float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
+        int32_t md = -1;
+        lds_fence();   // (the re-trace's earlier tile has read its tables)
+        traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, status, culls, bound);
+    }
+    if (!FIXUP && status != 0u) {   // (uniform) more levels needed
+        const uint32_t slot = wave_fetch_add(overflow_count, 1u);
+        overflow_list[slot] = group;   // uniform value and address
+    }
+    // ---- the tile's 64 results as a ballot, stored as trace_shadow_group stores them
+    const uint64_t litm = ~wave_ballot(h.hit);
+    const bool rows8 = (a.W & 7u) == 0u && (reinterpret_cast<uintptr_t>(vis) & 7u) == 0u &&
+                       tx * SF_TILE + SF_TILE <= a.W && ty * SF_TILE + SF_TILE <= a.H;   // (uniform)
+    if (rows8) {
+        if (lane < 8u) {
+            const uint64_t b = (litm >> (8u * lane)) & 0xffull;
+            const uint64_t s = (b * 0x0101010101010101ull) & 0x8040201008040201ull;   // byte k: bit k of b, in place
+            const uint64_t n = ((s + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;   // byte k: 1 if set
+            *reinterpret_cast<uint64_t*>(vis + (size_t)(ty * SF_TILE + lane) * a.W + tx * SF_TILE) = n * 0xffull;
+        }
+    } else if (valid) {
+        vis[(size_t)y * a.W + x] = h.hit ? (uint8_t)0 : (uint8_t)255;
+    }
+}
+
+}  // namespace
+
+// One tile per one-wave workgroup, dynamic LDS SF_LDS_RAYS_FLOATS(a.max_depth) (the mixed traversal's tables and
+// centre stack). Touches none of the context's statistics.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_sun_wave(FrameArgs a, const float* pos4, SunArgs sa,
+                                                                   uint8_t* vis, uint32_t groups,
+                                                                   uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    stage_root(lds, a.root);
+    trace_sun_group<false>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, build_column(a.consts), blockIdx.x,
+                           a.max_depth, overflow_list, overflow_count);
+}
+
+// Re-trace of the flagged tiles at SF_MAX_LEVELS (as sf_trace_shadow_fixup, whose list and counters it shares). The
+// mixed traversal reads the root image's columns and never writes it: staged once.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_sun_fixup(FrameArgs a, const float* pos4, SunArgs sa,
+                                                                    uint8_t* vis, const uint32_t* overflow_list,
+                                                                    uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    const uint32_t n = counters[parity];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        counters[parity ^ 1u] = 0u;
+        counters[2] += n;
+    }
+    if (blockIdx.x >= n) return;
+    stage_root(lds, a.root);
+    const float4 bcol = build_column(a.consts);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x)
+        trace_sun_group<true>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, bcol, overflow_list[i],
+                              SF_MAX_LEVELS, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------

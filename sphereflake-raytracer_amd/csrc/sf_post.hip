@@ -369,6 +369,28 @@ extern "C" __global__ void __launch_bounds__(256) sf_light_image_px(uint32_t W, 
     reinterpret_cast<uchar4*>(rgba)[px] = c;
 }
 
+// The same for a directional light (sf_light_image_sun, sf.h): lam = max(0, n . s) with s the
+// direction towards the sun as given -- no light position, no length, no division. sphereflake_amd/lights.py
+// (light_model_sun) restates it (tests/test_gpu_sun.py).
+extern "C" __global__ void __launch_bounds__(256) sf_light_image_sun_px(uint32_t W, uint32_t H, const float* pos4,
+                                                                     const float* nrm4, const uint8_t* vis, float sx,
+                                                                     float sy, float sz, float ambient, uint8_t* rgba)
+{
+    const uint32_t px = blockIdx.x * 256u + threadIdx.x;
+    if (px >= W * H) return;
+    const float4 P = ld4(pos4, px);
+    if (P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) return;   // a miss of the frame (post_final.glsl:20)
+    const float4 n = ld4(nrm4, px);
+    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(n.x, sx), __fmul_rn(n.y, sy)), __fmul_rn(n.z, sz));
+    const float lam = fmaxf(0.0f, dot);   // (a NaN product gives 0)
+    const float k = __fadd_rn(ambient, __fmul_rn(__fsub_rn(1.0f, ambient), vis[px] ? lam : 0.0f));
+    uchar4 c = reinterpret_cast<uchar4*>(rgba)[px];
+    c.x = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.x, k), 0.5f), 255.0f);
+    c.y = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.y, k), 0.5f), 255.0f);
+    c.z = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.z, k), 0.5f), 255.0f);
+    reinterpret_cast<uchar4*>(rgba)[px] = c;
+}
+
 // The same for many lights (sf_light_image_many, sf.h): one thread per pixel, S = sum over the lights
 // in index order of w_i (bit i of mask[p] ? lam_i : 0) with lam_i exactly sf_light_image_px's lam for light i, then
 // k = ambient + (1 - ambient) S (no clamp on S). The lights and weights are scalar loads from the argument segment.

@@ -82,6 +82,12 @@ class sf_shadows_params(ctypes.Structure):
                 ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
 
 
+class sf_sun_params(ctypes.Structure):
+    _fields_ = [("dir", ctypes.c_float * 3), ("distance", ctypes.c_float), ("bias", ctypes.c_float),
+                ("origin", ctypes.c_float * 3), ("use_origin", ctypes.c_uint32), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
 class sf_stats(ctypes.Structure):
     _fields_ = [("max_depth", ctypes.c_int32), ("closest", ctypes.c_float),
                 ("rays", ctypes.c_int64), ("overflow_tiles", ctypes.c_int64)]
@@ -136,6 +142,13 @@ SIGNATURES = {
     "sf_shadow_mask_buffer": (ctypes.c_int, [_CTX, ctypes.POINTER(ctypes.c_void_p)]),
     "sf_light_image_many": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shadows_params), ctypes.c_float, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_set_shadow_lod": (ctypes.c_int, [_CTX, ctypes.c_float]),
+    "sf_get_shadow_lod": (ctypes.c_float, [_CTX]),
+    "sf_sun_defaults": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_sun_params)]),
+    "sf_trace_sun_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_sun_params), ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_sun": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_sun_params)]),
+    "sf_light_image_sun": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_sun_params), ctypes.c_float, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_render_frames": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
                                         ctypes.POINTER(sf_render_params)]),
     "sf_slab_rows": (ctypes.c_uint32, [ctypes.c_uint32] * 4),
@@ -830,6 +843,13 @@ class Sphereflake:
           - a torch CUDA tensor [H, W, 4] (contiguous float32), or a (device address, width, height) tuple: zero
             copy, asynchronous; the result goes to `out`.
         out: a torch CUDA uint8 tensor of H x W elements, or a device address."""
+        return self._trace_vis(lambda W, H: self.shadow_params(light, bias, origin, W, H, max_depth, stream),
+                               "sf_trace_shadow", pos, out)
+
+    def _trace_vis(self, params, entry, pos, out):
+        """The `pos` / `out` forms of trace_shadow() and trace_sun(): params(width, height) makes the call's parameter
+        block; `entry` names the call into the context's own buffer, `entry`_to the one into a caller's."""
+        to, own = getattr(lib(), entry + "_to"), getattr(lib(), entry)
         if isinstance(pos, np.ndarray):
             pos = np.ascontiguousarray(pos, np.float32)
             if pos.ndim != 3 or pos.shape[-1] != 4:
@@ -840,25 +860,24 @@ class Sphereflake:
             vis = np.empty((H, W), np.uint8)
             if H * W == 0:
                 return vis
-            p = self.shadow_params(light, bias, origin, W, H, max_depth, stream)
+            p = params(W, H)
             with _DeviceScratch(self.device, pos.nbytes + H * W) as d:
                 d.upload(0, pos)
                 with self._mutex:
-                    _check(lib().sf_trace_shadow_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr),
-                                                    ctypes.c_void_p(d.ptr + pos.nbytes)), "sf_trace_shadow_to", self._ctx)
+                    _check(to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr), ctypes.c_void_p(d.ptr + pos.nbytes)),
+                           entry + "_to", self._ctx)
                     # (the scratch is freed on leaving: the trace that reads and writes it must be done)
                     _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
                 d.download(pos.nbytes, vis)
             return vis
         optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
         if pos is None:
-            p = self.shadow_params(light, bias, origin, 0, 0, max_depth, stream)
+            p = params(0, 0)
             with self._mutex:
                 if optr:
-                    _check(lib().sf_trace_shadow_to(self._ctx, ctypes.byref(p), None, ctypes.c_void_p(optr)),
-                           "sf_trace_shadow_to", self._ctx)
+                    _check(to(self._ctx, ctypes.byref(p), None, ctypes.c_void_p(optr)), entry + "_to", self._ctx)
                 else:
-                    _check(lib().sf_trace_shadow(self._ctx, ctypes.byref(p)), "sf_trace_shadow", self._ctx)
+                    _check(own(self._ctx, ctypes.byref(p)), entry, self._ctx)
             return None
         if hasattr(pos, "data_ptr"):
             shape = tuple(pos.shape)
@@ -870,10 +889,9 @@ class Sphereflake:
             pptr, W, H = (int(x) for x in pos)
         if not optr:
             raise ValueError("a device position image needs an `out` buffer")
-        p = self.shadow_params(light, bias, origin, W, H, max_depth, stream)
+        p = params(W, H)
         with self._mutex:
-            _check(lib().sf_trace_shadow_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(pptr), ctypes.c_void_p(optr)),
-                   "sf_trace_shadow_to", self._ctx)
+            _check(to(self._ctx, ctypes.byref(p), ctypes.c_void_p(pptr), ctypes.c_void_p(optr)), entry + "_to", self._ctx)
         return None
 
     def download_shadow(self) -> np.ndarray:
@@ -1012,6 +1030,51 @@ class Sphereflake:
             _check(lib().sf_light_image_many(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
                                              vp(mask_ptr), vp(rgba_ptr)), "sf_light_image_many", self._ctx)
         del keep
+
+    # the shadow traces' level of detail, shadows from a directional light (sf_set_shadow_lod, sf_trace_sun_to) -------
+    def set_shadow_lod(self, lod_constant):
+        """trace_shadow(), trace_shadows() and trace_sun() refine a node while sqrtf(t / r) < lod_constant instead of
+        the variant's 70 / 60; 0 restores the variant's own (the default). Nothing else is affected: Render(),
+        trace_dirs() and trace_rays() keep the variant's constant. sphereflake_amd.lights.matched_lod picks a value.
+        Synchronous."""
+        with self._mutex:
+            _check(lib().sf_set_shadow_lod(self._ctx, float(lod_constant)), "sf_set_shadow_lod", self._ctx)
+
+    def get_shadow_lod(self) -> float:
+        return float(lib().sf_get_shadow_lod(self._ctx))
+
+    def sun_params(self, direction, distance=None, bias=None, origin=None, width=0, height=0, max_depth=0, stream=None):
+        """sf_sun_defaults, overridden: distance and bias None keep the library's defaults (4, 2^-10)."""
+        p = sf_sun_params()
+        _check(lib().sf_sun_defaults(self._ctx, ctypes.byref(p)), "sf_sun_defaults")
+        p.dir[:] = [float(x) for x in _f32(direction, 3)]
+        if distance is not None:
+            p.distance = float(distance)
+        if bias is not None:
+            p.bias = float(bias)
+        if origin is not None:
+            p.origin[:] = [float(x) for x in _f32(origin, 3)]
+            p.use_origin = 1
+        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
+        return p
+
+    def trace_sun(self, direction, distance=None, bias=None, pos=None, out=None, origin=None, max_depth=0, stream=None):
+        """Which pixels of a position image does a directional light reach? `direction` points TOWARDS the sun (world,
+        used as given: sphereflake_amd.lights.sun_direction normalises); every pixel's ray starts `distance` up that
+        direction from its own surface point. 255 = lit or a miss of the frame, 0 = shadowed; the exact definition is
+        in sf.h and sphereflake_amd.lights.sun_model. `pos`, `out` and `origin` as trace_shadow's; the context's
+        visibility buffer is the one trace_shadow() writes (download_shadow(), light_image_sun() see it)."""
+        return self._trace_vis(lambda W, H: self.sun_params(direction, distance, bias, origin, W, H, max_depth, stream),
+                               "sf_trace_sun", pos, out)
+
+    def light_image_sun(self, direction, ambient=0.25, pos_ptr=0, nrm_ptr=0, vis_ptr=0, rgba_ptr=0, stream=None):
+        """Scale the image of PostProcess() in place by ambient + (1 - ambient) x (lit ? max(0, n . direction) : 0)
+        (sf_light_image_sun; sphereflake_amd.lights.light_model_sun). Pointers as light_image's. Asynchronous."""
+        p = self.sun_params(direction, None, None, None, 0, 0, 0, stream)
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        with self._mutex:
+            _check(lib().sf_light_image_sun(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
+                                            vp(vis_ptr), vp(rgba_ptr)), "sf_light_image_sun", self._ctx)
 
     def Synchronize(self):
         _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)

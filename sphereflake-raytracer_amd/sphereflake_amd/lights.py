@@ -8,6 +8,10 @@ A shadow ray is traced FROM THE LIGHT towards the surface point and its nearest 
 the point, so no ray starts on the flake and the reference's ``tca >= 0`` quirk (sphereflake_amd/rays.py) cannot
 bite while the light stays outside the flake's bounding ball (radius 2 about its centre). The level of detail is
 the light's: a node refines by its distance from the light, so a far light casts coarse shadows.
+
+A directional light (``Sphereflake.trace_sun`` / ``light_image_sun``: sun_model, light_model_sun, sun_direction)
+starts every pixel's ray a fixed distance up the sun direction from its own surface point instead, and
+``Sphereflake.set_shadow_lod`` with matched_lod chooses the level of detail of all the shadow traces.
 """
 from __future__ import annotations
 
@@ -68,6 +72,81 @@ def light_model(rgba, pos4, nrm4, vis, origin, light, ambient=0.25):
         e = l - w
         dot = (n[..., 0] * e[..., 0] + n[..., 1] * e[..., 1]) + n[..., 2] * e[..., 2]
         lam = np.fmax(_F(0.0), dot / length)
+        k = a + (_F(1.0) - a) * np.where(np.asarray(vis) != 0, lam, _F(0.0)).astype(_F)
+        rgb = np.fmin(out[..., :3].astype(_F) * k[..., None] + _F(0.5), _F(255.0))
+    assert rgb.dtype == _F
+    surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
+    out[..., :3] = np.where(surface[..., None], rgb.astype(np.uint8), out[..., :3])
+    return out
+
+
+# --- a directional light (sf_trace_sun_to, sf_light_image_sun, sf_set_shadow_lod) ---------------------------------
+# sf_sun_defaults' distance: |w| <= 2 for a surface point, so every ray starts outside the flake's radius-2 ball
+DEFAULT_SUN_DISTANCE = 4.0
+
+
+def sun_direction(v):
+    """The float32 unit vector along v (normalised in float64, then rounded): the `direction` of trace_sun, which
+    uses it as given. The reference's one directional light is sun_direction((0.7, 0.7, 0.2))
+    (Shaders/post_final.glsl:11). A zero or non-finite v has no direction: ValueError."""
+    v = np.asarray(v, np.float64).reshape(3)
+    n = np.linalg.norm(v)
+    if not (np.isfinite(n) and n > 0):
+        raise ValueError("the sun direction must be finite and not zero")
+    return (v / n).astype(_F)
+
+
+def matched_lod(distance, t_ref, base=70.0):
+    """The LOD constant for set_shadow_lod that gives a shadow ray starting `distance` from a surface the level of
+    detail the camera has at camera distance t_ref (e.g. stats().closest): a node refines while sqrt(t / r) < C, so
+    C = base sqrt(distance / t_ref) refines at `distance` exactly what `base` (the variant's constant: 70 AVX, 60
+    SSE) refines at t_ref. float32."""
+    distance, t_ref, base = float(distance), float(t_ref), float(base)
+    if not (np.isfinite(distance) and distance > 0 and np.isfinite(t_ref) and t_ref > 0 and np.isfinite(base) and base > 0):
+        raise ValueError("distance, t_ref and base must be finite and > 0")
+    return _F(base * np.sqrt(distance / t_ref))
+
+
+def sun_model(pos4, origin, direction, distance, bias):
+    """Steps 1-3 of sf_trace_sun_to's definition for a position image pos4 [..., 3 | 4] relative to `origin`, the
+    direction s towards the sun (as given), the distance tau and the relative bias:
+    (F [..., 3], d [..., 3], bound [...], is_surface [...]).
+
+    w = origin + P, f = s tau, F = w + f is the origin of the pixel's ray, d = (w - F) + 0 its unnormalised direction
+    (no -0 component) and bound = |d| (1 - bias) the distance a hit must stay under to shadow the pixel. is_surface is
+    False where P == (0, 0, 0), a miss of the frame (no ray: visible); F, d and bound of a miss pixel are formed all
+    the same and mean nothing."""
+    if not 0.0 <= float(bias) < 1.0:
+        raise ValueError("bias must be in [0, 1)")
+    tau = _F(distance)
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError("distance must be finite and > 0")
+    P, w = _world(pos4, origin)
+    s = np.asarray(direction, _F).reshape(3)
+    with np.errstate(invalid="ignore", over="ignore"):
+        f = s * tau
+        Fo = w + f
+        d = (w - Fo) + _F(0.0)
+        bound = _length(d) * (_F(1.0) - _F(bias))
+    is_surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
+    assert Fo.dtype == _F and d.dtype == _F and bound.dtype == _F
+    return Fo, d, bound, is_surface
+
+
+def light_model_sun(rgba, pos4, nrm4, vis, direction, ambient=0.25):
+    """What sf_light_image_sun makes of the RGBA8 image `rgba` [..., 4]: a new uint8 array. light_model with
+    lam = max(0, (n.x s.x + n.y s.y) + n.z s.z) (0 where that is NaN) for the direction s towards the sun, as given:
+    no light position and no division. vis [...] are the bytes of trace_sun for the same direction."""
+    a = _F(ambient)
+    if not 0.0 <= float(a) <= 1.0:
+        raise ValueError("ambient must be in [0, 1]")
+    out = np.array(rgba, np.uint8, copy=True)
+    P = np.asarray(pos4, _F)[..., :3]
+    n = np.asarray(nrm4, _F)[..., :3]
+    s = np.asarray(direction, _F).reshape(3)
+    with np.errstate(invalid="ignore", over="ignore"):
+        dot = (n[..., 0] * s[0] + n[..., 1] * s[1]) + n[..., 2] * s[2]
+        lam = np.fmax(_F(0.0), dot)
         k = a + (_F(1.0) - a) * np.where(np.asarray(vis) != 0, lam, _F(0.0)).astype(_F)
         rgb = np.fmin(out[..., :3].astype(_F) * k[..., None] + _F(0.5), _F(255.0))
     assert rgb.dtype == _F
