@@ -687,6 +687,10 @@ int sf_dist_slab_bytes(const sf_dist* dist);
 
 /* The context's own stream (hipStream_t) -- where calls with a NULL stream are queued. */
 void* sf_context_stream(sf_ctx* ctx);
+/* Trace launches of this context that took the lean tile loop (kernel sf_trace_queue1: whole-tile units of one plain
+   frame -- no aux channels, packed slab, band share, part units, tile costs or diagnostics; SF_LEAN=0 in the
+   environment of sf_create forces the general loop, sf_trace_queue1g, everywhere). For tests and measurements. */
+uint32_t sf_lean_launches(const sf_ctx* ctx);
 
 /* --- misc ---------------------------------------------------------------- */
 

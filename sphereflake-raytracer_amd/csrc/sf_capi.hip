@@ -24,6 +24,7 @@ extern "C" __global__ void sf_trace_wave2(FrameArgs a, uint32_t* overflow_list, 
 extern "C" __global__ void sf_trace_wave4(FrameArgs a, uint32_t* overflow_list, uint32_t* overflow_count);
 extern "C" __global__ void sf_trace_queue1(FrameArgs a);
 extern "C" __global__ void sf_trace_frames1(FrameBatch b);
+extern "C" __global__ void sf_trace_queue1g(FrameArgs a);
 extern "C" __global__ void sf_trace_queue1s(FrameArgs a);
 extern "C" __global__ void sf_trace_queue2(FrameArgs a);
 extern "C" __global__ void sf_trace_queue4(FrameArgs a);
@@ -230,6 +231,9 @@ struct sf_ctx {
     int pipe = -1;                               // env SF_PIPE = 0 | 1: latency variant of the trace (-1: auto)
     uint32_t prio_buckets = 8;                   // top cost buckets (3 octaves) traced at raised wave priority (env SF_PRIO_BUCKETS)
     int occ_key = -1, occ_blocks = 0;            // cached occupancy (waves per block, levels) -> blocks per CU
+    int occ_blocks_lean = 0;                     // the same of sf_trace_queue1, the lean tile loop (1 wave per block)
+    bool lean = true;                            // env SF_LEAN=0: the general tile loop (sf_trace_queue1g) everywhere
+    uint32_t lean_launches = 0;                  // trace launches that took the lean tile loop (sf_lean_launches)
     uint32_t max_blocks = 0;                     // diagnostics: env SF_MAX_BLOCKS caps the persistent grid
     int variant = SF_VARIANT_AVX;                // reference path reproduced (sf_set_variant)
     // frame-less progressive mode
@@ -629,6 +633,7 @@ int sf_create(int device, uint32_t width, uint32_t height, sf_ctx** out)
     if (const char* ev = std::getenv("SF_COMPACT")) c->compact = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("SF_PF_PRIO")) c->pf_prio = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("SF_TIE_INLINE")) c->tie_inline = std::atoi(ev) != 0;
+    if (const char* ev = std::getenv("SF_LEAN")) c->lean = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("SF_ORDER_RECORD")) c->order_record_env = std::atoi(ev) != 0 ? 1 : 0;
     if (const char* ev = std::getenv("SF_ORDER_EVERY")) c->order_every = std::atoi(ev) > 1 ? (uint32_t)std::atoi(ev) : 1u;   // (explicit)
     if (const char* ev = std::getenv("SF_PROG_BIN")) c->prog_bin = std::atoi(ev) != 0;
@@ -952,7 +957,14 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
         const bool tie_inline = bounded && c->persistent && front_first && c->tie_inline;
         if (tie_inline) a.flags |= SF_FLAG_TIE_INLINE;
         if (c->persistent) {
-            const void* kern = wpb == 1 ? (const void*)sf_trace_queue1
+            // The lean tile loop (sf_trace_queue1) serves a launch that asks for nothing it leaves out: whole-tile units
+            // of one plain frame. What the launch itself says is known here; what the schedule adds (part units, tile
+            // costs) below -- the grid is sized by the occupancy of the kernel the launch takes.
+            const uint32_t lean_off = SF_FLAG_DIAG_HALF | SF_FLAG_DIAG_HALF_SEL | SF_FLAG_DIAG_UNITS |
+                                      SF_FLAG_DIAG_FORCE_RETRACE | SF_FLAG_PRIO_FLAT;
+            const bool lean_ok = c->lean && wpb == 1 && band_count == 1u && !a.compact && !a.packed && !a.emit_aux &&
+                                 !a.tile_trace && (a.flags & lean_off) == 0u;
+            const void* kern = wpb == 1 ? (const void*)sf_trace_queue1g
                              : wpb == 2 ? (c->compact ? (const void*)sf_trace_queue2c : (const void*)sf_trace_queue2)
                                         : (const void*)sf_trace_queue4;
             const int key = (int)(wpb * 64 + a.max_depth) | (c->compact ? 1 << 20 : 0);
@@ -960,9 +972,14 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
                 int nb = 0;
                 SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, (int)block.x, wpb * lds));
                 c->occ_blocks = nb < 1 ? 1 : nb;
+                c->occ_blocks_lean = c->occ_blocks;
+                if (wpb == 1) {
+                    SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sf_trace_queue1, (int)block.x, lds));
+                    c->occ_blocks_lean = nb < 1 ? 1 : nb;
+                }
                 c->occ_key = key;
             }
-            uint32_t nblk = (uint32_t)c->occ_blocks * (uint32_t)c->cus;
+            uint32_t nblk = (uint32_t)(lean_ok ? c->occ_blocks_lean : c->occ_blocks) * (uint32_t)c->cus;
             const bool small = ntiles <= 2u * nblk * wpb;   // tiles fill the full persistent grid at most twice
             // The heavy-first order (and the splits it carries) only where the frame's tiles fill at most half
             // the grid's waves: there idle slots take the split heaviest tiles and shorten the frame. With 3
@@ -998,7 +1015,7 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
             const uint32_t need = (units_max + wpb - 1) / wpb;
             if (nblk > need) nblk = need;
             if (c->max_blocks && nblk > c->max_blocks) nblk = c->max_blocks;
-            const dim3 grid(nblk);
+            dim3 grid(nblk);
             // every queue group needs blocks of its own (the group is blockIdx mod xcds): fewer queues for a
             // grid of fewer blocks than groups
             while (a.xcds > 1u && a.xcds > nblk) a.xcds >>= 1;
@@ -1045,8 +1062,22 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
             // tiles' serial DFS is the frame, and the pipelined child loop shortens it (640x360 -4 %); full
             // grids are throughput-bound, where it costs more instructions than it hides (1080p +1.7 %)
             const bool pipe = c->pipe >= 0 ? c->pipe == 1 : small;
+            // lean: no part units in what the launch reads (the order's splits, row-major halves) and no tile costs
+            // recorded (the render a rebuild of the order reads takes the general loop)
+            const bool lean = lean_ok && !(use_order && split_buckets != 0u) && !halves && !a.tile_cost && !a.chunk_cnt &&
+                              !(a.flags & (SF_FLAG_SUBTREE | SF_FLAG_HALVES));
+            if (lean_ok && !lean && c->occ_blocks < c->occ_blocks_lean) {   // (the general loop after all: its own occupancy)
+                const uint32_t cap = (uint32_t)c->occ_blocks * (uint32_t)c->cus;
+                if (grid.x > cap) grid.x = cap;
+                while (a.xcds > 1u && a.xcds > grid.x) a.xcds >>= 1;
+                a.queues = a.xcds;
+                if (c->queues_per_xcd > 1u && grid.x * wpb >= 64u * a.xcds * c->queues_per_xcd)
+                    a.queues = a.xcds * c->queues_per_xcd;
+            }
+            if (lean) c->lean_launches += 1u;
             if (wpb == 1 && (a.flags & SF_FLAG_SUBTREE)) hipLaunchKernelGGL(sf_trace_queue1s, grid, block, lds, s, a);
-            else if (wpb == 1) hipLaunchKernelGGL(sf_trace_queue1, grid, block, lds, s, a);
+            else if (wpb == 1 && lean) hipLaunchKernelGGL(sf_trace_queue1, grid, block, lds, s, a);
+            else if (wpb == 1) hipLaunchKernelGGL(sf_trace_queue1g, grid, block, lds, s, a);
             else if (wpb == 2 && pipe) hipLaunchKernelGGL(sf_trace_queue2p, grid, block, 2 * lds, s, a);
             else if (wpb == 2 && c->compact) hipLaunchKernelGGL(sf_trace_queue2c, grid, block, 2 * lds, s, a);
             else if (wpb == 2) hipLaunchKernelGGL(sf_trace_queue2, grid, block, 2 * lds, s, a);
@@ -2605,6 +2636,7 @@ int sf_get_tile_order(sf_ctx* c, uint32_t* order, uint32_t* cost, size_t n)
 }
 
 void* sf_context_stream(sf_ctx* c) { return c ? (void*)c->stream : nullptr; }
+uint32_t sf_lean_launches(const sf_ctx* c) { return c ? c->lean_launches : 0u; }
 
 int sf_device_buffers(sf_ctx* c, float** pos4, float** nrm4, float** min_t, uint32_t** hidx)
 {

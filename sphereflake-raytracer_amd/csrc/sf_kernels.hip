@@ -37,6 +37,7 @@
 //   sf_mt_draws / sf_packet_* / sf_progressive_* -- frame-less progressive mode.
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "sf_internal.h"
@@ -76,21 +77,43 @@ __device__ __forceinline__ void normalize3(float& x, float& y, float& z, const u
 }
 
 // Ray direction (Sphereflake.cpp:149-150, 162-167): u = x/W, v = y/H at the pixel corner.
+// The per-context words of the constant block {rw, rh, fast_div, tx_magic} (DeviceConsts) as one scalar load
+struct FrameConsts {
+    float rw, rh;
+    uint32_t fast_div, tx_magic;
+};
+static_assert(offsetof(DeviceConsts, rw) % 16 == 0 && offsetof(DeviceConsts, tx_magic) == offsetof(DeviceConsts, rw) + 12,
+              "rw, rh, fast_div, tx_magic: one aligned 16-byte load");
+__device__ __forceinline__ FrameConsts frame_consts(const DeviceConsts* K)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) uint4* ConstU4;
+    const uint4 w = *(ConstU4)(const void*)&K->rw;
+    return FrameConsts{ __uint_as_float(w.x), __uint_as_float(w.y), w.z, w.w };
+#else
+    return FrameConsts{ K->rw, K->rh, K->fast_div, K->tx_magic };
+#endif
+}
+
 __device__ __forceinline__ void ray_dir(const FrameArgs& a, float x, float y, float& dx, float& dy, float& dz,
-                                        const uint32_t* __restrict__ lut)
+                                        const uint32_t* __restrict__ lut, const FrameConsts* fc = nullptr)
 {
     float u, v;
     // (uniform) RN(x / W) as one product and one fma correction (sfhost::division_by_reciprocal_exact); the
-    // context's reciprocals by scalar loads from the constant block
+    // context's reciprocals by scalar loads from the constant block (fc: already loaded, with tile_of's word)
+    float rw, rh;
+    uint32_t fast;
+    if (fc) {
+        rw = fc->rw, rh = fc->rh, fast = fc->fast_div;
+    } else {
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef const __attribute__((address_space(4))) DeviceConsts* ConstK;
-    const ConstK kc = (ConstK)(const void*)a.consts;
-    const float rw = kc->rw, rh = kc->rh;
-    const uint32_t fast = kc->fast_div;
+        typedef const __attribute__((address_space(4))) DeviceConsts* ConstK;
+        const ConstK kc = (ConstK)(const void*)a.consts;
+        rw = kc->rw, rh = kc->rh, fast = kc->fast_div;
 #else
-    const float rw = a.consts->rw, rh = a.consts->rh;
-    const uint32_t fast = a.consts->fast_div;
+        rw = a.consts->rw, rh = a.consts->rh, fast = a.consts->fast_div;
 #endif
+    }
     if (fast) {
         const float qu = x * rw, qv = y * rh;
         u = __builtin_fmaf(__builtin_fmaf(-qu, a.fw, x), rw, qu);
@@ -172,13 +195,21 @@ __device__ __forceinline__ void shade(float dx, float dy, float dz, const HitSta
     }
 }
 
-// max over the wave of a non-negative float (ordered as its bit pattern)
+// max over the wave of a non-negative float (ordered as its bit pattern), all 64 lanes active.
+// DPP row operations (six v_max_u32_dpp and one v_readlane, no LDS round trip): within each row of 16 lanes by
+// quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror and row_mirror -- every lane then holds its row's
+// maximum --, row 0 into row 1 and row 2 into row 3 by row_bcast:15 (row mask 0xa), rows 0-1 into rows 2-3 by
+// row_bcast:31 (row mask 0xc): lane 63 holds the wave's. A lane a step does not write keeps max(b, 0) = b.
 __device__ __forceinline__ float wave_max_pos(float v)
 {
     uint32_t b = __float_as_uint(v);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, m, 64));
-    return __uint_as_float(__builtin_amdgcn_readfirstlane(b));
+    b = max(b, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, 0xb1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
+    b = max(b, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, 0x4e, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
+    b = max(b, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, 0x141, 0xf, 0xf, false));   // row_half_mirror
+    b = max(b, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, 0x140, 0xf, 0xf, false));   // row_mirror
+    b = max(b, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, 0x142, 0xa, 0xf, false));   // row_bcast:15
+    b = max(b, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, 0x143, 0xc, 0xf, false));   // row_bcast:31
+    return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)b, 63));
 }
 
 __device__ __forceinline__ float wave_min(float v)
@@ -1146,18 +1177,47 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
     h.hit = false;
     uint64_t ancm = 0ull;   // lanes whose current best sphere is an ancestor of the open node (see self_test)
 
-    // ---- root node (depth 0): bounding sphere + LOD
+    // ---- LOD of one node whose bounding sphere the lanes of hbm hit (xs = R2b - d2, depth constants R2b, T, Tfar):
+    // the lanes that expand it (see traverse's test_child for the fast decisions and the certified bracket)
+    auto child_lod = [&](float tca, float d2, float xs, bool hb, uint64_t hbm, float R2b, float T, float Tfar) -> uint64_t {
+        const uint64_t nearm = wave_ballot(tca < T);
+        const uint64_t farm = wave_ballot(tca * (1.0f - 0x1p-8f) >= Tfar);
+        if ((hbm & ~(nearm | farm)) == 0ull) return hbm & nearm;
+        const float sq = __builtin_amdgcn_sqrtf(xs);
+        const float s_lo = __uint_as_float((uint32_t)max((int32_t)__float_as_uint(sq) - 2, 0));
+        const float s_hi = __uint_as_float(__float_as_uint(sq) + 2u);
+        const float t_hi = tca - s_lo;
+        const float t_lo = tca - s_hi;
+        const uint64_t tinym = wave_ballot(xs < 0x1p-96f);
+        const float thx = sel_mask(t_hi, __builtin_inff(), tinym);
+        const float tlx = sel_mask(t_lo, -__builtin_inff(), tinym);
+        const float th = hb ? thx : __builtin_inff();
+        const float tl = hb ? tlx : __builtin_inff();
+        uint64_t exm = wave_ballot(th < T);
+        const uint64_t undm = wave_ballot(sel_mask(tl, __builtin_inff(), exm) < T);
+        if (undm) {
+            const float te = near_root_exact(tca, d2, R2b);
+            exm |= undm & wave_ballot(te < T);
+        }
+        return exm;
+    };
+
+    // ---- root node (depth 0): bounding sphere + LOD, decided as a child's is (child_lod, with depth 0's constants:
+    // the bracket's bounds on t hold for any centre and bounding radius) -- from tca where that proves it, the exact
+    // root only for lanes in the band around T
     const float rcx = root[9], rcy = root[10], rcz = root[11];
     const float rcc = (rcx * rcx + rcy * rcy) + rcz * rcz;
-    bool ex0;
+    uint64_t ex0m;   // the lanes that expand the root
     {
         const float4 dt0 = depth_consts(K, 0u);
         const float tca = (rcx * dx + rcy * dy) + rcz * dz;
         const float d2 = rcc - tca * tca;
         const bool hb = valid && tca >= 0.0f && d2 <= dt0.x;
-        ex0 = hb && near_root(tca, d2, dt0.x) < dt0.w;
+        const uint64_t hbm = wave_ballot(hb);
+        if (hbm == 0ull) return;   // (maxd stays the caller's -1, whatever the seed: this traversal reached no depth)
+        ex0m = child_lod(tca, d2, dt0.x - d2, hb, hbm, dt0.x, dt0.w, depth_word_at(K, 0u, 6u));
+        if (ex0m == 0ull) return;
     }
-    if (!wave_ballot(ex0)) return;   // (maxd stays the caller's -1, whatever the seed: this traversal reached no depth)
     maxd = 0;
 
     // ---- the wave's ray cone (as in traverse)
@@ -1235,31 +1295,6 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
             return accm;
         }
         return 0ull;
-    };
-
-    // ---- LOD of one child whose bounding sphere the lanes of hbm hit (xs = R2b - d2, depth constants R2b, T, Tfar):
-    // the lanes that expand it (see traverse's test_child for the fast decisions and the certified bracket)
-    auto child_lod = [&](float tca, float d2, float xs, bool hb, uint64_t hbm, float R2b, float T, float Tfar) -> uint64_t {
-        const uint64_t nearm = wave_ballot(tca < T);
-        const uint64_t farm = wave_ballot(tca * (1.0f - 0x1p-8f) >= Tfar);
-        if ((hbm & ~(nearm | farm)) == 0ull) return hbm & nearm;
-        const float sq = __builtin_amdgcn_sqrtf(xs);
-        const float s_lo = __uint_as_float((uint32_t)max((int32_t)__float_as_uint(sq) - 2, 0));
-        const float s_hi = __uint_as_float(__float_as_uint(sq) + 2u);
-        const float t_hi = tca - s_lo;
-        const float t_lo = tca - s_hi;
-        const uint64_t tinym = wave_ballot(xs < 0x1p-96f);
-        const float thx = sel_mask(t_hi, __builtin_inff(), tinym);
-        const float tlx = sel_mask(t_lo, -__builtin_inff(), tinym);
-        const float th = hb ? thx : __builtin_inff();
-        const float tl = hb ? tlx : __builtin_inff();
-        uint64_t exm = wave_ballot(th < T);
-        const uint64_t undm = wave_ballot(sel_mask(tl, __builtin_inff(), exm) < T);
-        if (undm) {
-            const float te = near_root_exact(tca, d2, R2b);
-            exm |= undm & wave_ballot(te < T);
-        }
-        return exm;
     };
 
     // ---- expand the node with centre/|c|^2 pc at depth d (axis columns at col + j cs): build its 9 child
@@ -1349,8 +1384,9 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
     {
         lds_fence();
         const float4 pc = *reinterpret_cast<const float4*>(L.root());
-        actv = ex0 ? __builtin_inff() : -1.0f;
-        actbits = ex0 ? 1u : 0u;
+        actv = sel_mask(-1.0f, __builtin_inff(), ex0m);
+        actbits = 0u;
+        sel_in_place(actbits, 1u, ex0m);
         const float tca = (pc.x * dx + pc.y * dy) + pc.z * dz;
         const float d2 = pc.w - tca * tca;
         const uint64_t acc0 = self_test(pc, tca, d2, 0u, actv, 0u, depth_consts(K, 0u).y);
@@ -1560,7 +1596,10 @@ struct Tile {
 };
 
 // Tile of a wave: owned tile row k (band sharding) -> frame tile row.
-__device__ __forceinline__ Tile tile_of(const FrameArgs& a, uint32_t tile, uint32_t lane, uint32_t part = 0u)
+// LEAN (the whole frame's tiles as whole units, plain rows: one band, not compact; txm: the constant block's tx_magic,
+// already loaded): frame tile row = owned tile row, every lane in the unit.
+template <bool LEAN = false>
+__device__ __forceinline__ Tile tile_of(const FrameArgs& a, uint32_t tile, uint32_t lane, uint32_t part = 0u, uint32_t txm_lean = 0u)
 {
     // tile -> (k, tx) and k -> (band, row in band) by multiply-high with host magic numbers and one correction
     // (m = floor((2^32 - 1) / D) underestimates n / D by less than 1 for n < 2^31: q or q + 1), scalar
@@ -1574,6 +1613,17 @@ __device__ __forceinline__ Tile tile_of(const FrameArgs& a, uint32_t tile, uint3
         return q;
     };
     uint32_t tx, kr;
+    if constexpr (LEAN) {
+        const uint32_t k = divmod(tile, a.tiles_x, txm_lean, tx);
+        uint32_t l = lane;
+        __asm__ volatile("" : "+v"(l));
+        Tile t;
+        t.x = tx * SF_TILE + (l & 7u);
+        t.y = k * SF_TILE + (l >> 3);
+        t.valid = t.x < a.W && t.y < a.H;
+        t.orow = t.y;
+        return t;
+    }
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) DeviceConsts* ConstK;
     const uint32_t txm = ((ConstK)(const void*)a.consts)->tx_magic;
@@ -1603,12 +1653,19 @@ __device__ __forceinline__ Tile tile_of(const FrameArgs& a, uint32_t tile, uint3
 // G-buffer write (Sphereflake.cpp:186-196): (pos, 1), (nrm, 1); a miss writes (0,0,0,1).
 // Packed slabs (multi-GPU bands, a.packed): one float4 (nx, ny, nz, minT) -- the position is dir * minT, which
 // the receiving side recomputes bit for bit (sf_unpack_bands), so a band ships 16 B per pixel instead of 32.
+// LEAN: the plain G-buffer only (no packed slab, no aux channels).
+template <bool LEAN = false>
 __device__ __forceinline__ void write_pixel(const FrameArgs& a, const Tile& t, float dx, float dy, float dz,
                                             const HitState& h, const uint32_t* __restrict__ lut)
 {
     float px, py, pz, nx, ny, nz;
     shade(dx, dy, dz, h, lut, px, py, pz, nx, ny, nz);
     const size_t o = (size_t)t.orow * a.W + t.x;
+    if constexpr (LEAN) {
+        reinterpret_cast<float4*>(a.pos)[o] = make_float4(px, py, pz, 1.0f);
+        reinterpret_cast<float4*>(a.nrm)[o] = make_float4(nx, ny, nz, 1.0f);
+        return;
+    }
     if (a.packed) {   // (uniform)
         if (a.packed >= SF_PACKED_INDEX) {
             // 4 B: the hit's heap index; the receiver rebuilds the rest. (The host selects this format only where
@@ -1747,7 +1804,27 @@ __device__ __forceinline__ uint64_t* part_record(const FrameArgs& a, uint32_t sl
     return a.part_rec + (size_t)(slot * 4u + q) * 192u;
 }
 
-template <bool FIXUP, bool PIPE = false, class Prefetch = NoPrefetch, bool COMPACT = false, bool SPLIT = false>
+// The launch's FrameArgs once more from the kernel argument segment (the only kernel argument: offset 0), through an
+// address the compiler may not reason about: the fields read from the copy are scalar loads where they are used, and
+// none of them is held in a register from an earlier copy.
+__device__ __forceinline__ void kernarg_frame(FrameArgs& at, const FrameArgs& a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) FrameArgs* KernargArgs;
+    KernargArgs pa = (KernargArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    __asm__ volatile("" : "+s"(pa));
+    __builtin_memcpy(&at, (const FrameArgs*)pa, sizeof(FrameArgs));
+    (void)a;
+#else
+    at = a;
+#endif
+}
+
+// LEAN (sf_trace_queue1, the product launch's tile loop; trace_queue_body): a whole tile of a plain frame -- no part
+// units, no diagnostics (tile trace, diagnostic flags), no tile cost, no packed slab, no aux channels. `a` is then the
+// kernel's own argument: the epilogue reads the G-buffer pointers, W and the overflow list from the kernel argument
+// segment again instead of carrying them across the traversal.
+template <bool FIXUP, bool PIPE = false, class Prefetch = NoPrefetch, bool COMPACT = false, bool SPLIT = false, bool LEAN = false>
 __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __restrict__ L, const float4 bcol, uint32_t tile,
                                                 uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count,
                                                 uint32_t part = 0u, const Prefetch& pre = Prefetch(), uint32_t fl = ~0u,
@@ -1759,6 +1836,35 @@ __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __res
     const uint32_t flags = fl == ~0u ? a.flags : fl;
     const DeviceConsts* __restrict__ K = a.consts;
     const uint32_t lane = threadIdx.x & 63u;
+    if constexpr (LEAN) {
+        static_assert(!FIXUP && !SPLIT && !COMPACT, "the lean tile is the plain persistent loop's");
+        const FrameConsts fc = frame_consts(K);
+        const Tile t = tile_of<true>(a, tile, lane, 0u, fc.tx_magic);
+        float dx, dy, dz;
+        ray_dir(a, (float)t.x, (float)t.y, dx, dy, dz, K->lut, &fc);
+        const int32_t seed = seen.depth(flags);
+        HitState h;
+        int32_t maxd = -1;
+        uint32_t status = 0u;
+        traverse_ray<PIPE, false>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status, flags, nullptr, 36u,
+                                  nullptr, 0u, 0u, seed);
+        const bool overflowed = status != 0u;
+        const bool retrace = __builtin_amdgcn_readfirstlane((int)(status == SF_STATUS_TIE && (flags & SF_FLAG_TIE_INLINE))) != 0;
+        pre(retrace);
+        FrameArgs ae;
+        kernarg_frame(ae, a);
+        if (overflowed && !retrace) {
+            const uint32_t slot = wave_fetch_add(ae.counters + ae.parity, 1u);
+            ae.overflow_list[slot] = tile;   // uniform value and address
+        }
+        if (t.valid) write_pixel<true>(ae, t, dx, dy, dz, h, K->lut);
+        TileStats st;
+        st.maxd = maxd;
+        st.seed = seed;
+        st.closest = t.valid ? h.minT : FLT_MAX;
+        st.overflowed = overflowed;
+        return st;
+    }
     if (flags & SF_FLAG_DIAG_HALF) part = (flags & SF_FLAG_DIAG_HALF_SEL) ? 2u : 1u;
     // a subtree part unit: all 64 pixels, the depth-split_depth subtrees of heap index q mod 4 (SF_FLAG_SUBTREE)
     // (only the SPLIT kernel, sf_trace_queue1s, carries the split logic)
@@ -2040,7 +2146,12 @@ extern "C" __global__ __launch_bounds__(256) void sf_trace_wave4(FrameArgs a, ui
 // atomic queue until it runs dry. Dynamic balancing: tile costs vary ~100x (sky vs. deep flake),
 // and the in-order workgroup dispatcher otherwise idles CUs behind long tiles. counters: [0,1]
 // overflow counts, [2,3] tile queues, alternating per render (this render zeroes the next one's).
-template <int WAVES, bool PIPE = false, bool COMPACT = false, bool SPLIT = false>
+// LEAN: the product launch's instantiation (sf_trace_queue1; the host launches it exactly when the launch asks for
+// none of what it leaves out, sf_render_to): whole-tile units of one plain frame -- row-major or the ordered units
+// with their priority levels, the depth seed, the inline tie re-trace, the overflow list, the stats and the clock
+// probe; no part units (halves, quarters, subtree parts), no tile trace or diagnostic flags, no tile costs, no packed
+// slab, no aux channels, no band mapping. Every launch word is read from the kernel argument segment where it is used.
+template <int WAVES, bool PIPE = false, bool COMPACT = false, bool SPLIT = false, bool LEAN = false>
 __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
 {
     extern __shared__ float lds[];
@@ -2073,7 +2184,7 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
 #else
         nunits = a.order_meta[0];
 #endif
-    } else if (a.flags & SF_FLAG_HALVES) {
+    } else if (!LEAN && (a.flags & SF_FLAG_HALVES)) {
         nunits = 2u * ntiles;
     }
     stage_root(L, a.root);
@@ -2138,7 +2249,7 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
         uint32_t t = g, part = 0u;
         if (again) {
             t = g & SF_UNIT_TILE_MASK;
-            part = (g >> SF_UNIT_PRIO_SHIFT) & 7u;
+            if constexpr (!LEAN) part = (g >> SF_UNIT_PRIO_SHIFT) & 7u;
         } else if (at.tile_order) {      // heaviest tiles of the previous render first (scalar load)
 #if defined(__HIP_DEVICE_COMPILE__)
             typedef const __attribute__((address_space(4))) uint32_t* ConstU32;
@@ -2147,19 +2258,43 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
             const uint32_t u = at.tile_order[g];
 #endif
             t = u & SF_UNIT_TILE_MASK;
-            part = u >> SF_UNIT_PART_SHIFT;
+            if constexpr (!LEAN) part = u >> SF_UNIT_PART_SHIFT;
             // critical-path tiles (top cost buckets of the last render, order_meta[3]) at raised priority:
             // the SIMD's issue arbitration serves them first, the cheap tiles absorb the wait. Graded: the
             // raised buckets' lowest 3 (1.5 octaves) at 2, the ones above at 3, so the very heaviest tiles
             // also win the arbitration against the merely heavy (8 buckets: 0.1607 -> 0.1578 ms/frame against
             // all raised buckets at one level). The level comes with the unit (sf_order_scatter).
             const uint32_t pr = (u >> SF_UNIT_PRIO_SHIFT) & 3u;
-            if (pr == 2u && !(at.flags & SF_FLAG_PRIO_FLAT)) __builtin_amdgcn_s_setprio(3);
+            if (pr == 2u && (LEAN || !(at.flags & SF_FLAG_PRIO_FLAT))) __builtin_amdgcn_s_setprio(3);
             else if (pr != 0u) __builtin_amdgcn_s_setprio(2);
             else __builtin_amdgcn_s_setprio(0);
-        } else if (at.flags & SF_FLAG_HALVES) {   // (row-major halves: unit g = half g & 1 of tile g / 2)
+        } else if (!LEAN && (at.flags & SF_FLAG_HALVES)) {   // (row-major halves: unit g = half g & 1 of tile g / 2)
             t = g >> 1;
             part = SF_PART_HALF0 + (g & 1u);
+        }
+        if constexpr (LEAN) {
+            // the next unit's ticket, taken when this tile's traversal ends (the queue words' address from the kernel
+            // argument segment again, not carried across the traversal)
+            auto ticket = [&](bool retrace) {
+                if (retrace) {
+                    first = 0x80000000u | t;
+                } else {
+                    FrameArgs aq;
+                    kernarg_frame(aq, a);
+                    first = nwaves + wave_fetch_add(aq.counters + SF_QUEUE_WORD(aq.parity, k), 1u) * nq + k;   // uniform
+                }
+            };
+            const TileStats st = trace_tile<false, PIPE, decltype(ticket), false, false, true>(
+                at, L, bcol, t, at.max_depth, nullptr, nullptr, 0u, ticket,
+                again ? (at.flags | SF_FLAG_NO_FRONT_FIRST | SF_FLAG_REDO_PASS) : at.flags, 0u, seen);
+            maxd = st.maxd > maxd ? st.maxd : maxd;
+            if (st.seed >= 0 && st.maxd > st.seed) {   // (rare: see the general loop below)
+                FrameArgs ap;
+                kernarg_frame(ap, a);
+                publish_depth_early(ap, st.maxd);
+            }
+            closest = fminf(closest, st.closest);
+            continue;
         }
         const uint64_t u_start = (at.flags & SF_FLAG_DIAG_UNITS) ? __builtin_amdgcn_s_memrealtime() : 0ull;
         // the next unit's ticket, taken when this tile's traversal ends (see trace_tile)
@@ -2222,7 +2357,7 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
         cp[2] = __builtin_amdgcn_s_memtime();
         cp[3] = __builtin_amdgcn_s_memrealtime();
     }
-    if ((e.flags & SF_FLAG_DIAG_UNITS) && e.tile_trace) {   // diagnostics: this wave's {start, end}
+    if (!LEAN && (e.flags & SF_FLAG_DIAG_UNITS) && e.tile_trace) {   // diagnostics: this wave's {start, end}
         const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + wv);
         if (w < SF_DIAG_WAVES) {
             uint64_t* wt = e.tile_trace + (SF_TRACE_WORDS(e.tiles_x * e.tile_rows) - 2u * SF_DIAG_WAVES) + 2u * w;
@@ -2232,7 +2367,14 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
     }
 }
 
+// the product launch: the lean instantiation (whole tiles of one plain frame, see trace_queue_body)
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SF_WAVES_PER_EU, 8))) void sf_trace_queue1(FrameArgs a)
+{
+    trace_queue_body<1, false, false, false, true>(a);
+}
+// the general instantiation: every mode of the tile loop (part units, diagnostics, tile costs, packed slabs, aux
+// channels, band shares)
+extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SF_WAVES_PER_EU, 8))) void sf_trace_queue1g(FrameArgs a)
 {
     trace_queue_body<1>(a);
 }

@@ -200,6 +200,7 @@ SIGNATURES = {
     "sf_build_id": (ctypes.c_char_p, []),
     "sf_device_count": (ctypes.c_int, []),
     "sf_context_stream": (ctypes.c_void_p, [_CTX]),
+    "sf_lean_launches": (ctypes.c_uint32, [_CTX]),
     "sf_group_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
                                        ctypes.POINTER(ctypes.c_void_p)]),
     "sf_group_destroy": (None, [ctypes.c_void_p]),
@@ -1265,6 +1266,10 @@ class Sphereflake:
         with self._mutex:
             _check(lib().sf_get_stats(self._ctx, ctypes.byref(s)), "sf_get_stats", self._ctx)
         return s
+
+    def lean_launches(self) -> int:
+        """Trace launches of this context that took the lean tile loop (sf_lean_launches)."""
+        return int(lib().sf_lean_launches(self._ctx))
 
     def GetMaxDepthReached(self) -> int:
         return int(self.stats().max_depth)
