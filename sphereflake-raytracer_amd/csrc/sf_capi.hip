@@ -1139,28 +1139,49 @@ int sf_render_to(sf_ctx* c, const sf_render_params* p, float* pos4, float* nrm4,
     return launch(c, p, pos4, nrm4, min_t, hidx);
 }
 
-// Caller-supplied directions (sf.h; kernels sf_trace_dirs_wave / sf_trace_dirs_fixup). A one-shot grid, one wave per
-// group of 64 rays, with the levels of the geometric bound; flagged groups (more levels needed, or a tie under the
-// front-first order) are re-traced by the fixup launch behind it. Reads and writes none of the renders' state: not
-// the overflow counters' parity, the tile order or costs, the depth hint, the timing ring or the frame-less state.
-int sf_trace_dirs_to(sf_ctx* c, const sf_dirs_params* p, const float* dirs, float* pos4, float* nrm4, float* min_t,
-                     uint32_t* hidx)
+// ------------------------------------------------------------------------------------------
+// The five list traces (sf.h): sf_trace_dirs_to, sf_trace_rays_to, sf_trace_shadow_to,
+// sf_trace_shadows_to, sf_trace_sun_to. Each is a one-shot grid, one wave per group of 64 rays (an 8x8 tile of an
+// image, or 64 consecutive rays of a list), and a fixup launch behind it that re-traces the groups the waves flagged
+// (more levels needed, or a tie under the front-first order). They share one re-trace list and its counters (the
+// dirs_* fields; the calls are ordered on the context like any other pair of its calls), and read and write none of
+// the renders' state: not the overflow counters' parity, the tile order or costs, the depth hint, the timing ring or
+// the frame-less state.
+// ------------------------------------------------------------------------------------------
+
+extern "C++" {
+// One of list_trace's two launches: the geometry, and the arguments every trace's kernels end in.
+struct ListLaunch {
+    hipStream_t s;
+    uint32_t blocks, groups;
+    size_t lds;
+    uint32_t* list;       // the re-trace list: the wave kernel appends, the fixup reads
+    uint32_t* counters;   // {count of either parity, re-traced groups in all}
+    uint32_t parity;      // the wave kernel counts in counters[parity]
+    template <class Kernel, class... Args>
+    void wave(Kernel kernel, Args... args) const   // kernel(args..., groups, list, count)
+    {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), lds, s, args..., groups, list, counters + parity);
+    }
+    template <class Kernel, class... Args>
+    void fixup(Kernel kernel, Args... args) const   // kernel(args..., list, counters, parity)
+    {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), lds, s, args..., (const uint32_t*)list, counters, parity);
+    }
+};
+
+// The launch procedure, from validated parameters to SF_OK: order the stream after the context's earlier work, make
+// the counters and a list of `groups` entries, launch the wave kernel over `groups` one-wave blocks with `lds` bytes
+// and the fixup over at most `fixup_blocks` with `lds_fix`, flip the parity. wave(l) / fixup(l) call l.wave / l.fixup
+// with the trace's kernel and its own arguments.
+template <class Wave, class Fixup>
+static int list_trace(sf_ctx* c, void* stream, uint32_t groups, size_t lds, size_t lds_fix, uint32_t fixup_blocks,
+                      Wave wave, Fixup fixup)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if (p->stride != 3u && p->stride != 4u) return SF_EINVAL;
-    if (!dirs || (!pos4 && !nrm4 && !min_t && !hidx)) return SF_EINVAL;
-    if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
-    const uint64_t n = (uint64_t)p->width * p->height;
-    if (n == 0) return SF_OK;
-    if (n > 0x7fffffffull) return SF_EINVAL;   // (ray counts are 32-bit in the launch arguments)
-    const bool list = p->height == 1u || p->width == 1u;   // one row or one column: consecutive rays
-    const uint32_t tiles_x = (p->width + 7u) / 8u;
-    const uint32_t groups = list ? (uint32_t)((n + 63u) / 64u) : tiles_x * ((p->height + 7u) / 8u);
-    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     DevGuard g(c->device);
     if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
+    StreamMark mark_(c, s);   // (recorded behind both launches)
     if (!c->dirs_cnt) {
         SF_HIP(c, hipMalloc(&c->dirs_cnt, 3 * 4));
         SF_HIP(c, hipMemsetAsync(c->dirs_cnt, 0, 3 * 4, s));
@@ -1173,31 +1194,78 @@ int sf_trace_dirs_to(sf_ctx* c, const sf_dirs_params* p, const float* dirs, floa
         SF_HIP(c, hipMalloc(&c->dirs_ovf, (size_t)groups * 4));
         c->dirs_cap = groups;
     }
+    wave(ListLaunch{ s, groups, groups, lds, c->dirs_ovf, c->dirs_cnt, c->dirs_par });
+    SF_HIP(c, hipGetLastError());
+    fixup(ListLaunch{ s, groups < fixup_blocks ? groups : fixup_blocks, groups, lds_fix, c->dirs_ovf, c->dirs_cnt,
+                      c->dirs_par });
+    SF_HIP(c, hipGetLastError());
+    c->dirs_par ^= 1u;
+    return SF_OK;
+}
+}  // extern "C++"
+
+// The levels a launch provisions: at least 4, at most the LDS limit.
+static uint32_t clamp_levels(uint32_t levels)
+{
+    return levels < 4u ? 4u : levels > SF_MAX_DEPTH_LIMIT ? SF_MAX_DEPTH_LIMIT : levels;
+}
+
+// The grouping of width x height caller-supplied rays (sf_trace_dirs_to, sf_trace_rays_to): one row or one column is
+// a list of consecutive rays, anything else an image of 8x8 tiles. (groups holds for n < 2^31: the callers check.)
+struct RayGroups {
+    uint64_t n;
+    bool list;
+    uint32_t tiles_x, groups;
+};
+static RayGroups ray_groups(uint32_t width, uint32_t height)
+{
+    RayGroups r;
+    r.n = (uint64_t)width * height;
+    r.list = height == 1u || width == 1u;
+    r.tiles_x = (width + 7u) / 8u;
+    r.groups = r.list ? (uint32_t)((r.n + 63u) / 64u) : r.tiles_x * ((height + 7u) / 8u);
+    return r;
+}
+
+// The launch's FrameArgs for those rays and output buffers.
+static FrameArgs ray_frame_args(const sf_ctx* c, const RayGroups& r, uint32_t width, uint32_t height, uint32_t levels,
+                                float* pos4, float* nrm4, float* min_t, uint32_t* hidx)
+{
     FrameArgs a = frame_args(c);
-    a.W = list ? (uint32_t)n : p->width;
-    a.H = list ? 1u : p->height;
-    a.tiles_x = tiles_x;
-    bool bounded = false;
-    a.max_depth = p->max_depth ? p->max_depth : geometric_levels(c, &bounded);
-    if (a.max_depth < 4u) a.max_depth = 4u;
-    if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
+    a.W = r.list ? (uint32_t)r.n : width;
+    a.H = r.list ? 1u : height;
+    a.tiles_x = r.tiles_x;
+    a.max_depth = clamp_levels(levels);
     a.emit_aux = 1u;
     a.pos = pos4;
     a.nrm = nrm4;
     a.min_t = min_t;
     a.hit_index = hidx;
-    const size_t lds = (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4;
-    hipLaunchKernelGGL(sf_trace_dirs_wave, dim3(groups), dim3(64), lds, s, a, dirs, p->stride, groups, c->dirs_ovf,
-                       c->dirs_cnt + c->dirs_par);
-    SF_HIP(c, hipGetLastError());
-    const size_t lds_fix = (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4;
-    const uint32_t fb = groups < SF_PROG_FIXUP_BLOCKS ? groups : SF_PROG_FIXUP_BLOCKS;
-    hipLaunchKernelGGL(sf_trace_dirs_fixup, dim3(fb), dim3(64), lds_fix, s, a, dirs, p->stride,
-                       (const uint32_t*)c->dirs_ovf, c->dirs_cnt, c->dirs_par);
-    SF_HIP(c, hipGetLastError());
-    c->dirs_par ^= 1u;
-    c->rays += (int64_t)n;
-    return SF_OK;
+    return a;
+}
+
+// Caller-supplied directions (kernels sf_trace_dirs_wave / sf_trace_dirs_fixup), at the levels of the geometric bound.
+int sf_trace_dirs_to(sf_ctx* c, const sf_dirs_params* p, const float* dirs, float* pos4, float* nrm4, float* min_t,
+                     uint32_t* hidx)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (p->stride != 3u && p->stride != 4u) return SF_EINVAL;
+    if (!dirs || (!pos4 && !nrm4 && !min_t && !hidx)) return SF_EINVAL;
+    if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
+    const RayGroups r = ray_groups(p->width, p->height);
+    if (r.n == 0) return SF_OK;
+    if (r.n > 0x7fffffffull) return SF_EINVAL;   // (ray counts are 32-bit in the launch arguments)
+    bool bounded = false;
+    const uint32_t levels = p->max_depth ? p->max_depth : geometric_levels(c, &bounded);
+    const FrameArgs a = ray_frame_args(c, r, p->width, p->height, levels, pos4, nrm4, min_t, hidx);
+    const int rc = list_trace(
+        c, p->stream, r.groups, (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4,
+        (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, SF_PROG_FIXUP_BLOCKS,
+        [&](const ListLaunch& l) { l.wave(sf_trace_dirs_wave, a, dirs, p->stride); },
+        [&](const ListLaunch& l) { l.fixup(sf_trace_dirs_fixup, a, dirs, p->stride); });
+    if (rc == SF_OK) c->rays += (int64_t)r.n;
+    return rc;
 }
 
 int sf_trace_dirs(sf_ctx* c, const sf_dirs_params* p, const float* dirs)
@@ -1208,6 +1276,47 @@ int sf_trace_dirs(sf_ctx* c, const sf_dirs_params* p, const float* dirs)
     return sf_trace_dirs_to(c, p, dirs, c->pos, c->nrm, c->min_t, c->hit_index);
 }
 
+// The probes' device scratch (*buf, *cap rays of `words` floats each, + 3 for alignment), grown on demand.
+static int probe_scratch(sf_ctx* c, float** buf, uint32_t* cap, uint32_t n, uint32_t words)
+{
+    if (n <= *cap) return SF_OK;
+    if (int rc = ctx_drain(c)) return rc;   // an earlier probe's trace may still use the old scratch
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    SF_HIP(c, hipMalloc(buf, ((size_t)n * words + 3) * 4));
+    *cap = n;
+    return SF_OK;
+}
+
+// The probes' four output arrays, {pos 4, nrm 4, min_t 1, index 1} words per ray behind `in_words` input words per ray.
+struct ProbeOut {
+    float *pos, *nrm, *min_t;
+    uint32_t* idx;
+};
+static ProbeOut probe_outputs(float* buf, uint32_t cap, uint32_t in_words)
+{
+    const size_t in = (size_t)in_words * cap;
+    ProbeOut o;
+    o.pos = buf + in + (4u - in % 4u) % 4u;   // (16-B aligned)
+    o.nrm = o.pos + (size_t)4 * cap;
+    o.min_t = o.nrm + (size_t)4 * cap;
+    o.idx = reinterpret_cast<uint32_t*>(o.min_t + cap);
+    return o;
+}
+
+// Wait for the probe's trace and copy out the arrays the caller asked for.
+static int probe_download(sf_ctx* c, const ProbeOut& o, uint32_t n, float* min_t, uint32_t* hidx, float* pos4,
+                          float* nrm4)
+{
+    if (int rc = sf_synchronize(c)) return rc;
+    if (pos4) SF_HIP(c, hipMemcpy(pos4, o.pos, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (nrm4) SF_HIP(c, hipMemcpy(nrm4, o.nrm, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (min_t) SF_HIP(c, hipMemcpy(min_t, o.min_t, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (hidx) SF_HIP(c, hipMemcpy(hidx, o.idx, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return SF_OK;
+}
+
 int sf_probe_dirs(sf_ctx* c, const float* dirs3, uint32_t n, float* min_t, uint32_t* hidx, float* pos4, float* nrm4)
 {
     if (!c) return SF_EINVAL;
@@ -1216,19 +1325,9 @@ int sf_probe_dirs(sf_ctx* c, const float* dirs3, uint32_t n, float* min_t, uint3
     if (n == 0) return SF_OK;
     if (n > 0x7fffffffu) return SF_EINVAL;
     DevGuard g(c->device);
-    if (n > c->probe_cap) {
-        if (int rc = ctx_drain(c)) return rc;   // an earlier probe's trace may still use the old scratch
-        (void)hipFree(c->probe_buf);
-        c->probe_buf = nullptr;
-        c->probe_cap = 0;
-        SF_HIP(c, hipMalloc(&c->probe_buf, ((size_t)n * 13 + 3) * 4));
-        c->probe_cap = n;
-    }
+    if (int rc = probe_scratch(c, &c->probe_buf, &c->probe_cap, n, 13)) return rc;
     float* const d_dirs = c->probe_buf;
-    float* const d_pos = d_dirs + (size_t)3 * c->probe_cap + ((4u - (3u * c->probe_cap) % 4u) % 4u);   // (16-B aligned)
-    float* const d_nrm = d_pos + (size_t)4 * c->probe_cap;
-    float* const d_min = d_nrm + (size_t)4 * c->probe_cap;
-    uint32_t* const d_idx = reinterpret_cast<uint32_t*>(d_min + c->probe_cap);
+    const ProbeOut o = probe_outputs(c->probe_buf, c->probe_cap, 3);
     if (int rc = ctx_join(c, c->stream)) return rc;
     SF_HIP(c, hipMemcpyAsync(d_dirs, dirs3, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
     sf_dirs_params p;
@@ -1236,21 +1335,14 @@ int sf_probe_dirs(sf_ctx* c, const float* dirs3, uint32_t n, float* min_t, uint3
     p.width = n;
     p.height = 1;
     p.stride = 3;
-    if (int rc = sf_trace_dirs_to(c, &p, d_dirs, d_pos, d_nrm, d_min, d_idx)) return rc;
-    if (int rc = sf_synchronize(c)) return rc;
-    if (pos4) SF_HIP(c, hipMemcpy(pos4, d_pos, (size_t)n * 16, hipMemcpyDeviceToHost));
-    if (nrm4) SF_HIP(c, hipMemcpy(nrm4, d_nrm, (size_t)n * 16, hipMemcpyDeviceToHost));
-    if (min_t) SF_HIP(c, hipMemcpy(min_t, d_min, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (hidx) SF_HIP(c, hipMemcpy(hidx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return SF_OK;
+    if (int rc = sf_trace_dirs_to(c, &p, d_dirs, o.pos, o.nrm, o.min_t, o.idx)) return rc;
+    return probe_download(c, o, n, min_t, hidx, pos4, nrm4);
 }
 
-// Caller-supplied origins and directions (sf.h; kernels sf_trace_rays_wave / sf_trace_rays_fixup). Launched as
-// sf_trace_dirs_to launches, whose re-trace list and counters it shares (the two are ordered on the context like any
-// other pair of its calls). The levels are the default, not the view's geometric bound, which speaks of one origin.
-// Where the grouping proves that every group of 64 rays has one origin (one origin for all rays, or a list whose
-// rays_per_origin is a multiple of 64) the launch leaves out the mixed traversal's per-lane centre stack, which
-// is most of its LDS.
+// Caller-supplied origins and directions (kernels sf_trace_rays_wave / sf_trace_rays_one / sf_trace_rays_fixup). The
+// levels are the default, not the view's geometric bound, which speaks of one origin. Where the grouping proves that
+// every group of 64 rays has one origin (one origin for all rays, or a list whose rays_per_origin is a multiple of 64)
+// the launch leaves out the mixed traversal's per-lane centre stack, which is most of its LDS.
 int sf_trace_rays_to(sf_ctx* c, const sf_rays_params* p, const float* origins, const float* dirs, float* pos4,
                      float* nrm4, float* min_t, uint32_t* hidx)
 {
@@ -1260,60 +1352,28 @@ int sf_trace_rays_to(sf_ctx* c, const sf_rays_params* p, const float* origins, c
     if (p->origin_stride != 3u && p->origin_stride != 4u) return SF_EINVAL;
     if (!origins || !dirs || (!pos4 && !nrm4 && !min_t && !hidx)) return SF_EINVAL;
     if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
-    const uint64_t n = (uint64_t)p->width * p->height;
-    if (n == 0) return SF_OK;
-    if (n > 0x7fffffffull) return SF_EINVAL;   // (ray counts are 32-bit in the launch arguments)
-    const bool list = p->height == 1u || p->width == 1u;   // one row or one column: consecutive rays
-    const uint32_t tiles_x = (p->width + 7u) / 8u;
-    const uint32_t groups = list ? (uint32_t)((n + 63u) / 64u) : tiles_x * ((p->height + 7u) / 8u);
+    const RayGroups r = ray_groups(p->width, p->height);
+    if (r.n == 0) return SF_OK;
+    if (r.n > 0x7fffffffull) return SF_EINVAL;   // (ray counts are 32-bit in the launch arguments)
     const uint32_t rpo = p->rays_per_origin ? p->rays_per_origin : 1u;
-    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
-    if (!c->dirs_cnt) {
-        SF_HIP(c, hipMalloc(&c->dirs_cnt, 3 * 4));
-        SF_HIP(c, hipMemsetAsync(c->dirs_cnt, 0, 3 * 4, s));
-    }
-    if (groups > c->dirs_cap) {   // grown on demand; an earlier trace may still write the old list
-        SF_HIP(c, hipStreamSynchronize(s));
-        (void)hipFree(c->dirs_ovf);
-        c->dirs_ovf = nullptr;
-        c->dirs_cap = 0;
-        SF_HIP(c, hipMalloc(&c->dirs_ovf, (size_t)groups * 4));
-        c->dirs_cap = groups;
-    }
-    FrameArgs a = frame_args(c);
-    a.W = list ? (uint32_t)n : p->width;
-    a.H = list ? 1u : p->height;
-    a.tiles_x = tiles_x;
-    a.max_depth = p->max_depth ? p->max_depth : kDefaultLevels;
-    if (a.max_depth < 4u) a.max_depth = 4u;
-    if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
-    a.emit_aux = 1u;
-    a.pos = pos4;
-    a.nrm = nrm4;
-    a.min_t = min_t;
-    a.hit_index = hidx;
-    const bool one_origin_groups = rpo >= n || (list && rpo % 64u == 0u);
+    const uint32_t levels = p->max_depth ? p->max_depth : kDefaultLevels;
+    const FrameArgs a = ray_frame_args(c, r, p->width, p->height, levels, pos4, nrm4, min_t, hidx);
+    const bool one_origin_groups = rpo >= r.n || (r.list && rpo % 64u == 0u);
     const uint32_t mixed_ok = (!one_origin_groups || (a.flags & SF_FLAG_FORCE_MIXED)) ? 1u : 0u;
-    const size_t lds = (size_t)(mixed_ok ? SF_LDS_RAYS_FLOATS(a.max_depth) : SF_LDS_WAVE_FLOATS(a.max_depth)) * 4;
-    if (mixed_ok)
-        hipLaunchKernelGGL(sf_trace_rays_wave, dim3(groups), dim3(64), lds, s, a, origins, dirs, p->origin_stride,
-                           p->dir_stride, rpo, mixed_ok, groups, c->dirs_ovf, c->dirs_cnt + c->dirs_par);
-    else
-        hipLaunchKernelGGL(sf_trace_rays_one, dim3(groups), dim3(64), lds, s, a, origins, dirs, p->origin_stride,
-                           p->dir_stride, rpo, groups, c->dirs_ovf, c->dirs_cnt + c->dirs_par);
-    SF_HIP(c, hipGetLastError());
     // (secondary rays go deep: more re-trace blocks than the direction traces', about what the fixup's LDS lets reside)
-    const size_t lds_fix = (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4;
-    const uint32_t fb = groups < kRaysFixupBlocks ? groups : kRaysFixupBlocks;
-    hipLaunchKernelGGL(sf_trace_rays_fixup, dim3(fb), dim3(64), lds_fix, s, a, origins, dirs, p->origin_stride,
-                       p->dir_stride, rpo, (const uint32_t*)c->dirs_ovf, c->dirs_cnt, c->dirs_par);
-    SF_HIP(c, hipGetLastError());
-    c->dirs_par ^= 1u;
-    c->rays += (int64_t)n;
-    return SF_OK;
+    const int rc = list_trace(
+        c, p->stream, r.groups,
+        (size_t)(mixed_ok ? SF_LDS_RAYS_FLOATS(a.max_depth) : SF_LDS_WAVE_FLOATS(a.max_depth)) * 4,
+        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
+        [&](const ListLaunch& l) {
+            if (mixed_ok) l.wave(sf_trace_rays_wave, a, origins, dirs, p->origin_stride, p->dir_stride, rpo, mixed_ok);
+            else l.wave(sf_trace_rays_one, a, origins, dirs, p->origin_stride, p->dir_stride, rpo);
+        },
+        [&](const ListLaunch& l) {
+            l.fixup(sf_trace_rays_fixup, a, origins, dirs, p->origin_stride, p->dir_stride, rpo);
+        });
+    if (rc == SF_OK) c->rays += (int64_t)r.n;
+    return rc;
 }
 
 int sf_probe_rays(sf_ctx* c, const float* origins3, const float* dirs3, uint32_t n, uint32_t rays_per_origin,
@@ -1327,21 +1387,11 @@ int sf_probe_rays(sf_ctx* c, const float* origins3, const float* dirs3, uint32_t
     const uint32_t rpo = rays_per_origin ? rays_per_origin : 1u;
     const uint32_t norig = (n + rpo - 1u) / rpo;
     DevGuard g(c->device);
-    if (n > c->rprobe_cap) {
-        if (int rc = ctx_drain(c)) return rc;   // an earlier probe's trace may still use the old scratch
-        (void)hipFree(c->rprobe_buf);
-        c->rprobe_buf = nullptr;
-        c->rprobe_cap = 0;
-        SF_HIP(c, hipMalloc(&c->rprobe_buf, ((size_t)n * 16 + 3) * 4));
-        c->rprobe_cap = n;
-    }
     // {dirs 3, origins 3 (at most one per ray), pos 4, nrm 4, min_t 1, index 1} words per ray
+    if (int rc = probe_scratch(c, &c->rprobe_buf, &c->rprobe_cap, n, 16)) return rc;
     float* const d_dirs = c->rprobe_buf;
     float* const d_org = d_dirs + (size_t)3 * c->rprobe_cap;
-    float* const d_pos = d_org + (size_t)3 * c->rprobe_cap + ((4u - (6u * c->rprobe_cap) % 4u) % 4u);   // (16-B aligned)
-    float* const d_nrm = d_pos + (size_t)4 * c->rprobe_cap;
-    float* const d_min = d_nrm + (size_t)4 * c->rprobe_cap;
-    uint32_t* const d_idx = reinterpret_cast<uint32_t*>(d_min + c->rprobe_cap);
+    const ProbeOut o = probe_outputs(c->rprobe_buf, c->rprobe_cap, 6);
     if (int rc = ctx_join(c, c->stream)) return rc;
     SF_HIP(c, hipMemcpyAsync(d_dirs, dirs3, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
     SF_HIP(c, hipMemcpyAsync(d_org, origins3, (size_t)norig * 12, hipMemcpyHostToDevice, c->stream));
@@ -1352,20 +1402,93 @@ int sf_probe_rays(sf_ctx* c, const float* origins3, const float* dirs3, uint32_t
     p.dir_stride = 3;
     p.origin_stride = 3;
     p.rays_per_origin = rpo;
-    if (int rc = sf_trace_rays_to(c, &p, d_org, d_dirs, d_pos, d_nrm, d_min, d_idx)) return rc;
-    if (int rc = sf_synchronize(c)) return rc;
-    if (pos4) SF_HIP(c, hipMemcpy(pos4, d_pos, (size_t)n * 16, hipMemcpyDeviceToHost));
-    if (nrm4) SF_HIP(c, hipMemcpy(nrm4, d_nrm, (size_t)n * 16, hipMemcpyDeviceToHost));
-    if (min_t) SF_HIP(c, hipMemcpy(min_t, d_min, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (hidx) SF_HIP(c, hipMemcpy(hidx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (int rc = sf_trace_rays_to(c, &p, d_org, d_dirs, o.pos, o.nrm, o.min_t, o.idx)) return rc;
+    return probe_download(c, o, n, min_t, hidx, pos4, nrm4);
+}
+
+// ---- what the three shadow traces share (sf_trace_shadow_to, sf_trace_shadows_to, sf_trace_sun_to): one wave per 8x8
+// tile of a position image, the shadow traces' own constant block (sf_set_shadow_lod); they touch no statistic (not
+// the stats words, not the ray count).
+
+// The position image of a shadow trace: width and height 0 mean the context's size, a null pos4 the context's own
+// G-buffer (at its size only). Checks bias and max_depth with them; every failure here is SF_EINVAL.
+struct ShadowImage {
+    uint32_t W, H, tiles_x, groups;
+    const float* pos4;
+};
+static int shadow_image(const sf_ctx* c, float bias, uint32_t max_depth, uint32_t width, uint32_t height,
+                        const float* pos4, ShadowImage* im)
+{
+    if (!(bias >= 0.0f && bias < 1.0f)) return SF_EINVAL;   // (NaN fails both)
+    if (max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
+    if ((width == 0u) != (height == 0u)) return SF_EINVAL;
+    im->W = width ? width : c->W;
+    im->H = height ? height : c->H;
+    if (!pos4 && (im->W != c->W || im->H != c->H)) return SF_EINVAL;
+    if ((uint64_t)im->W * im->H > 0x7fffffffull) return SF_EINVAL;   // (pixel indices are 32-bit in the kernel)
+    im->pos4 = pos4 ? pos4 : c->pos;
+    im->tiles_x = (im->W + 7u) / 8u;
+    im->groups = im->tiles_x * ((im->H + 7u) / 8u);
     return SF_OK;
 }
 
-// Shadows from a point light (sf.h; kernels sf_trace_shadow_wave / sf_trace_shadow_fixup). Launched
-// as sf_trace_dirs_to launches, one wave per 8x8 tile of the position image, with the root transform of the LIGHT (the
-// context's columns, translation 0 - light) and the levels of the light's geometric bound; shares the direction traces'
-// re-trace list and counters. Touches no statistic (not the stats words, not the ray count) and none of the renders'
-// state.
+// The launch's FrameArgs for that image; the caller sets the root translation and the levels.
+static FrameArgs shadow_frame_args(const sf_ctx* c, const ShadowImage& im)
+{
+    FrameArgs a = frame_args(c);
+    a.W = im.W;
+    a.H = im.H;
+    a.tiles_x = im.tiles_x;
+    a.consts = c->shadow_consts;   // (sf_set_shadow_lod)
+    a.stats = nullptr;   // (no statistic is touched)
+    return a;
+}
+
+// The origin the position image is relative to, and 1 - bias.
+static void shadow_origin(const sf_ctx* c, uint32_t use_origin, const float origin[3], float bias, float o[3],
+                          float* keep)
+{
+    for (int k = 0; k < 3; ++k) o[k] = use_origin ? origin[k] : c->o[k];
+    *keep = 1.0f - bias;
+}
+
+extern "C++" {
+// The calls into the context's own result buffer (*buf, W x H elements, allocated on first use).
+template <class T>
+static int own_result_buffer(sf_ctx* c, uint32_t width, uint32_t height, T** buf)
+{
+    if (!c->has_view) return SF_ENOVIEW;
+    if ((width || height) && (width != c->W || height != c->H)) return SF_EINVAL;
+    if (!*buf) {
+        DevGuard g(c->device);
+        SF_HIP(c, hipMalloc(buf, (size_t)c->W * c->H * sizeof(T)));
+    }
+    return SF_OK;
+}
+
+// The three lighting passes: kernel(W, H, pos4, nrm4, mid..., ambient, rgba), one thread per pixel of the context's
+// frame, the buffers defaulted to the context's. have_vis: there is a visibility buffer to read.
+template <class Kernel, class... Mid>
+static int light_image_pass(sf_ctx* c, void* stream, float ambient, const float* pos4, const float* nrm4, bool have_vis,
+                            uint8_t* rgba, Kernel kernel, Mid... mid)
+{
+    if (!(ambient >= 0.0f && ambient <= 1.0f)) return SF_EINVAL;
+    if (!rgba && !c->image) return SF_ESTATE;
+    if (!have_vis) return SF_ESTATE;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
+                       nrm4 ? nrm4 : (const float*)c->nrm, mid..., ambient, rgba ? rgba : c->image);
+    SF_HIP(c, hipGetLastError());
+    return SF_OK;
+}
+}  // extern "C++"
+
+// Shadows from a point light (kernels sf_trace_shadow_wave / sf_trace_shadow_fixup), with the root
+// transform of the LIGHT (the context's columns, translation 0 - light) and the levels of the light's geometric bound.
 int sf_shadow_defaults(const sf_ctx* c, sf_shadow_params* p)
 {
     if (!c || !p) return SF_EINVAL;
@@ -1378,11 +1501,8 @@ int sf_shadow_defaults(const sf_ctx* c, sf_shadow_params* p)
 static ShadowArgs shadow_args(const sf_ctx* c, const sf_shadow_params* p)
 {
     ShadowArgs sa;
-    for (int k = 0; k < 3; ++k) {
-        sa.o[k] = p->use_origin ? p->origin[k] : c->o[k];
-        sa.l[k] = p->light[k];
-    }
-    sa.keep = 1.0f - p->bias;
+    shadow_origin(c, p->use_origin, p->origin, p->bias, sa.o, &sa.keep);
+    for (int k = 0; k < 3; ++k) sa.l[k] = p->light[k];
     return sa;
 }
 
@@ -1391,66 +1511,26 @@ int sf_trace_shadow_to(sf_ctx* c, const sf_shadow_params* p, const float* pos4, 
     if (!c || !p) return SF_EINVAL;
     if (!c->has_view) return SF_ENOVIEW;
     if (!vis) return SF_EINVAL;
-    if (!(p->bias >= 0.0f && p->bias < 1.0f)) return SF_EINVAL;   // (NaN fails both)
-    if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
-    if ((p->width == 0u) != (p->height == 0u)) return SF_EINVAL;
-    const uint32_t W = p->width ? p->width : c->W, H = p->height ? p->height : c->H;
-    if (!pos4 && (W != c->W || H != c->H)) return SF_EINVAL;
-    if ((uint64_t)W * H > 0x7fffffffull) return SF_EINVAL;   // (pixel indices are 32-bit in the kernel)
-    if (!pos4) pos4 = c->pos;
-    const uint32_t tiles_x = (W + 7u) / 8u;
-    const uint32_t groups = tiles_x * ((H + 7u) / 8u);
-    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
-    if (!c->dirs_cnt) {
-        SF_HIP(c, hipMalloc(&c->dirs_cnt, 3 * 4));
-        SF_HIP(c, hipMemsetAsync(c->dirs_cnt, 0, 3 * 4, s));
-    }
-    if (groups > c->dirs_cap) {   // grown on demand; an earlier trace may still write the old list
-        SF_HIP(c, hipStreamSynchronize(s));
-        (void)hipFree(c->dirs_ovf);
-        c->dirs_ovf = nullptr;
-        c->dirs_cap = 0;
-        SF_HIP(c, hipMalloc(&c->dirs_ovf, (size_t)groups * 4));
-        c->dirs_cap = groups;
-    }
+    ShadowImage im;
+    if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
     const ShadowArgs sa = shadow_args(c, p);
-    FrameArgs a = frame_args(c);
-    a.W = W;
-    a.H = H;
-    a.tiles_x = tiles_x;
+    FrameArgs a = shadow_frame_args(c, im);
     const float centre[3] = { 0.0f - sa.l[0], 0.0f - sa.l[1], 0.0f - sa.l[2] };   // (Sphereflake.cpp:83 at the light)
     for (int k = 0; k < 3; ++k) a.root[9 + k] = centre[k];
-    a.consts = c->shadow_consts;   // (sf_set_shadow_lod)
     bool bounded = false;
-    a.max_depth = p->max_depth ? p->max_depth : geometric_levels(c->host_shadow_consts.dt, centre, &bounded);
-    if (a.max_depth < 4u) a.max_depth = 4u;
-    if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
-    a.stats = nullptr;   // (no statistic is touched)
-    const size_t lds = (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4;
-    hipLaunchKernelGGL(sf_trace_shadow_wave, dim3(groups), dim3(64), lds, s, a, pos4, sa, vis, groups, c->dirs_ovf,
-                       c->dirs_cnt + c->dirs_par);
-    SF_HIP(c, hipGetLastError());
-    const size_t lds_fix = (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4;
-    const uint32_t fb = groups < SF_PROG_FIXUP_BLOCKS ? groups : SF_PROG_FIXUP_BLOCKS;
-    hipLaunchKernelGGL(sf_trace_shadow_fixup, dim3(fb), dim3(64), lds_fix, s, a, pos4, sa, vis,
-                       (const uint32_t*)c->dirs_ovf, c->dirs_cnt, c->dirs_par);
-    SF_HIP(c, hipGetLastError());
-    c->dirs_par ^= 1u;
-    return SF_OK;
+    a.max_depth =
+        clamp_levels(p->max_depth ? p->max_depth : geometric_levels(c->host_shadow_consts.dt, centre, &bounded));
+    return list_trace(
+        c, p->stream, im.groups, (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4,
+        (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, SF_PROG_FIXUP_BLOCKS,
+        [&](const ListLaunch& l) { l.wave(sf_trace_shadow_wave, a, im.pos4, sa, vis); },
+        [&](const ListLaunch& l) { l.fixup(sf_trace_shadow_fixup, a, im.pos4, sa, vis); });
 }
 
 int sf_trace_shadow(sf_ctx* c, const sf_shadow_params* p)
 {
     if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if ((p->width || p->height) && (p->width != c->W || p->height != c->H)) return SF_EINVAL;
-    if (!c->shadow) {
-        DevGuard g(c->device);
-        SF_HIP(c, hipMalloc(&c->shadow, (size_t)c->W * c->H));
-    }
+    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow)) return rc;
     return sf_trace_shadow_to(c, p, nullptr, c->shadow);
 }
 
@@ -1477,24 +1557,13 @@ int sf_light_image(sf_ctx* c, const sf_shadow_params* p, float ambient, const fl
 {
     if (!c || !p) return SF_EINVAL;
     if (!c->has_view && !p->use_origin) return SF_ENOVIEW;
-    if (!(ambient >= 0.0f && ambient <= 1.0f)) return SF_EINVAL;
-    if (!rgba && !c->image) return SF_ESTATE;
-    if (!vis && !c->shadow) return SF_ESTATE;
-    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
-    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
-    hipLaunchKernelGGL(sf_light_image_px, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
-                       nrm4 ? nrm4 : (const float*)c->nrm, vis ? vis : (const uint8_t*)c->shadow, shadow_args(c, p),
-                       ambient, rgba ? rgba : c->image);
-    SF_HIP(c, hipGetLastError());
-    return SF_OK;
+    return light_image_pass(c, p->stream, ambient, pos4, nrm4, vis || c->shadow, rgba, sf_light_image_px,
+                            vis ? vis : (const uint8_t*)c->shadow, shadow_args(c, p));
 }
 
-// Many lights per pixel in one launch (sf.h; kernels sf_trace_shadows_wave / sf_trace_shadows_fixup /
-// sf_light_image_many_px). The launch of sf_trace_shadow_to with the lights by value in the argument
-// segment; the levels are one value for the launch, the largest geometric bound over the lights.
+// Many lights per pixel in one launch (kernels sf_trace_shadows_wave / sf_trace_shadows_fixup / sf_light_image_many_px,
+// DESIGN.md §6.12). The launch of sf_trace_shadow_to with the lights by value in the argument segment; the levels are
+// one value for the launch, the largest geometric bound over the lights.
 static_assert(SF_SHADOW_LIGHTS == SF_SHADOW_LIGHTS_MAX, "one mask bit per light");
 static_assert(sizeof(FrameArgs) + sizeof(ShadowLights) + 64 <= 4096, "kernel argument segment");
 
@@ -1520,8 +1589,7 @@ static int shadows_check(const sf_shadows_params* p, bool weights)
 static void shadows_args(const sf_ctx* c, const sf_shadows_params* p, ShadowLights* sl)
 {
     std::memset(sl, 0, sizeof *sl);
-    for (int k = 0; k < 3; ++k) sl->o[k] = p->use_origin ? p->origin[k] : c->o[k];
-    sl->keep = 1.0f - p->bias;
+    shadow_origin(c, p->use_origin, p->origin, p->bias, sl->o, &sl->keep);
     sl->n = p->n;
     const float even = 1.0f / (float)p->n;
     for (uint32_t i = 0; i < p->n; ++i) {
@@ -1536,39 +1604,12 @@ int sf_trace_shadows_to(sf_ctx* c, const sf_shadows_params* p, const float* pos4
     if (!c->has_view) return SF_ENOVIEW;
     if (!mask) return SF_EINVAL;
     if (int rc = shadows_check(p, false)) return rc;
-    if (!(p->bias >= 0.0f && p->bias < 1.0f)) return SF_EINVAL;   // (NaN fails both)
-    if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
-    if ((p->width == 0u) != (p->height == 0u)) return SF_EINVAL;
-    const uint32_t W = p->width ? p->width : c->W, H = p->height ? p->height : c->H;
-    if (!pos4 && (W != c->W || H != c->H)) return SF_EINVAL;
-    if ((uint64_t)W * H > 0x7fffffffull) return SF_EINVAL;   // (pixel indices are 32-bit in the kernel)
-    if (!pos4) pos4 = c->pos;
-    const uint32_t tiles_x = (W + 7u) / 8u;
-    const uint32_t groups = tiles_x * ((H + 7u) / 8u);
-    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
-    if (!c->dirs_cnt) {
-        SF_HIP(c, hipMalloc(&c->dirs_cnt, 3 * 4));
-        SF_HIP(c, hipMemsetAsync(c->dirs_cnt, 0, 3 * 4, s));
-    }
-    if (groups > c->dirs_cap) {   // grown on demand; an earlier trace may still write the old list
-        SF_HIP(c, hipStreamSynchronize(s));
-        (void)hipFree(c->dirs_ovf);
-        c->dirs_ovf = nullptr;
-        c->dirs_cap = 0;
-        SF_HIP(c, hipMalloc(&c->dirs_ovf, (size_t)groups * 4));
-        c->dirs_cap = groups;
-    }
+    ShadowImage im;
+    if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
     ShadowLights sl;
     shadows_args(c, p, &sl);
-    FrameArgs a = frame_args(c);
-    a.W = W;
-    a.H = H;
-    a.tiles_x = tiles_x;
+    FrameArgs a = shadow_frame_args(c, im);
     for (int k = 0; k < 3; ++k) a.root[9 + k] = 0.0f;   // (the kernel stages each light's own translation)
-    a.consts = c->shadow_consts;   // (sf_set_shadow_lod)
     uint32_t levels = p->max_depth;
     if (!levels)
         for (uint32_t i = 0; i < sl.n; ++i) {
@@ -1578,32 +1619,18 @@ int sf_trace_shadows_to(sf_ctx* c, const sf_shadows_params* p, const float* pos4
             const uint32_t li = geometric_levels(c->host_shadow_consts.dt, centre, &bounded);
             if (li > levels) levels = li;
         }
-    a.max_depth = levels;
-    if (a.max_depth < 4u) a.max_depth = 4u;
-    if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
-    a.stats = nullptr;   // (no statistic is touched)
-    const size_t lds = (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4;
-    hipLaunchKernelGGL(sf_trace_shadows_wave, dim3(groups), dim3(64), lds, s, a, pos4, sl, mask, groups, c->dirs_ovf,
-                       c->dirs_cnt + c->dirs_par);
-    SF_HIP(c, hipGetLastError());
-    const size_t lds_fix = (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4;
-    const uint32_t fb = groups < SF_PROG_FIXUP_BLOCKS ? groups : SF_PROG_FIXUP_BLOCKS;
-    hipLaunchKernelGGL(sf_trace_shadows_fixup, dim3(fb), dim3(64), lds_fix, s, a, pos4, sl, mask,
-                       (const uint32_t*)c->dirs_ovf, c->dirs_cnt, c->dirs_par);
-    SF_HIP(c, hipGetLastError());
-    c->dirs_par ^= 1u;
-    return SF_OK;
+    a.max_depth = clamp_levels(levels);
+    return list_trace(
+        c, p->stream, im.groups, (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4,
+        (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, SF_PROG_FIXUP_BLOCKS,
+        [&](const ListLaunch& l) { l.wave(sf_trace_shadows_wave, a, im.pos4, sl, mask); },
+        [&](const ListLaunch& l) { l.fixup(sf_trace_shadows_fixup, a, im.pos4, sl, mask); });
 }
 
 int sf_trace_shadows(sf_ctx* c, const sf_shadows_params* p)
 {
     if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if ((p->width || p->height) && (p->width != c->W || p->height != c->H)) return SF_EINVAL;
-    if (!c->shadow_masks) {
-        DevGuard g(c->device);
-        SF_HIP(c, hipMalloc(&c->shadow_masks, (size_t)c->W * c->H * 8));
-    }
+    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow_masks)) return rc;
     return sf_trace_shadows_to(c, p, nullptr, c->shadow_masks);
 }
 
@@ -1630,22 +1657,11 @@ int sf_light_image_many(sf_ctx* c, const sf_shadows_params* p, float ambient, co
 {
     if (!c || !p) return SF_EINVAL;
     if (!c->has_view && !p->use_origin) return SF_ENOVIEW;
-    if (!(ambient >= 0.0f && ambient <= 1.0f)) return SF_EINVAL;
     if (int rc = shadows_check(p, true)) return rc;
-    if (!rgba && !c->image) return SF_ESTATE;
-    if (!mask && !c->shadow_masks) return SF_ESTATE;
-    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
     ShadowLights sl;
     shadows_args(c, p, &sl);
-    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
-    hipLaunchKernelGGL(sf_light_image_many_px, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
-                       nrm4 ? nrm4 : (const float*)c->nrm, mask ? mask : (const uint64_t*)c->shadow_masks, sl, ambient,
-                       rgba ? rgba : c->image);
-    SF_HIP(c, hipGetLastError());
-    return SF_OK;
+    return light_image_pass(c, p->stream, ambient, pos4, nrm4, mask || c->shadow_masks, rgba, sf_light_image_many_px,
+                            mask ? mask : (const uint64_t*)c->shadow_masks, sl);
 }
 
 // The LOD constant of the shadow traces (sf.h): a second constant block, the context's own but for the
@@ -1664,10 +1680,9 @@ int sf_set_shadow_lod(sf_ctx* c, float lod_constant)
 
 float sf_get_shadow_lod(const sf_ctx* c) { return c ? c->shadow_lod : NAN; }
 
-// Shadows from a directional light (sf.h; kernels sf_trace_sun_wave / sf_trace_sun_fixup / sf_light_image_sun_px,
-// DESIGN.md §6.13). Launched as sf_trace_shadow_to launches, with the context's own root columns (each lane forms its
-// own translation), the default levels of sf_trace_rays_to and the mixed traversal's LDS; shares the direction traces'
-// re-trace list and counters. Touches no statistic and none of the renders' state.
+// Shadows from a directional light (kernels sf_trace_sun_wave / sf_trace_sun_fixup / sf_light_image_sun_px, DESIGN.md
+// §6.13), with the context's own root columns (each lane forms its own translation), the default levels of
+// sf_trace_rays_to, the mixed traversal's LDS and sf_trace_rays_to's fixup grid.
 int sf_sun_defaults(const sf_ctx* c, sf_sun_params* p)
 {
     if (!c || !p) return SF_EINVAL;
@@ -1683,69 +1698,25 @@ int sf_trace_sun_to(sf_ctx* c, const sf_sun_params* p, const float* pos4, uint8_
     if (!c || !p) return SF_EINVAL;
     if (!c->has_view) return SF_ENOVIEW;
     if (!vis) return SF_EINVAL;
-    if (!(p->bias >= 0.0f && p->bias < 1.0f)) return SF_EINVAL;   // (NaN fails both)
     if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
-    if (p->max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
-    if ((p->width == 0u) != (p->height == 0u)) return SF_EINVAL;
-    const uint32_t W = p->width ? p->width : c->W, H = p->height ? p->height : c->H;
-    if (!pos4 && (W != c->W || H != c->H)) return SF_EINVAL;
-    if ((uint64_t)W * H > 0x7fffffffull) return SF_EINVAL;   // (pixel indices are 32-bit in the kernel)
-    if (!pos4) pos4 = c->pos;
-    const uint32_t tiles_x = (W + 7u) / 8u;
-    const uint32_t groups = tiles_x * ((H + 7u) / 8u);
-    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
-    if (!c->dirs_cnt) {
-        SF_HIP(c, hipMalloc(&c->dirs_cnt, 3 * 4));
-        SF_HIP(c, hipMemsetAsync(c->dirs_cnt, 0, 3 * 4, s));
-    }
-    if (groups > c->dirs_cap) {   // grown on demand; an earlier trace may still write the old list
-        SF_HIP(c, hipStreamSynchronize(s));
-        (void)hipFree(c->dirs_ovf);
-        c->dirs_ovf = nullptr;
-        c->dirs_cap = 0;
-        SF_HIP(c, hipMalloc(&c->dirs_ovf, (size_t)groups * 4));
-        c->dirs_cap = groups;
-    }
+    ShadowImage im;   // (its checks fail with SF_EINVAL as the distance does: their order cannot be told)
+    if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
     SunArgs sa;
-    for (int k = 0; k < 3; ++k) {
-        sa.o[k] = p->use_origin ? p->origin[k] : c->o[k];
-        sa.f[k] = p->dir[k] * p->distance;   // (one rounding: step 2 of the definition)
-    }
-    sa.keep = 1.0f - p->bias;
-    FrameArgs a = frame_args(c);
-    a.W = W;
-    a.H = H;
-    a.tiles_x = tiles_x;
-    a.consts = c->shadow_consts;   // (sf_set_shadow_lod)
-    a.max_depth = p->max_depth ? p->max_depth : kDefaultLevels;
-    if (a.max_depth < 4u) a.max_depth = 4u;
-    if (a.max_depth > SF_MAX_DEPTH_LIMIT) a.max_depth = SF_MAX_DEPTH_LIMIT;
-    a.stats = nullptr;   // (no statistic is touched)
-    const size_t lds = (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4;
-    hipLaunchKernelGGL(sf_trace_sun_wave, dim3(groups), dim3(64), lds, s, a, pos4, sa, vis, groups, c->dirs_ovf,
-                       c->dirs_cnt + c->dirs_par);
-    SF_HIP(c, hipGetLastError());
-    const size_t lds_fix = (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4;
-    const uint32_t fb = groups < kRaysFixupBlocks ? groups : kRaysFixupBlocks;
-    hipLaunchKernelGGL(sf_trace_sun_fixup, dim3(fb), dim3(64), lds_fix, s, a, pos4, sa, vis,
-                       (const uint32_t*)c->dirs_ovf, c->dirs_cnt, c->dirs_par);
-    SF_HIP(c, hipGetLastError());
-    c->dirs_par ^= 1u;
-    return SF_OK;
+    shadow_origin(c, p->use_origin, p->origin, p->bias, sa.o, &sa.keep);
+    for (int k = 0; k < 3; ++k) sa.f[k] = p->dir[k] * p->distance;   // (one rounding: step 2 of the definition)
+    FrameArgs a = shadow_frame_args(c, im);
+    a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
+    return list_trace(
+        c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
+        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
+        [&](const ListLaunch& l) { l.wave(sf_trace_sun_wave, a, im.pos4, sa, vis); },
+        [&](const ListLaunch& l) { l.fixup(sf_trace_sun_fixup, a, im.pos4, sa, vis); });
 }
 
 int sf_trace_sun(sf_ctx* c, const sf_sun_params* p)
 {
     if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if ((p->width || p->height) && (p->width != c->W || p->height != c->H)) return SF_EINVAL;
-    if (!c->shadow) {
-        DevGuard g(c->device);
-        SF_HIP(c, hipMalloc(&c->shadow, (size_t)c->W * c->H));
-    }
+    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow)) return rc;
     return sf_trace_sun_to(c, p, nullptr, c->shadow);
 }
 
@@ -1753,19 +1724,8 @@ int sf_light_image_sun(sf_ctx* c, const sf_sun_params* p, float ambient, const f
                        const uint8_t* vis, uint8_t* rgba)
 {
     if (!c || !p) return SF_EINVAL;
-    if (!(ambient >= 0.0f && ambient <= 1.0f)) return SF_EINVAL;
-    if (!rgba && !c->image) return SF_ESTATE;
-    if (!vis && !c->shadow) return SF_ESTATE;
-    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
-    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
-    hipLaunchKernelGGL(sf_light_image_sun_px, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
-                       nrm4 ? nrm4 : (const float*)c->nrm, vis ? vis : (const uint8_t*)c->shadow, p->dir[0], p->dir[1],
-                       p->dir[2], ambient, rgba ? rgba : c->image);
-    SF_HIP(c, hipGetLastError());
-    return SF_OK;
+    return light_image_pass(c, p->stream, ambient, pos4, nrm4, vis || c->shadow, rgba, sf_light_image_sun_px,
+                            vis ? vis : (const uint8_t*)c->shadow, p->dir[0], p->dir[1], p->dir[2]);
 }
 
 // Multi-frame persistent trace (sf.h; kernel sf_trace_frames1). One launch where every frame's own launch() would be

@@ -3196,31 +3196,194 @@ extern "C" __global__ __launch_bounds__(64) void sf_fixup_wave(FrameArgs a, cons
 // ------------------------------------------------------------------------------------------
 namespace {
 
+// ---- what the groups of the five list traces (this section and the four after it) share
+
+// The lane's ray of a group. A lane past the end of the list or off the image edge takes the nearest ray inside (a
+// real direction for the wave's cone) and traverses as an invalid lane: no load or store beyond the last ray.
+struct GroupLane {
+    uint32_t ray;      // index of the lane's ray or pixel, clamped into the list or image (< 2^31 of them)
+    bool valid;        // the lane's own ray exists
+    uint32_t mid;      // the cone axis lane: the tile's centre pixel (4, 4), or a mid lane of a list
+    uint32_t tx, ty;   // the group's tile (an image)
+    uint32_t x, y;     // the lane's own pixel, not clamped (an image)
+};
+
+// an 8x8 tile of the a.W x a.H image, a.tiles_x tiles per row
+__device__ __forceinline__ GroupLane tile_lane(const FrameArgs& a, uint32_t group)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    GroupLane g;
+    g.ty = group / a.tiles_x;
+    g.tx = group - g.ty * a.tiles_x;
+    g.x = g.tx * SF_TILE + (lane & 7u);
+    g.y = g.ty * SF_TILE + (lane >> 3);
+    g.valid = g.x < a.W && g.y < a.H;
+    g.ray = (g.y < a.H ? g.y : a.H - 1u) * a.W + (g.x < a.W ? g.x : a.W - 1u);
+    g.mid = 36u;
+    return g;
+}
+
+// 64 consecutive rays of a list (a.H == 1), else a tile
+__device__ __forceinline__ GroupLane group_lane(const FrameArgs& a, uint32_t group)
+{
+    if (a.H != 1u) return tile_lane(a, group);
+    GroupLane g;
+    const uint32_t i = group * 64u + (threadIdx.x & 63u);   // (< 2^31 + 64)
+    g.valid = i < a.W;
+    g.ray = g.valid ? i : a.W - 1u;
+    g.mid = 32u;
+    g.tx = g.ty = g.x = g.y = 0u;
+    return g;
+}
+
+// three finite numbers (no NaN, no infinity)
+__device__ __forceinline__ bool finite3(float x, float y, float z)
+{
+    auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
+    return finite(x) && finite(y) && finite(z);
+}
+
+__device__ __forceinline__ HitState miss_state()
+{
+    HitState h;
+    h.minT = FLT_MAX;
+    h.cx = h.cy = h.cz = 0.f;
+    h.index = 0xffffffffu;
+    h.depth = -1;
+    h.hit = false;
+    return h;
+}
+
+// The cone axis lane of the live lanes `m` (not empty): the mid lane if it is one, else the first of them (`first`,
+// where the caller has it already).
+__device__ __forceinline__ uint32_t axis_lane(uint64_t m, uint32_t mid, uint32_t first)
+{
+    return __builtin_amdgcn_readfirstlane(((m >> mid) & 1ull) ? mid : first);
+}
+__device__ __forceinline__ uint32_t axis_lane(uint64_t m, uint32_t mid)
+{
+    return axis_lane(m, mid, (uint32_t)__builtin_ctzll(m));
+}
+
+// The wave kernel flags its group (uniform): the fixup kernel re-traces it at SF_MAX_LEVELS and rewrites its rays.
+__device__ __forceinline__ void flag_group(uint32_t* overflow_list, uint32_t* overflow_count, uint32_t group)
+{
+    const uint32_t slot = wave_fetch_add(overflow_count, 1u);
+    overflow_list[slot] = group;   // uniform value and address
+}
+
+// The four outputs of a valid lane's ray, any of them NULL.
+__device__ __forceinline__ void store_ray(const FrameArgs& a, uint32_t ray, float dx, float dy, float dz,
+                                          const HitState& h, const uint32_t* __restrict__ lut)
+{
+    float px, py, pz, nx, ny, nz;
+    shade(dx, dy, dz, h, lut, px, py, pz, nx, ny, nz);
+    if (a.pos) reinterpret_cast<float4*>(a.pos)[ray] = make_float4(px, py, pz, 1.0f);
+    if (a.nrm) reinterpret_cast<float4*>(a.nrm)[ray] = make_float4(nx, ny, nz, 1.0f);
+    if (a.min_t) a.min_t[ray] = h.minT;
+    if (a.hit_index) a.hit_index[ray] = h.hit ? h.index : 0xffffffffu;
+}
+
+__device__ __forceinline__ TileStats group_stats(int32_t maxd, float closest, bool flagged)
+{
+    TileStats st;
+    st.maxd = maxd;
+    st.closest = closest;
+    st.overflowed = flagged;
+    return st;
+}
+
+// The shadow ray of the three shadow traces, from the surface point w and the ray's origin l (the
+// light): d = (w - l) + 0, len = sqrt((d.x d.x + d.y d.y) + d.z d.z), bound = len keep, d normalised -- every
+// operation rounded on its own, in this order: the bits are the contract.
+// (__builtin_sqrtf is the correctly rounded square root under the build's -fhip-fp32-correctly-rounded-divide-sqrt,
+// as in near_root; __fsqrt_rn compiles to the bare v_sqrt_f32 here, 1 ulp off for some arguments)
+__device__ __forceinline__ void shadow_ray(float wx, float wy, float wz, float lx, float ly, float lz, float keep,
+                                           const uint32_t* __restrict__ lut, float& dx, float& dy, float& dz,
+                                           float& bound)
+{
+    dx = __fadd_rn(__fsub_rn(wx, lx), 0.0f);
+    dy = __fadd_rn(__fsub_rn(wy, ly), 0.0f);
+    dz = __fadd_rn(__fsub_rn(wz, lz), 0.0f);
+    const float len = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    bound = __fmul_rn(len, keep);
+    normalize3(dx, dy, dz, lut);
+}
+
+// A tile's 64 visibility bytes (255 where the lane's ray was not stopped) from the ballot of `hit`. A whole tile of an
+// image whose rows are 8-byte aligned is written by 8 lanes, one 8-byte row each (bit k of the row's byte of the
+// ballot -> byte k, 255 where lit).
+__device__ __forceinline__ void store_vis_tile(const FrameArgs& a, uint8_t* __restrict__ vis, const GroupLane& g,
+                                               bool hit)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t litm = ~wave_ballot(hit);
+    const bool rows8 = (a.W & 7u) == 0u && (reinterpret_cast<uintptr_t>(vis) & 7u) == 0u &&
+                       g.tx * SF_TILE + SF_TILE <= a.W && g.ty * SF_TILE + SF_TILE <= a.H;   // (uniform)
+    if (rows8) {
+        if (lane < 8u) {
+            const uint64_t b = (litm >> (8u * lane)) & 0xffull;
+            const uint64_t s = (b * 0x0101010101010101ull) & 0x8040201008040201ull;   // byte k: bit k of b, in place
+            const uint64_t n = ((s + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;   // byte k: 1 if set
+            *reinterpret_cast<uint64_t*>(vis + (size_t)(g.ty * SF_TILE + lane) * a.W + g.tx * SF_TILE) = n * 0xffull;
+        }
+    } else if (g.valid) {
+        vis[(size_t)g.y * a.W + g.x] = hit ? (uint8_t)0 : (uint8_t)255;
+    }
+}
+
+// Where a fixup kernel stages the root image (stage_root of a.root) for the groups it re-traces.
+enum class RootStage {
+    Once,       // before the loop: the group reads the image and never writes it
+    PerGroup,   // before every group, behind an lds_fence: the group may overwrite the image (per-origin passes)
+    InGroup,    // not at all: the group stages what it needs itself
+};
+
+// The body of the five fixup kernels (as sf_fixup_wave): re-trace counters[parity] groups of `overflow_list` with
+// group_fn(group, bcol), one block at a time over the list; zero the next trace's counter and add this trace's to
+// counters[2], the re-traced groups sf_get_stats reports. STATS: group_fn returns the group's TileStats, published as
+// the renders' are (the shadow traces touch no statistic). (`a` by value: through a reference, sf_trace_rays_fixup
+// had stage_root's lane compares hoisted out of its loop, 3 more SGPR spills. `lds` is the group's own L: no restrict.)
+template <RootStage STAGE, bool STATS, class GroupFn>
+__device__ __forceinline__ void fixup_groups(const FrameArgs a, float* lds, const uint32_t* overflow_list,
+                                             uint32_t* counters, uint32_t parity, GroupFn group_fn)
+{
+    const uint32_t n = counters[parity];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        counters[parity ^ 1u] = 0u;
+        counters[2] += n;
+    }
+    if (blockIdx.x >= n) return;
+    int32_t maxd = -1;
+    float closest = FLT_MAX;
+    uint32_t unresolved = 0u;
+    if constexpr (STAGE == RootStage::Once) stage_root(lds, a.root);
+    const float4 bcol = build_column(a.consts);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        if constexpr (STAGE == RootStage::PerGroup) {
+            lds_fence();
+            stage_root(lds, a.root);
+        }
+        if constexpr (STATS) {
+            const TileStats st = group_fn(overflow_list[i], bcol);
+            maxd = st.maxd > maxd ? st.maxd : maxd;
+            closest = fminf(closest, st.closest);
+            unresolved += st.overflowed ? 1u : 0u;
+        } else {
+            group_fn(overflow_list[i], bcol);
+        }
+    }
+    if constexpr (STATS) publish_stats(a, maxd, closest, unresolved);
+}
+
 template <bool FIXUP>
 __device__ __forceinline__ TileStats trace_dir_group(const FrameArgs& a, const float* __restrict__ dirs, uint32_t stride,
                                                      float* __restrict__ L, const float4 bcol, uint32_t group,
                                                      uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
 {
     const DeviceConsts* __restrict__ K = a.consts;
-    const uint32_t lane = threadIdx.x & 63u;
-    // the lane's ray; a lane past the end of the list or off the image edge loads the nearest ray inside (a real
-    // direction for the wave's cone) and traverses as an invalid lane: no load or store beyond the last ray
-    size_t ray;
-    bool valid;
-    uint32_t mid;   // the cone axis lane: the tile's centre pixel (4, 4), or a mid lane of a list
-    if (a.H == 1u) {
-        const size_t i = (size_t)group * 64u + lane;
-        valid = i < a.W;
-        ray = valid ? i : (size_t)a.W - 1u;
-        mid = 32u;
-    } else {
-        const uint32_t ty = group / a.tiles_x, tx = group - ty * a.tiles_x;
-        const uint32_t x = tx * SF_TILE + (lane & 7u), y = ty * SF_TILE + (lane >> 3);
-        valid = x < a.W && y < a.H;
-        ray = (size_t)(y < a.H ? y : a.H - 1u) * a.W + (x < a.W ? x : a.W - 1u);
-        mid = 36u;
-    }
-    const float* const dp = dirs + ray * stride;
+    const GroupLane g = group_lane(a, group);
+    const float* const dp = dirs + (size_t)g.ray * stride;
     float dx = dp[0], dy = dp[1], dz = dp[2];
     normalize3(dx, dy, dz, K->lut);
     // A direction that does not normalise to three finite numbers (zero, tiny, huge, NaN or infinite input) misses
@@ -3230,20 +3393,13 @@ __device__ __forceinline__ TileStats trace_dir_group(const FrameArgs& a, const f
     // lane carrying the axis lane's direction, so the traversal's wave-level arithmetic (the cone, whose min
     // instructions drop NaNs) only ever sees finite directions; the axis lane is the mid lane, or where that one
     // is not finite the first lane that is.
-    auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
-    const bool fin = finite(dx) && finite(dy) && finite(dz);
+    const bool fin = finite3(dx, dy, dz);
     const uint64_t finm = wave_ballot(fin);
-    HitState h;
-    h.minT = FLT_MAX;
-    h.cx = h.cy = h.cz = 0.f;
-    h.index = 0xffffffffu;
-    h.depth = -1;
-    h.hit = false;
+    HitState h = miss_state();
     int32_t maxd = -1;
     uint32_t status = 0u;
     if (finm != 0ull) {   // (uniform; no finite lane: every ray of the group misses)
-        const uint32_t axl = __builtin_amdgcn_readfirstlane(
-            ((finm >> mid) & 1ull) ? mid : (uint32_t)__builtin_ctzll(finm));
+        const uint32_t axl = axis_lane(finm, g.mid);
         const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
         dx = fin ? dx : ax;
         dy = fin ? dy : ay;
@@ -3251,27 +3407,12 @@ __device__ __forceinline__ TileStats trace_dir_group(const FrameArgs& a, const f
         // only the culls' A/B switches of the context's flags reach this traversal; the fixup traces in index order
         const uint32_t flags = (a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST)) |
                                (FIXUP ? SF_FLAG_NO_FRONT_FIRST : 0u);
-        traverse_ray<>(K, a.root, L, bcol, levels, dx, dy, dz, valid && fin, h, maxd, status, flags, nullptr, axl);
+        traverse_ray<>(K, a.root, L, bcol, levels, dx, dy, dz, g.valid && fin, h, maxd, status, flags, nullptr, axl);
     }
     const bool flagged = status != 0u;   // (uniform) more levels needed, or a tie under the front-first order
-    if (!FIXUP && flagged) {
-        // the fixup kernel re-traces this group at SF_MAX_LEVELS in index order and rewrites its rays
-        const uint32_t slot = wave_fetch_add(overflow_count, 1u);
-        overflow_list[slot] = group;   // uniform value and address
-    }
-    if (valid) {
-        float px, py, pz, nx, ny, nz;
-        shade(dx, dy, dz, h, K->lut, px, py, pz, nx, ny, nz);
-        if (a.pos) reinterpret_cast<float4*>(a.pos)[ray] = make_float4(px, py, pz, 1.0f);
-        if (a.nrm) reinterpret_cast<float4*>(a.nrm)[ray] = make_float4(nx, ny, nz, 1.0f);
-        if (a.min_t) a.min_t[ray] = h.minT;
-        if (a.hit_index) a.hit_index[ray] = h.hit ? h.index : 0xffffffffu;
-    }
-    TileStats st;
-    st.maxd = maxd;
-    st.closest = valid ? h.minT : FLT_MAX;
-    st.overflowed = flagged;
-    return st;
+    if (!FIXUP && flagged) flag_group(overflow_list, overflow_count, group);   // (re-traced in index order)
+    if (g.valid) store_ray(a, g.ray, dx, dy, dz, h, K->lut);
+    return group_stats(maxd, g.valid ? h.minT : FLT_MAX, flagged);
 }
 
 }  // namespace
@@ -3289,32 +3430,16 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_dirs_wave(FrameArgs a,
     publish_stats(a, st.maxd, st.closest, 0u);
 }
 
-// Re-trace of the flagged groups (as sf_fixup_wave): counters[parity] groups of `overflow_list`; zeroes the next
-// trace's counter and adds this trace's to counters[2], the re-traced groups sf_get_stats reports.
+// Re-trace of the flagged groups at SF_MAX_LEVELS (fixup_groups). The traversal only reads the root image: staged once.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_dirs_fixup(FrameArgs a, const float* dirs, uint32_t stride,
                                                                      const uint32_t* overflow_list, uint32_t* counters,
                                                                      uint32_t parity)
 {
     extern __shared__ float lds[];
-    const uint32_t n = counters[parity];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        counters[parity ^ 1u] = 0u;
-        counters[2] += n;
-    }
-    if (blockIdx.x >= n) return;
-    int32_t maxd = -1;
-    float closest = FLT_MAX;
-    uint32_t unresolved = 0u;
-    stage_root(lds, a.root);
-    const float4 bcol = build_column(a.consts);
-    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-        const TileStats st = trace_dir_group<true>(a, dirs, stride, lds, bcol, overflow_list[i], SF_MAX_LEVELS, nullptr,
-                                                   nullptr);
-        maxd = st.maxd > maxd ? st.maxd : maxd;
-        closest = fminf(closest, st.closest);
-        unresolved += st.overflowed ? 1u : 0u;
-    }
-    publish_stats(a, maxd, closest, unresolved);
+    fixup_groups<RootStage::Once, true>(a, lds, overflow_list, counters, parity,
+                                        [&](uint32_t group, const float4 bcol) {
+        return trace_dir_group<true>(a, dirs, stride, lds, bcol, group, SF_MAX_LEVELS, nullptr, nullptr);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3597,22 +3722,9 @@ __device__ __forceinline__ TileStats trace_ray_group(const FrameArgs& a, const f
 {
     const DeviceConsts* __restrict__ K = a.consts;
     const uint32_t lane = threadIdx.x & 63u;
-    // the lane's ray, clamped into the list or image as in trace_dir_group
-    uint32_t ray;
-    bool valid;
-    uint32_t mid;
-    if (a.H == 1u) {
-        const uint64_t i = (uint64_t)group * 64u + lane;
-        valid = i < a.W;
-        ray = valid ? (uint32_t)i : a.W - 1u;
-        mid = 32u;
-    } else {
-        const uint32_t ty = group / a.tiles_x, tx = group - ty * a.tiles_x;
-        const uint32_t x = tx * SF_TILE + (lane & 7u), y = ty * SF_TILE + (lane >> 3);
-        valid = x < a.W && y < a.H;
-        ray = (y < a.H ? y : a.H - 1u) * a.W + (x < a.W ? x : a.W - 1u);   // (< 2^31 rays)
-        mid = 36u;
-    }
+    const GroupLane g = group_lane(a, group);
+    const uint32_t ray = g.ray, mid = g.mid;
+    const bool valid = g.valid;
     const float* const dp = dirs + (size_t)ray * dstride;
     const float* const op = origins + (size_t)(rpo > 1u ? ray / rpo : ray) * ostride;
     float dx = dp[0], dy = dp[1], dz = dp[2];
@@ -3623,16 +3735,9 @@ __device__ __forceinline__ TileStats trace_ray_group(const FrameArgs& a, const f
     // not finite: the root's tca is then NaN, -inf, or +inf with d2 = inf - inf = NaN, and the root is not entered --
     // traverse_mixed finds that by the reference's own arithmetic per lane, and a group that shares such an origin
     // leaves traverse_ray at its root test, before the cone.
-    auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
-    const bool fin = finite(dx) && finite(dy) && finite(dz);
-    const bool on = valid && fin;
+    const bool on = valid && finite3(dx, dy, dz);
     const uint64_t onm = wave_ballot(on);
-    HitState h;
-    h.minT = FLT_MAX;
-    h.cx = h.cy = h.cz = 0.f;
-    h.index = 0xffffffffu;
-    h.depth = -1;
-    h.hit = false;
+    HitState h = miss_state();
     int32_t maxd = -1;
     uint32_t status = 0u;
     if (onm != 0ull) {   // (uniform; else every ray of the group misses)
@@ -3649,11 +3754,7 @@ __device__ __forceinline__ TileStats trace_ray_group(const FrameArgs& a, const f
             if (status & SF_STATUS_ZSIGN) {   // per-ray zero signs: nothing of this pass is kept
                 status = 0u;
                 maxd = -1;
-                h.minT = FLT_MAX;
-                h.cx = h.cy = h.cz = 0.f;
-                h.index = 0xffffffffu;
-                h.depth = -1;
-                h.hit = false;
+                h = miss_state();
             } else {
                 todo = 0ull;
             }
@@ -3674,7 +3775,7 @@ __device__ __forceinline__ TileStats trace_ray_group(const FrameArgs& a, const f
                                              __float_as_uint(rz) == __float_as_uint(r[11])));
             const uint64_t m = todo & wave_ballot(mine);   // (holds l0)
             const bool member = ((m >> lane) & 1ull) != 0ull;
-            const uint32_t axl = __builtin_amdgcn_readfirstlane(((m >> mid) & 1ull) ? mid : l0);
+            const uint32_t axl = axis_lane(m, mid, l0);   // (the first lane of m is l0)
             const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
             lds_fence();
             stage_root(L, r);
@@ -3691,24 +3792,10 @@ __device__ __forceinline__ TileStats trace_ray_group(const FrameArgs& a, const f
         }
     }
     const bool flagged = status != 0u;   // (uniform) more levels needed, or a tie under the front-first order
-    if (!FIXUP && flagged) {
-        const uint32_t slot = wave_fetch_add(overflow_count, 1u);
-        overflow_list[slot] = group;   // uniform value and address
-    }
-    if (valid) {
-        // (a lane that is not `on` kept the initial miss; its direction may be non-finite and shade ignores it)
-        float px, py, pz, nx, ny, nz;
-        shade(dx, dy, dz, h, K->lut, px, py, pz, nx, ny, nz);
-        if (a.pos) reinterpret_cast<float4*>(a.pos)[ray] = make_float4(px, py, pz, 1.0f);
-        if (a.nrm) reinterpret_cast<float4*>(a.nrm)[ray] = make_float4(nx, ny, nz, 1.0f);
-        if (a.min_t) a.min_t[ray] = h.minT;
-        if (a.hit_index) a.hit_index[ray] = h.hit ? h.index : 0xffffffffu;
-    }
-    TileStats st;
-    st.maxd = maxd;
-    st.closest = valid ? h.minT : FLT_MAX;
-    st.overflowed = flagged;
-    return st;
+    if (!FIXUP && flagged) flag_group(overflow_list, overflow_count, group);
+    // (a lane that is not `on` kept the initial miss; its direction may be non-finite and shade ignores it)
+    if (valid) store_ray(a, ray, dx, dy, dz, h, K->lut);
+    return group_stats(maxd, valid ? h.minT : FLT_MAX, flagged);
 }
 
 }  // namespace
@@ -3744,33 +3831,19 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_rays_one(FrameArgs a, 
     publish_stats(a, st.maxd, st.closest, 0u);
 }
 
-// Re-trace of the flagged groups at SF_MAX_LEVELS (as sf_trace_dirs_fixup, whose list and counters it shares).
+// Re-trace of the flagged groups at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and counters). A group
+// traced per origin overwrites the root image: restaged before every group.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_rays_fixup(FrameArgs a, const float* origins, const float* dirs,
                                                                      uint32_t ostride, uint32_t dstride, uint32_t rpo,
                                                                      const uint32_t* overflow_list, uint32_t* counters,
                                                                      uint32_t parity)
 {
     extern __shared__ float lds[];
-    const uint32_t n = counters[parity];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        counters[parity ^ 1u] = 0u;
-        counters[2] += n;
-    }
-    if (blockIdx.x >= n) return;
-    int32_t maxd = -1;
-    float closest = FLT_MAX;
-    uint32_t unresolved = 0u;
-    const float4 bcol = build_column(a.consts);
-    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-        lds_fence();
-        stage_root(lds, a.root);   // (a group traced per origin overwrites the root image)
-        const TileStats st = trace_ray_group<true>(a, origins, dirs, ostride, dstride, rpo, 1u, lds, bcol,
-                                                   overflow_list[i], SF_MAX_LEVELS, nullptr, nullptr);
-        maxd = st.maxd > maxd ? st.maxd : maxd;
-        closest = fminf(closest, st.closest);
-        unresolved += st.overflowed ? 1u : 0u;
-    }
-    publish_stats(a, maxd, closest, unresolved);
+    fixup_groups<RootStage::PerGroup, true>(a, lds, overflow_list, counters, parity,
+                                            [&](uint32_t group, const float4 bcol) {
+        return trace_ray_group<true>(a, origins, dirs, ostride, dstride, rpo, 1u, lds, bcol, group, SF_MAX_LEVELS,
+                                     nullptr, nullptr);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3786,39 +3859,27 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_rays_fixup(FrameArgs a
 namespace {
 
 template <bool FIXUP>
-__device__ __forceinline__ bool trace_shadow_group(const FrameArgs& a, const float4* __restrict__ pos4,
+__device__ __forceinline__ void trace_shadow_group(const FrameArgs& a, const float4* __restrict__ pos4,
                                                    const ShadowArgs& sa, uint8_t* __restrict__ vis,
                                                    float* __restrict__ L, const float4 bcol, uint32_t group,
                                                    uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
 {
     const DeviceConsts* __restrict__ K = a.consts;
-    const uint32_t lane = threadIdx.x & 63u;
-    // the lane's pixel; a lane off the image edge loads the nearest pixel inside and traverses as an invalid lane
-    const uint32_t ty = group / a.tiles_x, tx = group - ty * a.tiles_x;
-    const uint32_t x = tx * SF_TILE + (lane & 7u), y = ty * SF_TILE + (lane >> 3);
-    const bool valid = x < a.W && y < a.H;
-    const uint32_t pix = (y < a.H ? y : a.H - 1u) * a.W + (x < a.W ? x : a.W - 1u);   // (< 2^31 pixels)
-    const float4 P = pos4[pix];
+    const GroupLane g = tile_lane(a, group);
+    const float4 P = pos4[g.ray];
     const bool surface = !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
-    float dx = __fadd_rn(__fsub_rn(__fadd_rn(sa.o[0], P.x), sa.l[0]), 0.0f);
-    float dy = __fadd_rn(__fsub_rn(__fadd_rn(sa.o[1], P.y), sa.l[1]), 0.0f);
-    float dz = __fadd_rn(__fsub_rn(__fadd_rn(sa.o[2], P.z), sa.l[2]), 0.0f);
-    // (__builtin_sqrtf is the correctly rounded square root under the build's -fhip-fp32-correctly-rounded-divide-sqrt,
-    // as in near_root; __fsqrt_rn compiles to the bare v_sqrt_f32 here, 1 ulp off for some arguments)
-    const float len = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-    const float bound = __fmul_rn(len, sa.keep);
-    normalize3(dx, dy, dz, K->lut);
+    float dx, dy, dz, bound;
+    shadow_ray(__fadd_rn(sa.o[0], P.x), __fadd_rn(sa.o[1], P.y), __fadd_rn(sa.o[2], P.z), sa.l[0], sa.l[1], sa.l[2],
+               sa.keep, K->lut, dx, dy, dz, bound);
     // a d that does not normalise to finite numbers misses (see trace_dir_group); a light that is not finite makes d
     // so for every pixel, and the root is not entered either (trace_ray_group)
-    auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
-    const bool on = valid && surface && finite(dx) && finite(dy) && finite(dz);
+    const bool on = g.valid && surface && finite3(dx, dy, dz);
     const uint64_t onm = wave_ballot(on);
     HitState h;
     h.hit = false;
     uint32_t status = 0u;
     if (onm != 0ull) {   // (uniform; else no ray of the group is traced)
-        // the cone axis lane as in trace_ray_group: the tile's centre pixel if it is traced, else the first live lane
-        const uint32_t axl = __builtin_amdgcn_readfirstlane(((onm >> 36u) & 1ull) ? 36u : (uint32_t)__builtin_ctzll(onm));
+        const uint32_t axl = axis_lane(onm, g.mid);
         const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
         const uint32_t culls = a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST);
         int32_t md = -1;
@@ -3834,27 +3895,8 @@ __device__ __forceinline__ bool trace_shadow_group(const FrameArgs& a, const flo
                                                 on, h, md, status, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
 #endif
     }
-    const bool flagged = status != 0u;   // (uniform) more levels needed
-    if (!FIXUP && flagged) {
-        const uint32_t slot = wave_fetch_add(overflow_count, 1u);
-        overflow_list[slot] = group;   // uniform value and address
-    }
-    // ---- the tile's 64 results as a ballot; a whole tile of an image whose rows are 8-byte aligned is written by 8
-    // lanes, one 8-byte row each (bit k of the row's byte of the ballot -> byte k, 255 where lit)
-    const uint64_t litm = ~wave_ballot(h.hit);
-    const bool rows8 = (a.W & 7u) == 0u && (reinterpret_cast<uintptr_t>(vis) & 7u) == 0u &&
-                       tx * SF_TILE + SF_TILE <= a.W && ty * SF_TILE + SF_TILE <= a.H;   // (uniform)
-    if (rows8) {
-        if (lane < 8u) {
-            const uint64_t b = (litm >> (8u * lane)) & 0xffull;
-            const uint64_t s = (b * 0x0101010101010101ull) & 0x8040201008040201ull;   // byte k: bit k of b, in place
-            const uint64_t n = ((s + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;   // byte k: 1 if set
-            *reinterpret_cast<uint64_t*>(vis + (size_t)(ty * SF_TILE + lane) * a.W + tx * SF_TILE) = n * 0xffull;
-        }
-    } else if (valid) {
-        vis[(size_t)y * a.W + x] = h.hit ? (uint8_t)0 : (uint8_t)255;
-    }
-    return flagged;
+    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);   // (uniform) more levels needed
+    store_vis_tile(a, vis, g, h.hit);
 }
 
 }  // namespace
@@ -3872,23 +3914,18 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_shadow_wave(FrameArgs 
                               a.max_depth, overflow_list, overflow_count);
 }
 
-// Re-trace of the flagged tiles at SF_MAX_LEVELS (as sf_trace_dirs_fixup, whose list and counters it shares).
+// Re-trace of the flagged tiles at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and counters). The
+// traversal only reads the light's root image: staged once.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_shadow_fixup(FrameArgs a, const float* pos4, ShadowArgs sa,
                                                                        uint8_t* vis, const uint32_t* overflow_list,
                                                                        uint32_t* counters, uint32_t parity)
 {
     extern __shared__ float lds[];
-    const uint32_t n = counters[parity];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        counters[parity ^ 1u] = 0u;
-        counters[2] += n;
-    }
-    if (blockIdx.x >= n) return;
-    stage_root(lds, a.root);
-    const float4 bcol = build_column(a.consts);
-    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x)
-        trace_shadow_group<true>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, bcol, overflow_list[i],
-                                 SF_MAX_LEVELS, nullptr, nullptr);
+    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
+                                         [&](uint32_t group, const float4 bcol) {
+        trace_shadow_group<true>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, bcol, group, SF_MAX_LEVELS,
+                                 nullptr, nullptr);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3919,38 +3956,27 @@ __device__ __forceinline__ void trace_shadows_group(const FrameArgs& a, const fl
                                                     uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
 {
     const DeviceConsts* __restrict__ K = a.consts;
-    const uint32_t lane = threadIdx.x & 63u;
-    // the lane's pixel, as in trace_shadow_group
-    const uint32_t ty = group / a.tiles_x, tx = group - ty * a.tiles_x;
-    const uint32_t x = tx * SF_TILE + (lane & 7u), y = ty * SF_TILE + (lane >> 3);
-    const bool valid = x < a.W && y < a.H;
-    const uint32_t pix = (y < a.H ? y : a.H - 1u) * a.W + (x < a.W ? x : a.W - 1u);   // (< 2^31 pixels)
-    const float4 P = pos4[pix];
-    const bool surface = valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    const GroupLane g = tile_lane(a, group);
+    const float4 P = pos4[g.ray];
+    const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
     const uint32_t n = sl.n;   // (uniform, 1..64)
     uint64_t shadowed = 0ull;   // bit i: light i does not reach the lane's pixel
     uint32_t status = 0u;
     if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss: every light's bit is set)
         const float wx = __fadd_rn(sl.o[0], P.x), wy = __fadd_rn(sl.o[1], P.y), wz = __fadd_rn(sl.o[2], P.z);
         const uint32_t culls = a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST);
-        auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
         lds_fence();
         stage_root(L, a.root);   // the columns, once per tile; each light restages its translation
 #pragma clang loop unroll(disable)
         for (uint32_t i = 0u; i < n; ++i) {
             const float lx = sl.l[i][0], ly = sl.l[i][1], lz = sl.l[i][2];
-            float dx = __fadd_rn(__fsub_rn(wx, lx), 0.0f);
-            float dy = __fadd_rn(__fsub_rn(wy, ly), 0.0f);
-            float dz = __fadd_rn(__fsub_rn(wz, lz), 0.0f);
-            // (the correctly rounded square root, see trace_shadow_group)
-            const float len = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-            const float bound = __fmul_rn(len, sl.keep);
-            normalize3(dx, dy, dz, K->lut);
+            float dx, dy, dz, bound;
+            shadow_ray(wx, wy, wz, lx, ly, lz, sl.keep, K->lut, dx, dy, dz, bound);
             // finiteness depends on the light: a light that is not finite leaves no lane on, and its bit stays set
-            const bool on = surface && finite(dx) && finite(dy) && finite(dz);
+            const bool on = surface && finite3(dx, dy, dz);
             const uint64_t onm = wave_ballot(on);
             if (onm == 0ull) continue;   // (uniform)
-            const uint32_t axl = __builtin_amdgcn_readfirstlane(((onm >> 36u) & 1ull) ? 36u : (uint32_t)__builtin_ctzll(onm));
+            const uint32_t axl = axis_lane(onm, g.mid);
             const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
             float r[12];   // (traverse_ray reads the translation only; the columns are in the staged image)
 #pragma unroll
@@ -3970,13 +3996,11 @@ __device__ __forceinline__ void trace_shadows_group(const FrameArgs& a, const fl
             shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
         }
     }
-    if (!FIXUP && status != 0u) {   // (uniform) more levels needed for some light: once on the list
-        const uint32_t slot = wave_fetch_add(overflow_count, 1u);
-        overflow_list[slot] = group;   // uniform value and address
-    }
+    // (uniform) more levels needed for some light: once on the list
+    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);
     // a tile row is 64 contiguous bytes: one 8-byte vector store per valid lane
     const uint64_t all = n >= 64u ? ~0ull : (1ull << n) - 1ull;
-    if (valid) mask[(size_t)y * a.W + x] = all & ~shadowed;
+    if (g.valid) mask[(size_t)g.y * a.W + g.x] = all & ~shadowed;
 }
 
 }  // namespace
@@ -3993,23 +4017,18 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_wave(FrameArgs
                                blockIdx.x, a.max_depth, overflow_list, overflow_count);
 }
 
-// Re-trace of the flagged tiles, for every light, at SF_MAX_LEVELS (as sf_trace_shadow_fixup, whose list and
-// counters it shares).
+// Re-trace of the flagged tiles, for every light, at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and
+// counters). The group stages the columns itself, and a tile without a surface pixel stages nothing.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_fixup(FrameArgs a, const float* pos4, ShadowLights sl,
                                                                         uint64_t* mask, const uint32_t* overflow_list,
                                                                         uint32_t* counters, uint32_t parity)
 {
     extern __shared__ float lds[];
-    const uint32_t n = counters[parity];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        counters[parity ^ 1u] = 0u;
-        counters[2] += n;
-    }
-    if (blockIdx.x >= n) return;
-    const float4 bcol = build_column(a.consts);
-    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x)
-        trace_shadows_group<true>(a, reinterpret_cast<const float4*>(pos4), sl, mask, lds, bcol, overflow_list[i],
-                                  SF_MAX_LEVELS, nullptr, nullptr);
+    fixup_groups<RootStage::InGroup, false>(a, lds, overflow_list, counters, parity,
+                                            [&](uint32_t group, const float4 bcol) {
+        trace_shadows_group<true>(a, reinterpret_cast<const float4*>(pos4), sl, mask, lds, bcol, group, SF_MAX_LEVELS,
+                                  nullptr, nullptr);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4031,28 +4050,17 @@ __device__ __forceinline__ void trace_sun_group(const FrameArgs& a, const float4
                                                 uint32_t* overflow_count)
 {
     const DeviceConsts* __restrict__ K = a.consts;
-    const uint32_t lane = threadIdx.x & 63u;
-    // the lane's pixel; a lane off the image edge loads the nearest pixel inside and traverses as an invalid lane
-    const uint32_t ty = group / a.tiles_x, tx = group - ty * a.tiles_x;
-    const uint32_t x = tx * SF_TILE + (lane & 7u), y = ty * SF_TILE + (lane >> 3);
-    const bool valid = x < a.W && y < a.H;
-    const uint32_t pix = (y < a.H ? y : a.H - 1u) * a.W + (x < a.W ? x : a.W - 1u);   // (< 2^31 pixels)
-    const float4 P = pos4[pix];
+    const GroupLane g = tile_lane(a, group);
+    const float4 P = pos4[g.ray];
     const bool surface = !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
     const float wx = __fadd_rn(sa.o[0], P.x), wy = __fadd_rn(sa.o[1], P.y), wz = __fadd_rn(sa.o[2], P.z);
     const float Fx = __fadd_rn(wx, sa.f[0]), Fy = __fadd_rn(wy, sa.f[1]), Fz = __fadd_rn(wz, sa.f[2]);
-    float dx = __fadd_rn(__fsub_rn(wx, Fx), 0.0f);
-    float dy = __fadd_rn(__fsub_rn(wy, Fy), 0.0f);
-    float dz = __fadd_rn(__fsub_rn(wz, Fz), 0.0f);
-    // (the correctly rounded square root, see trace_shadow_group)
-    const float len = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-    const float bound = __fmul_rn(len, sa.keep);
-    normalize3(dx, dy, dz, K->lut);
+    float dx, dy, dz, bound;
+    shadow_ray(wx, wy, wz, Fx, Fy, Fz, sa.keep, K->lut, dx, dy, dz, bound);
     // the lane's root centre (Sphereflake.cpp:83 at F)
     const float rx = __fsub_rn(0.0f, Fx), ry = __fsub_rn(0.0f, Fy), rz = __fsub_rn(0.0f, Fz);
     // a d that does not normalise to finite numbers misses (see trace_dir_group); an F that is not finite makes d so
-    auto finite = [](float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; };
-    const bool on = valid && surface && finite(dx) && finite(dy) && finite(dz);
+    const bool on = g.valid && surface && finite3(dx, dy, dz);
     HitState h;
     h.hit = false;
     uint32_t status = 0u;
@@ -4063,24 +4071,8 @@ __device__ __forceinline__ void trace_sun_group(const FrameArgs& a, const float4
         lds_fence();   // (the re-trace's earlier tile has read its tables)
         traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, status, culls, bound);
     }
-    if (!FIXUP && status != 0u) {   // (uniform) more levels needed
-        const uint32_t slot = wave_fetch_add(overflow_count, 1u);
-        overflow_list[slot] = group;   // uniform value and address
-    }
-    // ---- the tile's 64 results as a ballot, stored as trace_shadow_group stores them
-    const uint64_t litm = ~wave_ballot(h.hit);
-    const bool rows8 = (a.W & 7u) == 0u && (reinterpret_cast<uintptr_t>(vis) & 7u) == 0u &&
-                       tx * SF_TILE + SF_TILE <= a.W && ty * SF_TILE + SF_TILE <= a.H;   // (uniform)
-    if (rows8) {
-        if (lane < 8u) {
-            const uint64_t b = (litm >> (8u * lane)) & 0xffull;
-            const uint64_t s = (b * 0x0101010101010101ull) & 0x8040201008040201ull;   // byte k: bit k of b, in place
-            const uint64_t n = ((s + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;   // byte k: 1 if set
-            *reinterpret_cast<uint64_t*>(vis + (size_t)(ty * SF_TILE + lane) * a.W + tx * SF_TILE) = n * 0xffull;
-        }
-    } else if (valid) {
-        vis[(size_t)y * a.W + x] = h.hit ? (uint8_t)0 : (uint8_t)255;
-    }
+    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);   // (uniform) more levels needed
+    store_vis_tile(a, vis, g, h.hit);
 }
 
 }  // namespace
@@ -4098,24 +4090,18 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_sun_wave(FrameArgs a, 
                            a.max_depth, overflow_list, overflow_count);
 }
 
-// Re-trace of the flagged tiles at SF_MAX_LEVELS (as sf_trace_shadow_fixup, whose list and counters it shares). The
-// mixed traversal reads the root image's columns and never writes it: staged once.
+// Re-trace of the flagged tiles at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and counters). The mixed
+// traversal reads the root image's columns and never writes it: staged once.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_sun_fixup(FrameArgs a, const float* pos4, SunArgs sa,
                                                                     uint8_t* vis, const uint32_t* overflow_list,
                                                                     uint32_t* counters, uint32_t parity)
 {
     extern __shared__ float lds[];
-    const uint32_t n = counters[parity];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        counters[parity ^ 1u] = 0u;
-        counters[2] += n;
-    }
-    if (blockIdx.x >= n) return;
-    stage_root(lds, a.root);
-    const float4 bcol = build_column(a.consts);
-    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x)
-        trace_sun_group<true>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, bcol, overflow_list[i],
-                              SF_MAX_LEVELS, nullptr, nullptr);
+    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
+                                         [&](uint32_t group, const float4 bcol) {
+        trace_sun_group<true>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, bcol, group, SF_MAX_LEVELS,
+                              nullptr, nullptr);
+    });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -623,6 +623,39 @@ class Sphereflake:
                "sf_render_to", self._ctx)
 
     # caller-supplied directions (sf_trace_dirs_to / sf_trace_dirs / sf_probe_dirs) ------------
+    @staticmethod
+    def _out_ptrs(out):
+        """`out` of trace_dirs() / trace_rays(), four tensors or device addresses, as pointers (None for None / 0)."""
+        addr = [0 if o is None else o.data_ptr() if hasattr(o, "data_ptr") else int(o) for o in out]
+        return [ctypes.c_void_p(a) if a else None for a in addr]
+
+    def _trace_host(self, lead, n, inputs, trace, outputs=True):
+        """The numpy forms of trace_dirs() and trace_rays(): `inputs` uploaded to a scratch (16-byte aligned, in order),
+        trace(input pointers, the four output pointers) under the mutex, a wait, and (pos4, nrm4, min_t, hit_index)
+        shaped `lead` downloaded -- without `outputs` the trace writes elsewhere, and None is returned."""
+        pos = np.empty(lead + (4,), np.float32)
+        nrm = np.empty(lead + (4,), np.float32)
+        mint = np.empty(lead, np.float32)
+        idx = np.empty(lead, np.uint32)
+        if n == 0:
+            return pos, nrm, mint, idx
+        offs, o0 = [], 0
+        for a in inputs:
+            offs.append(o0)
+            o0 += (a.nbytes + 15) // 16 * 16
+        res = ((pos, 0), (nrm, 16 * n), (mint, 32 * n), (idx, 36 * n)) if outputs else ()
+        with _DeviceScratch(self.device, o0 + (n * 40 if outputs else 16)) as d:
+            for a, off in zip(inputs, offs):
+                d.upload(off, a)
+            with self._mutex:
+                trace([ctypes.c_void_p(d.ptr + off) for off in offs],
+                      [ctypes.c_void_p(d.ptr + o0 + off) for _, off in res])
+                # (the scratch is freed on leaving: the trace that reads and writes it must be done)
+                _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
+            for a, off in res:
+                d.download(o0 + off, a)
+        return (pos, nrm, mint, idx) if outputs else None
+
     def trace_dirs(self, dirs, width=None, height=None, out=None, stride=None, max_depth=0, stream=None):
         """Trace caller-supplied directions from the current view's origin (sphereflake_amd.dirs has generators).
 
@@ -668,40 +701,20 @@ class Sphereflake:
                 raise ValueError("device directions need `out` buffers (or the context's frame size)")
             if len(out) != 4:
                 raise ValueError("out must be (pos4, nrm4, min_t, hit_index)")
-            addr = [0 if o is None else o.data_ptr() if hasattr(o, "data_ptr") else int(o) for o in out]
-            ptrs = [ctypes.c_void_p(a) if a else None for a in addr]
             with self._mutex:
-                _check(lib().sf_trace_dirs_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(dptr), *ptrs),
+                _check(lib().sf_trace_dirs_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(dptr), *self._out_ptrs(out)),
                        "sf_trace_dirs_to", self._ctx)
             return None
         if out is not None and not isinstance(out, str):
             raise ValueError("host directions return host arrays: out must be None or 'host'")
         lead = shape[:-1] if len(shape) == 3 else (n,)
-        pos = np.empty(lead + (4,), np.float32)
-        nrm = np.empty(lead + (4,), np.float32)
-        mint = np.empty(lead, np.float32)
-        idx = np.empty(lead, np.uint32)
-        if n == 0:
-            return pos, nrm, mint, idx
-        with _DeviceScratch(self.device, dirs.nbytes + 16 + (0 if to_ctx else n * 40)) as d:
-            d.upload(0, dirs)
-            o0 = (dirs.nbytes + 15) // 16 * 16
-            with self._mutex:
-                if to_ctx:
-                    _check(lib().sf_trace_dirs(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr)), "sf_trace_dirs",
-                           self._ctx)
-                else:
-                    _check(lib().sf_trace_dirs_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr),
-                                                  ctypes.c_void_p(d.ptr + o0), ctypes.c_void_p(d.ptr + o0 + 16 * n),
-                                                  ctypes.c_void_p(d.ptr + o0 + 32 * n),
-                                                  ctypes.c_void_p(d.ptr + o0 + 36 * n)), "sf_trace_dirs_to", self._ctx)
-                # (the scratch is freed on leaving: the trace that reads and writes it must be done)
-                _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
+
+        def trace(ins, outs):
             if to_ctx:
-                return None
-            for a, off in ((pos, 0), (nrm, 16 * n), (mint, 32 * n), (idx, 36 * n)):
-                d.download(o0 + off, a)
-        return pos, nrm, mint, idx
+                _check(lib().sf_trace_dirs(self._ctx, ctypes.byref(p), ins[0]), "sf_trace_dirs", self._ctx)
+            else:
+                _check(lib().sf_trace_dirs_to(self._ctx, ctypes.byref(p), ins[0], *outs), "sf_trace_dirs_to", self._ctx)
+        return self._trace_host(lead, n, (dirs,), trace, outputs=not to_ctx)
 
     def probe(self, dirs):
         """A few rays from the current view's origin, host arrays in and out (sf_probe_dirs; synchronous): picking,
@@ -770,36 +783,16 @@ class Sphereflake:
                 raise ValueError("device rays need out = (pos4, nrm4, min_t, hit_index)")
             dptr = dirs.data_ptr() if shape else int(dirs)
             optr = origins.data_ptr() if oshape else int(origins)
-            addr = [0 if o is None else o.data_ptr() if hasattr(o, "data_ptr") else int(o) for o in out]
-            ptrs = [ctypes.c_void_p(a) if a else None for a in addr]
             with self._mutex:
                 _check(lib().sf_trace_rays_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(optr or None),
-                                              ctypes.c_void_p(dptr or None), *ptrs), "sf_trace_rays_to", self._ctx)
+                                              ctypes.c_void_p(dptr or None), *self._out_ptrs(out)), "sf_trace_rays_to",
+                       self._ctx)
             return None
         if out is not None and not isinstance(out, str):
             raise ValueError("host rays return host arrays: out must be None or 'host'")
         lead = shape[:-1] if len(shape) == 3 else (n,)
-        pos = np.empty(lead + (4,), np.float32)
-        nrm = np.empty(lead + (4,), np.float32)
-        mint = np.empty(lead, np.float32)
-        idx = np.empty(lead, np.uint32)
-        if n == 0:
-            return pos, nrm, mint, idx
-        od = (dirs.nbytes + 15) // 16 * 16
-        o0 = od + (origins.nbytes + 15) // 16 * 16
-        with _DeviceScratch(self.device, o0 + n * 40) as d:
-            d.upload(0, dirs)
-            d.upload(od, origins)
-            with self._mutex:
-                _check(lib().sf_trace_rays_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr + od),
-                                              ctypes.c_void_p(d.ptr), ctypes.c_void_p(d.ptr + o0),
-                                              ctypes.c_void_p(d.ptr + o0 + 16 * n), ctypes.c_void_p(d.ptr + o0 + 32 * n),
-                                              ctypes.c_void_p(d.ptr + o0 + 36 * n)), "sf_trace_rays_to", self._ctx)
-                # (the scratch is freed on leaving: the trace that reads and writes it must be done)
-                _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
-            for a, off in ((pos, 0), (nrm, 16 * n), (mint, 32 * n), (idx, 36 * n)):
-                d.download(o0 + off, a)
-        return pos, nrm, mint, idx
+        return self._trace_host(lead, n, (dirs, origins), lambda ins, outs: _check(
+            lib().sf_trace_rays_to(self._ctx, ctypes.byref(p), ins[1], ins[0], *outs), "sf_trace_rays_to", self._ctx))
 
     def probe_rays(self, origins, dirs, rays_per_origin=1):
         """A few rays from caller-supplied origins, host arrays in and out (sf_probe_rays; synchronous): the
@@ -847,10 +840,16 @@ class Sphereflake:
         return self._trace_vis(lambda W, H: self.shadow_params(light, bias, origin, W, H, max_depth, stream),
                                "sf_trace_shadow", pos, out)
 
-    def _trace_vis(self, params, entry, pos, out):
-        """The `pos` / `out` forms of trace_shadow() and trace_sun(): params(width, height) makes the call's parameter
-        block; `entry` names the call into the context's own buffer, `entry`_to the one into a caller's."""
+    def _trace_vis(self, params, entry, pos, out, dtype=np.uint8):
+        """The `pos` / `out` forms of trace_shadow(), trace_shadows() and trace_sun(): params(width, height) makes the
+        call's parameter block, or (block, the host arrays it points into, kept alive until the call has returned);
+        `entry` names the call into the context's own buffer, `entry`_to the one into a caller's; `dtype` is the
+        result's per pixel."""
         to, own = getattr(lib(), entry + "_to"), getattr(lib(), entry)
+
+        def make(W, H):
+            p = params(W, H)
+            return p if isinstance(p, tuple) else (p, None)
         if isinstance(pos, np.ndarray):
             pos = np.ascontiguousarray(pos, np.float32)
             if pos.ndim != 3 or pos.shape[-1] != 4:
@@ -858,11 +857,11 @@ class Sphereflake:
             if out is not None:
                 raise ValueError("a host position image returns a host array: out must be None")
             H, W = pos.shape[:2]
-            vis = np.empty((H, W), np.uint8)
+            vis = np.empty((H, W), dtype)
+            p, keep = make(W, H)
             if H * W == 0:
                 return vis
-            p = params(W, H)
-            with _DeviceScratch(self.device, pos.nbytes + H * W) as d:
+            with _DeviceScratch(self.device, pos.nbytes + vis.nbytes) as d:
                 d.upload(0, pos)
                 with self._mutex:
                     _check(to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr), ctypes.c_void_p(d.ptr + pos.nbytes)),
@@ -873,7 +872,7 @@ class Sphereflake:
             return vis
         optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
         if pos is None:
-            p = params(0, 0)
+            p, keep = make(0, 0)
             with self._mutex:
                 if optr:
                     _check(to(self._ctx, ctypes.byref(p), None, ctypes.c_void_p(optr)), entry + "_to", self._ctx)
@@ -890,7 +889,7 @@ class Sphereflake:
             pptr, W, H = (int(x) for x in pos)
         if not optr:
             raise ValueError("a device position image needs an `out` buffer")
-        p = params(W, H)
+        p, keep = make(W, H)
         with self._mutex:
             _check(to(self._ctx, ctypes.byref(p), ctypes.c_void_p(pptr), ctypes.c_void_p(optr)), entry + "_to", self._ctx)
         return None
@@ -955,55 +954,8 @@ class Sphereflake:
           - a torch CUDA tensor [H, W, 4] (contiguous float32), or a (device address, width, height) tuple: zero
             copy, asynchronous; the result goes to `out`.
         out: a torch CUDA tensor of H x W 8-byte elements, or a device address (8-byte aligned)."""
-        if isinstance(pos, np.ndarray):
-            pos = np.ascontiguousarray(pos, np.float32)
-            if pos.ndim != 3 or pos.shape[-1] != 4:
-                raise ValueError("pos must be [H, W, 4]")
-            if out is not None:
-                raise ValueError("a host position image returns a host array: out must be None")
-            H, W = pos.shape[:2]
-            mask = np.empty((H, W), np.uint64)
-            p, keep = self.shadows_params(lights, None, bias, origin, W, H, max_depth, stream)
-            if H * W == 0:
-                return mask
-            with _DeviceScratch(self.device, pos.nbytes + mask.nbytes) as d:
-                d.upload(0, pos)
-                with self._mutex:
-                    _check(lib().sf_trace_shadows_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr),
-                                                     ctypes.c_void_p(d.ptr + pos.nbytes)), "sf_trace_shadows_to",
-                           self._ctx)
-                    # (the scratch is freed on leaving: the trace that reads and writes it must be done)
-                    _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
-                d.download(pos.nbytes, mask)
-            del keep
-            return mask
-        optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
-        if pos is None:
-            p, keep = self.shadows_params(lights, None, bias, origin, 0, 0, max_depth, stream)
-            with self._mutex:
-                if optr:
-                    _check(lib().sf_trace_shadows_to(self._ctx, ctypes.byref(p), None, ctypes.c_void_p(optr)),
-                           "sf_trace_shadows_to", self._ctx)
-                else:
-                    _check(lib().sf_trace_shadows(self._ctx, ctypes.byref(p)), "sf_trace_shadows", self._ctx)
-            del keep
-            return None
-        if hasattr(pos, "data_ptr"):
-            shape = tuple(pos.shape)
-            if len(shape) != 3 or shape[-1] != 4 or not (pos.is_cuda and pos.is_contiguous() and pos.element_size() == 4
-                                                         and pos.dtype.is_floating_point):
-                raise ValueError("pos must be a contiguous float32 CUDA tensor [H, W, 4]")
-            pptr, W, H = pos.data_ptr(), shape[1], shape[0]
-        else:
-            pptr, W, H = (int(x) for x in pos)
-        if not optr:
-            raise ValueError("a device position image needs an `out` buffer")
-        p, keep = self.shadows_params(lights, None, bias, origin, W, H, max_depth, stream)
-        with self._mutex:
-            _check(lib().sf_trace_shadows_to(self._ctx, ctypes.byref(p), ctypes.c_void_p(pptr), ctypes.c_void_p(optr)),
-                   "sf_trace_shadows_to", self._ctx)
-        del keep
-        return None
+        return self._trace_vis(lambda W, H: self.shadows_params(lights, None, bias, origin, W, H, max_depth, stream),
+                               "sf_trace_shadows", pos, out, np.uint64)
 
     def download_shadow_masks(self) -> np.ndarray:
         """[H, W] uint64 of the last trace_shadows() into the context's mask buffer (synchronous)."""

@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 CHANNELS = ("pos4", "nrm4", "minT", "index")
 LOD = {"avx": 70.0, "sse": 60.0}
 SENTINEL = np.float32(-12345.5)
+FIXUP_LOOP_COPIES = 38   # (t3 at 4 levels flags every group of the list, 56.25 a copy: about 2140)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -203,6 +204,24 @@ def test_overflow_groups_are_retraced():
         assert_same(got, scattered_oracle("t4"), "t4 scattered")
         s.Synchronize()
         assert s.stats().max_depth == scattered_oracle("t4")["stats"]["max_depth"]
+
+
+def test_more_flagged_groups_than_fixup_blocks():
+    """t3's pinhole directions R times over as one list at max_depth = 4: more flagged groups than the re-trace launch
+    has blocks (1024 is the larger of the two fixup grids), so its blocks walk the list more than once. 3600 rays are
+    56.25 groups: the copies are grouped differently, the per-ray results are the frame's all the same."""
+    R = FIXUP_LOOP_COPIES
+    ref = frame("t3")
+    flat = pinhole("t3").reshape(-1, 3)
+    n = flat.shape[0]
+    want = {k: np.concatenate([ref[k].reshape((n,) + ref[k].shape[2:])] * R) for k in CHANNELS}
+    with flake("t3") as s:
+        o0 = s.stats().overflow_tiles
+        got = trace(s, np.concatenate([flat] * R), max_depth=4)
+        moved = s.stats().overflow_tiles - o0
+    print("flagged groups", moved, "per copy", moved / R)
+    assert moved > 1024
+    assert_same(got, want, f"t3 pinhole x {R}, 4 levels")
 
 
 # 6 ---------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 SENTINEL = np.float32(-12345.5)
 FORCE_MIXED = "0x8000"   # SF_FLAG_FORCE_MIXED
 MISS4 = np.array([0.0, 0.0, 0.0, 1.0], np.float32)
+FIXUP_LOOP_COPIES = 132   # (the reflect set at 4 levels flags all 16 groups of a copy: 2112)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -167,6 +168,23 @@ def test_secondary_rays_overflow_and_are_retraced(name, max_depth):
     assert st.overflow_tiles > 0
     assert st.max_depth == ref["stats"]["max_depth"]
     assert np.float32(st.closest) == np.float32(ref["stats"]["closest"])
+
+
+def test_more_flagged_groups_than_fixup_blocks():
+    """The reflect set R times over as one list (an origin per ray: the mixed path) at max_depth = 4: more flagged
+    groups than the re-trace launch has blocks (1024), so its blocks walk the list more than once, restaging the root
+    image between groups."""
+    R = FIXUP_LOOP_COPIES
+    o, d = rayscheck.reflect()
+    ref = set_oracle("reflect")
+    want = {k: np.concatenate([ref[k]] * R) for k in CHANNELS}
+    with flake("t3") as s:
+        o0 = s.stats().overflow_tiles
+        got = trace(s, np.concatenate([o] * R), np.concatenate([d] * R), max_depth=4)
+        moved = s.stats().overflow_tiles - o0
+    print("flagged groups", moved, "per copy", moved / R)
+    assert moved > 1024
+    assert_same(got, want, f"reflect x {R}, 4 levels")
 
 
 def test_towards_out_sees_nothing():

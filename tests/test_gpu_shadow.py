@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 
 BIASES = (0.0, 2.0 ** -11, 2.0 ** -7)
 B9 = 2.0 ** -9
+FIXUP_LOOP_COPIES = 40   # (t3 at 4 levels flags about 53 of a copy's 56.25 tiles: about 2130)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -86,6 +87,22 @@ def test_overflow_tiles_are_retraced():
             got = s.trace_shadow(light_of(light_name), bias=B9, pos=pos, max_depth=4)
             assert np.array_equal(got, sc.oracle_vis("t3", light_name, B9)), light_name
         assert s.stats().overflow_tiles > o0
+
+
+def test_more_flagged_tiles_than_fixup_blocks():
+    """t3's position image stacked R times into one 80 x 45R image at max_depth = 4: more flagged tiles than the
+    re-trace launch has blocks (1024 is the larger of the two fixup grids), so its blocks walk the list more than once.
+    45 is no multiple of 8: the copies fall differently into tiles, the per-pixel bytes are the oracle's all the same."""
+    R = FIXUP_LOOP_COPIES
+    pos = np.concatenate([frame("t3")["pos4"]] * R)
+    want = np.concatenate([sc.oracle_vis("t3", "side", B9)] * R)
+    with flake("t3") as s:
+        o0 = s.stats().overflow_tiles
+        got = s.trace_shadow(light_of("side"), bias=B9, pos=pos, max_depth=4)
+        moved = s.stats().overflow_tiles - o0
+    print("flagged tiles", moved, "per copy", moved / R)
+    assert moved > 1024
+    assert np.array_equal(got, want)
 
 
 # 3 ---------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 BIASES = (0.0, 2.0 ** -11, 2.0 ** -7)
 B9 = 2.0 ** -9
+FIXUP_LOOP_COPIES = 38   # (t3 at 4 levels flags about 55.7 of a copy's 56.25 tiles: about 2115)
 NAMED = {"t1": ("side", "low", "inside"), "t3": ("side", "top")}
 U1 = np.uint64(1)
 
@@ -124,6 +125,23 @@ def test_overflow_tiles_are_retraced_for_every_light():
         assert_mask(got, want, "max_depth = 4")
         assert s.stats().overflow_tiles > o0
         assert_mask(s.trace_shadows(points(names), bias=B9, pos=pos), want, "auto levels")
+
+
+def test_more_flagged_tiles_than_fixup_blocks():
+    """t3's position image stacked R times into one 80 x 45R image, three lights, max_depth = 4: more flagged tiles than
+    the re-trace launch has blocks (1024 is the larger of the two fixup grids), so its blocks walk the list more than
+    once. 45 is no multiple of 8: the copies fall differently into tiles, the per-pixel masks are the same."""
+    R = FIXUP_LOOP_COPIES
+    names = ("side", "top", "side")
+    pos = np.concatenate([frame("t3")["pos4"]] * R)
+    want = np.concatenate([oracle_mask("t3", names, B9)] * R)
+    with flake("t3") as s:
+        o0 = s.stats().overflow_tiles
+        got = s.trace_shadows(points(names), bias=B9, pos=pos, max_depth=4)
+        moved = s.stats().overflow_tiles - o0
+    print("flagged tiles", moved, "per copy", moved / R)
+    assert moved > 1024
+    assert_mask(got, want, f"t3 x {R}, 4 levels")
 
 
 # 4 ---------------------------------------------------------------------------------------------------

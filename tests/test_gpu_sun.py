@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 
 BIASES = (0.0, su.B10)
 FORCE_MIXED = "0x8000"   # SF_FLAG_FORCE_MIXED
+FIXUP_LOOP_COPIES = 38   # (t3 at 4 levels flags about 55.8 of a copy's 56.25 tiles: about 2120)
 # (fixture, direction, tau, variant): t1's 36 rows end in partial tiles
 CASES = (("t1", "side", 4.0, "avx"), ("t3", "cam", 4.0, "avx"), ("t3", "cam", 8.0, "avx"), ("t1", "side", 4.0, "sse"))
 
@@ -105,6 +106,22 @@ def test_overflow_tiles_are_retraced():
     with flake("t1") as s:
         got = s.trace_sun(su.direction("side"), su.TAU, bias=su.B10, pos=frame("t1")["pos4"], max_depth=4)
         assert np.array_equal(got, su.oracle_vis("t1", "side", su.B10))
+
+
+def test_more_flagged_tiles_than_fixup_blocks():
+    """t3's position image stacked R times into one 80 x 45R image at max_depth = 4: more flagged tiles than the
+    re-trace launch has blocks (1024), so its blocks walk the list more than once. 45 is no multiple of 8: the copies
+    fall differently into tiles, the per-pixel bytes are the oracle's all the same."""
+    R = FIXUP_LOOP_COPIES
+    pos = np.concatenate([frame("t3")["pos4"]] * R)
+    want = np.concatenate([su.oracle_vis("t3", "cam", su.B10)] * R)
+    with flake("t3") as s:
+        o0 = s.stats().overflow_tiles
+        got = s.trace_sun(su.direction("cam"), su.TAU, bias=su.B10, pos=pos, max_depth=4)
+        moved = s.stats().overflow_tiles - o0
+    print("flagged tiles", moved, "per copy", moved / R)
+    assert moved > 1024
+    assert np.array_equal(got, want)
 
 
 # 4 ---------------------------------------------------------------------------------------------------
