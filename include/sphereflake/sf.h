@@ -687,10 +687,20 @@ int sf_dist_slab_bytes(const sf_dist* dist);
 
 /* The context's own stream (hipStream_t) -- where calls with a NULL stream are queued. */
 void* sf_context_stream(sf_ctx* ctx);
-/* Trace launches of this context that took the lean tile loop (kernel sf_trace_queue1: whole-tile units of one plain
-   frame -- no aux channels, packed slab, band share, part units, tile costs or diagnostics; SF_LEAN=0 in the
-   environment of sf_create forces the general loop, sf_trace_queue1g, everywhere). For tests and measurements. */
+/* Trace launches of this context that took the lean tile loop (kernels sf_trace_queue1t, and sf_trace_queue1 / 1c over
+   pair units: whole units of one plain frame -- no aux channels, packed slab, band share, part units or diagnostics;
+   SF_LEAN=0 in the environment of sf_create forces the general loop, sf_trace_queue1g, everywhere). For tests and
+   measurements. */
 uint32_t sf_lean_launches(const sf_ctx* ctx);
+/* Those of them that took the pair-unit loop (sf_trace_queue1, and sf_trace_queue1c on the render that rebuilds the
+   unit order): two horizontally adjacent 8x8 tiles per wave, which share the traversal's upper levels. By default a
+   launch the lean loop can serve takes it where the frame has more tiles than twice the pair kernel's persistent grid
+   (1920x1080 and up); SF_PAIR=0 in the environment of sf_create turns pair units off, SF_PAIR=1 takes them at every
+   frame size. Results are the same bit for bit. */
+uint32_t sf_pair_launches(const sf_ctx* ctx);
+/* Units the context's current unit order was built over -- tiles, or pair units where the renders take those: the
+   entries of sf_get_tile_order's `cost` that are meaningful (0: no order yet). */
+uint32_t sf_order_units(const sf_ctx* ctx);
 
 /* --- misc ---------------------------------------------------------------- */
 

@@ -12,6 +12,11 @@
  * Variants (mode bits) model candidate kernel changes so they can be priced before they are written:
  *   1: per-node cone -- the cone cull of a node's children uses the half-angle of the lanes visiting the node
  *      (around the tile axis) instead of the whole tile's.
+ * The unit a wave traces is TW x TH pixels, compile-time (-DTW=16 -DTH=8; default 8 x 8, one tile): lane l is pixel
+ * (l % TW, l / TW) of the unit, TW TH <= 128 lanes (lane masks are unsigned __int128), the cone axis is the centre
+ * pixel's lane (TH / 2) TW + TW / 2 -- a pair unit of the kernel is 16 x 8 with two rays per hardware lane. half_exp /
+ * half_iter count, per depth, the expansions and child iterations whose visiting lanes all lie in one 8 x 8 tile of
+ * the unit (a subtree the pair kernel runs on its one-ray loop).
  * Built by scripts/experiments/wave_sim.py against oracle/sf_oracle.c (included).
  */
 #include <stdlib.h>
@@ -20,6 +25,31 @@
 #include "../../oracle/sf_oracle.c"
 
 #define NST 32
+#ifndef TW
+#define TW 8
+#endif
+#ifndef TH
+#define TH 8
+#endif
+#define NL (TW * TH)
+#if NL > 128 || TW % 8 != 0 || TH % 8 != 0
+#error "a unit is whole 8x8 tiles, at most 128 lanes"
+#endif
+typedef unsigned __int128 lmask_t;
+#define LM1 ((lmask_t)1)
+#define AXIS_LANE ((TH / 2) * TW + TW / 2)
+static int lm_pop(lmask_t m) { return __builtin_popcountll((uint64_t)m) + __builtin_popcountll((uint64_t)(m >> 64)); }
+/* all lanes of m lie in one 8x8 tile of the unit */
+static int lm_one_half(lmask_t m)
+{
+    int first = -1;
+    for (int l = 0; l < NL; ++l) {
+        if (!((m >> l) & 1)) continue;
+        const int h = ((l / TW) / 8) * (TW / 8) + (l % TW) / 8;
+        if (first < 0) first = h; else if (h != first) return 0;
+    }
+    return 1;
+}
 #define SF_OCCL_MARGIN_SIM 0x1.8p-9f
 
 /* the kernel's per-depth constants (sf_capi.hip upload_consts, sf_setup.cpp depth_tables / leaf_threshold) */
@@ -61,6 +91,7 @@ typedef struct {
     long long cone_tested[NST], cone_culled[NST];
     long long skip_exp[NST], skip_lost[NST];   /* expansions the useless-cone predicate skips; culls lost by it */
     long long cache_hit[NST];                  /* expansions whose level table already holds their children */
+    long long half_exp[NST], half_iter[NST];   /* expansions / iterations whose visiting lanes lie in one 8x8 tile */
 } sim_stats_t;
 
 typedef struct {
@@ -70,12 +101,12 @@ typedef struct {
     int mode;
     float skip_k, skip_f;
     /* tile */
-    float D[64][3];
+    float D[NL][3];
     float ax[3], cosT, sinT;
-    float s2[64];            /* per lane |d x a|^2 (mode 1) */
-    float minT[64];
-    uint64_t idx[64];
-    int hdepth[64];
+    float s2[NL];            /* per lane |d x a|^2 (mode 1) */
+    float minT[NL];
+    uint64_t idx[NL];
+    int hdepth[NL];
     int maxd;
     float cull_t;
     sim_stats_t* st;
@@ -108,9 +139,9 @@ static float near_root_f(float tca, float d2, float R2)
 }
 
 /* self test of sphere (centre C, cc) at depth dd, heap index id, for the lanes of m */
-static void self_test(wsim_t* S, const float C[3], float cc, int dd, uint64_t id, uint64_t m)
+static void self_test(wsim_t* S, const float C[3], float cc, int dd, uint64_t id, lmask_t m)
 {
-    for (int l = 0; l < 64; ++l) {
+    for (int l = 0; l < NL; ++l) {
         if (!((m >> l) & 1)) continue;
         const float* D = S->D[l];
         float tca = (C[0] * D[0] + C[1] * D[1]) + C[2] * D[2];
@@ -128,10 +159,12 @@ static void self_test(wsim_t* S, const float C[3], float cc, int dd, uint64_t id
 }
 
 /* the node at depth d with frame M (16 floats) is entered by the lanes of A (already self-tested) and expands */
-static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, uint64_t A)
+static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, lmask_t A)
 {
     sim_stats_t* st = S->st;
     st->exp[d]++;
+    const int one_half = lm_one_half(A);
+    st->half_exp[d] += one_half;
     if (S->owner[d] == node) st->cache_hit[d]++;
     S->owner[d] = node;
     const int saved_part = S->cur_part;
@@ -148,7 +181,7 @@ static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, uint64_
     float sinT = S->sinT, cosT = S->cosT;
     if (S->mode & 1) {   /* per-node cone: max over the visiting lanes */
         float smax = 0.0f;
-        for (int l = 0; l < 64; ++l)
+        for (int l = 0; l < NL; ++l)
             if ((A >> l) & 1) smax = S->s2[l] > smax ? S->s2[l] : smax;
         float sm = sqrtf(smax) * (1.0f + 0x1p-16f) + 0x1p-16f;
         sinT = 1.0f; cosT = 0.0f;
@@ -232,7 +265,7 @@ static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, uint64_
                 double dd = S->pl[k][0] * C[0] + S->pl[k][1] * C[1] + S->pl[k][2] * C[2];
                 if (dd < -R) {
                     culled[i] = 1; st->skip_lost[d]++;
-                    if (getenv("DBG")) for (int l = 0; l < 64; ++l) {
+                    if (getenv("DBG")) for (int l = 0; l < NL; ++l) {
                         const float* D = S->D[l];
                         float tca = (C[0] * D[0] + C[1] * D[1]) + C[2] * D[2];
                         float d2 = w - tca * tca;
@@ -260,31 +293,32 @@ static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, uint64_
         if (S->solo >= 0 && S->split_p > 0 && dc == S->split_k &&
             (int)((9 * node + 1 + (uint64_t)c) % (uint64_t)S->split_p) != S->solo) continue;
         st->iter[d]++;
+        st->half_iter[d] += one_half;
         SIM_WORK(1.0);
-        st->act[d] += __builtin_popcountll(A);
-        uint64_t hb = 0, ex = 0;
-        for (int l = 0; l < 64; ++l) {
+        st->act[d] += lm_pop(A);
+        lmask_t hb = 0, ex = 0;
+        for (int l = 0; l < NL; ++l) {
             if (!((A >> l) & 1)) continue;
             const float* D = S->D[l];
             float tca = (C[0] * D[0] + C[1] * D[1]) + C[2] * D[2];
             float d2 = cc[c] - tca * tca;
             if (!(tca >= 0.0f && d2 <= S->r2b[dc])) continue;
-            hb |= 1ull << l;
+            hb |= LM1 << l;
             float t = near_root_f(tca, d2, S->r2b[dc]);
-            if (t < S->T[dc]) ex |= 1ull << l;
+            if (t < S->T[dc]) ex |= LM1 << l;
         }
-        st->hitl[d] += __builtin_popcountll(hb);
+        st->hitl[d] += lm_pop(hb);
         if (!hb) { st->miss[d]++; continue; }
         if (!ex) { st->lodnone[d]++; continue; }
         if (dc > S->maxd) { S->maxd = dc; S->cull_t = S->T[dc + 1]; }
-        uint64_t am = ex;
-        for (int l = 0; l < 64; ++l) {
+        lmask_t am = ex;
+        for (int l = 0; l < NL; ++l) {
             if (!((ex >> l) & 1)) continue;
             const float* D = S->D[l];
             float tca = (C[0] * D[0] + C[1] * D[1]) + C[2] * D[2];
             float v1 = tca - S->minT[l], v2 = tca - S->cull_t;
             float v = v1 < v2 ? v1 : v2;
-            if (v - SF_OCCL_MARGIN_SIM * tca > S->cull[dc]) am &= ~(1ull << l);
+            if (v - SF_OCCL_MARGIN_SIM * tca > S->cull[dc]) am &= ~(LM1 << l);
         }
         if (!am) { st->occlnone[d]++; continue; }
         st->entered[d]++;
@@ -320,15 +354,15 @@ int wsim_tiles(uint32_t W, uint32_t H, const float o[3], const float tl[3], cons
     const float fw = (float)W, fh = (float)H;
     const float dh[3] = { tr[0] - tl[0], tr[1] - tl[1], tr[2] - tl[2] };
     const float dv[3] = { bl[0] - tl[0], bl[1] - tl[1], bl[2] - tl[2] };
-    const uint32_t tw = (W + 7) / 8;
+    const uint32_t tw = (W + TW - 1) / TW;   /* units per row */
     for (int k = 0; k < NST; ++k) S.owner[k] = ~0ull;
     const uint32_t run = (mode & 8) ? 4u : (mode & 16) ? 2u : 1u;   /* tiles per wave run (cache kept within a run) */
     for (uint32_t t = t0; t < t1; ++t) {
         const uint32_t tx = t % tw, ty = t / tw;
         if ((t - t0) % run == 0) for (int k = 0; k < NST; ++k) S.owner[k] = ~0ull;
-        uint64_t valid = 0;
-        for (int l = 0; l < 64; ++l) {
-            uint32_t x = tx * 8 + (l & 7), y = ty * 8 + (l >> 3);
+        lmask_t valid = 0;
+        for (int l = 0; l < NL; ++l) {
+            uint32_t x = tx * TW + (l % TW), y = ty * TH + (l / TW);
             float u = (float)x / fw, v = (float)y / fh;
             float* D = S.D[l];
             D[0] = ((tl[0] + dh[0] * u) + dv[0] * v) - o[0];
@@ -336,15 +370,17 @@ int wsim_tiles(uint32_t W, uint32_t H, const float o[3], const float tl[3], cons
             D[2] = ((tl[2] + dh[2] * u) + dv[2] * v) - o[2];
             normalize3(D, lut);
             int in = 1;   /* part units (the kernel's tile_of): 1/2 rows 0-3 / 4-7, 3..6 the 4x4 quarters */
+#if NL == 64 && TW == 8
             if (S.part >= 1 && S.part <= 2) in = (l >> 5) + 1 == S.part;
             if (S.part >= 3) { int q = S.part - 3; in = (l >> 5) == (q >> 1) && ((l >> 2) & 1) == (q & 1); }
-            if (x < W && y < H && in) valid |= 1ull << l;
+#endif
+            if (x < W && y < H && in) valid |= LM1 << l;
             S.minT[l] = FLT_MAX; S.idx[l] = 0xffffffffu; S.hdepth[l] = -1;
         }
-        /* tile cone around lane 36's ray */
-        memcpy(S.ax, S.D[36], sizeof S.ax);
+        /* unit cone around the centre lane's ray (lane 36 of an 8x8 tile) */
+        memcpy(S.ax, S.D[AXIS_LANE], sizeof S.ax);
         float smax = 0.0f;
-        for (int l = 0; l < 64; ++l) {
+        for (int l = 0; l < NL; ++l) {
             const float* D = S.D[l];
             const float* a = S.ax;
             float c0 = D[1] * a[2] - D[2] * a[1], c1 = D[2] * a[0] - D[0] * a[2], c2 = D[0] * a[1] - D[1] * a[0];
@@ -358,41 +394,41 @@ int wsim_tiles(uint32_t W, uint32_t H, const float o[3], const float tl[3], cons
         S.sinT = 1.0f; S.cosT = 0.0f;
         if (sm < 0.5f) { S.sinT = sm; S.cosT = sqrtf(1.0f - sm * sm) * (1.0f - 0x1p-16f); }
         {   /* mode 32: pyramid of the valid lanes' extreme rays: corners of the tile's valid pixel rectangle */
-            int xs = 7, ys = 7;
-            while (xs > 0 && tx * 8 + xs >= W) xs--;
-            while (ys > 0 && ty * 8 + ys >= H) ys--;
-            const float* Cn[4] = { S.D[0], S.D[xs], S.D[ys * 8 + xs], S.D[ys * 8] };
+            int xs = TW - 1, ys = TH - 1;
+            while (xs > 0 && tx * TW + xs >= W) xs--;
+            while (ys > 0 && ty * TH + ys >= H) ys--;
+            const float* Cn[4] = { S.D[0], S.D[xs], S.D[ys * TW + xs], S.D[ys * TW] };
             for (int k = 0; k < 4; ++k) {
                 const float* a = Cn[k]; const float* b = Cn[(k + 1) & 3];
                 double n0 = (double)a[1] * b[2] - (double)a[2] * b[1], n1 = (double)a[2] * b[0] - (double)a[0] * b[2],
                        n2 = (double)a[0] * b[1] - (double)a[1] * b[0];
                 double nn = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
                 /* orient inward: the tile centre ray on the positive side */
-                const float* c = S.D[36];
+                const float* c = S.D[AXIS_LANE];
                 double sg = n0 * c[0] + n1 * c[1] + n2 * c[2];
                 if (sg < 0) nn = -nn;
                 S.pl[k][0] = n0 / nn; S.pl[k][1] = n1 / nn; S.pl[k][2] = n2 / nn;
             }
         }
         if (mode & (128 | 8192)) {   /* the planned kernel's per-tile frustum, fp32 */
-            const int cidx[4] = { 0, 7, 63, 56 };
+            const int cidx[4] = { 0, TW - 1, NL - 1, NL - TW };
             float mneg = 0.0f, dmax = 0.0f;
             for (int k = 0; k < 4; ++k) {
                 const float* a = S.D[cidx[k]]; const float* b = S.D[cidx[(k + 1) & 3]];
                 float n0 = a[1] * b[2] - a[2] * b[1], n1 = a[2] * b[0] - a[0] * b[2], n2 = a[0] * b[1] - a[1] * b[0];
-                const float* c = S.D[36];
+                const float* c = S.D[AXIS_LANE];
                 float sg = (n0 * c[0] + n1 * c[1]) + n2 * c[2];
                 float nn = (n0 * n0 + n1 * n1) + n2 * n2;
                 float r = 1.0f / sqrtf(nn);
                 if (sg < 0.0f) r = -r;
                 S.fn[k][0] = n0 * r; S.fn[k][1] = n1 * r; S.fn[k][2] = n2 * r;
-                for (int l = 0; l < 64; ++l) {
+                for (int l = 0; l < NL; ++l) {
                     const float* D = S.D[l];
                     float v = (S.fn[k][0] * D[0] + S.fn[k][1] * D[1]) + S.fn[k][2] * D[2];
                     if (-v > mneg) mneg = -v;
                 }
             }
-            for (int l = 0; l < 64; ++l) {
+            for (int l = 0; l < NL; ++l) {
                 const float* D = S.D[l];
                 float e = fmaf(D[2], D[2], fmaf(D[1], D[1], fmaf(D[0], D[0], -1.0f)));
                 if (e > dmax) dmax = e;
@@ -427,13 +463,13 @@ int wsim_tiles(uint32_t W, uint32_t H, const float o[3], const float tl[3], cons
         for (int q = 0; q < 8; ++q) S.part_work[q] = 0.0;
         const float* C = root + 12;
         const float rcc = (C[0] * C[0] + C[1] * C[1]) + C[2] * C[2];
-        uint64_t ex0 = 0;
-        for (int l = 0; l < 64; ++l) {
+        lmask_t ex0 = 0;
+        for (int l = 0; l < NL; ++l) {
             if (!((valid >> l) & 1)) continue;
             const float* D = S.D[l];
             float tca = (C[0] * D[0] + C[1] * D[1]) + C[2] * D[2];
             float d2 = rcc - tca * tca;
-            if (tca >= 0.0f && d2 <= S.r2b[0] && near_root_f(tca, d2, S.r2b[0]) < S.T[0]) ex0 |= 1ull << l;
+            if (tca >= 0.0f && d2 <= S.r2b[0] && near_root_f(tca, d2, S.r2b[0]) < S.T[0]) ex0 |= LM1 << l;
         }
         st->tiles++;
         if (ex0) {
@@ -451,8 +487,8 @@ int wsim_tiles(uint32_t W, uint32_t H, const float o[3], const float tl[3], cons
             tile_work[3 * (t - t0) + 2] = mx;
         }
         if (ref_minT) {
-            for (int l = 0; l < 64; ++l) {
-                uint32_t x = tx * 8 + (l & 7), y = ty * 8 + (l >> 3);
+            for (int l = 0; l < NL; ++l) {
+                uint32_t x = tx * TW + (l % TW), y = ty * TH + (l / TW);
                 if (x >= W || y >= H) continue;
                 size_t p = (size_t)y * W + x;
                 uint32_t a, b;

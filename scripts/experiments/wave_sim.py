@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Drive wave_sim.c: the product kernel's wave-coherent traversal modelled on the CPU, its work counted per depth
-(experiment, not product). Usage: wave_sim.py [setup=c3] [tile_step=1] [mode=0 ...]"""
+(experiment, not product). Usage: [WAVE_UNIT=16x8] wave_sim.py [setup=c3] [tile_step=1] [mode=0 ...]
+WAVE_UNIT: the pixels a wave traces, TWxTH (default 8x8, one tile; 16x8 or 8x16: the pair unit), at most 128 lanes."""
 import ctypes
 import os
 import subprocess
@@ -14,8 +15,9 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(REPO, "oracle"))
 import pyoracle  # noqa: E402
 
-SO = "/tmp/wave_sim.so"
-subprocess.check_call(["gcc", "-O2", "-mno-fma", "-ffp-contract=off", "-shared", "-fPIC", "-o", SO,
+TW, TH = (int(v) for v in os.environ.get("WAVE_UNIT", "8x8").split("x"))
+SO = f"/tmp/wave_sim_{TW}x{TH}.so"
+subprocess.check_call(["gcc", "-O2", "-mno-fma", "-ffp-contract=off", f"-DTW={TW}", f"-DTH={TH}", "-shared", "-fPIC", "-o", SO,
                        os.path.join(HERE, "wave_sim.c"), "-lm"])
 L = ctypes.CDLL(SO)
 NST = 32
@@ -27,7 +29,8 @@ class Stats(ctypes.Structure):
     _fields_ = [(f, ctypes.c_longlong * NST) for f in FIELDS] + [(f, ctypes.c_longlong) for f in TAIL] + \
                [("cone_tested", ctypes.c_longlong * NST), ("cone_culled", ctypes.c_longlong * NST),
                 ("skip_exp", ctypes.c_longlong * NST), ("skip_lost", ctypes.c_longlong * NST),
-                ("cache_hit", ctypes.c_longlong * NST)]
+                ("cache_hit", ctypes.c_longlong * NST), ("half_exp", ctypes.c_longlong * NST),
+                ("half_iter", ctypes.c_longlong * NST)]
 
 
 fp = ctypes.POINTER(ctypes.c_float)
@@ -47,7 +50,7 @@ def run(name="c3", tile_step=1, mode=0, check=True, split=(0, 0)):
     child = child.reshape(-1)
     d8 = np.zeros(NST * 8, np.float32)
     L.wsim_depth8(70.0, d8.ctypes.data_as(fp))
-    tw, th = (W + 7) // 8, (H + 7) // 8
+    tw, th = (W + TW - 1) // TW, (H + TH - 1) // TH   # units per row, unit rows
     trows = list(range(0, th, tile_step))
     ref_m = ref_i = None
     if check:
@@ -67,7 +70,7 @@ def run(name="c3", tile_step=1, mode=0, check=True, split=(0, 0)):
                      ctypes.byref(parts[k]), split[0], split[1], works[k].ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
     with ThreadPoolExecutor(8) as ex:
         list(ex.map(work, range(len(trows))))
-    tot = {f: np.sum([np.array(getattr(p, f)[:]) for p in parts], 0) for f in FIELDS + ["cone_tested", "cone_culled", "skip_exp", "skip_lost", "cache_hit"]}
+    tot = {f: np.sum([np.array(getattr(p, f)[:]) for p in parts], 0) for f in FIELDS + ["cone_tested", "cone_culled", "skip_exp", "skip_lost", "cache_hit", "half_exp", "half_iter"]}
     for f in TAIL:
         tot[f] = max(getattr(p, f) for p in parts) if f == "maxd" else sum(getattr(p, f) for p in parts)
     tot["scale"] = tile_step
@@ -90,6 +93,13 @@ def report(t, label=""):
     tot = lambda f: int(t[f].sum()) * sc
     print(f"all {tot('exp'):8d} {tot('iter'):8d} {tot('miss'):7d} {tot('lodnone'):7d} {tot('occlnone'):7d} {tot('entered'):7d}"
           f" {tot('leaf'):7d} {tot('push'):7d} {t['act'].sum()/max(t['iter'].sum(),1):6.1f}")
+    if TW * TH > 64:   # a unit of more than one tile: what of it is visited by lanes of one 8x8 tile only
+        print(f"unit {TW}x{TH}: visited by lanes of one 8x8 tile only")
+        print(" d  exp-one-half    of     iter-one-half    of")
+        for d in range(NST):
+            if t["exp"][d]:
+                print(f"{d:2d} {t['half_exp'][d]*sc:9d} {t['exp'][d]*sc:9d} {t['half_iter'][d]*sc:11d} {t['iter'][d]*sc:9d}")
+        print(f"all {tot('half_exp'):8d} {tot('exp'):9d} {tot('half_iter'):11d} {tot('iter'):9d}")
 
 
 if __name__ == "__main__":

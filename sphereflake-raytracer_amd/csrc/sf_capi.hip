@@ -23,6 +23,8 @@ extern "C" __global__ void sf_trace_wave1(FrameArgs a, uint32_t* overflow_list, 
 extern "C" __global__ void sf_trace_wave2(FrameArgs a, uint32_t* overflow_list, uint32_t* overflow_count);
 extern "C" __global__ void sf_trace_wave4(FrameArgs a, uint32_t* overflow_list, uint32_t* overflow_count);
 extern "C" __global__ void sf_trace_queue1(FrameArgs a);
+extern "C" __global__ void sf_trace_queue1c(FrameArgs a);
+extern "C" __global__ void sf_trace_queue1t(FrameArgs a);
 extern "C" __global__ void sf_trace_frames1(FrameBatch b);
 extern "C" __global__ void sf_trace_queue1g(FrameArgs a);
 extern "C" __global__ void sf_trace_queue1s(FrameArgs a);
@@ -231,7 +233,11 @@ struct sf_ctx {
     int pipe = -1;                               // env SF_PIPE = 0 | 1: latency variant of the trace (-1: auto)
     uint32_t prio_buckets = 8;                   // top cost buckets (3 octaves) traced at raised wave priority (env SF_PRIO_BUCKETS)
     int occ_key = -1, occ_blocks = 0;            // cached occupancy (waves per block, levels) -> blocks per CU
-    int occ_blocks_lean = 0;                     // the same of sf_trace_queue1, the lean tile loop (1 wave per block)
+    int occ_blocks_lean = 0;                     // the same of sf_trace_queue1t, the lean tile loop (1 wave per block)
+    int occ_blocks_pair = 0;                     // the same of sf_trace_queue1 / 1c, the pair-unit loop
+    int pair = -1;                               // pair units (env SF_PAIR): 0 never, 1 wherever the lean loop may run,
+                                                 // -1 where the frame has at least as many pairs as the grid has waves
+    uint32_t pair_launches = 0;                  // trace launches that took the pair-unit loop (sf_pair_launches)
     bool lean = true;                            // env SF_LEAN=0: the general tile loop (sf_trace_queue1g) everywhere
     uint32_t lean_launches = 0;                  // trace launches that took the lean tile loop (sf_lean_launches)
     uint32_t max_blocks = 0;                     // diagnostics: env SF_MAX_BLOCKS caps the persistent grid
@@ -333,7 +339,8 @@ struct sf_ctx {
     // (0: the view's deepest LOD-passable depth - 2)
     uint64_t* part_rec = nullptr;
     uint32_t split_depth_env = 0;
-    uint32_t order_n = 0;              // tile count the current tile_order is a permutation of (0: none)
+    uint32_t order_n = 0;              // unit count the current tile_order is a permutation of (0: none)
+    bool order_pair = false;           // its units are pair units (sf_trace_queue1), not tiles
     // Stream ordering across calls: every call that enqueues work on the context's buffers first joins
     // the stream of the previous such call (ctx_join), so renders, frame-less batches, post-processing
     // and downloads issued on different streams of one context run in call order, as on one stream.
@@ -634,6 +641,7 @@ int sf_create(int device, uint32_t width, uint32_t height, sf_ctx** out)
     if (const char* ev = std::getenv("SF_PF_PRIO")) c->pf_prio = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("SF_TIE_INLINE")) c->tie_inline = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("SF_LEAN")) c->lean = std::atoi(ev) != 0;
+    if (const char* ev = std::getenv("SF_PAIR")) c->pair = std::atoi(ev) != 0 ? 1 : 0;
     if (const char* ev = std::getenv("SF_ORDER_RECORD")) c->order_record_env = std::atoi(ev) != 0 ? 1 : 0;
     if (const char* ev = std::getenv("SF_ORDER_EVERY")) c->order_every = std::atoi(ev) > 1 ? (uint32_t)std::atoi(ev) : 1u;   // (explicit)
     if (const char* ev = std::getenv("SF_PROG_BIN")) c->prog_bin = std::atoi(ev) != 0;
@@ -807,7 +815,8 @@ static FrameArgs frame_args(const sf_ctx* c)
 
 // The next render's tile order from the tile costs the render just enqueued on `s` recorded (sf_order_scan /
 // sf_order_bucket_scan + sf_order_scatter_plan); `waves`: resident waves of its persistent grid.
-static int order_rebuild(sf_ctx* c, hipStream_t s, uint32_t ntiles, uint32_t waves, uint32_t split_buckets)
+// (ntiles: the units the costs are indexed by -- tiles, or with `pair` the pair units of sf_trace_queue1c)
+static int order_rebuild(sf_ctx* c, hipStream_t s, uint32_t ntiles, uint32_t waves, uint32_t split_buckets, bool pair = false)
 {
     const uint32_t nc = (ntiles + 63u) / 64u;
     const uint32_t spare = waves > ntiles ? waves - ntiles : 0u;
@@ -830,6 +839,7 @@ static int order_rebuild(sf_ctx* c, hipStream_t s, uint32_t ntiles, uint32_t wav
         SF_HIP(c, hipGetLastError());
     }
     c->order_n = ntiles;
+    c->order_pair = pair;
     return SF_OK;
 }
 
@@ -935,7 +945,7 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
         a.phase_sums = c->tile_trace + 3 * ntr;
     }
 
-    const uint32_t ntiles = a.tiles_x * tile_rows;
+    uint32_t ntiles = a.tiles_x * tile_rows;   // (the persistent trace's units: pair units where it takes them)
     const uint32_t blocks = (ntiles + SF_WAVES_PER_BLOCK - 1) / SF_WAVES_PER_BLOCK;
     if (p.kernel == SF_KERNEL_PER_RAY) {
         a.max_depth = 31;
@@ -957,13 +967,14 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
         const bool tie_inline = bounded && c->persistent && front_first && c->tie_inline;
         if (tie_inline) a.flags |= SF_FLAG_TIE_INLINE;
         if (c->persistent) {
-            // The lean tile loop (sf_trace_queue1) serves a launch that asks for nothing it leaves out: whole-tile units
+            // The lean tile loop (sf_trace_queue1t) serves a launch that asks for nothing it leaves out: whole-tile units
             // of one plain frame. What the launch itself says is known here; what the schedule adds (part units, tile
             // costs) below -- the grid is sized by the occupancy of the kernel the launch takes.
             const uint32_t lean_off = SF_FLAG_DIAG_HALF | SF_FLAG_DIAG_HALF_SEL | SF_FLAG_DIAG_UNITS |
                                       SF_FLAG_DIAG_FORCE_RETRACE | SF_FLAG_PRIO_FLAT;
-            const bool lean_ok = c->lean && wpb == 1 && band_count == 1u && !a.compact && !a.packed && !a.emit_aux &&
-                                 !a.tile_trace && (a.flags & lean_off) == 0u;
+            const bool plain = c->lean && wpb == 1 && band_count == 1u && !a.compact && !a.packed && !a.emit_aux &&
+                               !a.tile_trace;
+            const bool lean_ok = plain && (a.flags & lean_off) == 0u;
             const void* kern = wpb == 1 ? (const void*)sf_trace_queue1g
                              : wpb == 2 ? (c->compact ? (const void*)sf_trace_queue2c : (const void*)sf_trace_queue2)
                                         : (const void*)sf_trace_queue4;
@@ -973,13 +984,37 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
                 SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, (int)block.x, wpb * lds));
                 c->occ_blocks = nb < 1 ? 1 : nb;
                 c->occ_blocks_lean = c->occ_blocks;
+                c->occ_blocks_pair = c->occ_blocks;
                 if (wpb == 1) {
-                    SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sf_trace_queue1, (int)block.x, lds));
+                    SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sf_trace_queue1t, (int)block.x, lds));
                     c->occ_blocks_lean = nb < 1 ? 1 : nb;
+                    SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sf_trace_queue1, (int)block.x, lds));
+                    c->occ_blocks_pair = nb < 1 ? 1 : nb;
+                    SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sf_trace_queue1c, (int)block.x, lds));
+                    if (nb >= 1 && nb < c->occ_blocks_pair) c->occ_blocks_pair = nb;   // (one grid for both pair kernels)
                 }
                 c->occ_key = key;
             }
-            uint32_t nblk = (uint32_t)(lean_ok ? c->occ_blocks_lean : c->occ_blocks) * (uint32_t)c->cus;
+            // Pair units (sf_trace_queue1: two adjacent tiles per wave, the traversal's upper levels walked once): a
+            // launch the lean loop could serve -- the pair loop also serves the forced re-trace itself -- of a frame
+            // with more tiles than twice the persistent grid, the pair kernel's and the single-tile lean loop's: there
+            // are then at least as many pairs as waves, and the frame is one today's schedule calls `large` (1080p and
+            // up; 1280x720, 14 400 tiles against 2 x 7 168 and 2 x 8 192 waves, keeps its single-tile path: with one
+            // pair per wave it measured 0.028 -> 0.040 ms). Every schedule quantity below then counts pair units, and
+            // the render that rebuilds the order records unit costs in the pair loop (sf_trace_queue1c): a context
+            // never mixes tile and pair orders.
+            const uint32_t pair_off = lean_off & ~SF_FLAG_DIAG_FORCE_RETRACE;
+            const uint32_t pair_grid = (uint32_t)(c->occ_blocks_pair > c->occ_blocks_lean ? c->occ_blocks_pair
+                                                                                          : c->occ_blocks_lean) * (uint32_t)c->cus;
+            // (a context told to split tiles, SF_SPLIT_BUCKETS, keeps tile units by default: pair units have no parts)
+            const bool pair = plain && (a.flags & pair_off) == 0u && c->halves <= 0 && c->pair != 0 &&
+                              (c->pair > 0 || (ntiles > 2u * pair_grid && !(c->split_env && c->split_buckets != 0u)));
+            if (pair) {
+                const uint32_t pairs_x = (a.tiles_x + 1u) / 2u;
+                ntiles = pairs_x * tile_rows;
+                a.px_magic = 0xffffffffu / pairs_x;
+            }
+            uint32_t nblk = (uint32_t)(pair ? c->occ_blocks_pair : lean_ok ? c->occ_blocks_lean : c->occ_blocks) * (uint32_t)c->cus;
             const bool small = ntiles <= 2u * nblk * wpb;   // tiles fill the full persistent grid at most twice
             // The heavy-first order (and the splits it carries) only where the frame's tiles fill at most half
             // the grid's waves: there idle slots take the split heaviest tiles and shorten the frame. With 3
@@ -1005,7 +1040,7 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
             // interleaved runs a side, profiles/r4/split0_ab.txt).
             const bool large = !small && band_count == 1u;
             const bool use_order = c->order_mode > 0 || (c->order_mode < 0 && (tiny || large));
-            const uint32_t split_buckets = (large && !c->split_env) ? 0u : c->split_buckets;
+            const uint32_t split_buckets = (pair || (large && !c->split_env)) ? 0u : c->split_buckets;   // (pairs: no parts)
             // row-major halves (SF_FLAG_HALVES): every tile as two units of its pixel rows 0-3 / 4-7
             const bool halves = !use_order && c->halves > 0;
             if (halves) a.flags |= SF_FLAG_HALVES;
@@ -1035,7 +1070,8 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
             // frame queued behind it: the driver's 20-step loop 0.0727-0.0743 -> 0.0721-0.0722 ms in two 5-run A/Bs;
             // a one-wave scan, or the rebuild on a stream of its own, measured slower, profiles/r5/order/)
             const uint32_t every = c->order_every ? c->order_every : (small ? 3u : large ? 64u : 1u);
-            const bool rebuild = use_order && (c->order_n != ntiles || c->order_phase + 1u >= every);
+            const bool have_order = c->order_n == ntiles && c->order_pair == pair;   // (an order of this launch's units)
+            const bool rebuild = use_order && (!have_order || c->order_phase + 1u >= every);
             if (use_order) c->order_phase = rebuild ? 0u : c->order_phase + 1u;
             if (use_order) {
                 // tile costs: recorded by every render, or only by the render whose costs the rebuild reads
@@ -1049,7 +1085,7 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
                     a.split_depth = c->split_depth_env ? c->split_depth_env : (levels > 3u ? levels - 3u : 1u);
                     a.flags |= SF_FLAG_SUBTREE;
                 }
-                a.tile_order = c->order_n == ntiles ? c->tile_order : nullptr;   // ordered by ctx_join
+                a.tile_order = have_order ? c->tile_order : nullptr;   // ordered by ctx_join
                 a.order_meta = c->order_meta;
             }
             const bool timed = c->timing && c->ev_phase == 0;
@@ -1064,8 +1100,8 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
             const bool pipe = c->pipe >= 0 ? c->pipe == 1 : small;
             // lean: no part units in what the launch reads (the order's splits, row-major halves) and no tile costs
             // recorded (the render a rebuild of the order reads takes the general loop)
-            const bool lean = lean_ok && !(use_order && split_buckets != 0u) && !halves && !a.tile_cost && !a.chunk_cnt &&
-                              !(a.flags & (SF_FLAG_SUBTREE | SF_FLAG_HALVES));
+            const bool lean = pair || (lean_ok && !(use_order && split_buckets != 0u) && !halves && !a.tile_cost &&
+                                       !a.chunk_cnt && !(a.flags & (SF_FLAG_SUBTREE | SF_FLAG_HALVES)));
             if (lean_ok && !lean && c->occ_blocks < c->occ_blocks_lean) {   // (the general loop after all: its own occupancy)
                 const uint32_t cap = (uint32_t)c->occ_blocks * (uint32_t)c->cus;
                 if (grid.x > cap) grid.x = cap;
@@ -1075,8 +1111,11 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
                     a.queues = a.xcds * c->queues_per_xcd;
             }
             if (lean) c->lean_launches += 1u;
-            if (wpb == 1 && (a.flags & SF_FLAG_SUBTREE)) hipLaunchKernelGGL(sf_trace_queue1s, grid, block, lds, s, a);
-            else if (wpb == 1 && lean) hipLaunchKernelGGL(sf_trace_queue1, grid, block, lds, s, a);
+            if (pair) c->pair_launches += 1u;
+            if (pair && a.tile_cost) hipLaunchKernelGGL(sf_trace_queue1c, grid, block, lds, s, a);
+            else if (pair) hipLaunchKernelGGL(sf_trace_queue1, grid, block, lds, s, a);
+            else if (wpb == 1 && (a.flags & SF_FLAG_SUBTREE)) hipLaunchKernelGGL(sf_trace_queue1s, grid, block, lds, s, a);
+            else if (wpb == 1 && lean) hipLaunchKernelGGL(sf_trace_queue1t, grid, block, lds, s, a);
             else if (wpb == 1) hipLaunchKernelGGL(sf_trace_queue1g, grid, block, lds, s, a);
             else if (wpb == 2 && pipe) hipLaunchKernelGGL(sf_trace_queue2p, grid, block, 2 * lds, s, a);
             else if (wpb == 2 && c->compact) hipLaunchKernelGGL(sf_trace_queue2c, grid, block, 2 * lds, s, a);
@@ -1089,7 +1128,7 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
                 c->ev_count = c->ev_count < (uint32_t)sf_ctx::kTimed ? c->ev_count + 1u : c->ev_count;
             }
             if (rebuild) {   // the next render's tile order, from this render's tile costs
-                if (int rc = order_rebuild(c, s, ntiles, nblk * wpb, split_buckets)) return rc;
+                if (int rc = order_rebuild(c, s, ntiles, nblk * wpb, split_buckets, pair)) return rc;
             }
         } else {
             const dim3 grid((ntiles + wpb - 1) / wpb);
@@ -1813,7 +1852,8 @@ int sf_render_frames(sf_ctx* const* cs, uint32_t n, const sf_render_params* pp)
     uint32_t queues = xcds;
     if (c0->queues_per_xcd > 1u && nblk >= 64u * xcds * c0->queues_per_xcd) queues = xcds * c0->queues_per_xcd;
     const uint32_t every = c0->order_every ? c0->order_every : (small ? 3u : large ? 64u : 1u);
-    const bool rebuild = use_order && (c0->order_n != ntiles || c0->order_phase + 1u >= every);
+    const bool have_order = c0->order_n == ntiles && !c0->order_pair;   // (a tile order, not sf_render_to's pair units)
+    const bool rebuild = use_order && (!have_order || c0->order_phase + 1u >= every);
     if (use_order) c0->order_phase = rebuild ? 0u : c0->order_phase + 1u;
     const bool record = use_order && (c0->order_record_env >= 0 ? c0->order_record_env != 0 : !large);
     const bool front_first = (c0->flags & (SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST)) == 0u;
@@ -1845,7 +1885,7 @@ int sf_render_frames(sf_ctx* const* cs, uint32_t n, const sf_render_params* pp)
         a.xcds = xcds;
         a.queues = queues;
         if (use_order) {
-            a.tile_order = c0->order_n == ntiles ? c0->tile_order : nullptr;
+            a.tile_order = have_order ? c0->tile_order : nullptr;
             a.order_meta = c0->order_meta;
             a.part_cost = c0->part_cost;
             a.part_done = c0->part_done;
@@ -2597,6 +2637,8 @@ int sf_get_tile_order(sf_ctx* c, uint32_t* order, uint32_t* cost, size_t n)
 
 void* sf_context_stream(sf_ctx* c) { return c ? (void*)c->stream : nullptr; }
 uint32_t sf_lean_launches(const sf_ctx* c) { return c ? c->lean_launches : 0u; }
+uint32_t sf_pair_launches(const sf_ctx* c) { return c ? c->pair_launches : 0u; }
+uint32_t sf_order_units(const sf_ctx* c) { return c ? c->order_n : 0u; }
 
 int sf_device_buffers(sf_ctx* c, float** pos4, float** nrm4, float** min_t, uint32_t** hidx)
 {

@@ -23,8 +23,11 @@
 #ifndef SF_WAVES_PER_EU
 #define SF_WAVES_PER_EU 8      // occupancy target of the persistent trace kernels (waves per SIMD)
 #endif
+#ifndef SF_PAIR_WAVES_PER_EU
+#define SF_PAIR_WAVES_PER_EU 7 // the same of the pair-unit kernels (two rays per lane: 72 VGPRs)
+#endif
 #ifndef SF_TRACE_WAVES
-#define SF_TRACE_WAVES 1       // independent waves per workgroup of the wave kernels (round 4: 1 -- 1080p 0.0718-0.0723
+#define SF_TRACE_WAVES 1      // independent waves per workgroup of the wave kernels (round 4: 1 -- 1080p 0.0718-0.0723
                                // -> 0.0697-0.0707 ms against 2, profiles/r4/waves_ab.txt; the pipelined and compaction
                                // variants exist at 2 and take 2)
 #endif
@@ -188,6 +191,7 @@ struct FrameArgs {
     uint64_t* part_rec;               // SF_FLAG_SUBTREE: per split slot x part, 3 x 64 u64 -- each lane's
                                       // {minT | cx}, {cy | cz}, {index | depth} (merged by the last part)
     uint32_t split_depth;             // SF_FLAG_SUBTREE: depth of the nodes the parts divide (>= 1)
+    uint32_t px_magic;                // pair units (sf_trace_queue1): floor((2^32 - 1) / ceil(tiles_x / 2)) (trace_pair)
 };
 #define SF_CLOCK_WAVES 8u             // live shader clock samples per timed render (one per XCD group)
 

@@ -24,8 +24,10 @@
 //                      semantics through lane masks. When a node expands, 36 lanes build its 9 child
 //                      transforms cooperatively (one 4-float column each) into the wave's LDS level,
 //                      instead of every ray doing 9 4x4 products per node as the reference packets do.
-//                      sf_trace_queue1/4: 1 / 4 waves per workgroup; sf_trace_queue2p: the latency variant
-//                      (pipelined child loop) for frames that fill the grid less than twice.
+//                      sf_trace_queue1g/4: 1 / 4 waves per workgroup; sf_trace_queue2p: the latency variant
+//                      (pipelined child loop) for frames that fill the grid less than twice; sf_trace_queue1t:
+//                      the lean loop over whole tiles of one plain frame; sf_trace_queue1 (and 1c, which records
+//                      unit costs): the lean loop over pair units, two adjacent tiles per wave (traverse_pair).
 //   sf_order_scan / sf_order_scatter -- the next render's unit order from this render's tile costs.
 //   sf_trace_wave{1,2,4} -- the same traversal, one workgroup per tile group (non-persistent A/B path).
 //   sf_fixup_wave   -- re-traces the tiles flagged as needing more LDS levels than provisioned, with
@@ -1590,6 +1592,418 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
 #endif
 }
 
+// ---- The pair unit (sf_trace_queue1): two horizontally adjacent 8x8 tiles traced by one wave. Lane l
+// carries ray A (its pixel of the left tile) and ray B (the same pixel of the right tile). Neighbouring tiles walk the
+// same upper nodes of the flake; the pair walks them once: one LDS level table, one VGPR stack, one cone, one child
+// build, cone cull, push and pop per node for both rays. Everything per ray -- the direction, the hit, the visiting
+// lanes (actv, actbits), the ancestor mask -- is doubled (PairRay, ancm), and every per-ray float operation is exactly
+// the one traverse_ray does on that ray, so results are the single tile's bit for bit. A branch the one-ray loop takes
+// on a ballot is taken on the union of the two rays' ballots.
+// A child entered by lanes of one ray only stays that ray's for its whole subtree (a lane's activity only shrinks down
+// the tree): it runs the one-ray loop (dfs_one) on the "A" registers -- the two sets swapped around it for ray B --
+// until it pops back to the level it was entered from.
+struct PairRay {
+    float dx, dy, dz;
+    HitState h;
+    float actv;         // +inf if the lane's ray visits the open node, -1 otherwise
+    uint32_t actbits;   // bit k set if it visits the open node's level-k ancestor
+};
+
+__device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K, const float* root, float* __restrict__ Lbase,
+                                              const float4 bcol, uint32_t levels, PairRay& ra, PairRay& rb, bool validA,
+                                              bool validB, int32_t& maxd, uint32_t& status, uint32_t K_flags,
+                                              int32_t seed)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t axl = 39u;   // ray A of pixel (7, 4) of the left tile: next to the pair's centre
+    const TraverseLds L{ Lbase };
+    const bool cone_cull = (K_flags & SF_FLAG_NO_CONE_CULL) == 0u;
+    const bool occl_cull = (K_flags & SF_FLAG_NO_OCCL_CULL) == 0u;
+    const bool front_first = (K_flags & (SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST)) == 0u;
+
+    auto init = [](PairRay& r) {
+        r.h.minT = FLT_MAX;
+        r.h.cx = r.h.cy = r.h.cz = 0.f;
+        r.h.index = 0xffffffffu;
+        r.h.depth = -1;
+        r.h.hit = false;
+    };
+    init(ra);
+    init(rb);
+    uint64_t ancA = 0ull, ancB = 0ull;   // per ray: lanes whose best sphere is an ancestor of the open node
+
+    // (traverse_ray's child_lod)
+    auto child_lod = [&](float tca, float d2, float xs, bool hb, uint64_t hbm, float R2b, float T, float Tfar) -> uint64_t {
+        const uint64_t nearm = wave_ballot(tca < T);
+        const uint64_t farm = wave_ballot(tca * (1.0f - 0x1p-8f) >= Tfar);
+        if ((hbm & ~(nearm | farm)) == 0ull) return hbm & nearm;
+        const float sq = __builtin_amdgcn_sqrtf(xs);
+        const float s_lo = __uint_as_float((uint32_t)max((int32_t)__float_as_uint(sq) - 2, 0));
+        const float s_hi = __uint_as_float(__float_as_uint(sq) + 2u);
+        const float t_hi = tca - s_lo;
+        const float t_lo = tca - s_hi;
+        const uint64_t tinym = wave_ballot(xs < 0x1p-96f);
+        const float thx = sel_mask(t_hi, __builtin_inff(), tinym);
+        const float tlx = sel_mask(t_lo, -__builtin_inff(), tinym);
+        const float th = hb ? thx : __builtin_inff();
+        const float tl = hb ? tlx : __builtin_inff();
+        uint64_t exm = wave_ballot(th < T);
+        const uint64_t undm = wave_ballot(sel_mask(tl, __builtin_inff(), exm) < T);
+        if (undm) {
+            const float te = near_root_exact(tca, d2, R2b);
+            exm |= undm & wave_ballot(te < T);
+        }
+        return exm;
+    };
+
+    // ---- root: bounding + LOD per ray; the pair leaves only when neither ray expands the root
+    const float rcx = root[9], rcy = root[10], rcz = root[11];
+    const float rcc = (rcx * rcx + rcy * rcy) + rcz * rcz;
+    uint64_t ex0A = 0ull, ex0B = 0ull;
+    {
+        const float4 dt0 = depth_consts(K, 0u);
+        const float Tfar0 = depth_word_at(K, 0u, 6u);
+        auto root_lod = [&](const PairRay& r, bool valid) -> uint64_t {
+            const float tca = (rcx * r.dx + rcy * r.dy) + rcz * r.dz;
+            const float d2 = rcc - tca * tca;
+            const bool hb = valid && tca >= 0.0f && d2 <= dt0.x;
+            const uint64_t hbm = wave_ballot(hb);
+            if (hbm == 0ull) return 0ull;
+            return child_lod(tca, d2, dt0.x - d2, hb, hbm, dt0.x, dt0.w, Tfar0);
+        };
+        ex0A = root_lod(ra, validA);
+        ex0B = root_lod(rb, validB);
+        if ((ex0A | ex0B) == 0ull) return;
+    }
+    maxd = 0;
+
+    // ---- one cone for both rays
+    // (uniform; kept for the one-ray loop's kp: there ray A's registers may hold ray B)
+    const float ax = readlane_f(ra.dx, axl), ay = readlane_f(ra.dy, axl), az = readlane_f(ra.dz, axl);
+    {
+        float cosT = 0.0f, sinT = 1.0f;
+        if (cone_cull) {
+            auto s2m_of = [&](const PairRay& r) -> float {
+                const float cx_ = r.dy * az - r.dz * ay, cy_ = r.dz * ax - r.dx * az, cz_ = r.dx * ay - r.dy * ax;
+                const float s2 = (cx_ * cx_ + cy_ * cy_) + cz_ * cz_;
+                const bool fwd = (r.dx * ax + r.dy * ay) + r.dz * az > 0.0f;
+                return fwd ? s2 : 1.0f;
+            };
+            const float s2m = __builtin_fmaxf(s2m_of(ra), s2m_of(rb));
+            const float sm = __builtin_amdgcn_sqrtf(wave_max_pos(s2m)) * (1.0f + 0x1p-16f) + 0x1p-16f;
+            if (sm < 0.5f) {
+                sinT = sm;
+                cosT = __builtin_amdgcn_sqrtf(1.0f - sm * sm) * (1.0f - 0x1p-16f);
+            }
+        }
+        if (lane < 5u) L.cone()[lane] = lane == 0u ? ax : lane == 1u ? ay : lane == 2u ? az : lane == 3u ? cosT : sinT;
+    }
+
+    float cull_t = depth_consts(K, (uint32_t)(seed > 0 ? seed : 0) + 1u).w;
+
+    const uint32_t bi = build_child(lane);
+    const uint32_t bc = lane < 27u ? lane / 9u : 3u;
+    const float b[4] = { bcol.x, bcol.y, bcol.z, bcol.w };
+    const uint32_t slot = bc == 3u ? (lane >= 32u && bi == 8u ? (uint32_t)SF_LDS_TABLE + 3u : bi * 4u)
+                                   : SF_LDS_PLANE + bc * SF_LDS_COLS + bi * 3u;
+
+    uint32_t d = 0;
+    uint32_t idxB = 1;
+
+    // (traverse_ray's self_test on one ray's state)
+    auto self_test = [&](PairRay& r, uint64_t& ancm, const float4 pc, float tca, float d2, uint32_t dd, float actv,
+                         uint32_t idx, float R2s) {
+        const uint64_t hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);
+        if (hsm) {
+            const float xs = R2s - d2;
+            float ts;
+            if ((wave_ballot(!(xs >= 0x1p-96f)) & hsm) != 0ull) ts = near_root_exact(tca, d2, R2s);
+            else ts = near_root_big(tca, xs);
+            uint64_t accm = hsm & wave_ballot(ts < r.h.minT);
+            const uint64_t tie = hsm & wave_ballot(ts == r.h.minT);
+            if (tie != 0ull) {
+                accm |= tie & ancm;
+                if (front_first && (tie & ~ancm) != 0ull) status |= SF_STATUS_TIE;
+            }
+            sel_in_place(r.h.minT, ts, accm);
+            sel_in_place(r.h.cx, pc.x, accm);
+            sel_in_place(r.h.cy, pc.y, accm);
+            sel_in_place(r.h.cz, pc.z, accm);
+            sel_in_place(r.h.index, idx, accm);
+            uint32_t hd = (uint32_t)r.h.depth;
+            sel_in_place(hd, dd, accm);
+            r.h.depth = (int32_t)hd;
+            ancm |= accm;
+        }
+    };
+
+    const uint32_t lv32 = __builtin_amdgcn_readfirstlane(levels << 5);
+    const uint32_t index_order = front_first ? 0u : 0x1ffu;
+    // (traverse_ray's expand; at the deepest provisioned level the children are tested for both rays -- a ray that
+    // does not visit the node has actv -1 and passes nothing)
+    auto expand = [&](const float4 pc, const float* col, uint32_t cs, float* tb, uint32_t ko, float kp) -> uint32_t {
+        lds_fence();
+        const float3 p0 = *reinterpret_cast<const float3*>(col);
+        const float3 p1 = *reinterpret_cast<const float3*>(col + cs);
+        const float3 p2 = *reinterpret_cast<const float3*>(col + 2u * cs);
+        const float4 cn = *reinterpret_cast<const float4*>(L.cone());
+        const float sinT = L.cone()[4];
+        const float4 dtn = depth_consts_at(K, ko - (1u << 5));
+        const float4 dtc = depth_consts_at(K, ko);
+        const float sm = bc == 3u ? dtn.z : 1.0f;
+        const float b0 = b[0] * sm, b1 = b[1] * sm, b2 = b[2] * sm;
+        const float x = __builtin_fmaf(pc.x, b[3], (p0.x * b0 + p1.x * b1) + p2.x * b2);
+        const float y = __builtin_fmaf(pc.y, b[3], (p0.y * b0 + p1.y * b1) + p2.y * b2);
+        const float z = __builtin_fmaf(pc.z, b[3], (p0.z * b0 + p1.z * b1) + p2.z * b2);
+        const float w = (x * x + y * y) + z * z;
+        const float R2b = dtc.x;
+        const float ax = cn.x, ay = cn.y, az = cn.z, cosT = cn.w;
+        const float ca = __builtin_fmaf(x, ax, __builtin_fmaf(y, ay, z * az));
+        const float sq = __builtin_amdgcn_sqrtf(__builtin_fmaxf(__builtin_fmaf(-ca, ca, w), 0.0f));
+        const float X = __builtin_fmaf(sq, cosT, -(ca * sinT));
+        const float Y = __builtin_fmaf(X, X, -(R2b + w * (0x1p-18f + 0x1p-19f)));
+        const float reg = __builtin_fmaf(w, 1.0f - 0x1p-16f, -2.0f * R2b);
+        const float mk = __builtin_fminf(__builtin_fminf(ca, reg), __builtin_fminf(X, Y));
+        uint32_t M = (uint32_t)(wave_ballot(!(mk > 0.0f)) >> 32) & 0x1ffu;
+        M = __builtin_amdgcn_readfirstlane(M);
+        const uint32_t front = ((uint32_t)(wave_ballot(ca < kp) >> 32) & 0x1ffu) | index_order;
+        if (ko < lv32) {
+            *reinterpret_cast<float3*>(tb + slot) = make_float3(x, y, z);
+            *(bc == 3u ? tb + slot + 3u : L.cone() + 5u) = w;
+            return (M & front) | ((M & ~front) << 16);
+        }
+        {
+            const float T = dtc.w, Tfar = depth_word_at(K, ko, 6u);
+            while (M) {
+                const uint32_t i = __builtin_ctz(M);
+                M &= ~(1u << i);
+                const float cx = readlane_f(x, 32u + i), cy = readlane_f(y, 32u + i);
+                const float cz = readlane_f(z, 32u + i), cc = readlane_f(w, 32u + i);
+                auto passes = [&](const PairRay& r) -> bool {
+                    const float tca = (cx * r.dx + cy * r.dy) + cz * r.dz;
+                    const float d2 = cc - tca * tca;
+                    const float xs = R2b - d2;
+                    const bool hb = __builtin_fminf(__builtin_fminf(tca, xs), r.actv) >= 0.0f;
+                    const uint64_t hbm = wave_ballot(hb);
+                    return hbm != 0ull && child_lod(tca, d2, xs, hb, hbm, R2b, T, Tfar) != 0ull;
+                };
+                if (passes(ra) || passes(rb)) {
+                    status |= SF_STATUS_OVERFLOW;
+                    break;
+                }
+            }
+            return 0u;
+        }
+    };
+
+    uint32_t stk_pc = 0u, stk_ix = 0u;
+    float* tcur = L.table(0u);
+    uint32_t kofs = 1u << 5;
+    float R2c = depth_consts_at(K, kofs).x;
+    uint32_t C = 0u;
+
+    // ---- the one-ray loop (traverse_ray's) on ray A's registers, from the open node at depth `base`, whose children
+    // are in C, until that node is finished (C == 0 at depth base; its pop is the caller's)
+    auto dfs_one = [&](const uint32_t base) {
+        for (;;) {
+            d = __builtin_amdgcn_readfirstlane(d);
+            if (C) {
+                const uint32_t p = __builtin_ctz(C);
+                __asm__("s_bitset0_b32 %0, %1" : "+s"(C) : "s"(p));
+                const uint32_t c = p & 15u;
+                const float4 dc = depth_consts_at(K, kofs);
+                lds_fence();
+                const float4 pc = *reinterpret_cast<const float4*>(tcur + c * 4u);
+                const float tca = (pc.x * ra.dx + pc.y * ra.dy) + pc.z * ra.dz;
+                const float d2 = pc.w - tca * tca;
+                const float xs = R2c - d2;
+                const bool hb = __builtin_fminf(__builtin_fminf(tca, xs), ra.actv) >= 0.0f;
+                const uint64_t hbm = wave_ballot(hb);
+                if (hbm == 0ull) continue;
+                const float4 dk = depth_consts_at(K, kofs + 16u);
+                const float Tfar = dk.z;
+                const float cull_r = dk.y;
+                const uint64_t exm = child_lod(tca, d2, xs, hb, hbm, dc.x, dc.w, Tfar);
+                if (exm == 0ull) continue;
+                if ((int32_t)d + 1 > maxd) {
+                    maxd = (int32_t)d + 1;
+                    if ((int32_t)d + 1 > seed) cull_t = depth_consts_at(K, kofs + (1u << 5)).w;
+                }
+                uint64_t amx = exm;
+                if (occl_cull) {
+                    const float v = __builtin_fminf(tca - ra.h.minT, tca - cull_t);
+                    const uint64_t cm = wave_ballot(v - SF_OCCL_MARGIN * tca > cull_r);
+                    amx = exm & ~cm;
+                    if (amx == 0ull) continue;
+                }
+                const float avx = sel_mask(-1.0f, __builtin_inff(), amx);
+                self_test(ra, ancA, pc, tca, d2, d + 1u, avx, idxB + c, dc.y);
+                if (wave_ballot(pc.w > dk.x) != 0ull) {
+                    ancA &= wave_ballot(ra.h.depth != (int32_t)d + 1);
+                    continue;
+                }
+                stk_pc = writelane_s(C, d, stk_pc);
+                stk_ix = writelane_s(idxB, d, stk_ix);
+                {
+                    const uint32_t bit = 2u << d;
+                    uint32_t ab = ra.actbits & ~bit;
+                    sel_in_place(ab, ab | bit, amx);
+                    ra.actbits = ab;
+                }
+                idxB = 9u * (idxB + c) + 1u;
+                d += 1u;
+                ra.actv = avx;
+                const float* const col = tcur + SF_LDS_PLANE + 3u * c;
+                tcur += SF_LDS_LEVEL;
+                kofs += 1u << 5;
+                // (kp from the axis itself: the axis lane's tca of the node, whichever ray these registers hold)
+                C = expand(pc, col, SF_LDS_COLS, tcur, kofs,
+                           __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(
+                               __builtin_bit_cast(int, (pc.x * ax + pc.y * ay) + pc.z * az))));
+                R2c = depth_consts_at(K, kofs).x;
+                continue;
+            }
+            ancA &= wave_ballot(ra.h.depth != (int32_t)d);
+            if (d == base) break;
+            d -= 1u;
+            tcur -= SF_LDS_LEVEL;
+            kofs -= 1u << 5;
+            R2c = depth_consts_at(K, kofs).x;
+            C = (uint32_t)__builtin_amdgcn_readlane(stk_pc, d);
+            idxB = (uint32_t)__builtin_amdgcn_readlane(stk_ix, d);
+            ra.actv = ((ra.actbits >> d) & 1u) ? __builtin_inff() : -1.0f;
+        }
+    };
+    // the subtree of the open node (depth d) for the one ray that visits it: B's through A's registers
+    auto single_half = [&](bool isB) {
+        isB = __builtin_amdgcn_readfirstlane((int)isB) != 0;
+        auto swap = [&]() {
+            auto sw = [](auto& x, auto& y) {
+                const auto t = x;
+                x = y;
+                y = t;
+            };
+            sw(ra.dx, rb.dx), sw(ra.dy, rb.dy), sw(ra.dz, rb.dz);
+            sw(ra.h.minT, rb.h.minT), sw(ra.h.cx, rb.h.cx), sw(ra.h.cy, rb.h.cy), sw(ra.h.cz, rb.h.cz);
+            sw(ra.h.index, rb.h.index), sw(ra.h.depth, rb.h.depth);
+            sw(ra.actv, rb.actv), sw(ra.actbits, rb.actbits);
+            const uint64_t m = ancA;
+            ancA = ancB;
+            ancB = m;
+        };
+        if (isB) swap();
+        dfs_one(d);
+        if (isB) swap();
+    };
+
+    {
+        lds_fence();
+        const float4 pc = *reinterpret_cast<const float4*>(L.root());
+        const float R2s0 = depth_consts(K, 0u).y;
+        auto enter_root = [&](PairRay& r, uint64_t& ancm, uint64_t ex0m) -> float {
+            r.actv = sel_mask(-1.0f, __builtin_inff(), ex0m);
+            r.actbits = 0u;
+            sel_in_place(r.actbits, 1u, ex0m);
+            const float tca = (pc.x * r.dx + pc.y * r.dy) + pc.z * r.dz;
+            const float d2 = pc.w - tca * tca;
+            self_test(r, ancm, pc, tca, d2, 0u, r.actv, 0u, R2s0);
+            return tca;
+        };
+        const float tcaA = enter_root(ra, ancA, ex0A);
+        enter_root(rb, ancB, ex0B);
+        if (!__builtin_amdgcn_readfirstlane((int)(pc.w > depth_leaf(K, 0u))))
+            C = expand(pc, L.root() + 4u, 4u, tcur, kofs, readlane_f(tcaA, axl));
+    }
+    if (ex0A == 0ull || ex0B == 0ull) {   // one half is empty or misses the root: a single tile from the start
+        single_half(ex0A == 0ull);
+        C = 0u;
+    }
+
+    for (;;) {
+        d = __builtin_amdgcn_readfirstlane(d);
+        if (C) {
+            const uint32_t p = __builtin_ctz(C);
+            __asm__("s_bitset0_b32 %0, %1" : "+s"(C) : "s"(p));
+            const uint32_t c = p & 15u;
+            const float4 dc = depth_consts_at(K, kofs);
+            lds_fence();
+            const float4 pc = *reinterpret_cast<const float4*>(tcur + c * 4u);
+            const float tcaA = (pc.x * ra.dx + pc.y * ra.dy) + pc.z * ra.dz;
+            const float tcaB = (pc.x * rb.dx + pc.y * rb.dy) + pc.z * rb.dz;
+            const float d2A = pc.w - tcaA * tcaA;
+            const float d2B = pc.w - tcaB * tcaB;
+            const float xsA = R2c - d2A;
+            const float xsB = R2c - d2B;
+            const bool hbA = __builtin_fminf(__builtin_fminf(tcaA, xsA), ra.actv) >= 0.0f;
+            const bool hbB = __builtin_fminf(__builtin_fminf(tcaB, xsB), rb.actv) >= 0.0f;
+            const uint64_t hbmA = wave_ballot(hbA), hbmB = wave_ballot(hbB);
+            if ((hbmA | hbmB) == 0ull) continue;
+            const float4 dk = depth_consts_at(K, kofs + 16u);
+            const float Tfar = dk.z;
+            const float cull_r = dk.y;
+            const uint64_t exmA = hbmA ? child_lod(tcaA, d2A, xsA, hbA, hbmA, dc.x, dc.w, Tfar) : 0ull;
+            const uint64_t exmB = hbmB ? child_lod(tcaB, d2B, xsB, hbB, hbmB, dc.x, dc.w, Tfar) : 0ull;
+            if ((exmA | exmB) == 0ull) continue;
+            if ((int32_t)d + 1 > maxd) {
+                maxd = (int32_t)d + 1;
+                if ((int32_t)d + 1 > seed) cull_t = depth_consts_at(K, kofs + (1u << 5)).w;
+            }
+            uint64_t amxA = exmA, amxB = exmB;
+            if (occl_cull) {
+                const float vA = __builtin_fminf(tcaA - ra.h.minT, tcaA - cull_t);
+                const float vB = __builtin_fminf(tcaB - rb.h.minT, tcaB - cull_t);
+                amxA = exmA & ~wave_ballot(vA - SF_OCCL_MARGIN * tcaA > cull_r);
+                amxB = exmB & ~wave_ballot(vB - SF_OCCL_MARGIN * tcaB > cull_r);
+                if ((amxA | amxB) == 0ull) continue;
+            }
+            const float avxA = sel_mask(-1.0f, __builtin_inff(), amxA);
+            const float avxB = sel_mask(-1.0f, __builtin_inff(), amxB);
+            self_test(ra, ancA, pc, tcaA, d2A, d + 1u, avxA, idxB + c, dc.y);
+            self_test(rb, ancB, pc, tcaB, d2B, d + 1u, avxB, idxB + c, dc.y);
+            if (wave_ballot(pc.w > dk.x) != 0ull) {   // an inline leaf: the child is finished
+                ancA &= wave_ballot(ra.h.depth != (int32_t)d + 1);
+                ancB &= wave_ballot(rb.h.depth != (int32_t)d + 1);
+                continue;
+            }
+            stk_pc = writelane_s(C, d, stk_pc);
+            stk_ix = writelane_s(idxB, d, stk_ix);
+            {
+                const uint32_t bit = 2u << d;
+                uint32_t abA = ra.actbits & ~bit, abB = rb.actbits & ~bit;
+                sel_in_place(abA, abA | bit, amxA);
+                sel_in_place(abB, abB | bit, amxB);
+                ra.actbits = abA;
+                rb.actbits = abB;
+            }
+            idxB = 9u * (idxB + c) + 1u;
+            d += 1u;
+            ra.actv = avxA;
+            rb.actv = avxB;
+            const float* const col = tcur + SF_LDS_PLANE + 3u * c;
+            tcur += SF_LDS_LEVEL;
+            kofs += 1u << 5;
+            C = expand(pc, col, SF_LDS_COLS, tcur, kofs, readlane_f(tcaA, axl));
+            R2c = depth_consts_at(K, kofs).x;
+            // entered by one ray only: its subtree on the one-ray loop, back here with the node finished
+            if (amxA == 0ull || amxB == 0ull) single_half(amxA == 0ull);
+            continue;
+        }
+        ancA &= wave_ballot(ra.h.depth != (int32_t)d);
+        ancB &= wave_ballot(rb.h.depth != (int32_t)d);
+        if (d == 0u) break;
+        d -= 1u;
+        tcur -= SF_LDS_LEVEL;
+        kofs -= 1u << 5;
+        R2c = depth_consts_at(K, kofs).x;
+        C = (uint32_t)__builtin_amdgcn_readlane(stk_pc, d);
+        idxB = (uint32_t)__builtin_amdgcn_readlane(stk_ix, d);
+        ra.actv = ((ra.actbits >> d) & 1u) ? __builtin_inff() : -1.0f;
+        rb.actv = ((rb.actbits >> d) & 1u) ? __builtin_inff() : -1.0f;
+    }
+    ra.h.hit = ra.h.depth >= 0;
+    rb.h.hit = rb.h.depth >= 0;
+}
+
 struct Tile {
     uint32_t x, y, orow;
     bool valid;
@@ -1820,7 +2234,7 @@ __device__ __forceinline__ void kernarg_frame(FrameArgs& at, const FrameArgs& a)
 #endif
 }
 
-// LEAN (sf_trace_queue1, the product launch's tile loop; trace_queue_body): a whole tile of a plain frame -- no part
+// LEAN (sf_trace_queue1t, the product launch's single-tile loop; trace_queue_body): a whole tile of a plain frame -- no part
 // units, no diagnostics (tile trace, diagnostic flags), no tile cost, no packed slab, no aux channels. `a` is then the
 // kernel's own argument: the epilogue reads the G-buffer pointers, W and the overflow list from the kernel argument
 // segment again instead of carrying them across the traversal.
@@ -2042,6 +2456,75 @@ __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __res
     return st;
 }
 
+// A pair unit of the lean loop (trace_queue_body<PAIR>): what trace_tile<LEAN> does, for the tiles (2 px, ty) and
+// (2 px + 1, ty) of pair `unit` = ty x pairs_x + px. With an odd tiles_x the last pair of a row has no B tile: its B
+// lanes lie beyond W and are invalid. The pair loop serves SF_FLAG_DIAG_FORCE_RETRACE itself (one scalar test per
+// unit). COST: the unit's cycles into tile_cost[unit] and the chunk histogram, as the general loop records a tile's.
+template <bool COST, class Prefetch>
+__device__ __forceinline__ TileStats trace_pair(const FrameArgs& a, float* __restrict__ L, const float4 bcol, uint32_t unit,
+                                                uint32_t levels, const Prefetch& pre, uint32_t flags, const DepthSeed seen)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const FrameConsts fc = frame_consts(K);
+    const uint64_t c_start = COST ? __builtin_amdgcn_s_memtime() : 0ull;
+    const uint32_t pairs_x = (a.tiles_x + 1u) >> 1;
+    uint32_t ty = __umulhi(unit, a.px_magic);   // (tile_of's divmod)
+    uint32_t px = unit - ty * pairs_x;
+    if (px >= pairs_x) {
+        ty += 1u;
+        px -= pairs_x;
+    }
+    uint32_t l = threadIdx.x & 63u;
+    __asm__ volatile("" : "+v"(l));
+    Tile tA, tB;
+    tA.x = px * (2u * SF_TILE) + (l & 7u);
+    tA.y = tB.y = ty * SF_TILE + (l >> 3);
+    tB.x = tA.x + SF_TILE;
+    tA.orow = tB.orow = tA.y;
+    tA.valid = tA.x < a.W && tA.y < a.H;
+    tB.valid = tB.x < a.W && tA.y < a.H;
+    PairRay ra, rb;
+    ray_dir(a, (float)tA.x, (float)tA.y, ra.dx, ra.dy, ra.dz, K->lut, &fc);
+    ray_dir(a, (float)tB.x, (float)tB.y, rb.dx, rb.dy, rb.dz, K->lut, &fc);
+    const int32_t seed = seen.depth(flags);
+    int32_t maxd = -1;
+    uint32_t status = 0u;
+    traverse_pair(K, a.root, L, bcol, levels, ra, rb, tA.valid, tB.valid, maxd, status, flags, seed);
+    if ((flags & (SF_FLAG_DIAG_FORCE_RETRACE | SF_FLAG_REDO_PASS)) == SF_FLAG_DIAG_FORCE_RETRACE) status |= SF_STATUS_TIE;
+    const bool overflowed = status != 0u;
+    const bool retrace = __builtin_amdgcn_readfirstlane((int)(status == SF_STATUS_TIE && (flags & SF_FLAG_TIE_INLINE))) != 0;
+    pre(retrace);
+    FrameArgs ae;
+    kernarg_frame(ae, a);
+    if constexpr (COST) {
+        if (ae.tile_cost && !(flags & SF_FLAG_REDO_PASS)) {   // (uniform values and addresses)
+            const uint64_t cyc = __builtin_amdgcn_s_memtime() - c_start;
+            const uint32_t cost = cyc > 0xffffffffull ? 0xffffffffu : (uint32_t)cyc;
+            ae.tile_cost[unit] = cost;
+            if (ae.chunk_cnt) {
+                const uint32_t cs = __builtin_amdgcn_readfirstlane((unit >> 6) * SF_ORDER_BUCKETS + cost_bucket(cost));
+                wave_atomic_inc_nowait(ae.chunk_cnt + cs);
+            }
+        }
+    }
+    if (overflowed && !retrace) {
+        // both tiles to the overflow list (sf_fixup_wave re-traces tiles), their slots reserved by one add
+        const uint32_t tile = ty * ae.tiles_x + 2u * px;
+        const uint32_t n = 2u * px + 1u < ae.tiles_x ? 2u : 1u;
+        const uint32_t slot = wave_fetch_add(ae.counters + ae.parity, n);
+        ae.overflow_list[slot] = tile;   // uniform values and addresses
+        if (n == 2u) ae.overflow_list[slot + 1u] = tile + 1u;
+    }
+    if (tA.valid) write_pixel<true>(ae, tA, ra.dx, ra.dy, ra.dz, ra.h, K->lut);
+    if (tB.valid) write_pixel<true>(ae, tB, rb.dx, rb.dy, rb.dz, rb.h, K->lut);
+    TileStats st;
+    st.maxd = maxd;
+    st.seed = seed;
+    st.closest = fminf(tA.valid ? ra.h.minT : FLT_MAX, tB.valid ? rb.h.minT : FLT_MAX);
+    st.overflowed = overflowed;
+    return st;
+}
+
 // Publish one wave's stats (outside any loop: lane-0 regions are harmless here). `closest` per lane.
 // Thousands of waves end together and atomics on one address serialise (~10 ns each), so a wave
 // first reads the current value and issues the atomic only if it would change it. The read may be
@@ -2146,14 +2629,18 @@ extern "C" __global__ __launch_bounds__(256) void sf_trace_wave4(FrameArgs a, ui
 // atomic queue until it runs dry. Dynamic balancing: tile costs vary ~100x (sky vs. deep flake),
 // and the in-order workgroup dispatcher otherwise idles CUs behind long tiles. counters: [0,1]
 // overflow counts, [2,3] tile queues, alternating per render (this render zeroes the next one's).
-// LEAN: the product launch's instantiation (sf_trace_queue1; the host launches it exactly when the launch asks for
+// LEAN: the product launch's instantiation (sf_trace_queue1t; the host launches it exactly when the launch asks for
 // none of what it leaves out, sf_render_to): whole-tile units of one plain frame -- row-major or the ordered units
 // with their priority levels, the depth seed, the inline tie re-trace, the overflow list, the stats and the clock
 // probe; no part units (halves, quarters, subtree parts), no tile trace or diagnostic flags, no tile costs, no packed
 // slab, no aux channels, no band mapping. Every launch word is read from the kernel argument segment where it is used.
-template <int WAVES, bool PIPE = false, bool COMPACT = false, bool SPLIT = false, bool LEAN = false>
+// PAIR (with LEAN; 1: sf_trace_queue1, 2: sf_trace_queue1c, which also records unit costs for the render that rebuilds
+// the order): the lean loop over pair units (trace_pair) -- the unit word's tile field holds the pair index, the
+// row-major units are the ceil(tiles_x / 2) x tile_rows pairs.
+template <int WAVES, bool PIPE = false, bool COMPACT = false, bool SPLIT = false, bool LEAN = false, int PAIR = 0>
 __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
 {
+    static_assert(PAIR == 0 || LEAN, "pair units are the lean loop's");
     extern __shared__ float lds[];
     const uint64_t w_start = __builtin_amdgcn_s_memrealtime();
     const uint32_t wv = threadIdx.x >> 6;
@@ -2173,7 +2660,7 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
         a.counters[SF_QUEUE_WORD(a.parity ^ 1u, threadIdx.x)] = 0u;   // the next render's queues
     if (blockIdx.x == 0 && threadIdx.x == 0) a.counters[a.parity ^ 1u] = 0u;   // and overflow count
     float* const L = lds + wv * SF_LDS_WAVE_FLOATS(a.max_depth);
-    const uint32_t ntiles = a.tiles_x * a.tile_rows;
+    const uint32_t ntiles = (PAIR ? (a.tiles_x + 1u) >> 1 : a.tiles_x) * a.tile_rows;
     // work units: tiles in row-major order, or the previous render's heavy-first order in which the
     // heaviest tiles come as two half units (order_meta[0] entries)
     uint32_t nunits = ntiles;
@@ -2284,9 +2771,13 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
                     first = nwaves + wave_fetch_add(aq.counters + SF_QUEUE_WORD(aq.parity, k), 1u) * nq + k;   // uniform
                 }
             };
-            const TileStats st = trace_tile<false, PIPE, decltype(ticket), false, false, true>(
-                at, L, bcol, t, at.max_depth, nullptr, nullptr, 0u, ticket,
-                again ? (at.flags | SF_FLAG_NO_FRONT_FIRST | SF_FLAG_REDO_PASS) : at.flags, 0u, seen);
+            const uint32_t ufl = again ? (at.flags | SF_FLAG_NO_FRONT_FIRST | SF_FLAG_REDO_PASS) : at.flags;
+            TileStats st;
+            if constexpr (PAIR != 0)
+                st = trace_pair<PAIR == 2>(at, L, bcol, t, at.max_depth, ticket, ufl, seen);
+            else
+                st = trace_tile<false, PIPE, decltype(ticket), false, false, true>(
+                    at, L, bcol, t, at.max_depth, nullptr, nullptr, 0u, ticket, ufl, 0u, seen);
             maxd = st.maxd > maxd ? st.maxd : maxd;
             if (st.seed >= 0 && st.maxd > st.seed) {   // (rare: see the general loop below)
                 FrameArgs ap;
@@ -2367,8 +2858,22 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
     }
 }
 
-// the product launch: the lean instantiation (whole tiles of one plain frame, see trace_queue_body)
-extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SF_WAVES_PER_EU, 8))) void sf_trace_queue1(FrameArgs a)
+// the product launch of frames of many tiles (1080p and up): the lean loop over pair units -- two adjacent tiles per
+// wave, sharing the traversal's upper levels (traverse_pair)
+extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SF_PAIR_WAVES_PER_EU, SF_PAIR_WAVES_PER_EU)))
+void sf_trace_queue1(FrameArgs a)
+{
+    trace_queue_body<1, false, false, false, true, 1>(a);
+}
+// the same recording unit costs: the render that rebuilds the order of pair units
+extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SF_PAIR_WAVES_PER_EU, SF_PAIR_WAVES_PER_EU)))
+void sf_trace_queue1c(FrameArgs a)
+{
+    trace_queue_body<1, false, false, false, true, 2>(a);
+}
+// the lean loop over single tiles (whole tiles of one plain frame, see trace_queue_body): the product launch of the
+// smaller frames
+extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SF_WAVES_PER_EU, 8))) void sf_trace_queue1t(FrameArgs a)
 {
     trace_queue_body<1, false, false, false, true>(a);
 }

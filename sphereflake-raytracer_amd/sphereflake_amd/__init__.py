@@ -201,6 +201,8 @@ SIGNATURES = {
     "sf_device_count": (ctypes.c_int, []),
     "sf_context_stream": (ctypes.c_void_p, [_CTX]),
     "sf_lean_launches": (ctypes.c_uint32, [_CTX]),
+    "sf_pair_launches": (ctypes.c_uint32, [_CTX]),
+    "sf_order_units": (ctypes.c_uint32, [_CTX]),
     "sf_group_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
                                        ctypes.POINTER(ctypes.c_void_p)]),
     "sf_group_destroy": (None, [ctypes.c_void_p]),
@@ -1178,9 +1180,9 @@ class Sphereflake:
         return out[:3 * n].reshape(n, 3)
 
     def tile_order(self):
-        """Heavy-first schedule: (units, cost) uint32 arrays -- the work units (tile | part << 29) the
-        next persistent render takes in order, and the last render's per-tile shader cycles they were
-        computed from -- or None before any ordered render."""
+        """Heavy-first schedule: (units, cost) uint32 arrays -- the work units (tile | part << 29; where the renders
+        take pair units, pair_launches(), the pair index and no parts) the next persistent render takes in order, and
+        the last render's per-unit shader cycles they were computed from -- or None before any ordered render."""
         n = ((self.width + 7) // 8) * ((self.height + 7) // 8)
         order = np.zeros(4 * n, np.uint32)
         cost = np.zeros(n, np.uint32)
@@ -1188,7 +1190,7 @@ class Sphereflake:
         k = lib().sf_get_tile_order(self._ctx, order.ctypes.data_as(P), cost.ctypes.data_as(P), 4 * n)
         if k < 0:
             _check(k, "sf_get_tile_order", self._ctx)
-        return (order[:k], cost) if k else None
+        return (order[:k], cost[:int(lib().sf_order_units(self._ctx))]) if k else None
 
     def kernel_timing(self, enable: bool | None = None, n: int = 64, period: int = 1):
         """Measurement: enable HIP events around the main trace kernel of every `period`-th render, or
@@ -1222,6 +1224,10 @@ class Sphereflake:
     def lean_launches(self) -> int:
         """Trace launches of this context that took the lean tile loop (sf_lean_launches)."""
         return int(lib().sf_lean_launches(self._ctx))
+
+    def pair_launches(self) -> int:
+        """Those of them that took the pair-unit loop, two adjacent tiles per wave (sf_pair_launches)."""
+        return int(lib().sf_pair_launches(self._ctx))
 
     def GetMaxDepthReached(self) -> int:
         return int(self.stats().max_depth)
