@@ -30,7 +30,6 @@ extern "C" __global__ void sf_trace_queue1g(FrameArgs a);
 extern "C" __global__ void sf_trace_queue1s(FrameArgs a);
 extern "C" __global__ void sf_trace_queue2(FrameArgs a);
 extern "C" __global__ void sf_trace_queue4(FrameArgs a);
-extern "C" __global__ void sf_trace_queue2p(FrameArgs a);
 extern "C" __global__ void sf_trace_queue2c(FrameArgs a);
 extern "C" __global__ void sf_order_scan(uint32_t* chunk_cnt, uint32_t nc, uint32_t n_tiles,
                                          uint32_t split_buckets, uint32_t parts, uint32_t spare, uint32_t waves,
@@ -230,7 +229,6 @@ struct sf_ctx {
     int cus = 256;
     uint32_t queues = 8;                         // persistent trace: XCD queue groups, one per XCD (power of 2)
     uint32_t queues_per_xcd = 4;                 // env SF_QUEUES_PER_XCD = 1 | 2 | 4: tile queues per XCD (full grids)
-    int pipe = -1;                               // env SF_PIPE = 0 | 1: latency variant of the trace (-1: auto)
     uint32_t prio_buckets = 8;                   // top cost buckets (3 octaves) traced at raised wave priority (env SF_PRIO_BUCKETS)
     int occ_key = -1, occ_blocks = 0;            // cached occupancy (waves per block, levels) -> blocks per CU
     int occ_blocks_lean = 0;                     // the same of sf_trace_queue1t, the lean tile loop (1 wave per block)
@@ -629,7 +627,6 @@ int sf_create(int device, uint32_t width, uint32_t height, sf_ctx** out)
             const int v = std::atoi(ev);
             if (v == 1 || v == 2 || v == 4 || v == 8) c->queues = (uint32_t)v;
         }
-        if (const char* ev = std::getenv("SF_PIPE")) c->pipe = std::atoi(ev) != 0 ? 1 : 0;
         if (const char* ev = std::getenv("SF_QUEUES_PER_XCD")) {
             const int v = std::atoi(ev);
             if (v == 1 || v == 2 || v == 4) c->queues_per_xcd = (uint32_t)v;
@@ -667,11 +664,14 @@ int sf_create(int device, uint32_t width, uint32_t height, sf_ctx** out)
     if (const char* ev = std::getenv("SF_MAX_BLOCKS")) c->max_blocks = (uint32_t)std::atoi(ev);
     if (const char* ev = std::getenv("SF_PRIO_BUCKETS")) c->prio_buckets = (uint32_t)std::atoi(ev);
     if (const char* ev = std::getenv("SF_FLAGS")) c->flags = (uint32_t)std::strtoul(ev, nullptr, 0);
+    const char* const pipe_env = std::getenv("SF_PIPE");
     if (const char* ev = std::getenv("SF_TRACE_WAVES")) {
         const int w = std::atoi(ev);
         c->waves_per_block = (w == 1 || w == 2 || w == 4) ? (uint32_t)w : SF_TRACE_WAVES;
-    } else if (c->compact || c->pipe == 1) {
-        c->waves_per_block = 2;   // the compaction and pipelined (latency) variants are 2-wave kernels
+    } else if (c->compact || (pipe_env && std::atoi(pipe_env) != 0)) {
+        // the compaction variant is a 2-wave kernel; SF_PIPE=1 once chose a latency variant that was one too, and
+        // still means two waves per workgroup (SF_PIPE=0: nothing)
+        c->waves_per_block = 2;
     }
     if (const char* ev = std::getenv("SF_LEVELS")) {
         const int l = std::atoi(ev);
@@ -1094,10 +1094,6 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
                 SF_HIP(c, hipEventRecord(c->ev[c->ev_next][0], s));
                 a.clock_probe = c->clock_buf + (size_t)c->ev_next * SF_CLOCK_WAVES * 4u;
             }
-            // small frames (tiles fill the persistent grid less than twice) are latency-bound: the heaviest
-            // tiles' serial DFS is the frame, and the pipelined child loop shortens it (640x360 -4 %); full
-            // grids are throughput-bound, where it costs more instructions than it hides (1080p +1.7 %)
-            const bool pipe = c->pipe >= 0 ? c->pipe == 1 : small;
             // lean: no part units in what the launch reads (the order's splits, row-major halves) and no tile costs
             // recorded (the render a rebuild of the order reads takes the general loop)
             const bool lean = pair || (lean_ok && !(use_order && split_buckets != 0u) && !halves && !a.tile_cost &&
@@ -1117,7 +1113,6 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
             else if (wpb == 1 && (a.flags & SF_FLAG_SUBTREE)) hipLaunchKernelGGL(sf_trace_queue1s, grid, block, lds, s, a);
             else if (wpb == 1 && lean) hipLaunchKernelGGL(sf_trace_queue1t, grid, block, lds, s, a);
             else if (wpb == 1) hipLaunchKernelGGL(sf_trace_queue1g, grid, block, lds, s, a);
-            else if (wpb == 2 && pipe) hipLaunchKernelGGL(sf_trace_queue2p, grid, block, 2 * lds, s, a);
             else if (wpb == 2 && c->compact) hipLaunchKernelGGL(sf_trace_queue2c, grid, block, 2 * lds, s, a);
             else if (wpb == 2) hipLaunchKernelGGL(sf_trace_queue2, grid, block, 2 * lds, s, a);
             else hipLaunchKernelGGL(sf_trace_queue4, grid, block, 4 * lds, s, a);

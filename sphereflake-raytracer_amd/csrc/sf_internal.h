@@ -46,7 +46,7 @@
 #define SF_LDS_TABLE (SF_LDS_PLANE + 3 * SF_LDS_COLS)   // the 9 child transforms of the node open at a level
 #define SF_LDS_E 32                       // 64 lanes x u16: per-lane child-expand bits of that node
 #define SF_LDS_LEVEL (SF_LDS_TABLE + SF_LDS_E + 1)      // (+1: levels stay 16-byte aligned)
-// levels - 1 level images: the deepest provisioned level's table is never read (see traverse)
+// levels - 1 level images: the deepest provisioned level's table is never read (see build_children)
 #define SF_LDS_WAVE_FLOATS(levels) (SF_LDS_ROOT + SF_LDS_CONE + ((levels) - 1) * SF_LDS_LEVEL)
 // Mixed-origin traversal (sf_trace_rays_to): a level table for each of the `levels` depths a node can be open at
 // (columns and the children's shared centre offsets, in the table layout above), then the per-lane centre stack,
@@ -130,7 +130,7 @@ struct DeviceConsts {
     // the same interleaved per depth d, one scalar load: {r2_bound, r2_self, scale, lod,
     // leaf, cull, far, 0}; leaf = |c|^2 threshold beyond which no child of a depth-d node centred at c can
     // pass the LOD test for any ray (sfhost::leaf_threshold); cull = 2 r_d (1 + 2 SF_OCCL_MARGIN), rounded
-    // up: the occlusion cull's fattened bounding radius without its |c| term (see traverse); far =
+    // up: the occlusion cull's fattened bounding radius without its |c| term (see occluded); far =
     // T_d + 2 r_d (1 + 2^-18), rounded up: a bounding hit with tca (1 - 2^-8) >= far cannot pass LOD
     float depth8[SF_DEPTH_TABLE][8];
     uint32_t lut[2048];               // x86 rsqrtps table (rsqrtps_lut.inc)

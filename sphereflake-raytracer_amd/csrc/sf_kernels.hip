@@ -24,10 +24,10 @@
 //                      semantics through lane masks. When a node expands, 36 lanes build its 9 child
 //                      transforms cooperatively (one 4-float column each) into the wave's LDS level,
 //                      instead of every ray doing 9 4x4 products per node as the reference packets do.
-//                      sf_trace_queue1g/4: 1 / 4 waves per workgroup; sf_trace_queue2p: the latency variant
-//                      (pipelined child loop) for frames that fill the grid less than twice; sf_trace_queue1t:
-//                      the lean loop over whole tiles of one plain frame; sf_trace_queue1 (and 1c, which records
-//                      unit costs): the lean loop over pair units, two adjacent tiles per wave (traverse_pair).
+//                      sf_trace_queue1g/4: 1 / 4 waves per workgroup; sf_trace_queue2c / 1s: the opt-in
+//                      active-ray compaction and subtree-split units; sf_trace_queue1t: the lean loop over whole
+//                      tiles of one plain frame; sf_trace_queue1 (and 1c, which records unit costs): the lean loop
+//                      over pair units, two adjacent tiles per wave (traverse_pair).
 //   sf_order_scan / sf_order_scatter -- the next render's unit order from this render's tile costs.
 //   sf_trace_wave{1,2,4} -- the same traversal, one workgroup per tile group (non-persistent A/B path).
 //   sf_fixup_wave   -- re-traces the tiles flagged as needing more LDS levels than provisioned, with
@@ -176,7 +176,7 @@ struct HitState {
     float minT;
     float cx, cy, cz;     // centre of the nearest accepted sphere
     uint32_t index;       // its heap index (low 32 bits)
-    int32_t depth;        // its depth (wave traversal: tie-breaking, see traverse)
+    int32_t depth;        // its depth (wave traversal: tie-breaking, see accept_self)
     bool hit;
 };
 
@@ -268,18 +268,13 @@ __device__ __forceinline__ float near_root_exact(float tca, float d2, float R2)
     return near_root(tca, d2, R2);
 }
 
-// "Any lane of my group": a group is the lane itself (PW = 0, per-ray semantics) or the PW lanes of a
-// reference packet (packet semantics: movemask early-outs, SIMD_AVX.h:247,255, Sphereflake.h:140,149,207;
-// PW = 8 for the AVX path, 4 for the SSE path, SIMD_SSE.h).
+// "Any lane of my group": the PW lanes of a reference packet (packet semantics: movemask early-outs,
+// SIMD_AVX.h:247,255, Sphereflake.h:140,149,207; PW = 8 for the AVX path, 4 for the SSE path, SIMD_SSE.h).
 template <int PW>
 __device__ __forceinline__ bool group_any(bool p)
 {
-    if constexpr (PW != 0) {
-        const uint64_t b = wave_ballot(p);
-        return ((b >> (threadIdx.x & (64u - PW))) & ((1ull << PW) - 1ull)) != 0ull;
-    } else {
-        return p;
-    }
+    const uint64_t b = wave_ballot(p);
+    return ((b >> (threadIdx.x & (64u - PW))) & ((1ull << PW) - 1ull)) != 0ull;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -291,13 +286,13 @@ __device__ __forceinline__ bool group_any(bool p)
 //      (36 lanes: one column each; child translation scaled by (4/3) r, world = parent * child,
 //      SIMD_AVX.h:59-81, Sphereflake.h:162-172) plus Dot(centre, centre) of each child;
 //   2. culls the children no ray of the tile's cone can reach (9 centre lanes in parallel), then tests
-//      the remaining ones one after the other in index order (a uniform loop over a 9-bit mask), giving
-//      each lane a 9-bit "child expands" vector E and the wave a 9-bit "pending" mask of children some
-//      lane expands.
-// Children are then entered in index order. A node's own sphere is tested when the node is entered
-// (pre-order) with an ancestor tie-break that reproduces the reference's post-order "first strictly smaller
-// t wins" (Sphereflake.h:174-224) -- see self_test. Children that no lane expands cost only their bounding
-// test, as in the reference.
+//      the remaining ones one after the other (a uniform loop over a 9-bit mask): the per-ray traversals
+//      (traverse_ray, traverse_pair, traverse_mixed) enter a child as soon as its test passes; the packet
+//      traversal (traverse_packet) first gives each lane a 9-bit "child expands" vector E and the wave a 9-bit
+//      "pending" mask of children some lane expands, and enters those after.
+// A node's own sphere is tested when the node is entered (pre-order) with an ancestor tie-break that
+// reproduces the reference's post-order "first strictly smaller t wins" (Sphereflake.h:174-224) -- see
+// accept_self. Children that no lane expands cost only their bounding test, as in the reference.
 //
 // Per node (group = the lane itself for per-ray semantics, the 8 lanes of a reference AVX packet
 // for packet semantics):
@@ -429,7 +424,8 @@ __device__ __forceinline__ float4 depth_consts(const DeviceConsts* K, uint32_t d
     return reinterpret_cast<const float4*>(K->depth8)[2u * d];   // host pass: never executed
 #endif
 }
-// depth_consts / depth_cull / depth_far of the depth whose byte offset `o` = d << 5 the caller carries
+// depth_consts, and word w of the eight (DeviceConsts::depth8), of the depth whose byte offset `o` = d << 5 the caller
+// carries
 __device__ __forceinline__ float4 depth_consts_at(const DeviceConsts* K, uint32_t o)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -462,33 +458,9 @@ __device__ __forceinline__ float depth_leaf(const DeviceConsts* K, uint32_t d)
 #endif
 }
 
-// {.., cull} of depth d: 2 r_d (1 + 2 SF_OCCL_MARGIN), rounded up (see DeviceConsts::depth8)
-__device__ __forceinline__ float depth_cull(const DeviceConsts* K, uint32_t d)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef const __attribute__((address_space(4))) float* ConstF;
-    typedef const __attribute__((address_space(4))) char* ConstC;
-    return *(ConstF)((ConstC)(const void*)K->depth8 + (d << 5) + 20u);
-#else
-    return reinterpret_cast<const float4*>(K->depth8)[2u * d + 1u].y;
-#endif
-}
-
-// traverse's status bits: the tile needs more levels than provisioned; an exact tie under the front-first order
+// the traversals' status bits: the tile needs more levels than provisioned; an exact tie under the front-first order
 #define SF_STATUS_OVERFLOW 1u
 #define SF_STATUS_TIE 2u
-
-// {.., far} of depth d: T_d + 2 r_d (1 + 2^-18), rounded up (see DeviceConsts::depth8)
-__device__ __forceinline__ float depth_far(const DeviceConsts* K, uint32_t d)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef const __attribute__((address_space(4))) float* ConstF;
-    typedef const __attribute__((address_space(4))) char* ConstC;
-    return *(ConstF)((ConstC)(const void*)K->depth8 + (d << 5) + 24u);
-#else
-    return reinterpret_cast<const float4*>(K->depth8)[2u * d + 1u].z;
-#endif
-}
 
 // Root transform -> the wave's LDS image in the transform layout (Sphereflake.cpp:83). The same for
 // every tile of a frame: kernels stage it once per wave, before any tile loop.
@@ -529,13 +501,9 @@ __device__ __forceinline__ void stage_root_all_lanes(float* __restrict__ Lbase, 
     Lbase[l] = v;   // TraverseLds::root()
 }
 
-// PW: packet width of the semantics (0 per ray, 8 (AVX) or 4 (SSE) frame-less packets); PIPE: the latency
-// variant of the per-ray child loop (small frames, whose heaviest tiles' serial DFS is the frame)
 // Lane -> (child bi, column bc) of the cooperative child build: lanes 0..26 the axis columns of child lane % 9
 // (bc = lane / 9), lanes 27..63 centres (bc = 3) -- lanes 32 + i child i (the ballot lanes), lanes 27..31 child 8,
-// the rest repeats. (Lanes 27..31 build child 8 so that traverse_ray can store child 8's centre from the low lane
-// group: the centres are 16-B aligned, child i's x at bank 4 i mod 32, so child 8's and child 0's stores from one
-// lane group of ds_write_b32 were a 2-way bank conflict on every table store of every expansion.)
+// the rest repeats (see BuildLane for the layout and its bank-conflict reasons).
 __device__ __forceinline__ uint32_t build_child(uint32_t lane)
 {
     return lane < 27u ? lane % 9u : lane < 32u ? 8u : (lane - 32u) % 9u;
@@ -557,30 +525,301 @@ __device__ __forceinline__ float4 build_column(const DeviceConsts* __restrict__ 
     return r;
 }
 
-template <int PW, bool PIPE = false>
-__device__ __forceinline__ void traverse(const DeviceConsts* __restrict__ K, const float* root, float* __restrict__ Lbase,
-                                         const float4 bcol, uint32_t levels, float dx, float dy, float dz, bool valid, HitState& h,
-                                         int32_t& maxd, uint32_t& status, uint32_t K_flags,
-                                         uint64_t* phase_sums = nullptr, uint32_t axl = 36u,
-                                         uint64_t* tile_counts = nullptr)
-{
-    constexpr bool PACKET = PW != 0;
-    const uint32_t lane = threadIdx.x & 63u;
-    const TraverseLds L{ Lbase };
-    const bool cone_cull = (K_flags & SF_FLAG_NO_CONE_CULL) == 0u;
-    const bool occl_cull = (K_flags & SF_FLAG_NO_OCCL_CULL) == 0u;
-    // front-first child order (per-ray semantics, with the occlusion cull)
-    const bool front_first = !PACKET && (K_flags & (SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST)) == 0u;
-    SF_STAMP_DECL;
+// ------------------------------------------------------------------------------------------
+// The building blocks the traversals below share. Their exact operation order is the contract (frames are bit
+// exact against the reference), so each exists once.
+// ------------------------------------------------------------------------------------------
 
-    h.minT = FLT_MAX;
+__device__ __forceinline__ void reset_hit(HitState& h, float minT)
+{
+    h.minT = minT;
     h.cx = h.cy = h.cz = 0.f;
     h.index = 0xffffffffu;
     h.depth = -1;
     h.hit = false;   // set on return: hit <=> depth >= 0
-    // Lanes whose current best sphere is an ancestor of the node being expanded (see the self test):
-    // a wave lane mask, so the tie-break and its updates are scalar mask algebra.
-    uint64_t ancm = 0ull;
+}
+
+// This lane's part in the cooperative child build: column bc of child bi, the column's constants b0..b3
+// (build_column) and where the built column goes in a level table (slot). The 27 axis columns (column bc = lane / 9 of child
+// bi = lane % 9) are built by lanes 0..26 of the first 32-lane LDS bank group, the 9 centres (column 3) by lanes
+// 32 + i of the second group: lanes 32..40 hold the 9 child centres (read back by v_readlane), and a ballot's
+// per-child mask is bits 0..8 of its high word, one scalar AND (centres on lanes 31..39 had a mask straddling the
+// two words: a 64-bit shift and an AND per ballot). Every other lane repeats a builder (27..31: child 8's centre;
+// 41..63: children (lane - 32) % 9 again) -- the same value, so there is no divergent region, and the build's VALU
+// cost is per wave either way.
+// slot: centre lanes (bc = 3) store xyz + cc at plane 0 (child i at float 4 i), the others xyz in their column
+// plane; the centre lanes' cc store goes to plane 0, the others' to one junk word of the cone block, so both stores
+// are unconditional. With the column planes skewed by 2 floats (SF_LDS_PLANE) no store of the build has two
+// distinct addresses on one bank within a lane group -- except child 8's centre: the centres are 16-B aligned,
+// child i's x at bank 4 i mod 32, so child 8's and child 0's stores from one lane group of ds_write_b32 were a
+// 2-way bank conflict on every table store of every expansion. So child 8's centre is stored by lanes 27..31 of
+// the low group, and the high group's child-8 lanes store into the level's E words, which the per-ray traversals
+// do not use, at a float offset of 2 mod 4 (the levels are 32-B aligned): store k then hits bank 2 + k mod 4, no
+// centre store's 4 i + k. (An earlier layout -- centres on lanes 27..35, lanes 36..63 mirroring 0..27 -- put
+// 4.9 M extra cycles per 1080p frame into bank conflicts, 40 % of the LDS instruction cycles.)
+// (The packet traversal keeps its E words: its lanes 32 + 8 store child 8's centre in place, see traverse_packet.)
+struct BuildLane {
+    uint32_t bi, bc, slot;
+    float b0, b1, b2, b3;
+};
+__device__ __forceinline__ BuildLane build_lane(const float4 bcol, uint32_t lane, uint32_t bi)
+{
+    const uint32_t bc = lane < 27u ? lane / 9u : 3u;
+    const uint32_t slot = bc == 3u ? (lane >= 32u && bi == 8u ? (uint32_t)SF_LDS_TABLE + 3u : bi * 4u)
+                                   : SF_LDS_PLANE + bc * SF_LDS_COLS + bi * 3u;
+    return BuildLane{ bi, bc, slot, bcol.x, bcol.y, bcol.z, bcol.w };
+}
+
+// ---- The wave's ray cone: axis a = the axis lane's direction (the tile's centre pixel), sinT bounds the sine of
+// every ray's angle to it. cone_s2m: one ray's |d x a|^2 (|d|, |a| = 1 +- 2^-20), 1 for a ray pointing away from the
+// axis. stage_cone: s2m = this lane's largest over its rays; the wave's largest, plus 2^-16 slack, is sinT. A wide
+// cone (scattered packets of the frame-less mode, or sinT >= 1/2) -- or cone_cull off -- disables the child cone cull
+// through cosT = 0, sinT = 1. {a, cosT, sinT} are kept in LDS (read with the node at every expansion): as uniform
+// registers they would spill SGPRs.
+__device__ __forceinline__ float cone_s2m(float dx, float dy, float dz, float ax, float ay, float az)
+{
+    const float cx_ = dy * az - dz * ay, cy_ = dz * ax - dx * az, cz_ = dx * ay - dy * ax;
+    const float s2 = (cx_ * cx_ + cy_ * cy_) + cz_ * cz_;
+    const bool fwd = (dx * ax + dy * ay) + dz * az > 0.0f;
+    return fwd ? s2 : 1.0f;
+}
+template <class S2m>   // (s2m: a callable, so that its arithmetic stays inside the cone_cull branch)
+__device__ __forceinline__ void stage_cone(const TraverseLds& L, uint32_t lane, bool cone_cull, float ax, float ay,
+                                           float az, S2m s2m)
+{
+    float cosT = 0.0f, sinT = 1.0f;
+    if (cone_cull) {
+        const float sm = __builtin_amdgcn_sqrtf(wave_max_pos(s2m())) * (1.0f + 0x1p-16f) + 0x1p-16f;
+        if (sm < 0.5f) {
+            sinT = sm;
+            cosT = __builtin_amdgcn_sqrtf(1.0f - sm * sm) * (1.0f - 0x1p-16f);
+        }
+    }
+    if (lane < 5u) L.cone()[lane] = lane == 0u ? ax : lane == 1u ? ay : lane == 2u ? az : lane == 3u ? cosT : sinT;
+}
+
+// ---- LOD of one node whose bounding sphere the lanes of hbm hit (hb: this lane's bit of hbm; xs = R2b - d2; the
+// node's depth constants R2b = (2r)^2, T, Tfar): the lanes that expand it, i.e. whose t = fl(tca - sqrt_rn(R2b - d2))
+// (SIMD_AVX.h:260-267; t0 <= t1 picks t1 for thc >= 0) is below T. The bounds on t hold for any centre and bounding
+// radius, the root's included.
+// Most bounding hits are decided without the root: t = fl(tca - s) <= tca (s >= 0, rounding is monotone), so
+// tca < T expands. And on a bounding hit s <= 2r (1 + 2^-19) + 2^-9.7 tca (d2 can be negative by rounding, down to
+// -2^-19.4 |c|^2, |c|^2 <= tca^2 + R2b), so tca (1 - 2^-8) >= T + 2r (1 + 2^-18) (`Tfar`, rounded up) means t >= T:
+// no expansion. Only lanes in between take the bracket (rare: a band of width ~2r + 2^-8 tca around T).
+// The bracket: the hardware sqrt is within 2 ulp of sqrt_rn and t is monotone in it, so
+// t_lo = fl(tca - (s + 2ulp)) <= t <= t_hi = fl(tca - (s - 2ulp)): t_hi < T decides "expands", t_lo >= T decides
+// "does not"; the exact IEEE root runs only for lanes in between, or with a tiny sqrt argument.
+__device__ __forceinline__ uint64_t lod_expands(float tca, float d2, float xs, bool hb, uint64_t hbm, float R2b, float T,
+                                                float Tfar)
+{
+    const uint64_t nearm = wave_ballot(tca < T);
+    const uint64_t farm = wave_ballot(tca * (1.0f - 0x1p-8f) >= Tfar);
+    if ((hbm & ~(nearm | farm)) == 0ull) return hbm & nearm;
+    const float sq = __builtin_amdgcn_sqrtf(xs);
+    const float s_lo = __uint_as_float((uint32_t)max((int32_t)__float_as_uint(sq) - 2, 0));
+    const float s_hi = __uint_as_float(__float_as_uint(sq) + 2u);
+    const float t_hi = tca - s_lo;
+    const float t_lo = tca - s_hi;
+    // The decision as per-lane values instead of scalar mask algebra: th / tl are t_hi / t_lo on the lanes with a
+    // bounding hit and +inf elsewhere; a tiny sqrt argument makes the bracket (-inf, +inf), i.e. undecided.
+    // expands: th < T; undecided: tl < T <= th.
+    const uint64_t tinym = wave_ballot(xs < 0x1p-96f);
+    // (the tiny select is opaque asm, so the hb select below stays one v_cndmask on the VCC of the bounding compare
+    // instead of being merged into scalar mask algebra)
+    const float thx = sel_mask(t_hi, __builtin_inff(), tinym);
+    const float tlx = sel_mask(t_lo, -__builtin_inff(), tinym);
+    const float th = hb ? thx : __builtin_inff();
+    const float tl = hb ? tlx : __builtin_inff();
+    uint64_t exm = wave_ballot(th < T);
+    const uint64_t undm = wave_ballot(sel_mask(tl, __builtin_inff(), exm) < T);
+    if (undm) {   // rare: exact IEEE root for the undecided lanes (disjoint from exm)
+        const float te = near_root_exact(tca, d2, R2b);
+        exm |= undm & wave_ballot(te < T);
+    }
+    return exm;
+}
+
+// Bounding (SIMD_AVX.h:247-258) + LOD of the child with centre c, |c|^2 cc for one ray of every lane (actv: +inf on
+// the lanes visiting the parent, -1 elsewhere): does any lane expand it? tca >= 0 && d2 <= R2b as ONE compare,
+// min(tca, R2b - d2, actv) >= 0: with denormals kept, fl(R2b - d2) >= 0 exactly when d2 <= R2b (no NaN operands).
+__device__ __forceinline__ bool child_expands(float cx, float cy, float cz, float cc, float dx, float dy, float dz,
+                                              float actv, float R2b, float T, float Tfar)
+{
+    const float tca = (cx * dx + cy * dy) + cz * dz;
+    const float d2 = cc - tca * tca;
+    const float xs = R2b - d2;
+    const bool hb = __builtin_fminf(__builtin_fminf(tca, xs), actv) >= 0.0f;
+    const uint64_t hbm = wave_ballot(hb);
+    return hbm != 0ull && lod_expands(tca, d2, xs, hb, hbm, R2b, T, Tfar) != 0ull;
+}
+
+// ---- The own sphere (radius^2 R2s) of a node with centre/|c|^2 pc, depth dd, heap index idx (Sphereflake.h:174-224,
+// SIMD_AVX.h:236-270), tested when the node is entered for the lanes of actv (+inf on them, -1 elsewhere: one v_min3
+// folds the visiting lanes into the hit compare), with tca and d2 as the node's child test formed them. Returns the
+// accepting lanes.
+// The reference tests a node's sphere after its children (post-order) and accepts strictly smaller t, so on an exact
+// tie the earlier node in post-order wins. Pre-order differs from post-order only for ancestor/descendant pairs,
+// hence: a tie is accepted iff the lane's current best is an ancestor of this node -- ancm, a wave lane mask, so the
+// rule and its updates are scalar mask algebra; the caller clears a lane when the node at its best's depth is
+// finished. A tie with a best that is not an ancestor: in index order that sphere came first in the reference's
+// post-order too (rejecting is right); under the front-first child order it may not have, so with flag_ties the tile
+// is flagged (SF_STATUS_TIE) and re-traced in index order (never seen on the BASELINE views).
+// ANYHIT (the shadow traces): only "some visited sphere has ts < h.minT, the lane's bound" is wanted, so an
+// accepting lane only gets its finished flag (h.depth >= 0); a tie is not `<`: never accepted, never flagged.
+// INDEX_ORDER (traverse_mixed): the children are always entered in index order, nothing is ever flagged, and the tie
+// rule is applied without a branch of its own.
+template <bool ANYHIT, bool INDEX_ORDER = false>
+__device__ __forceinline__ uint64_t accept_self(HitState& h, uint64_t& ancm, uint32_t& status, bool flag_ties,
+                                                const float4 pc, float tca, float d2, uint32_t dd, float actv,
+                                                uint32_t idx, float R2s)
+{
+    const uint64_t hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);
+    if (hsm) {
+        // (the general correctly rounded root only when a hitting lane's argument is tiny: a uniform branch)
+        const float xs = R2s - d2;
+        float ts;
+        if ((wave_ballot(!(xs >= 0x1p-96f)) & hsm) != 0ull) ts = near_root_exact(tca, d2, R2s);
+        else ts = near_root_big(tca, xs);
+        // strictly nearer lanes accept; exact ties (rare) take a branch of their own
+        uint64_t accm = hsm & wave_ballot(ts < h.minT);
+        if constexpr (ANYHIT) {   // (the finished flag only)
+            uint32_t hd = (uint32_t)h.depth;
+            sel_in_place(hd, dd, accm);
+            h.depth = (int32_t)hd;
+            return accm;
+        }
+        const uint64_t tie = hsm & wave_ballot(ts == h.minT);
+        if constexpr (INDEX_ORDER) accm |= tie & ancm;
+        else if (tie != 0ull) {
+            accm |= tie & ancm;
+            if (flag_ties && (tie & ~ancm) != 0ull) status |= SF_STATUS_TIE;
+        }
+        sel_in_place(h.minT, ts, accm);
+        sel_in_place(h.cx, pc.x, accm);
+        sel_in_place(h.cy, pc.y, accm);
+        sel_in_place(h.cz, pc.z, accm);
+        sel_in_place(h.index, idx, accm);
+        uint32_t hd = (uint32_t)h.depth;
+        sel_in_place(hd, dd, accm);
+        h.depth = (int32_t)hd;
+        ancm |= accm;
+        return accm;
+    }
+    return 0ull;
+}
+
+// ---- Occlusion cull of a child (centre c, a lane's tca = c.d) that passed bounding + LOD: the lanes that need not
+// enter it. Every sphere of the child's subtree, and every bounding sphere the subtree's LOD tests use, lies in the
+// child's bounding ball (radius R = 2r around c). A lane whose float test of any of them accepts has
+// t >= c.d - rho, rho = R + m (|c| + R), m = SF_OCCL_MARGIN covering every rounding of those tests (tca, the d2
+// cancellation -- the dominant 2^-9.2 (|c| + R) --, the centres' transform chain, |d| != 1). So where
+// c.d - rho > minT the lane can accept nothing in the subtree (ties included: strict), and where c.d - rho >= cull_t,
+// the LOD threshold of the depth after the deepest already reached, no node of the subtree can pass LOD deeper than
+// that depth (T falls with depth): the max-depth statistic is unchanged. (The child itself passed LOD for some
+// lane: the caller's maxd counts it either way.)
+// rho without |c|: a lane that hit the bounding sphere has |c|^2 = d2 + tca^2 <= R^2 + tca^2 (+ the float test's
+// slack, 2^-9.6 |c|), so |c| <= tca + R (+ 2^-9.6 |c|, whose m multiple is far inside m's safety factor) and
+// rho <= R (1 + 2 m) + m tca = cull_r + m tca per lane (cull_r: the `cull` word of DeviceConsts::depth8), no square root.
+// ANYHIT: the distance condition alone -- no sphere of the subtree nearer than the lane's bound; there is no
+// max-depth statistic to protect.
+template <bool ANYHIT>
+__device__ __forceinline__ uint64_t occluded(float tca, float minT, float cull_t, float cull_r)
+{
+    float v = tca - minT;
+    if constexpr (!ANYHIT) v = __builtin_fminf(v, tca - cull_t);
+    return wave_ballot(v - SF_OCCL_MARGIN * tca > cull_r);
+}
+
+// ---- Expand the node with centre/|c|^2 pc (its axis columns j = 0..2 at col + j cs: col = root image + 4, cs = 4
+// for the root; the parent table's column planes + 3 c, cs = SF_LDS_COLS for child c of a level): build its 9 child
+// transforms into table tb and cull the children no ray of the wave's cone can reach. Returns the children left to
+// test, in entry order (front child i at bit i, the others at 16 + i).
+// (ko: byte offset of the children's depth constants; lv32: the provisioned levels in the same units; kp: the node
+// centre's projection on the cone axis; index_order: 0x1ff to enter the children in index order, else 0)
+// table(levels - 1) is never read -- entering a child of the deepest provisioned level overflows first --, so it is
+// neither allocated nor stored: there the children are tested here, from the centre lanes (`expands(cx, cy, cz, cc,
+// R2b, T, Tfar)`: does the child expand for any of the caller's rays?); one that does flags the tile for the deeper
+// re-trace (SF_STATUS_OVERFLOW), and none is entered.
+//
+// Cone cull of child bi (centre c in lanes 32..40): no ray of the wave's cone (axis a, half-angle theta) can hit its
+// bounding sphere. With ca = c.a and |q|^2 = |c|^2 - ca^2 (q = c - ca a), every ray's angle phi to c is at least
+// c's angle to the axis less theta, so its line passes at distance |c| sin(phi) >= X = |q| cosT - ca sinT from c. A
+// float hit (tca >= 0, cc - tca^2 <= R^2, SIMD_AVX.h:247-258) needs |c| sin(phi) <= sqrt(R^2 + dl), dl = 2^-18
+// |c|^2 covering the rounding of tca, d2, |c|^2 and |d| (~12 ulp + 2^-21). Skip when ca > 0, |c|^2 > 2 (R^2 + dl)
+// (c's angle to the axis below 45 deg while theta < 30 deg keeps every phi in a range that also covers the 8-lane
+// packet tests), X > 0 and X^2 > R^2 + dl + 2^-19 |c|^2. The added 32 u |c|^2 covers this test's own rounding:
+// |q|^2 is off by <= 10 u |c|^2 (cancellation), which moves X^2 by <= 2 X dq <= 10 u |c|^2; the hardware sqrt, X and
+// X^2 add <= 7 u |c|^2. (|c|^2 - ca^2 is clamped at 0: no NaN, which the min would drop.) Such a child changes
+// nothing for any lane in the reference: it is skipped for the whole wave.
+// The test is this kernel's own arithmetic, not the reference's, so it fuses: ca, |c|^2 - ca^2, X and Y by fma --
+// each fused step rounds once where the unfused one rounds twice, so the bounds behind the slack hold -- and the
+// regime condition as w (1 - 2^-16) > 2 R^2, a slightly stronger one. 15 VALU per expansion. The four conditions
+// are compares of a v_min3 and a v_min (with denormals kept, a > b exactly when fl(a - b) > 0; every operand is
+// finite): the kept children come from one ballot. (w itself stays the reference's |c|^2: it is the table's cc.)
+struct ChildBuild {
+    float x, y, z, w;    // this lane's built column (BuildLane), w = its |.|^2: child i's centre and cc on lane 32 + i
+    uint32_t M, front;   // uniform: the children the cone cull kept; the front children (all, in index order)
+    float4 dtc;          // the children's depth constants
+};
+__device__ __forceinline__ ChildBuild build_children(const DeviceConsts* K, const TraverseLds& L, const BuildLane& B,
+                                                     const float4 pc, const float* col, uint32_t cs, uint32_t ko,
+                                                     float kp, uint32_t index_order)
+{
+    lds_fence();
+    const float3 p0 = *reinterpret_cast<const float3*>(col);
+    const float3 p1 = *reinterpret_cast<const float3*>(col + cs);
+    const float3 p2 = *reinterpret_cast<const float3*>(col + 2u * cs);
+    // the wave's ray cone, read with the node (before this level's stores: the junk cc store below goes to the cone
+    // block, so a read after it would wait for a second LDS round trip)
+    const float4 cn = *reinterpret_cast<const float4*>(L.cone());
+    const float sinT = L.cone()[4];
+    const float4 dtn = depth_consts_at(K, ko - (1u << 5));   // this node: (4/3) r
+    const float4 dtc = depth_consts_at(K, ko);               // children: (2r)^2, T
+    // world = parent * child (SIMD_AVX.h:59-81), child translation scaled by (4/3) r (Sphereflake.h:162-172):
+    // column 3 lanes multiply b0..b2 by s, the others by 1 (exact)
+    const float sm = B.bc == 3u ? dtn.z : 1.0f;
+    const float b0 = B.b0 * sm, b1 = B.b1 * sm, b2 = B.b2 * sm;
+    const float x = __builtin_fmaf(pc.x, B.b3, (p0.x * b0 + p1.x * b1) + p2.x * b2);
+    const float y = __builtin_fmaf(pc.y, B.b3, (p0.y * b0 + p1.y * b1) + p2.y * b2);
+    const float z = __builtin_fmaf(pc.z, B.b3, (p0.z * b0 + p1.z * b1) + p2.z * b2);
+    const float w = (x * x + y * y) + z * z;   // Dot(centre, centre) on the centre lanes (bc = 3)
+    const float R2b = dtc.x;
+    const float ax = cn.x, ay = cn.y, az = cn.z, cosT = cn.w;
+    const float ca = __builtin_fmaf(x, ax, __builtin_fmaf(y, ay, z * az));
+    const float sq = __builtin_amdgcn_sqrtf(__builtin_fmaxf(__builtin_fmaf(-ca, ca, w), 0.0f));
+    const float X = __builtin_fmaf(sq, cosT, -(ca * sinT));
+    const float Y = __builtin_fmaf(X, X, -(R2b + w * (0x1p-18f + 0x1p-19f)));
+    const float reg = __builtin_fmaf(w, 1.0f - 0x1p-16f, -2.0f * R2b);
+    const float mk = __builtin_fminf(__builtin_fminf(ca, reg), __builtin_fminf(X, Y));
+    uint32_t M = (uint32_t)(wave_ballot(!(mk > 0.0f)) >> 32) & 0x1ffu;
+    M = __builtin_amdgcn_readfirstlane(M);
+    // entry order as bit order: the front children (nearer than this node's centre along the cone axis) at bits 0..8,
+    // the others at 16..24 -- one find-first-set per child picks the next, and its low 4 bits are the child's number
+    // (index order: every child "front" -- an OR with a per-traversal mask, not a branch)
+    const uint32_t front = ((uint32_t)(wave_ballot(ca < kp) >> 32) & 0x1ffu) | index_order;
+    return ChildBuild{ x, y, z, w, M, front, dtc };
+}
+
+// ------------------------------------------------------------------------------------------
+// Packet semantics (the frame-less progressive mode, progressive_trace): the original traversal. PW = the reference
+// packet's width, 8 (AVX) or 4 (SSE): every test is "any lane of my packet" (group_any), as the reference's movemask
+// early-outs are. It tests all children of a node first, keeps each lane's 9 "expands" bits in LDS (the level's E
+// words) and enters the pending children after, in index order; inline leaves and the cone cull as in the per-ray
+// traversals below, no occlusion cull and no front-first order (both rest on per-ray bounds).
+// ------------------------------------------------------------------------------------------
+template <int PW>
+__device__ __forceinline__ void traverse_packet(const DeviceConsts* __restrict__ K, const float* root,
+                                                float* __restrict__ Lbase, const float4 bcol, uint32_t levels, float dx,
+                                                float dy, float dz, bool valid, HitState& h, int32_t& maxd,
+                                                uint32_t& status, uint32_t K_flags)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const TraverseLds L{ Lbase };
+    const bool cone_cull = (K_flags & SF_FLAG_NO_CONE_CULL) == 0u;
+    SF_STAMP_DECL;   // (diagnostic builds: stamps and counts are taken, but this traversal has nowhere to flush them)
+
+    reset_hit(h, FLT_MAX);
+    uint64_t ancm = 0ull;   // lanes whose current best sphere is an ancestor of the open node (see accept_self)
 
     // ---- root node (depth 0): bounding sphere + LOD, centre straight from the kernel arguments
     const float rcx = root[9], rcy = root[10], rcz = root[11];
@@ -596,39 +835,14 @@ __device__ __forceinline__ void traverse(const DeviceConsts* __restrict__ K, con
     if (!wave_ballot(ex0)) return;
     maxd = 0;
 
-    // ---- the wave's ray cone: axis = lane axl's direction (pixel (4, 4) of the tile), sinT bounds the
-    // sine of every lane's angle to it (|d x a| with |d|, |a| = 1 +- 2^-20, plus 2^-16 slack). A wide
-    // cone (scattered packets of the frame-less mode, or sinT >= 1/2) disables the child cone cull
-    // below through cosT = 0, sinT = 1.
-    // Kept in LDS (read with the node in expand): as uniform registers they would spill SGPRs.
+    // ---- the wave's ray cone, around lane 36's ray (scattered packets make it wide: no cull then)
     {
-    // (half units: axl = the centre pixel of the traced half, (4, 2) or (4, 6))
-    const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
-    float cosT = 0.0f, sinT = 1.0f;
-    if (cone_cull) {
-        const float cx_ = dy * az - dz * ay, cy_ = dz * ax - dx * az, cz_ = dx * ay - dy * ax;
-        const float s2 = (cx_ * cx_ + cy_ * cy_) + cz_ * cz_;
-        const bool fwd = (dx * ax + dy * ay) + dz * az > 0.0f;
-        const float s2m = fwd ? s2 : 1.0f;
-        const float sm = __builtin_amdgcn_sqrtf(wave_max_pos(s2m)) * (1.0f + 0x1p-16f) + 0x1p-16f;
-        if (sm < 0.5f) {
-            sinT = sm;
-            cosT = __builtin_amdgcn_sqrtf(1.0f - sm * sm) * (1.0f - 0x1p-16f);
-        }
-    }
-    if (lane < 5u) L.cone()[lane] = lane == 0u ? ax : lane == 1u ? ay : lane == 2u ? az : lane == 3u ? cosT : sinT;
+        const float ax = readlane_f(dx, 36u), ay = readlane_f(dy, 36u), az = readlane_f(dz, 36u);
+        stage_cone(L, lane, cone_cull, ax, ay, az, [&] { return cone_s2m(dx, dy, dz, ax, ay, az); });
     }
 
-    // This lane's column of the cooperative child build. The 27 axis columns (column c = lane / 9 of child
-    // i = lane % 9) are built by lanes 0..26 of the first 32-lane LDS bank group, the 9 centres (column 3)
-    // by lanes 32 + i of the second group. With the column planes skewed by 2 floats (SF_LDS_PLANE) no store of
-    // the table build has two distinct addresses on one bank in a group; every other lane repeats a builder
-    // (27..31: child 0's centre; 41..63: children (lane - 32) % 9 again) -- the same address and value, merged by
-    // the LDS, not a conflict. (Round 2's layout -- centres on lanes 27..35, lanes 36..63 mirroring 0..27 -- put
-    // 4.9 M extra cycles per 1080p frame into bank conflicts, 40 % of the LDS instruction cycles.) No divergent
-    // region; the build's VALU cost is per wave either way. Lanes 32..40 hold the 9 child centres (read back by
-    // v_readlane), and a ballot's per-child mask is bits 0..8 of its high word: one scalar AND (round 3 had the
-    // centres on lanes 31..39, whose mask straddled the two words: a 64-bit shift and an AND per ballot).
+    // This lane's column of the cooperative child build (BuildLane's lanes). This traversal uses the levels' E words,
+    // so every centre lane stores in place: child 8's centre from lanes 32 + 8 and 27..31 alike.
     const uint32_t bi = build_child(lane);
     const uint32_t bc = lane < 27u ? lane / 9u : 3u;
     // The leaf-threshold skip bounds t from below for every ray. In packet semantics a lane with tca < 0
@@ -642,51 +856,32 @@ __device__ __forceinline__ void traverse(const DeviceConsts* __restrict__ K, con
     // per-ray leaf threshold applies. Checked as tca >= 0 and tca^2 >= (2r)^2 (1 + 2^-6), the margin
     // covering the rounding of tca, |d| and the threshold.
     auto leaf_front = [&](const float4 pc, float R2b) -> bool {
-        if constexpr (!PACKET) return true;
         const float tca = (pc.x * dx + pc.y * dy) + pc.z * dz;
         return wave_ballot(!(tca >= 0.0f && tca * tca >= R2b * (1.0f + 0x1p-6f))) == 0ull;
     };
     const float b[4] = { bcol.x, bcol.y, bcol.z, bcol.w };   // (build_column)
-    // where this lane's column goes in a level table: centre lanes (bc = 3) xyz + cc at plane 0, the others
-    // xyz in their column plane; the centre lanes' cc store goes to plane 0, the others' to one junk word of
-    // the cone block (so both stores are unconditional: no divergent region; one address, no conflict)
     const uint32_t slot = bc == 3u ? bi * 4u : SF_LDS_PLANE + bc * SF_LDS_COLS + bi * 3u;
 
     uint32_t d = 0;                 // uniform: depth of the open (expanded) node
     uint32_t idxB = 1;              // uniform: 9 x its heap index + 1 mod 2^32 (root 0, child i of n: 9n+1+i),
                                     // i.e. the heap index of its child 0
 
-    // ---- the own sphere of a node (Sphereflake.h:174-224) with centre/|c|^2 `pc`, depth dd, heap index
-    // idx, tested when the node opens. The reference tests it after the children (post-order) and
-    // accepts strictly smaller t, so on an exact tie the earlier node in post-order wins. Pre-order
-    // differs from post-order only for ancestor/descendant pairs, hence: a tie is accepted iff the
-    // current best is an ancestor of this node (`anc`). Same result as the reference's order in every case.
-    // (actm / actv: the lanes for which the node is visited, as a wave mask (packet semantics) and as a
-    // float, +inf on those lanes and -1 on the others (per-ray semantics: one v_min3 folds the visiting
-    // lanes into the hit compare, so the hit mask needs no scalar AND)
-    auto self_test = [&](const float4 pc, uint32_t dd, uint64_t actm, float actv, uint32_t idx, float R2s) {
+    // ---- the own sphere of a node with centre/|c|^2 `pc`, depth dd, heap index idx, tested when the node opens for
+    // the lanes of actm: accept_self's rule (pre-order, a tie accepted iff the best is an ancestor) in packet form --
+    // the hit test is the packet's, and there is no front-first order, so nothing is flagged
+    auto self_test = [&](const float4 pc, uint32_t dd, uint64_t actm, uint32_t idx, float R2s) {
         const float tca = (pc.x * dx + pc.y * dy) + pc.z * dz;
         const float d2 = pc.w - tca * tca;
         const bool f0 = tca >= 0.0f, in = d2 <= R2s;
-        uint64_t hsm;
-        if constexpr (PACKET) hsm = actm & wave_ballot(group_any<PW>(f0) && group_any<PW>(in));
-        else hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);   // f0 && in (child loop)
+        const uint64_t hsm = actm & wave_ballot(group_any<PW>(f0) && group_any<PW>(in));
         if (hsm) {
-#ifndef SF_NO_FAST_SQRT
             // (the general correctly rounded path only when a hitting lane's argument is tiny: a uniform branch)
             const float xs = R2s - d2;
             float ts;
             if ((wave_ballot(!(xs >= 0x1p-96f)) & hsm) != 0ull) ts = near_root_exact(tca, d2, R2s);
             else ts = near_root_big(tca, xs);
-#else
-            const float ts = near_root(tca, d2, R2s);
-#endif
             const uint64_t eqm = wave_ballot(ts == h.minT);
             const uint64_t accm = hsm & (wave_ballot(ts < h.minT) | (eqm & ancm));
-            // an exact tie with a best sphere that is not an ancestor: in index order that sphere came first in
-            // the reference's post-order too (rejecting is right); with the front-first order it may not have,
-            // so the caller re-traces the tile in index order (never seen on the BASELINE views)
-            if (front_first && (hsm & eqm & ~ancm) != 0ull) status |= SF_STATUS_TIE;
             sel_in_place(h.minT, ts, accm);
             sel_in_place(h.cx, pc.x, accm);
             sel_in_place(h.cy, pc.y, accm);
@@ -701,20 +896,18 @@ __device__ __forceinline__ void traverse(const DeviceConsts* __restrict__ K, con
 
     // ---- expand the node with centre/|c|^2 `pc` (depth d, columns in LDS): build its 9 child transforms into
     // table(d), then test the children (depth d+1) for the lanes in `act`. Returns this lane's 9-bit
-    // "child expands" vector; *pend = the wave's mask of children some lane expands.
-    // (pc: the node's {centre, cc}, read by the caller; its columns j = 0..2 (xyz) at col + j * cs: col = node + 4,
-    // cs = 4 for the root image; col = the table's column planes + 3 c, cs = SF_LDS_COLS for child c of a level)
+    // "child expands" vector; pend = the wave's mask of children some lane expands; leafm = the children that are
+    // inline leaves.
+    // (pc: the node's {centre, cc}, read by the caller; its columns j = 0..2 (xyz) at col + j * cs, as build_children's)
     // (the node's own sphere is tested by the caller when the node is entered, before this)
-    // (act: the lanes visiting the node, as a per-lane bool for the packet semantics and as the wave mask actm)
-    auto expand = [&](const float4 pc, const float* col, uint32_t cs, uint32_t d, bool act, uint64_t actm,
-                      float actv, uint32_t& pend, uint32_t& leafm) -> uint32_t {
+    auto expand = [&](const float4 pc, const float* col, uint32_t cs, uint32_t d, bool act, uint32_t& pend,
+                      uint32_t& leafm) -> uint32_t {
         d = __builtin_amdgcn_readfirstlane(d);   // wave-uniform: depth constants come by scalar loads
         lds_fence();
         const float3 p0 = *reinterpret_cast<const float3*>(col);
         const float3 p1 = *reinterpret_cast<const float3*>(col + cs);
         const float3 p2 = *reinterpret_cast<const float3*>(col + 2u * cs);
-        // the wave's ray cone, read with the node (before this level's stores: the junk cc store below goes
-        // to the cone block, so a read after it would wait for a second LDS round trip)
+        // the wave's ray cone, read with the node (before this level's stores, see build_children)
         const float4 cn = *reinterpret_cast<const float4*>(L.cone());
         const float sinT = L.cone()[4];
         const float4 dtn = depth_consts(K, d);        // this node: (4/3) r
@@ -722,8 +915,7 @@ __device__ __forceinline__ void traverse(const DeviceConsts* __restrict__ K, con
         // children's leaf threshold (+inf: no inline leaves when the LOD cull is off), loaded with the others
         const float leaf1 = depth_leaf(K, d + 1u);
         const float leafc = lod_cull ? leaf1 : __builtin_inff();
-        // world = parent * child (SIMD_AVX.h:59-81), child translation scaled by (4/3) r (Sphereflake.h:162-172):
-        // column 3 lanes multiply b0..b2 by s, the others by 1 (exact)
+        // world = parent * child, as build_children's
         const float sm = bc == 3u ? dtn.z : 1.0f;
         const float b0 = b[0] * sm, b1 = b[1] * sm, b2 = b[2] * sm;
         const float x = __builtin_fmaf(pc.x, b[3], (p0.x * b0 + p1.x * b1) + p2.x * b2);
@@ -739,261 +931,86 @@ __device__ __forceinline__ void traverse(const DeviceConsts* __restrict__ K, con
         }
         const float R2b = dtc.x;
         const float T = dtc.w;
-        const float Tfar = depth_far(K, d + 1u);
-        // Cone cull of child bi (centre c in lanes 32..40): no ray of the wave's cone can hit its bounding
-        // sphere. With ca = c.a, q = c - ca a, every lane's angle phi to c is >= alpha - theta, so its
-        // line passes at distance |c| sin(phi) >= |q| cosT - ca sinT from c. A float hit
-        // (tca >= 0, cc - tca^2 <= R^2, SIMD_AVX.h:247-258) needs |c| sin(phi) <= sqrt(R^2 + dl),
-        // dl = 2^-18 |c|^2 covering the rounding of tca, d2, |c|^2 and |d| (~12 ulp + 2^-21); the last
-        // terms cover this test's own rounding (hardware sqrt). With beta < 45 deg and theta < 30 deg
-        // every lane's phi stays in [beta, 180 - beta], which also covers the 8-lane packet tests.
-        // Such a child changes nothing for any lane in the reference: skip it for the whole wave.
+        // Cone cull of child bi: build_children's test and slack, in its unfused form (each product and sum rounded
+        // on its own, the regime condition as w > 2 (R2b + dl), dl = 2^-18 |c|^2).
         const float ax = cn.x, ay = cn.y, az = cn.z, cosT = cn.w;
         const float dl = w * 0x1p-18f;
         const float ca = (x * ax + y * ay) + z * az;
-#ifndef SF_OLD_CONE
-        // In squares, with |q| from |c|^2 - ca^2 (no q vector, one hardware sqrt): X = |q| cosT - ca sinT bounds
-        // |c| sin(phi) from below; skip when X > 0 and X^2 > R^2 + dl + 2^-19 |c|^2. The added 32 u |c|^2 covers
-        // this test's own rounding: |q|^2 = |c|^2 - ca^2 is off by <= 10 u |c|^2 (cancellation), which moves X^2 by
-        // <= 2 X dq <= 10 u |c|^2; the sqrt, X and X^2 add <= 7 u |c|^2. (w - ca^2 clamped at 0: no NaN, which
-        // the min below would drop.)
         const float sq = __builtin_amdgcn_sqrtf(__builtin_fmaxf(w - ca * ca, 0.0f));
         const float X = sq * cosT - ca * sinT;
         const float Y = X * X - (R2b + w * (0x1p-18f + 0x1p-19f));
-        // skip = ca > 0 && w > 2 (R2b + dl) && X > 0 && Y > 0, as compares of a v_min3 and a v_min (with
-        // denormals kept, a > b exactly when fl(a - b) > 0; every operand is finite): the kept children from a ballot
         const float mk = __builtin_fminf(__builtin_fminf(ca, w - 2.0f * (R2b + dl)), __builtin_fminf(X, Y));
-#else
-        const float qx = x - ca * ax, qy = y - ca * ay, qz = z - ca * az;
-        const float sq = __builtin_amdgcn_sqrtf((qx * qx + qy * qy) + qz * qz);
-        const float lhs = sq * cosT - ca * sinT;
-        const float rhs = __builtin_amdgcn_sqrtf(R2b + dl) * (1.0f + 0x1p-18f) + (ca + sq) * 0x1p-18f;
-        // skip = ca > 0 && w > 2 (R2b + dl) && lhs > rhs, as ONE compare of a v_min3 (with denormals kept,
-        // a > b exactly when fl(a - b) > 0; every operand is finite): the kept children straight from a ballot
-        const float mk = __builtin_fminf(__builtin_fminf(ca, w - 2.0f * (R2b + dl)), lhs - rhs);
-#endif
         uint32_t M = (uint32_t)(wave_ballot(!(mk > 0.0f)) >> 32) & 0x1ffu;
         M = __builtin_amdgcn_readfirstlane(M);
         SF_STAMP(6);
         uint32_t e = 0, pm = 0;
-        if constexpr (!PACKET) {
-            // Per-ray semantics. "Any lane" tests are scalar ANDs of ballots of single compares
-            // (each ballot is the compare's own lane mask: no bool materialisation); per-lane bools
-            // are formed only where a lane's own bit is needed (its E bit).
-            SF_COUNT(0, 1);
-            SF_COUNT(7, __builtin_popcountll(actm));
-            // child i's {centre, cc}: a broadcast LDS read of plane 0 of the table just stored (one LDS
-            // instruction instead of four v_readlane on the VALU); the deepest provisioned level keeps no
-            // table, there the centre lanes are read back
-            // (the loop is instantiated twice, for the LDS and the readlane centres, so the choice is not
-            // re-tested in every iteration)
-            // actv (+inf on the lanes visiting the node, -1 on the others): ONE v_min3 + compare gives the
-            // bounding mask already restricted to the visiting lanes, and the loop branches on it (VCC)
-            // without scalar mask algebra
-            // one child test: bounding + LOD of child i (centre c, |c|^2 cc) for every lane
-            auto test_child = [&](uint32_t i, float cx, float cy, float cz, float cc) {
-                SF_COUNT(1, 1);
-                const float tca = (cx * dx + cy * dy) + cz * dz;
-                const float d2 = cc - tca * tca;
-                // bounding (SIMD_AVX.h:247-258): tca >= 0 && d2 <= R2b as ONE compare, min(tca, R2b - d2) >= 0:
-                // with denormals kept, fl(R2b - d2) >= 0 exactly when d2 <= R2b (no NaN operands here)
+        // The children some ray of the cone can reach, in index order, with the early-outs over the PW lanes of a
+        // reference packet. Child i's {centre, cc}: a broadcast LDS read of plane 0 of the table just stored (one
+        // LDS instruction instead of four v_readlane on the VALU); the deepest provisioned level keeps no table,
+        // there the centre lanes are read back. (The loop is instantiated for both sources, so the choice is not
+        // re-tested in every iteration.) LOD by lod_expands' 2-ulp bracket, per lane.
+        auto packet_loop = [&](auto tab) {
+        const float* ctab = L.table(d);
+        while (M) {
+            const uint32_t i = __builtin_ctz(M);
+            M &= M - 1u;
+            float cx, cy, cz, cc;
+            if constexpr (decltype(tab)::value) {
+                const float4 c4 = *reinterpret_cast<const float4*>(ctab + i * 4u);
+                cx = c4.x, cy = c4.y, cz = c4.z, cc = c4.w;
+            } else {
+                cx = readlane_f(x, 32u + i), cy = readlane_f(y, 32u + i);
+                cz = readlane_f(z, 32u + i), cc = readlane_f(w, 32u + i);
+            }
+            const float tca = (cx * dx + cy * dy) + cz * dz;
+            const float d2 = cc - tca * tca;
+            const bool hb = act & group_any<PW>(tca >= 0.0f) & group_any<PW>(d2 <= R2b);
+            if (wave_ballot(hb)) {
                 const float xs = R2b - d2;
-                const bool hb = __builtin_fminf(__builtin_fminf(tca, xs), actv) >= 0.0f;
-                const uint64_t hbm = wave_ballot(hb);
-#ifdef SF_EXP_PAD   // experiment builds only: independent VALU filler per child iteration (issue-bound test)
-                {
-                    float pad = dx;
-#pragma unroll
-                    for (int k_ = 0; k_ < SF_EXP_PAD; ++k_) __asm__ volatile("v_mov_b32 %0, %0" : "+v"(pad));
-                }
-#endif
-#ifdef SF_EXP_SPAD  // experiment builds only: SALU filler per child iteration (scalar-unit-bound test)
-                {
-                    uint32_t spad = i;
-#pragma unroll
-                    for (int k_ = 0; k_ < SF_EXP_SPAD; ++k_) __asm__ volatile("s_add_u32 %0, %0, 1" : "+s"(spad)::"scc");
-                }
-#endif
-                SF_COUNT(5, __builtin_popcountll(actm));
-                SF_COUNT(6, __builtin_popcountll(hbm));
-                SF_COUNT(10, d >= 4u ? 1 : 0);
-                SF_COUNT(11, d >= 4u ? __builtin_popcountll(actm) : 0);
-                SF_COUNT(12, 0);
-                SF_COUNT(13, 0);
-                SF_COUNT(14, __builtin_popcountll(actm) <= 32 ? 1 : 0);
-                if (hbm == 0ull) {
-                    SF_COUNT(2, 1);
-                    return;
-                }
-                // Most bounding hits are decided without the root: t = fl(tca - s) <= tca (s >= 0, rounding is
-                // monotone), so tca < T expands. And on a bounding hit s <= 2r (1 + 2^-19) + 2^-9.7 tca (d2 can be
-                // negative by rounding, down to -2^-19.4 |c|^2, |c|^2 <= tca^2 + R2b), so tca (1 - 2^-8) >= T + 2r
-                // (1 + 2^-18) (`Tfar`, rounded up) means t >= T: no expansion. Only lanes in between take the
-                // bracket below (rare: a band of width ~2r + 2^-8 tca around T).
-                const uint64_t nearm = wave_ballot(tca < T);
-                const uint64_t farm = wave_ballot(tca * (1.0f - 0x1p-8f) >= Tfar);
-                if ((hbm & ~(nearm | farm)) == 0ull) {
-                    const uint64_t exf = hbm & nearm;
-                    sel_in_place(e, e | (1u << i), exf);
-                    if (exf != 0ull) pm |= 1u << i;
-                    SF_COUNT(3, exf != 0ull ? 1 : 0);
-                    return;
-                }
-                // LOD on t = fl(tca - sqrt_rn(R2b - d2)) (SIMD_AVX.h:260-267; t0 <= t1 picks t1 for
-                // thc >= 0). Fast bracket: the hardware sqrt is within 2 ulp of sqrt_rn and t is
-                // monotone in it, so t_lo = fl(tca - (s + 2ulp)) <= t <= t_hi = fl(tca - (s - 2ulp)):
-                // t_hi < T decides "expands", t_lo >= T decides "does not"; the exact path runs only
-                // for lanes in between (or with a tiny sqrt argument).
                 const float sq = __builtin_amdgcn_sqrtf(xs);
                 const float s_lo = __uint_as_float((uint32_t)max((int32_t)__float_as_uint(sq) - 2, 0));
                 const float s_hi = __uint_as_float(__float_as_uint(sq) + 2u);
-                const float t_hi = tca - s_lo;
-                const float t_lo = tca - s_hi;
-                // The decision as per-lane values instead of scalar mask algebra: th / tl are t_hi / t_lo on
-                // the lanes with a bounding hit and +inf elsewhere; a tiny sqrt argument makes the bracket
-                // (-inf, +inf), i.e. undecided. expands: th < T; undecided: tl < T <= th.
-                const uint64_t tinym = wave_ballot(xs < 0x1p-96f);
-                // (the tiny select is opaque asm, so the hb select below stays one v_cndmask on the VCC of the
-                // bounding compare instead of being merged into scalar mask algebra)
-                const float thx = sel_mask(t_hi, __builtin_inff(), tinym);
-                const float tlx = sel_mask(t_lo, -__builtin_inff(), tinym);
-                const float th = hb ? thx : __builtin_inff();
-                const float tl = hb ? tlx : __builtin_inff();
-                uint64_t exm = wave_ballot(th < T);
-                const uint64_t undm = wave_ballot(sel_mask(tl, __builtin_inff(), exm) < T);
-                if (undm) {   // rare: exact IEEE root for the undecided lanes (disjoint from exm)
-                    const float te = near_root_exact(tca, d2, R2b);
-                    exm |= undm & wave_ballot(te < T);
-                }
-                sel_in_place(e, e | (1u << i), exm);   // the lanes of exm get bit i
-                if (exm != 0ull) pm |= 1u << i;
-                SF_COUNT(3, exm != 0ull ? 1 : 0);
-            };
-            auto child_loop = [&](auto tab) {
-                const float* ctab = L.table(d);
-                if constexpr (PIPE && decltype(tab)::value) {
-                    // latency variant (small frames): software-pipelined two ways -- the next child's {centre,
-                    // cc} is read into the other register set while this one is tested, so the LDS latency
-                    // overlaps the test. Scalar loads are drained first so the waits count LDS reads only.
-                    // Child 8 is read again past the last child: harmless.
-                    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
-                    if (M) {
-                        uint32_t i = __builtin_ctz(M);
-                        float4 ca = *reinterpret_cast<const float4*>(ctab + i * 4u), cb;
-                        for (;;) {
-                            uint32_t ci = i;
-                            M &= ~(1u << ci);
-                            i = __builtin_ctz(M | 0x100u);
-                            cb = *reinterpret_cast<const float4*>(ctab + i * 4u);
-                            test_child(ci, ca.x, ca.y, ca.z, ca.w);
-                            if (!M) break;
-                            ci = i;
-                            M &= ~(1u << ci);
-                            i = __builtin_ctz(M | 0x100u);
-                            ca = *reinterpret_cast<const float4*>(ctab + i * 4u);
-                            test_child(ci, cb.x, cb.y, cb.z, cb.w);
-                            if (!M) break;
-                        }
-                    }
-                }
-                else
-                while (M) {   // uniform loop over the children some lane can reach, in index order
-                    const uint32_t i = __builtin_ctz(M);
-                    M &= ~(1u << i);
-                    float cx, cy, cz, cc;
-                    if constexpr (decltype(tab)::value) {
-                        const float4 c4 = *reinterpret_cast<const float4*>(ctab + i * 4u);
-                        cx = c4.x, cy = c4.y, cz = c4.z, cc = c4.w;
-                    } else {
-                        cx = readlane_f(x, 32u + i), cy = readlane_f(y, 32u + i);
-                        cz = readlane_f(z, 32u + i), cc = readlane_f(w, 32u + i);
-                    }
-                    test_child(i, cx, cy, cz, cc);
-                }
-                // children of a node at the deepest provisioned level (no table) would need a level that does
-                // not exist: flag the tile for the deeper re-trace instead of entering them
-                if constexpr (!decltype(tab)::value) {
-                    if (pm != 0u) status |= SF_STATUS_OVERFLOW;
-                    pm = 0u;
-                }
-            };
-            if (d + 1u < levels) child_loop(BoolC<true>{});
-            else child_loop(BoolC<false>{});
-        } else {
-            // Packet semantics (frame-less mode): early-outs over the 8 lanes of a reference packet.
-            // (child centres from the LDS table by broadcast reads where the level has one, as in the per-ray
-            // loop; the loop is instantiated for both sources)
-            auto packet_loop = [&](auto tab) {
-            const float* ctab = L.table(d);
-            while (M) {
-                const uint32_t i = __builtin_ctz(M);
-                M &= M - 1u;
-                float cx, cy, cz, cc;
-                if constexpr (decltype(tab)::value) {
-                    const float4 c4 = *reinterpret_cast<const float4*>(ctab + i * 4u);
-                    cx = c4.x, cy = c4.y, cz = c4.z, cc = c4.w;
-                } else {
-                    cx = readlane_f(x, 32u + i), cy = readlane_f(y, 32u + i);
-                    cz = readlane_f(z, 32u + i), cc = readlane_f(w, 32u + i);
-                }
-                const float tca = (cx * dx + cy * dy) + cz * dz;
-                const float d2 = cc - tca * tca;
-                const bool hb = act & group_any<PW>(tca >= 0.0f) & group_any<PW>(d2 <= R2b);
-                if (wave_ballot(hb)) {
-                    const float xs = R2b - d2;
-                    const float sq = __builtin_amdgcn_sqrtf(xs);
-                    const float s_lo = __uint_as_float((uint32_t)max((int32_t)__float_as_uint(sq) - 2, 0));
-                    const float s_hi = __uint_as_float(__float_as_uint(sq) + 2u);
-                    const float t_hi = tca - s_lo;           // >= t
-                    const float t_lo = tca - s_hi;           // <= t
-                    float t_dec = t_hi < T ? t_hi : t_lo;    // on the same side of T as t when decided
-                    const bool undecided = hb & ((!(t_hi < T) & !(t_lo >= T)) | (xs < 0x1p-96f));
-                    if (wave_ballot(undecided)) t_dec = undecided ? near_root_exact(tca, d2, R2b) : t_dec;
-                    const bool exi = hb & group_any<PW>(t_dec < T);
-                    const uint64_t mi = wave_ballot(exi);
-                    e |= exi ? (1u << i) : 0u;
-                    pm |= (mi != 0ull ? 1u : 0u) << i;
-                }
+                const float t_hi = tca - s_lo;           // >= t
+                const float t_lo = tca - s_hi;           // <= t
+                float t_dec = t_hi < T ? t_hi : t_lo;    // on the same side of T as t when decided
+                const bool undecided = hb & ((!(t_hi < T) & !(t_lo >= T)) | (xs < 0x1p-96f));
+                if (wave_ballot(undecided)) t_dec = undecided ? near_root_exact(tca, d2, R2b) : t_dec;
+                const bool exi = hb & group_any<PW>(t_dec < T);
+                const uint64_t mi = wave_ballot(exi);
+                e |= exi ? (1u << i) : 0u;
+                pm |= (mi != 0ull ? 1u : 0u) << i;
             }
-            };
-            if (d + 1u < levels) packet_loop(BoolC<true>{});
-            else packet_loop(BoolC<false>{});
-            if (d + 1u >= levels) {   // (as in the per-ray loop without a table)
-                if (pm != 0u) status |= SF_STATUS_OVERFLOW;
-                pm = 0u;
-            }
+        }
+        };
+        if (d + 1u < levels) packet_loop(BoolC<true>{});
+        else packet_loop(BoolC<false>{});
+        // children of a node at the deepest provisioned level (no table) would need a level that does not exist:
+        // flag the tile for the deeper re-trace instead of entering them
+        if (d + 1u >= levels) {
+            if (pm != 0u) status |= SF_STATUS_OVERFLOW;
+            pm = 0u;
         }
         pend = pm;
         // children none of whose own children can pass LOD for any ray (sfhost::leaf_threshold of their depth;
         // |c|^2 of child i is w on lane 32 + i): entered as inline leaves
         leafm = (uint32_t)(wave_ballot(w > leafc) >> 32) & 0x1ffu;
-        // front-first order (per-ray, occlusion cull on): bits 9..17 = the children whose centre lies nearer
-        // than this node's along the cone axis; they are entered first, so their hits cull the far ones more
-        if constexpr (!PACKET) {
-            if (front_first) {
-                const float kp = (pc.x * ax + pc.y * ay) + pc.z * az;
-                leafm |= ((uint32_t)(wave_ballot(ca < kp) >> 32) & 0x1ffu) << 9;
-            }
-        }
         return e;
     };
 
-    // DFS stack in VGPR lanes (lane L = level L): {pending children | leaf and front bits << 9}, heap index.
+    // DFS stack in VGPR lanes (lane L = level L): {pending children | leaves << 9}, heap index.
     // Lane selects: no LDS traffic and no lane-0-only region in the loop.
     uint32_t stk_pc = 0u, stk_ix = 0u;
     uint32_t pend = 0u, eN = 0u;
-    uint32_t leafN = 0u;            // uniform: the open node's children that are inline leaves (bit i: child i),
-                                    // its front children at bits 9..17 (see expand)
+    uint32_t leafN = 0u;            // uniform: the open node's children that are inline leaves (bit i: child i)
     {
         // the root: its own sphere, then -- unless no child of it can pass LOD for any ray
-        // (sfhost::leaf_threshold; per-ray semantics only) -- its children
+        // (sfhost::leaf_threshold, with leaf_front) -- its children
         lds_fence();
         const float4 pc = *reinterpret_cast<const float4*>(L.root());
-        const float av0 = ex0 ? __builtin_inff() : -1.0f;
-        self_test(pc, 0u, wave_ballot(ex0), av0, 0u, depth_consts(K, 0u).y);
+        self_test(pc, 0u, wave_ballot(ex0), 0u, depth_consts(K, 0u).y);
         if (!(lod_cull && __builtin_amdgcn_readfirstlane((int)(pc.w > depth_leaf(K, 0u))) &&
               leaf_front(pc, depth_consts(K, 0u).x)))
-            eN = expand(pc, L.root() + 4u, 4u, 0u, ex0, wave_ballot(ex0), av0, pend, leafN);
+            eN = expand(pc, L.root() + 4u, 4u, 0u, ex0, pend, leafN);
         else SF_COUNT(4, 1);
     }
 
@@ -1001,48 +1018,24 @@ __device__ __forceinline__ void traverse(const DeviceConsts* __restrict__ K, con
         d = __builtin_amdgcn_readfirstlane(d);
         SF_STAMP(0);
         if (pend) {
-            const uint32_t fp = pend & (leafN >> 9);   // front children still pending first
+            // (bits 9..17 of leafN were the per-ray traversal's front children: always 0 here, but the compiler cannot
+            // see that through the stack, and dropping the select changes the progressive kernels' code -- kept until a
+            // measured change removes it)
+            const uint32_t fp = pend & (leafN >> 9);
             const uint32_t c = __builtin_ctz(fp ? fp : pend);
             const uint32_t cbit = 1u << c;
             pend &= ~cbit;
             // (d + 1 < levels here: expand never leaves children pending at the deepest provisioned level)
             const bool a = (eN & cbit) != 0u;
             const uint64_t am = wave_ballot(a);
-            const float av = a ? __builtin_inff() : -1.0f;
             const float* node = L.table(d) + c * 4u;
-            // enter child c: its own sphere first (pre-order, see self_test), in one place for every child
+            // enter child c: its own sphere first (pre-order, self_test above), in one place for every child
             maxd = (int32_t)d + 1 > maxd ? (int32_t)d + 1 : maxd;   // Sphereflake.h:157-160
-            // (the cull's scalar loads first, so that they are in flight with the LDS read below)
-            const float cull_r = depth_cull(K, d + 1u);
-            const float cull_t = depth_consts(K, (uint32_t)maxd + 1u).w;
+            const uint32_t ko = (d + 1u) << 5;   // byte offset of the child's depth constants
             lds_fence();
             const float4 pc = *reinterpret_cast<const float4*>(node);
-            const float4 dc1 = depth_consts(K, d + 1u);
-            if constexpr (!PACKET) __asm__ volatile("" ::"s"(cull_r), "s"(cull_t));   // (issued here, not in the branch)
-            // Occlusion cull (per-ray semantics): every sphere of the child's subtree, and every bounding sphere
-            // the subtree's LOD tests use, lies in the child's bounding ball (radius R = 2r around c). A lane
-            // whose float test of any of them accepts has t >= c.d - rho, rho = R + m (|c| + R), m =
-            // SF_OCCL_MARGIN covering every rounding of those tests (tca, the d2 cancellation -- the dominant
-            // 2^-9.2 (|c| + R) --, the centres' transform chain, |d| != 1). So where c.d - rho > minT the lane
-            // can accept nothing in the subtree (ties included: strict), and where c.d - rho >= T of depth
-            // maxd + 1 no node of the subtree can pass LOD deeper than the depth already reached (T falls with
-            // depth): the max-depth statistic is unchanged. Such lanes do not enter; if none is left, the child
-            // is skipped. (The child itself passed LOD for some lane: maxd above counts it either way.)
-            uint64_t amx = am;
-            float avx = av;
-            if constexpr (!PACKET) {
-                if (occl_cull) {
-                    const float tca = (pc.x * dx + pc.y * dy) + pc.z * dz;
-                    const float rho = cull_r + SF_OCCL_MARGIN * __builtin_amdgcn_sqrtf(pc.w);
-                    const uint64_t cm = wave_ballot(__builtin_fminf(tca - h.minT, tca - cull_t) > rho);
-                    amx = am & ~cm;
-                    SF_COUNT(13, 1);
-                    SF_COUNT(12, amx == 0ull ? 1 : 0);
-                    if (amx == 0ull) continue;
-                    avx = sel_mask(av, -1.0f, cm);
-                }
-            }
-            self_test(pc, d + 1u, am, av, idxB + c, dc1.y);
+            const float4 dc1 = depth_consts_at(K, ko);
+            self_test(pc, d + 1u, am, idxB + c, dc1.y);
             // A child none of whose children can pass LOD for any ray (sfhost::leaf_threshold) only needs its
             // own sphere: no push, no level, no child build. (leafN: decided for all 9 children when the parent
             // expanded)
@@ -1060,7 +1053,7 @@ __device__ __forceinline__ void traverse(const DeviceConsts* __restrict__ K, con
             idxB = 9u * (idxB + c) + 1u;
             d += 1u;
             SF_STAMP(1);
-            eN = expand(pc, L.table(d - 1u) + SF_LDS_PLANE + 3u * c, SF_LDS_COLS, d, a, amx, avx, pend, leafN);
+            eN = expand(pc, L.table(d - 1u) + SF_LDS_PLANE + 3u * c, SF_LDS_COLS, d, a, pend, leafN);
             SF_STAMP(2);
             continue;
         }
@@ -1082,22 +1075,11 @@ __device__ __forceinline__ void traverse(const DeviceConsts* __restrict__ K, con
         SF_STAMP(5);
     }
     h.hit = h.depth >= 0;
-    SF_STAMP_FLUSH(phase_sums);
-#ifdef SF_COUNTS
-    // per tile (COUNTS=1 builds): expanded nodes | child iterations << 16 | bounding-hit iterations << 32 |
-    // inline leaf tests << 48 (16 bits each, saturating)
-    if (tile_counts) {
-        auto sat = [](uint64_t v) { return v > 0xffffull ? 0xffffull : v; };
-        *tile_counts = sat(ph_sum[0]) | (sat(ph_sum[1]) << 16) | (sat(ph_sum[1] - ph_sum[2]) << 32) | (sat(ph_sum[8]) << 48);
-    }
-#else
-    (void)tile_counts;
-#endif
 }
 
 // ------------------------------------------------------------------------------------------
-// Per-ray semantics (full frames), round 3: a child is entered as soon as its own test passes. The reference
-// itself recurses into child i before testing child i + 1 (Sphereflake.h:162-172); `traverse` above tests all
+// Per-ray semantics (full frames): a child is entered as soon as its own test passes. The reference
+// itself recurses into child i before testing child i + 1 (Sphereflake.h:162-172); traverse_packet above tests all
 // children of a node first, keeps each lane's 9 "expands" bits in LDS and enters the pending children after.
 // Per-ray, the tests of child i + 1 do not depend on anything child i's subtree does (bounding and LOD involve
 // only the ray and the child; acceptance is the self test's, at entry), so entering at once gives the same
@@ -1154,7 +1136,7 @@ __device__ __forceinline__ uint32_t split_mask(uint32_t q, uint32_t idxB)
 // maintained past 0), and the traversal ends when no lane is live. On return h.depth >= 0 (h.hit) marks the finished
 // lanes; the other fields of h are not maintained. The visits are a subset of the closest-hit traversal's and every
 // sphere left out cannot be accepted below `bound`, so h.hit is exactly (the closest hit's min_t < bound).
-template <bool PIPE = false, bool COMPACT = false, bool SPLIT = false, bool SHADOW = false>
+template <bool COMPACT = false, bool SPLIT = false, bool SHADOW = false>
 __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K, const float* root, float* __restrict__ Lbase,
                                              const float4 bcol, uint32_t levels, float dx, float dy, float dz, bool valid,
                                              HitState& h, int32_t& maxd, uint32_t& status, uint32_t K_flags,
@@ -1171,42 +1153,10 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
     const bool front_first = (K_flags & (SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST)) == 0u;
     SF_STAMP_DECL;
 
-    if constexpr (SHADOW) h.minT = bound;
-    else h.minT = FLT_MAX;
-    h.cx = h.cy = h.cz = 0.f;
-    h.index = 0xffffffffu;
-    h.depth = -1;
-    h.hit = false;
-    uint64_t ancm = 0ull;   // lanes whose current best sphere is an ancestor of the open node (see self_test)
+    reset_hit(h, SHADOW ? bound : FLT_MAX);
+    uint64_t ancm = 0ull;   // lanes whose current best sphere is an ancestor of the open node (see accept_self)
 
-    // ---- LOD of one node whose bounding sphere the lanes of hbm hit (xs = R2b - d2, depth constants R2b, T, Tfar):
-    // the lanes that expand it (see traverse's test_child for the fast decisions and the certified bracket)
-    auto child_lod = [&](float tca, float d2, float xs, bool hb, uint64_t hbm, float R2b, float T, float Tfar) -> uint64_t {
-        const uint64_t nearm = wave_ballot(tca < T);
-        const uint64_t farm = wave_ballot(tca * (1.0f - 0x1p-8f) >= Tfar);
-        if ((hbm & ~(nearm | farm)) == 0ull) return hbm & nearm;
-        const float sq = __builtin_amdgcn_sqrtf(xs);
-        const float s_lo = __uint_as_float((uint32_t)max((int32_t)__float_as_uint(sq) - 2, 0));
-        const float s_hi = __uint_as_float(__float_as_uint(sq) + 2u);
-        const float t_hi = tca - s_lo;
-        const float t_lo = tca - s_hi;
-        const uint64_t tinym = wave_ballot(xs < 0x1p-96f);
-        const float thx = sel_mask(t_hi, __builtin_inff(), tinym);
-        const float tlx = sel_mask(t_lo, -__builtin_inff(), tinym);
-        const float th = hb ? thx : __builtin_inff();
-        const float tl = hb ? tlx : __builtin_inff();
-        uint64_t exm = wave_ballot(th < T);
-        const uint64_t undm = wave_ballot(sel_mask(tl, __builtin_inff(), exm) < T);
-        if (undm) {
-            const float te = near_root_exact(tca, d2, R2b);
-            exm |= undm & wave_ballot(te < T);
-        }
-        return exm;
-    };
-
-    // ---- root node (depth 0): bounding sphere + LOD, decided as a child's is (child_lod, with depth 0's constants:
-    // the bracket's bounds on t hold for any centre and bounding radius) -- from tca where that proves it, the exact
-    // root only for lanes in the band around T
+    // ---- root node (depth 0): bounding sphere + LOD, decided as a child's is (lod_expands with depth 0's constants)
     const float rcx = root[9], rcy = root[10], rcz = root[11];
     const float rcc = (rcx * rcx + rcy * rcy) + rcz * rcz;
     uint64_t ex0m;   // the lanes that expand the root
@@ -1217,27 +1167,16 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
         const bool hb = valid && tca >= 0.0f && d2 <= dt0.x;
         const uint64_t hbm = wave_ballot(hb);
         if (hbm == 0ull) return;   // (maxd stays the caller's -1, whatever the seed: this traversal reached no depth)
-        ex0m = child_lod(tca, d2, dt0.x - d2, hb, hbm, dt0.x, dt0.w, depth_word_at(K, 0u, 6u));
+        ex0m = lod_expands(tca, d2, dt0.x - d2, hb, hbm, dt0.x, dt0.w, depth_word_at(K, 0u, 6u));
         if (ex0m == 0ull) return;
     }
     maxd = 0;
 
-    // ---- the wave's ray cone (as in traverse)
+    // ---- the wave's ray cone
+    // (half units: axl = the centre pixel of the traced half, (4, 2) or (4, 6))
     {
         const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
-        float cosT = 0.0f, sinT = 1.0f;
-        if (cone_cull) {
-            const float cx_ = dy * az - dz * ay, cy_ = dz * ax - dx * az, cz_ = dx * ay - dy * ax;
-            const float s2 = (cx_ * cx_ + cy_ * cy_) + cz_ * cz_;
-            const bool fwd = (dx * ax + dy * ay) + dz * az > 0.0f;
-            const float s2m = fwd ? s2 : 1.0f;
-            const float sm = __builtin_amdgcn_sqrtf(wave_max_pos(s2m)) * (1.0f + 0x1p-16f) + 0x1p-16f;
-            if (sm < 0.5f) {
-                sinT = sm;
-                cosT = __builtin_amdgcn_sqrtf(1.0f - sm * sm) * (1.0f - 0x1p-16f);
-            }
-        }
-        if (lane < 5u) L.cone()[lane] = lane == 0u ? ax : lane == 1u ? ay : lane == 2u ? az : lane == 3u ? cosT : sinT;
+        stage_cone(L, lane, cone_cull, ax, ay, az, [&] { return cone_s2m(dx, dy, dz, ax, ay, az); });
     }
 
     // The cull's depth bound starts from the seed: the word maxd is published to holds at least that already, so the
@@ -1246,127 +1185,43 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
     // uniform: depth max(maxd, seed) + 1's LOD threshold, reloaded when maxd grows beyond the seed
     float cull_t = depth_consts(K, (uint32_t)(seed > 0 ? seed : 0) + 1u).w;
 
-    // this lane's column of the cooperative child build (see traverse)
-    const uint32_t bi = build_child(lane);
-    const uint32_t bc = lane < 27u ? lane / 9u : 3u;
-    const float b[4] = { bcol.x, bcol.y, bcol.z, bcol.w };
-    // child 8's centre is stored by lanes 27..31; the high group's child-8 lanes store into the level's E words,
-    // which this traversal does not use, at a float offset of 2 mod 4 (the levels are 32-B aligned): store k then
-    // hits bank 2 + k mod 4, no centre store's 4 i + k
-    const uint32_t slot = bc == 3u ? (lane >= 32u && bi == 8u ? (uint32_t)SF_LDS_TABLE + 3u : bi * 4u)
-                                   : SF_LDS_PLANE + bc * SF_LDS_COLS + bi * 3u;
+    const BuildLane B = build_lane(bcol, lane, build_child(lane));
 
     uint32_t d = 0;      // uniform: depth of the open node
     uint32_t idxB = 1;   // uniform: the heap index of the open node's child 0 (9 n + 1)
 
-    // ---- the own sphere of a node entered for the lanes of actv (+inf on them, -1 elsewhere), with its tca and
-    // d2 already formed by its child test (the same operations: Sphereflake.h:174-224, SIMD_AVX.h:236-270).
-    // Pre-order with the ancestor tie rule (see traverse's self_test).
-    // (returns the accepting lanes: the shadow mode's finished lanes)
+    // (the own sphere of a node, tested when it is entered: accept_self)
     auto self_test = [&](const float4 pc, float tca, float d2, uint32_t dd, float actv, uint32_t idx,
                          float R2s) -> uint64_t {
-        const uint64_t hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);
-        if (hsm) {
-            const float xs = R2s - d2;
-            float ts;
-            if ((wave_ballot(!(xs >= 0x1p-96f)) & hsm) != 0ull) ts = near_root_exact(tca, d2, R2s);
-            else ts = near_root_big(tca, xs);
-            // strictly nearer lanes accept; exact ties (rare) take a branch of their own: a tie is accepted where
-            // the best is an ancestor, and one with a non-ancestor flags the tile (front-first order, see traverse)
-            uint64_t accm = hsm & wave_ballot(ts < h.minT);
-            if constexpr (SHADOW) {   // (the finished flag only)
-                uint32_t hd = (uint32_t)h.depth;
-                sel_in_place(hd, dd, accm);
-                h.depth = (int32_t)hd;
-                return accm;
-            }
-            const uint64_t tie = hsm & wave_ballot(ts == h.minT);
-            if (tie != 0ull) {
-                accm |= tie & ancm;
-                if (front_first && (tie & ~ancm) != 0ull) status |= SF_STATUS_TIE;
-            }
-            sel_in_place(h.minT, ts, accm);
-            sel_in_place(h.cx, pc.x, accm);
-            sel_in_place(h.cy, pc.y, accm);
-            sel_in_place(h.cz, pc.z, accm);
-            sel_in_place(h.index, idx, accm);
-            uint32_t hd = (uint32_t)h.depth;
-            sel_in_place(hd, dd, accm);
-            h.depth = (int32_t)hd;
-            ancm |= accm;
-            return accm;
-        }
-        return 0ull;
+        return accept_self<SHADOW>(h, ancm, status, front_first, pc, tca, d2, dd, actv, idx, R2s);
     };
 
-    // ---- expand the node with centre/|c|^2 pc at depth d (axis columns at col + j cs): build its 9 child
-    // transforms into table(d) and cull the children no ray of the tile's cone can reach. Returns the children
-    // left to test, in entry order (front child i at bit i, the others at 16 + i). At the deepest provisioned level
-    // (no table for the children's children) the children are tested here, from the centre lanes: any that some
-    // lane expands flags the tile for the deeper re-trace, and none is entered.
     const uint32_t lv32 = __builtin_amdgcn_readfirstlane(levels << 5);   // levels, in depth-constant offset units
     const uint32_t index_order = front_first ? 0u : 0x1ffu;
-    // (tb: table(d), ko: d + 1's constants offset -- the caller's carried values, not formed here again)
+    // (expand_node for this traversal's ray. tb: table(d), ko: d + 1's constants offset -- the caller's carried values,
+    // not formed here again; kp: the caller passes the axis lane's tca of the node, (pc.x ax + pc.y ay) + pc.z az on the
+    // same operands -- the cone axis IS that lane's direction)
     auto expand = [&](const float4 pc, const float* col, uint32_t cs, uint32_t d, float actv,
                       float* tb, uint32_t ko, float kp) -> uint32_t {
         d = __builtin_amdgcn_readfirstlane(d);
         SF_COUNT(0, 1);
         SF_COUNT(7, __builtin_popcountll(wave_ballot(actv >= 0.0f)));   // (COUNTS builds: lanes visiting the node)
-        lds_fence();
-        const float3 p0 = *reinterpret_cast<const float3*>(col);
-        const float3 p1 = *reinterpret_cast<const float3*>(col + cs);
-        const float3 p2 = *reinterpret_cast<const float3*>(col + 2u * cs);
-        const float4 cn = *reinterpret_cast<const float4*>(L.cone());
-        const float sinT = L.cone()[4];
-        const float4 dtn = depth_consts_at(K, ko - (1u << 5));
-        const float4 dtc = depth_consts_at(K, ko);
-        const float sm = bc == 3u ? dtn.z : 1.0f;
-        const float b0 = b[0] * sm, b1 = b[1] * sm, b2 = b[2] * sm;
-        const float x = __builtin_fmaf(pc.x, b[3], (p0.x * b0 + p1.x * b1) + p2.x * b2);
-        const float y = __builtin_fmaf(pc.y, b[3], (p0.y * b0 + p1.y * b1) + p2.y * b2);
-        const float z = __builtin_fmaf(pc.z, b[3], (p0.z * b0 + p1.z * b1) + p2.z * b2);
-        const float w = (x * x + y * y) + z * z;
-        const float R2b = dtc.x;
-        // cone cull of child bi (centre lanes 32..40), in squares (see traverse). The test is this kernel's own
-        // arithmetic, not the reference's, so it fuses: ca, |c|^2 - ca^2, X and Y by fma -- each fused step rounds
-        // once where the unfused one rounded twice, so the error bounds behind the slack (traverse) still hold --
-        // and the regime condition |c|^2 > 2 (R^2 + 2^-18 |c|^2) as w (1 - 2^-16) > 2 R^2, a slightly stronger
-        // one. 15 VALU instead of 23 per expansion. (w itself stays the reference's |c|^2: it is the table's cc.)
-        const float ax = cn.x, ay = cn.y, az = cn.z, cosT = cn.w;
-        const float ca = __builtin_fmaf(x, ax, __builtin_fmaf(y, ay, z * az));
-        const float sq = __builtin_amdgcn_sqrtf(__builtin_fmaxf(__builtin_fmaf(-ca, ca, w), 0.0f));
-        const float X = __builtin_fmaf(sq, cosT, -(ca * sinT));
-        const float Y = __builtin_fmaf(X, X, -(R2b + w * (0x1p-18f + 0x1p-19f)));
-        const float reg = __builtin_fmaf(w, 1.0f - 0x1p-16f, -2.0f * R2b);
-        const float mk = __builtin_fminf(__builtin_fminf(ca, reg), __builtin_fminf(X, Y));
-        uint32_t M = (uint32_t)(wave_ballot(!(mk > 0.0f)) >> 32) & 0x1ffu;
-        M = __builtin_amdgcn_readfirstlane(M);
-        // entry order as bit order: the front children (nearer than this node's centre along the cone axis) at
-        // bits 0..8, the others at 16..24 -- one find-first-set per child picks the next, and its low 4 bits are
-        // the child's number
-        // (index order, front_first false: every child "front" -- an OR with a per-traversal mask, not a branch)
-        // (kp = (pc.x ax + pc.y ay) + pc.z az, the node's own projection: the caller passes the axis lane's tca of the
-        // node, the same operations on the same operands -- the cone axis IS that lane's direction)
-        const uint32_t front = ((uint32_t)(wave_ballot(ca < kp) >> 32) & 0x1ffu) | index_order;
+        const ChildBuild cb = build_children(K, L, B, pc, col, cs, ko, kp, index_order);
         // (one levels test for both outcomes: stored after the cull, the table is read only once this returns)
         if (ko < lv32) {   // (d + 1 < levels)
-            *reinterpret_cast<float3*>(tb + slot) = make_float3(x, y, z);
-            *(bc == 3u ? tb + slot + 3u : L.cone() + 5u) = w;
-            return (M & front) | ((M & ~front) << 16);
+            *reinterpret_cast<float3*>(tb + B.slot) = make_float3(cb.x, cb.y, cb.z);
+            *(B.bc == 3u ? tb + B.slot + 3u : L.cone() + 5u) = cb.w;
+            return (cb.M & cb.front) | ((cb.M & ~cb.front) << 16);
         }
         {   // (d + 1 >= levels)
-            const float T = dtc.w, Tfar = depth_word_at(K, ko, 6u);   // depth_far(K, d + 1)
+            const float R2b = cb.dtc.x, T = cb.dtc.w, Tfar = depth_word_at(K, ko, 6u);   // (depth8: far)
+            uint32_t M = cb.M;
             while (M) {
                 const uint32_t i = __builtin_ctz(M);
                 M &= ~(1u << i);
-                const float cx = readlane_f(x, 32u + i), cy = readlane_f(y, 32u + i);
-                const float cz = readlane_f(z, 32u + i), cc = readlane_f(w, 32u + i);
-                const float tca = (cx * dx + cy * dy) + cz * dz;
-                const float d2 = cc - tca * tca;
-                const float xs = R2b - d2;
-                const bool hb = __builtin_fminf(__builtin_fminf(tca, xs), actv) >= 0.0f;
-                const uint64_t hbm = wave_ballot(hb);
-                if (hbm != 0ull && child_lod(tca, d2, xs, hb, hbm, R2b, T, Tfar) != 0ull) {
+                const float cx = readlane_f(cb.x, 32u + i), cy = readlane_f(cb.y, 32u + i);
+                const float cz = readlane_f(cb.z, 32u + i), cc = readlane_f(cb.w, 32u + i);
+                if (child_expands(cx, cy, cz, cc, dx, dy, dz, actv, R2b, T, Tfar)) {
                     status |= SF_STATUS_OVERFLOW;
                     break;
                 }
@@ -1442,9 +1297,9 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
             }
             // depth d + 1's {leaf, cull, far} words: one scalar load
             const float4 dk = depth_consts_at(K, kofs + 16u);
-            const float Tfar = dk.z;     // depth_far(K, d + 1)
-            const float cull_r = dk.y;   // depth_cull(K, d + 1)
-            const uint64_t exm = child_lod(tca, d2, xs, hb, hbm, dc.x, dc.w, Tfar);
+            const float Tfar = dk.z;     // (depth8: far)
+            const float cull_r = dk.y;   // (depth8: cull)
+            const uint64_t exm = lod_expands(tca, d2, xs, hb, hbm, dc.x, dc.w, Tfar);
             SF_STAMP(2);
             if (exm == 0ull) continue;
             // ---- child c passed bounding + LOD for the lanes of exm: enter it
@@ -1453,23 +1308,15 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
                 maxd = (int32_t)d + 1;
                 if ((int32_t)d + 1 > seed) cull_t = depth_consts_at(K, kofs + (1u << 5)).w;
             }
-            // occlusion cull (see traverse): lanes for which no sphere of the child's subtree can be accepted or
+            // occlusion cull (occluded): lanes for which no sphere of the child's subtree can be accepted or
             // pass LOD deeper than the depth already reached do not enter. "Already reached" is max(maxd, seed):
             // the seed is a depth the stats word already holds (the word is a running maximum, only raised by depths
             // really reached and only lowered by a reset, which is ordered after every launch), so a subtree that
             // cannot go deeper than it cannot change the word's final value -- and the pixels never depend on this
             // condition.
-            // The fattened radius rho = R (1 + m) + m |c| (see traverse) without |c|: a lane of exm hit the bounding
-            // sphere, so |c|^2 = d2 + tca^2 <= R^2 + tca^2 (+ the float test's slack, 2^-9.6 |c|) and
-            // |c| <= tca + R (+ 2^-9.6 |c|, whose m multiple is far inside m's safety factor): rho <= R (1 + 2 m) +
-            // m tca = cull_r + m tca per lane, no square root.
             uint64_t amx = exm;
             if (occl_cull) {
-                // (shadow mode: the distance condition alone -- no sphere of the subtree nearer than the lane's bound)
-                float v = tca - h.minT;
-                if constexpr (!SHADOW) v = __builtin_fminf(v, tca - cull_t);
-                const uint64_t cm = wave_ballot(v - SF_OCCL_MARGIN * tca > cull_r);
-                amx = exm & ~cm;
+                amx = exm & ~occluded<SHADOW>(tca, h.minT, cull_t, cull_r);
                 SF_COUNT(13, 1);
                 SF_COUNT(12, amx == 0ull ? 1 : 0);
                 if (amx == 0ull) continue;
@@ -1621,40 +1468,9 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
     const bool occl_cull = (K_flags & SF_FLAG_NO_OCCL_CULL) == 0u;
     const bool front_first = (K_flags & (SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST)) == 0u;
 
-    auto init = [](PairRay& r) {
-        r.h.minT = FLT_MAX;
-        r.h.cx = r.h.cy = r.h.cz = 0.f;
-        r.h.index = 0xffffffffu;
-        r.h.depth = -1;
-        r.h.hit = false;
-    };
-    init(ra);
-    init(rb);
+    reset_hit(ra.h, FLT_MAX);
+    reset_hit(rb.h, FLT_MAX);
     uint64_t ancA = 0ull, ancB = 0ull;   // per ray: lanes whose best sphere is an ancestor of the open node
-
-    // (traverse_ray's child_lod)
-    auto child_lod = [&](float tca, float d2, float xs, bool hb, uint64_t hbm, float R2b, float T, float Tfar) -> uint64_t {
-        const uint64_t nearm = wave_ballot(tca < T);
-        const uint64_t farm = wave_ballot(tca * (1.0f - 0x1p-8f) >= Tfar);
-        if ((hbm & ~(nearm | farm)) == 0ull) return hbm & nearm;
-        const float sq = __builtin_amdgcn_sqrtf(xs);
-        const float s_lo = __uint_as_float((uint32_t)max((int32_t)__float_as_uint(sq) - 2, 0));
-        const float s_hi = __uint_as_float(__float_as_uint(sq) + 2u);
-        const float t_hi = tca - s_lo;
-        const float t_lo = tca - s_hi;
-        const uint64_t tinym = wave_ballot(xs < 0x1p-96f);
-        const float thx = sel_mask(t_hi, __builtin_inff(), tinym);
-        const float tlx = sel_mask(t_lo, -__builtin_inff(), tinym);
-        const float th = hb ? thx : __builtin_inff();
-        const float tl = hb ? tlx : __builtin_inff();
-        uint64_t exm = wave_ballot(th < T);
-        const uint64_t undm = wave_ballot(sel_mask(tl, __builtin_inff(), exm) < T);
-        if (undm) {
-            const float te = near_root_exact(tca, d2, R2b);
-            exm |= undm & wave_ballot(te < T);
-        }
-        return exm;
-    };
 
     // ---- root: bounding + LOD per ray; the pair leaves only when neither ray expands the root
     const float rcx = root[9], rcy = root[10], rcz = root[11];
@@ -1669,7 +1485,7 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
             const bool hb = valid && tca >= 0.0f && d2 <= dt0.x;
             const uint64_t hbm = wave_ballot(hb);
             if (hbm == 0ull) return 0ull;
-            return child_lod(tca, d2, dt0.x - d2, hb, hbm, dt0.x, dt0.w, Tfar0);
+            return lod_expands(tca, d2, dt0.x - d2, hb, hbm, dt0.x, dt0.w, Tfar0);
         };
         ex0A = root_lod(ra, validA);
         ex0B = root_lod(rb, validB);
@@ -1681,111 +1497,49 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
     // (uniform; kept for the one-ray loop's kp: there ray A's registers may hold ray B)
     const float ax = readlane_f(ra.dx, axl), ay = readlane_f(ra.dy, axl), az = readlane_f(ra.dz, axl);
     {
-        float cosT = 0.0f, sinT = 1.0f;
-        if (cone_cull) {
-            auto s2m_of = [&](const PairRay& r) -> float {
-                const float cx_ = r.dy * az - r.dz * ay, cy_ = r.dz * ax - r.dx * az, cz_ = r.dx * ay - r.dy * ax;
-                const float s2 = (cx_ * cx_ + cy_ * cy_) + cz_ * cz_;
-                const bool fwd = (r.dx * ax + r.dy * ay) + r.dz * az > 0.0f;
-                return fwd ? s2 : 1.0f;
-            };
-            const float s2m = __builtin_fmaxf(s2m_of(ra), s2m_of(rb));
-            const float sm = __builtin_amdgcn_sqrtf(wave_max_pos(s2m)) * (1.0f + 0x1p-16f) + 0x1p-16f;
-            if (sm < 0.5f) {
-                sinT = sm;
-                cosT = __builtin_amdgcn_sqrtf(1.0f - sm * sm) * (1.0f - 0x1p-16f);
-            }
-        }
-        if (lane < 5u) L.cone()[lane] = lane == 0u ? ax : lane == 1u ? ay : lane == 2u ? az : lane == 3u ? cosT : sinT;
+        // (cone_s2m's text on a ray held by reference: called as a function, the compiler commutes two of its additions)
+        auto s2m_of = [&](const PairRay& r) -> float {
+            const float cx_ = r.dy * az - r.dz * ay, cy_ = r.dz * ax - r.dx * az, cz_ = r.dx * ay - r.dy * ax;
+            const float s2 = (cx_ * cx_ + cy_ * cy_) + cz_ * cz_;
+            const bool fwd = (r.dx * ax + r.dy * ay) + r.dz * az > 0.0f;
+            return fwd ? s2 : 1.0f;
+        };
+        stage_cone(L, lane, cone_cull, ax, ay, az, [&] { return __builtin_fmaxf(s2m_of(ra), s2m_of(rb)); });
     }
 
     float cull_t = depth_consts(K, (uint32_t)(seed > 0 ? seed : 0) + 1u).w;
 
-    const uint32_t bi = build_child(lane);
-    const uint32_t bc = lane < 27u ? lane / 9u : 3u;
-    const float b[4] = { bcol.x, bcol.y, bcol.z, bcol.w };
-    const uint32_t slot = bc == 3u ? (lane >= 32u && bi == 8u ? (uint32_t)SF_LDS_TABLE + 3u : bi * 4u)
-                                   : SF_LDS_PLANE + bc * SF_LDS_COLS + bi * 3u;
+    const BuildLane B = build_lane(bcol, lane, build_child(lane));
 
     uint32_t d = 0;
     uint32_t idxB = 1;
 
-    // (traverse_ray's self_test on one ray's state)
     auto self_test = [&](PairRay& r, uint64_t& ancm, const float4 pc, float tca, float d2, uint32_t dd, float actv,
                          uint32_t idx, float R2s) {
-        const uint64_t hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);
-        if (hsm) {
-            const float xs = R2s - d2;
-            float ts;
-            if ((wave_ballot(!(xs >= 0x1p-96f)) & hsm) != 0ull) ts = near_root_exact(tca, d2, R2s);
-            else ts = near_root_big(tca, xs);
-            uint64_t accm = hsm & wave_ballot(ts < r.h.minT);
-            const uint64_t tie = hsm & wave_ballot(ts == r.h.minT);
-            if (tie != 0ull) {
-                accm |= tie & ancm;
-                if (front_first && (tie & ~ancm) != 0ull) status |= SF_STATUS_TIE;
-            }
-            sel_in_place(r.h.minT, ts, accm);
-            sel_in_place(r.h.cx, pc.x, accm);
-            sel_in_place(r.h.cy, pc.y, accm);
-            sel_in_place(r.h.cz, pc.z, accm);
-            sel_in_place(r.h.index, idx, accm);
-            uint32_t hd = (uint32_t)r.h.depth;
-            sel_in_place(hd, dd, accm);
-            r.h.depth = (int32_t)hd;
-            ancm |= accm;
-        }
+        accept_self<false>(r.h, ancm, status, front_first, pc, tca, d2, dd, actv, idx, R2s);
     };
 
     const uint32_t lv32 = __builtin_amdgcn_readfirstlane(levels << 5);
     const uint32_t index_order = front_first ? 0u : 0x1ffu;
-    // (traverse_ray's expand; at the deepest provisioned level the children are tested for both rays -- a ray that
-    // does not visit the node has actv -1 and passes nothing)
+    // (expand_node for both rays: at the deepest provisioned level a ray that does not visit the node has actv -1 and
+    // passes nothing)
     auto expand = [&](const float4 pc, const float* col, uint32_t cs, float* tb, uint32_t ko, float kp) -> uint32_t {
-        lds_fence();
-        const float3 p0 = *reinterpret_cast<const float3*>(col);
-        const float3 p1 = *reinterpret_cast<const float3*>(col + cs);
-        const float3 p2 = *reinterpret_cast<const float3*>(col + 2u * cs);
-        const float4 cn = *reinterpret_cast<const float4*>(L.cone());
-        const float sinT = L.cone()[4];
-        const float4 dtn = depth_consts_at(K, ko - (1u << 5));
-        const float4 dtc = depth_consts_at(K, ko);
-        const float sm = bc == 3u ? dtn.z : 1.0f;
-        const float b0 = b[0] * sm, b1 = b[1] * sm, b2 = b[2] * sm;
-        const float x = __builtin_fmaf(pc.x, b[3], (p0.x * b0 + p1.x * b1) + p2.x * b2);
-        const float y = __builtin_fmaf(pc.y, b[3], (p0.y * b0 + p1.y * b1) + p2.y * b2);
-        const float z = __builtin_fmaf(pc.z, b[3], (p0.z * b0 + p1.z * b1) + p2.z * b2);
-        const float w = (x * x + y * y) + z * z;
-        const float R2b = dtc.x;
-        const float ax = cn.x, ay = cn.y, az = cn.z, cosT = cn.w;
-        const float ca = __builtin_fmaf(x, ax, __builtin_fmaf(y, ay, z * az));
-        const float sq = __builtin_amdgcn_sqrtf(__builtin_fmaxf(__builtin_fmaf(-ca, ca, w), 0.0f));
-        const float X = __builtin_fmaf(sq, cosT, -(ca * sinT));
-        const float Y = __builtin_fmaf(X, X, -(R2b + w * (0x1p-18f + 0x1p-19f)));
-        const float reg = __builtin_fmaf(w, 1.0f - 0x1p-16f, -2.0f * R2b);
-        const float mk = __builtin_fminf(__builtin_fminf(ca, reg), __builtin_fminf(X, Y));
-        uint32_t M = (uint32_t)(wave_ballot(!(mk > 0.0f)) >> 32) & 0x1ffu;
-        M = __builtin_amdgcn_readfirstlane(M);
-        const uint32_t front = ((uint32_t)(wave_ballot(ca < kp) >> 32) & 0x1ffu) | index_order;
+        const ChildBuild cb = build_children(K, L, B, pc, col, cs, ko, kp, index_order);
         if (ko < lv32) {
-            *reinterpret_cast<float3*>(tb + slot) = make_float3(x, y, z);
-            *(bc == 3u ? tb + slot + 3u : L.cone() + 5u) = w;
-            return (M & front) | ((M & ~front) << 16);
+            *reinterpret_cast<float3*>(tb + B.slot) = make_float3(cb.x, cb.y, cb.z);
+            *(B.bc == 3u ? tb + B.slot + 3u : L.cone() + 5u) = cb.w;
+            return (cb.M & cb.front) | ((cb.M & ~cb.front) << 16);
         }
         {
-            const float T = dtc.w, Tfar = depth_word_at(K, ko, 6u);
+            const float R2b = cb.dtc.x, T = cb.dtc.w, Tfar = depth_word_at(K, ko, 6u);
+            uint32_t M = cb.M;
             while (M) {
                 const uint32_t i = __builtin_ctz(M);
                 M &= ~(1u << i);
-                const float cx = readlane_f(x, 32u + i), cy = readlane_f(y, 32u + i);
-                const float cz = readlane_f(z, 32u + i), cc = readlane_f(w, 32u + i);
+                const float cx = readlane_f(cb.x, 32u + i), cy = readlane_f(cb.y, 32u + i);
+                const float cz = readlane_f(cb.z, 32u + i), cc = readlane_f(cb.w, 32u + i);
                 auto passes = [&](const PairRay& r) -> bool {
-                    const float tca = (cx * r.dx + cy * r.dy) + cz * r.dz;
-                    const float d2 = cc - tca * tca;
-                    const float xs = R2b - d2;
-                    const bool hb = __builtin_fminf(__builtin_fminf(tca, xs), r.actv) >= 0.0f;
-                    const uint64_t hbm = wave_ballot(hb);
-                    return hbm != 0ull && child_lod(tca, d2, xs, hb, hbm, R2b, T, Tfar) != 0ull;
+                    return child_expands(cx, cy, cz, cc, r.dx, r.dy, r.dz, r.actv, R2b, T, Tfar);
                 };
                 if (passes(ra) || passes(rb)) {
                     status |= SF_STATUS_OVERFLOW;
@@ -1823,7 +1577,7 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
                 const float4 dk = depth_consts_at(K, kofs + 16u);
                 const float Tfar = dk.z;
                 const float cull_r = dk.y;
-                const uint64_t exm = child_lod(tca, d2, xs, hb, hbm, dc.x, dc.w, Tfar);
+                const uint64_t exm = lod_expands(tca, d2, xs, hb, hbm, dc.x, dc.w, Tfar);
                 if (exm == 0ull) continue;
                 if ((int32_t)d + 1 > maxd) {
                     maxd = (int32_t)d + 1;
@@ -1831,9 +1585,7 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
                 }
                 uint64_t amx = exm;
                 if (occl_cull) {
-                    const float v = __builtin_fminf(tca - ra.h.minT, tca - cull_t);
-                    const uint64_t cm = wave_ballot(v - SF_OCCL_MARGIN * tca > cull_r);
-                    amx = exm & ~cm;
+                    amx = exm & ~occluded<false>(tca, ra.h.minT, cull_t, cull_r);
                     if (amx == 0ull) continue;
                 }
                 const float avx = sel_mask(-1.0f, __builtin_inff(), amx);
@@ -1941,8 +1693,8 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
             const float4 dk = depth_consts_at(K, kofs + 16u);
             const float Tfar = dk.z;
             const float cull_r = dk.y;
-            const uint64_t exmA = hbmA ? child_lod(tcaA, d2A, xsA, hbA, hbmA, dc.x, dc.w, Tfar) : 0ull;
-            const uint64_t exmB = hbmB ? child_lod(tcaB, d2B, xsB, hbB, hbmB, dc.x, dc.w, Tfar) : 0ull;
+            const uint64_t exmA = hbmA ? lod_expands(tcaA, d2A, xsA, hbA, hbmA, dc.x, dc.w, Tfar) : 0ull;
+            const uint64_t exmB = hbmB ? lod_expands(tcaB, d2B, xsB, hbB, hbmB, dc.x, dc.w, Tfar) : 0ull;
             if ((exmA | exmB) == 0ull) continue;
             if ((int32_t)d + 1 > maxd) {
                 maxd = (int32_t)d + 1;
@@ -1950,6 +1702,8 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
             }
             uint64_t amxA = exmA, amxB = exmB;
             if (occl_cull) {
+                // (occluded, for the two rays at once: both distances before the two ballots -- called per ray the
+                // schedule of this loop changes)
                 const float vA = __builtin_fminf(tcaA - ra.h.minT, tcaA - cull_t);
                 const float vB = __builtin_fminf(tcaB - rb.h.minT, tcaB - cull_t);
                 amxA = exmA & ~wave_ballot(vA - SF_OCCL_MARGIN * tcaA > cull_r);
@@ -2238,7 +1992,7 @@ __device__ __forceinline__ void kernarg_frame(FrameArgs& at, const FrameArgs& a)
 // units, no diagnostics (tile trace, diagnostic flags), no tile cost, no packed slab, no aux channels. `a` is then the
 // kernel's own argument: the epilogue reads the G-buffer pointers, W and the overflow list from the kernel argument
 // segment again instead of carrying them across the traversal.
-template <bool FIXUP, bool PIPE = false, class Prefetch = NoPrefetch, bool COMPACT = false, bool SPLIT = false, bool LEAN = false>
+template <bool FIXUP, class Prefetch = NoPrefetch, bool COMPACT = false, bool SPLIT = false, bool LEAN = false>
 __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __restrict__ L, const float4 bcol, uint32_t tile,
                                                 uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count,
                                                 uint32_t part = 0u, const Prefetch& pre = Prefetch(), uint32_t fl = ~0u,
@@ -2260,8 +2014,8 @@ __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __res
         HitState h;
         int32_t maxd = -1;
         uint32_t status = 0u;
-        traverse_ray<PIPE, false>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status, flags, nullptr, 36u,
-                                  nullptr, 0u, 0u, seed);
+        traverse_ray<>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status, flags, nullptr, 36u, nullptr, 0u, 0u,
+                       seed);
         const bool overflowed = status != 0u;
         const bool retrace = __builtin_amdgcn_readfirstlane((int)(status == SF_STATUS_TIE && (flags & SF_FLAG_TIE_INLINE))) != 0;
         pre(retrace);
@@ -2296,22 +2050,16 @@ __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __res
     uint64_t tile_counts = 0;
     // The main kernels enter children front-first (with the occlusion cull); an exact non-ancestor tie under
     // that order flags the tile like an overflow, and the fixup re-traces it in index order -- the reference's
-    // tie rule (see traverse). The fixup kernel always traces in index order.
-#ifndef SF_OLD_TRAVERSE
+    // tie rule (see accept_self). The fixup kernel always traces in index order.
     if constexpr (SPLIT)   // one traversal: the split depth never matches on whole units
-        traverse_ray<PIPE, COMPACT, true>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status,
-                                          FIXUP ? (flags | SF_FLAG_NO_FRONT_FIRST) : flags,
-                                          FIXUP ? nullptr : a.phase_sums, part_axis_lane(sub ? 0u : part), &tile_counts,
-                                          sub ? part - SF_PART_QUARTER0 : 0u, sub ? a.split_depth : 0xffffffffu, seed);
-    else
-        traverse_ray<PIPE, COMPACT>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status,
+        traverse_ray<COMPACT, true>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status,
                                     FIXUP ? (flags | SF_FLAG_NO_FRONT_FIRST) : flags,
-                                    FIXUP ? nullptr : a.phase_sums, part_axis_lane(part), &tile_counts, 0u, 0u, seed);
-#else
-    traverse<0, PIPE>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status,
-                      FIXUP ? (flags | SF_FLAG_NO_FRONT_FIRST) : flags,
-                      FIXUP ? nullptr : a.phase_sums, part_axis_lane(part), &tile_counts);
-#endif
+                                    FIXUP ? nullptr : a.phase_sums, part_axis_lane(sub ? 0u : part), &tile_counts,
+                                    sub ? part - SF_PART_QUARTER0 : 0u, sub ? a.split_depth : 0xffffffffu, seed);
+    else
+        traverse_ray<COMPACT>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status,
+                              FIXUP ? (flags | SF_FLAG_NO_FRONT_FIRST) : flags,
+                              FIXUP ? nullptr : a.phase_sums, part_axis_lane(part), &tile_counts, 0u, 0u, seed);
     if (!FIXUP && (flags & (SF_FLAG_DIAG_FORCE_RETRACE | SF_FLAG_REDO_PASS)) == SF_FLAG_DIAG_FORCE_RETRACE)
         status |= SF_STATUS_TIE;
     bool merger = true;   // this wave writes the tile (a subtree part: only the part that merges)
@@ -2637,7 +2385,7 @@ extern "C" __global__ __launch_bounds__(256) void sf_trace_wave4(FrameArgs a, ui
 // PAIR (with LEAN; 1: sf_trace_queue1, 2: sf_trace_queue1c, which also records unit costs for the render that rebuilds
 // the order): the lean loop over pair units (trace_pair) -- the unit word's tile field holds the pair index, the
 // row-major units are the ceil(tiles_x / 2) x tile_rows pairs.
-template <int WAVES, bool PIPE = false, bool COMPACT = false, bool SPLIT = false, bool LEAN = false, int PAIR = 0>
+template <int WAVES, bool COMPACT = false, bool SPLIT = false, bool LEAN = false, int PAIR = 0>
 __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
 {
     static_assert(PAIR == 0 || LEAN, "pair units are the lean loop's");
@@ -2693,9 +2441,6 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
         k = __builtin_amdgcn_readfirstlane(k);
     }
     int32_t maxd = -1;
-#ifdef SF_SEED_READ_ONCE
-    int32_t word_once = -1;
-#endif
     float closest = FLT_MAX;   // per lane
     // The first unit of every wave is static: wave w (in dispatch order) takes unit w, so the head of the
     // heavy-first order starts as the waves arrive instead of behind ~900 simultaneous atomics per queue;
@@ -2726,13 +2471,7 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
         if (!again && g >= nunits) break;
         // the cull's depth seed (DepthSeed): the word's load is issued per unit, here, ahead of the unit's ray
         // generation, and waited for after it (trace_tile)
-#ifndef SF_SEED_READ_ONCE
         const DepthSeed seen{ maxd, stats_word(at) };
-#else   // (A/B build: only the wave's first unit reads the word)
-        if (g == __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + wv))
-            word_once = __builtin_amdgcn_readfirstlane(stats_word(at));
-        const DepthSeed seen{ maxd, word_once };
-#endif
         uint32_t t = g, part = 0u;
         if (again) {
             t = g & SF_UNIT_TILE_MASK;
@@ -2776,7 +2515,7 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
             if constexpr (PAIR != 0)
                 st = trace_pair<PAIR == 2>(at, L, bcol, t, at.max_depth, ticket, ufl, seen);
             else
-                st = trace_tile<false, PIPE, decltype(ticket), false, false, true>(
+                st = trace_tile<false, decltype(ticket), false, false, true>(
                     at, L, bcol, t, at.max_depth, nullptr, nullptr, 0u, ticket, ufl, 0u, seen);
             maxd = st.maxd > maxd ? st.maxd : maxd;
             if (st.seed >= 0 && st.maxd > st.seed) {   // (rare: see the general loop below)
@@ -2797,7 +2536,7 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
             first = retrace ? (0x80000000u | (rp << SF_UNIT_PRIO_SHIFT) | t)
                             : nwaves + wave_fetch_add(at.counters + SF_QUEUE_WORD(at.parity, k), 1u) * nq + k;   // uniform
         };
-        const TileStats st = trace_tile<false, PIPE, decltype(ticket), COMPACT, SPLIT>(at, L, bcol, t, at.max_depth, at.overflow_list,
+        const TileStats st = trace_tile<false, decltype(ticket), COMPACT, SPLIT>(at, L, bcol, t, at.max_depth, at.overflow_list,
                                                                                at.counters + at.parity, part,
                                                ticket, again ? (at.flags | SF_FLAG_NO_FRONT_FIRST | SF_FLAG_REDO_PASS)
                                                              : at.flags, g >> 2, seen);
@@ -2863,19 +2602,19 @@ __device__ __forceinline__ void trace_queue_body(const FrameArgs& a)
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SF_PAIR_WAVES_PER_EU, SF_PAIR_WAVES_PER_EU)))
 void sf_trace_queue1(FrameArgs a)
 {
-    trace_queue_body<1, false, false, false, true, 1>(a);
+    trace_queue_body<1, false, false, true, 1>(a);
 }
 // the same recording unit costs: the render that rebuilds the order of pair units
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SF_PAIR_WAVES_PER_EU, SF_PAIR_WAVES_PER_EU)))
 void sf_trace_queue1c(FrameArgs a)
 {
-    trace_queue_body<1, false, false, false, true, 2>(a);
+    trace_queue_body<1, false, false, true, 2>(a);
 }
 // the lean loop over single tiles (whole tiles of one plain frame, see trace_queue_body): the product launch of the
 // smaller frames
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SF_WAVES_PER_EU, 8))) void sf_trace_queue1t(FrameArgs a)
 {
-    trace_queue_body<1, false, false, false, true>(a);
+    trace_queue_body<1, false, false, true>(a);
 }
 // the general instantiation: every mode of the tile loop (part units, diagnostics, tile costs, packed slabs, aux
 // channels, band shares)
@@ -2886,7 +2625,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S
 // the same with subtree-split units (SF_FLAG_SUBTREE): renders whose unit order holds split tiles
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SF_WAVES_PER_EU, 8))) void sf_trace_queue1s(FrameArgs a)
 {
-    trace_queue_body<1, false, false, true>(a);
+    trace_queue_body<1, false, true>(a);
 }
 extern "C" __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SF_WAVES_PER_EU, 8))) void sf_trace_queue2(FrameArgs a)
 {
@@ -2898,11 +2637,6 @@ extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
 }
 // active-ray compaction of sparse nodes (opt-in, SF_COMPACT=1; see traverse_ray): measured against the default
 extern "C" __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SF_WAVES_PER_EU, 8))) void sf_trace_queue2c(FrameArgs a)
-{
-    trace_queue_body<2, false, true>(a);
-}
-// latency variant (pipelined child loop) for frames whose tiles do not fill the persistent grid twice
-extern "C" __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SF_WAVES_PER_EU, 8))) void sf_trace_queue2p(FrameArgs a)
 {
     trace_queue_body<2, true>(a);
 }
@@ -3051,7 +2785,7 @@ __device__ __forceinline__ void trace_frames_body()
         };
         // the cull's depth seed is per frame, as the stats words are: frame f's word and this wave's maximum in frame f
         const DepthSeed seen{ (int32_t)__builtin_amdgcn_readlane(stat_d, f), stats_word(at) };
-        const TileStats st = trace_tile<false, false, decltype(ticket)>(at, L, bcol, t, at.max_depth, at.overflow_list,
+        const TileStats st = trace_tile<false, decltype(ticket)>(at, L, bcol, t, at.max_depth, at.overflow_list,
                                                                       at.counters + at.parity, part, ticket,
                                                                       again ? (at.flags | SF_FLAG_NO_FRONT_FIRST |
                                                                                SF_FLAG_REDO_PASS)
@@ -3984,12 +3718,7 @@ __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ 
     const TraverseLds L{ Lbase };
     const bool occl_cull = (K_flags & SF_FLAG_NO_OCCL_CULL) == 0u;
 
-    if constexpr (ANYHIT) h.minT = bound;
-    else h.minT = FLT_MAX;
-    h.cx = h.cy = h.cz = 0.f;
-    h.index = 0xffffffffu;
-    h.depth = -1;
-    h.hit = false;
+    reset_hit(h, ANYHIT ? bound : FLT_MAX);
     uint64_t ancm = 0ull;   // lanes whose current best sphere is an ancestor of the open node
 
     // ---- root node (depth 0): bounding sphere + LOD, per lane on the lane's own root centre
@@ -4002,89 +3731,33 @@ __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ 
     maxd = 0;
     float cull_t = depth_consts(K, 1u).w;
 
-    // this lane's column of the cooperative child build, and where it stores it (as traverse_ray)
-    const uint32_t bi = build_child(lane);
-    const uint32_t bc = lane < 27u ? lane / 9u : 3u;
-    const float b[4] = { bcol.x, bcol.y, bcol.z, bcol.w };
-    const uint32_t slot = bc == 3u ? (lane >= 32u && bi == 8u ? (uint32_t)SF_LDS_TABLE + 3u : bi * 4u)
-                                   : SF_LDS_PLANE + bc * SF_LDS_COLS + bi * 3u;
+    const BuildLane B = build_lane(bcol, lane, build_child(lane));
 
-    // (traverse_ray's self_test in index order: a tie is accepted where the best is an ancestor, else dropped)
-    // (returns the accepting lanes: the any-hit mode's finished lanes)
+    // (accept_self in index order: a tie is accepted where the best is an ancestor, else dropped, never flagged)
     auto self_test = [&](const float4 pc, float tca, float d2, uint32_t dd, float actv, uint32_t idx,
                          float R2s) -> uint64_t {
-        const uint64_t hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);
-        if (hsm) {
-            const float xs = R2s - d2;
-            float ts;
-            if ((wave_ballot(!(xs >= 0x1p-96f)) & hsm) != 0ull) ts = near_root_exact(tca, d2, R2s);
-            else ts = near_root_big(tca, xs);
-            uint64_t accm = hsm & wave_ballot(ts < h.minT);
-            if constexpr (ANYHIT) {   // (the finished flag only)
-                uint32_t hd = (uint32_t)h.depth;
-                sel_in_place(hd, dd, accm);
-                h.depth = (int32_t)hd;
-                return accm;
-            }
-            const uint64_t tie = hsm & wave_ballot(ts == h.minT);
-            accm |= tie & ancm;
-            sel_in_place(h.minT, ts, accm);
-            sel_in_place(h.cx, pc.x, accm);
-            sel_in_place(h.cy, pc.y, accm);
-            sel_in_place(h.cz, pc.z, accm);
-            sel_in_place(h.index, idx, accm);
-            uint32_t hd = (uint32_t)h.depth;
-            sel_in_place(hd, dd, accm);
-            h.depth = (int32_t)hd;
-            ancm |= accm;
-            return accm;
-        }
-        return 0ull;
-    };
-
-    // (traverse_ray's child_lod)
-    auto child_lod = [&](float tca, float d2, float xs, bool hb, uint64_t hbm, float R2b, float T, float Tfar) -> uint64_t {
-        const uint64_t nearm = wave_ballot(tca < T);
-        const uint64_t farm = wave_ballot(tca * (1.0f - 0x1p-8f) >= Tfar);
-        if ((hbm & ~(nearm | farm)) == 0ull) return hbm & nearm;
-        const float sq = __builtin_amdgcn_sqrtf(xs);
-        const float s_lo = __uint_as_float((uint32_t)max((int32_t)__float_as_uint(sq) - 2, 0));
-        const float s_hi = __uint_as_float(__float_as_uint(sq) + 2u);
-        const float t_hi = tca - s_lo;
-        const float t_lo = tca - s_hi;
-        const uint64_t tinym = wave_ballot(xs < 0x1p-96f);
-        const float thx = sel_mask(t_hi, __builtin_inff(), tinym);
-        const float tlx = sel_mask(t_lo, -__builtin_inff(), tinym);
-        const float th = hb ? thx : __builtin_inff();
-        const float tl = hb ? tlx : __builtin_inff();
-        uint64_t exm = wave_ballot(th < T);
-        const uint64_t undm = wave_ballot(sel_mask(tl, __builtin_inff(), exm) < T);
-        if (undm) {
-            const float te = near_root_exact(tca, d2, R2b);
-            exm |= undm & wave_ballot(te < T);
-        }
-        return exm;
+        return accept_self<ANYHIT, true>(h, ancm, status, false, pc, tca, d2, dd, actv, idx, R2s);
     };
 
     // ---- the shared part of the 9 children of the node whose axis columns are at col + j cs, into table tb: their
-    // axis columns (lanes 0..26) and their centre offsets S (the other lanes), the sums of traverse_ray's expand
+    // axis columns (lanes 0..26) and their centre offsets S (the other lanes), the sums of build_children
     // without its fma of the parent centre (ko: byte offset of the children's depth constants)
     auto expand = [&](const float* col, uint32_t cs, float* tb, uint32_t ko) {
         lds_fence();
         const float3 p0 = *reinterpret_cast<const float3*>(col);
         const float3 p1 = *reinterpret_cast<const float3*>(col + cs);
         const float3 p2 = *reinterpret_cast<const float3*>(col + 2u * cs);
-        const float sm = bc == 3u ? depth_word_at(K, ko - (1u << 5), 2u) : 1.0f;   // (4/3) r of the node's depth
-        const float b0 = b[0] * sm, b1 = b[1] * sm, b2 = b[2] * sm;
+        const float sm = B.bc == 3u ? depth_word_at(K, ko - (1u << 5), 2u) : 1.0f;   // (4/3) r of the node's depth
+        const float b0 = B.b0 * sm, b1 = B.b1 * sm, b2 = B.b2 * sm;
         const float x = (p0.x * b0 + p1.x * b1) + p2.x * b2;
         const float y = (p0.y * b0 + p1.y * b1) + p2.y * b2;
         const float z = (p0.z * b0 + p1.z * b1) + p2.z * b2;
         if constexpr (!ANYHIT) {
-            const bool negz = bc != 3u && (__float_as_uint(x) == 0x80000000u || __float_as_uint(y) == 0x80000000u ||
+            const bool negz = B.bc != 3u && (__float_as_uint(x) == 0x80000000u || __float_as_uint(y) == 0x80000000u ||
                                            __float_as_uint(z) == 0x80000000u);
             if (wave_ballot(negz) != 0ull) status |= SF_STATUS_ZSIGN;
         }
-        *reinterpret_cast<float3*>(tb + slot) = make_float3(x, y, z);
+        *reinterpret_cast<float3*>(tb + B.slot) = make_float3(x, y, z);
     };
 
     uint32_t stk_pc = 0u, stk_ix = 0u;   // VGPR stack, lane k = level k: untested children, idxB
@@ -4134,7 +3807,7 @@ __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ 
             const uint64_t hbm = wave_ballot(hb);
             if (hbm == 0ull) continue;
             const float4 dk = depth_consts_at(K, kofs + 16u);   // depth d + 1's {leaf, cull, far}
-            const uint64_t exm = child_lod(tca, d2, xs, hb, hbm, dc.x, dc.w, dk.z);
+            const uint64_t exm = lod_expands(tca, d2, xs, hb, hbm, dc.x, dc.w, dk.z);
             if (exm == 0ull) continue;
             if (kofs >= lv32) {   // (d + 1 >= levels) the group is re-traced with more levels: nothing here is kept
                 status |= SF_STATUS_OVERFLOW;
@@ -4144,13 +3817,10 @@ __device__ __forceinline__ void traverse_mixed(const DeviceConsts* __restrict__ 
                 maxd = (int32_t)d + 1;
                 cull_t = depth_consts_at(K, kofs + (1u << 5)).w;
             }
-            // occlusion cull, per lane (see traverse_ray)
-            // (any-hit mode: the distance condition alone -- no sphere of the subtree nearer than the lane's bound)
+            // occlusion cull, per lane (occluded)
             uint64_t amx = exm;
             if (occl_cull) {
-                float v = tca - h.minT;
-                if constexpr (!ANYHIT) v = __builtin_fminf(v, tca - cull_t);
-                amx = exm & ~wave_ballot(v - SF_OCCL_MARGIN * tca > dk.y);
+                amx = exm & ~occluded<ANYHIT>(tca, h.minT, cull_t, dk.y);
                 if (amx == 0ull) continue;
             }
             const float avx = sel_mask(-1.0f, __builtin_inff(), amx);
@@ -4396,7 +4066,7 @@ __device__ __forceinline__ void trace_shadow_group(const FrameArgs& a, const flo
         h.hit = on && h.minT < bound;
 #else
         // (a tie never flags in the shadow mode, so the re-trace keeps the front-first order)
-        traverse_ray<false, false, false, true>(K, a.root, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az,
+        traverse_ray<false, false, true>(K, a.root, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az,
                                                 on, h, md, status, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
 #endif
     }
@@ -4495,7 +4165,7 @@ __device__ __forceinline__ void trace_shadows_group(const FrameArgs& a, const fl
             h.hit = false;
             int32_t md = -1;
             uint32_t st = 0u;
-            traverse_ray<false, false, false, true>(K, r, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az, on, h,
+            traverse_ray<false, false, true>(K, r, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az, on, h,
                                                     md, st, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
             status |= st;
             shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
@@ -5149,7 +4819,7 @@ __device__ __forceinline__ void progressive_trace(const FrameArgs& a, const uint
     int32_t maxd = -1;
     uint32_t status = 0u;
     stage_root(lds, a.root);
-    traverse<PW>(K, a.root, lds, build_column(K), levels, dx, dy, dz, valid, h, maxd, status, a.flags);
+    traverse_packet<PW>(K, a.root, lds, build_column(K), levels, dx, dy, dz, valid, h, maxd, status, a.flags);
     const bool overflowed = (status & SF_STATUS_OVERFLOW) != 0u;
 
     PacketLane out;

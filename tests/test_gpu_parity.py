@@ -339,8 +339,9 @@ def test_several_queues_per_xcd_bit_exact(monkeypatch, qpx):
 
 @pytest.mark.parametrize("name,pipe", [("c1", "0"), ("c3", "1")])
 def test_trace_variants_forced_bit_exact(monkeypatch, name, pipe):
-    """The persistent trace has a latency variant (sf_trace_queue2p, pipelined child loop) that the host
-    picks for small frames; SF_PIPE forces either. Each variant on the other's frame size: golden frame."""
+    """SF_PIPE once chose between a throughput and a latency variant of the persistent trace; the two were the
+    same code, and one kernel is left. What the knob still does: SF_PIPE=1 runs two waves per workgroup
+    (sf_trace_queue2), SF_PIPE=0 changes nothing. Either setting on a large and a small frame: golden frame."""
     monkeypatch.setenv("SF_PIPE", pipe)
     fx = load_frame(name)
     W, H, K = fx["W"], fx["H"], float.fromhex(fx["K"])

@@ -33,8 +33,8 @@ def random_view(rng, k):
 @pytest.mark.parametrize("variant", ["avx", "sse", "compact", "subtree", "subtree_d2"])
 @pytest.mark.parametrize("seed", range(16))
 def test_random_view_bit_exact(seed, variant, monkeypatch):
-    """("compact": the AVX variant traced by the opt-in active-ray compaction kernel, SF_COMPACT=1 with the
-    throughput variant forced, SF_PIPE=0, since these small frames would take the latency variant. "subtree":
+    """("compact": the AVX variant traced by the opt-in active-ray compaction kernel, SF_COMPACT=1; SF_PIPE=0,
+    which once kept these small frames off a latency variant that shadowed it, no longer changes anything. "subtree":
     the AVX variant with the split tiles traced as subtree parts, SF_SPLIT_PARTS=subtree, at the default split
     depth and at depth 2 -- these frames leave idle waves, so renders 2 and 3 split their heaviest tiles.)"""
     if variant == "compact":
