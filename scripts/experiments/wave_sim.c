@@ -16,7 +16,14 @@
  * (l % TW, l / TW) of the unit, TW TH <= 128 lanes (lane masks are unsigned __int128), the cone axis is the centre
  * pixel's lane (TH / 2) TW + TW / 2 -- a pair unit of the kernel is 16 x 8 with two rays per hardware lane. half_exp /
  * half_iter count, per depth, the expansions and child iterations whose visiting lanes all lie in one 8 x 8 tile of
- * the unit (a subtree the pair kernel runs on its one-ray loop).
+ * the unit (a subtree of one tile, which the pair kernel runs on its one-ray loop).
+ * The pair kernel's hardware lane of a pixel is its lane within its own 8 x 8 tile: lane l of the wave carries a ray of
+ * each tile. A node that no hardware lane visits with two tiles (one-tile nodes included) runs the one-ray loop too,
+ * the lanes that visit with ray B exchanged into ray A's registers (traverse_pair's one_ray_subtree): fold_exp /
+ * fold_iter count the expansions and iterations under such nodes, root_a / root_b / root_d the roots of such subtrees
+ * by the depth they are entered at (visited by tile A only, tile B only, both on disjoint hardware lanes; depth 0 is
+ * the unit's root, deeper ones are entered from a two-ray node), and side_iter / side_lod the iterations of the
+ * two-ray loop whose bounding hits lie in one tile only, and those of them that pass LOD (16 x 8 units only).
  * Built by scripts/experiments/wave_sim.py against oracle/sf_oracle.c (included).
  */
 #include <stdlib.h>
@@ -49,6 +56,17 @@ static int lm_one_half(lmask_t m)
         if (first < 0) first = h; else if (h != first) return 0;
     }
     return 1;
+}
+/* the lanes of m in tile h of the unit, as a mask over the tile's 64 hardware lanes */
+static uint64_t lm_tile_lanes(lmask_t m, int h)
+{
+    uint64_t r = 0;
+    for (int l = 0; l < NL; ++l) {
+        if (!((m >> l) & 1)) continue;
+        const int x = l % TW, y = l / TW;
+        if ((y / 8) * (TW / 8) + x / 8 == h) r |= 1ull << ((y % 8) * 8 + x % 8);
+    }
+    return r;
 }
 #define SF_OCCL_MARGIN_SIM 0x1.8p-9f
 
@@ -92,6 +110,9 @@ typedef struct {
     long long skip_exp[NST], skip_lost[NST];   /* expansions the useless-cone predicate skips; culls lost by it */
     long long cache_hit[NST];                  /* expansions whose level table already holds their children */
     long long half_exp[NST], half_iter[NST];   /* expansions / iterations whose visiting lanes lie in one 8x8 tile */
+    long long fold_exp[NST], fold_iter[NST];   /* ... whose visiting lanes share no hardware lane between the two tiles */
+    long long root_a[NST], root_b[NST], root_d[NST];   /* roots of such subtrees: tile A only, B only, both (disjoint) */
+    long long side_iter[NST], side_lod[NST];   /* two-ray iterations with bounding hits in one tile only; passing LOD */
 } sim_stats_t;
 
 typedef struct {
@@ -122,6 +143,7 @@ typedef struct {
     double pl[4][3];
     float fn[4][3], fbeta, fs, fbh, fbc;
     int npairs, pairs[4][2];   /* mode 128: the kernel's fp32 frustum (normals, beta, slack) */
+    int fold;                    /* inside a subtree that runs the one-ray loop (16 x 8 units) */
     long long fr_culled;         /* mode 32: the tile pyramid's side planes (inward unit normals, through the origin) */
 } wsim_t;
 
@@ -165,6 +187,18 @@ static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, lmask_t
     st->exp[d]++;
     const int one_half = lm_one_half(A);
     st->half_exp[d] += one_half;
+#if TW == 16 && TH == 8
+    const uint64_t vA = lm_tile_lanes(A, 0), vB = lm_tile_lanes(A, 1);
+    const int fold = (vA & vB) == 0;
+#else
+    const int fold = 0;
+#endif
+    const int saved_fold = S->fold;
+#if TW == 16 && TH == 8
+    if (fold && !saved_fold) (vB == 0 ? st->root_a : vA == 0 ? st->root_b : st->root_d)[d]++;
+#endif
+    S->fold = fold;
+    st->fold_exp[d] += fold;
     if (S->owner[d] == node) st->cache_hit[d]++;
     S->owner[d] = node;
     const int saved_part = S->cur_part;
@@ -294,6 +328,7 @@ static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, lmask_t
             (int)((9 * node + 1 + (uint64_t)c) % (uint64_t)S->split_p) != S->solo) continue;
         st->iter[d]++;
         st->half_iter[d] += one_half;
+        st->fold_iter[d] += fold;
         SIM_WORK(1.0);
         st->act[d] += lm_pop(A);
         lmask_t hb = 0, ex = 0;
@@ -308,6 +343,12 @@ static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, lmask_t
             if (t < S->T[dc]) ex |= LM1 << l;
         }
         st->hitl[d] += lm_pop(hb);
+#if TW == 16 && TH == 8
+        if (!fold && hb && (lm_tile_lanes(hb, 0) == 0 || lm_tile_lanes(hb, 1) == 0)) {
+            st->side_iter[d]++;
+            st->side_lod[d] += ex != 0;
+        }
+#endif
         if (!hb) { st->miss[d]++; continue; }
         if (!ex) { st->lodnone[d]++; continue; }
         if (dc > S->maxd) { S->maxd = dc; S->cull_t = S->T[dc + 1]; }
@@ -329,6 +370,7 @@ static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, lmask_t
         expand_node(S, W[c], dc, id, am);
     }
     S->cur_part = saved_part;
+    S->fold = saved_fold;
 }
 
 int wsim_tiles(uint32_t W, uint32_t H, const float o[3], const float tl[3], const float tr[3], const float bl[3],
@@ -473,6 +515,7 @@ int wsim_tiles(uint32_t W, uint32_t H, const float o[3], const float tl[3], cons
         }
         st->tiles++;
         if (ex0) {
+            S.fold = 0;
             S.maxd = 0;
             S.cull_t = S.T[1];
             self_test(&S, C, rcc, 0, 0, ex0);

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Drive wave_sim.c: the product kernel's wave-coherent traversal modelled on the CPU, its work counted per depth
 (experiment, not product). Usage: [WAVE_UNIT=16x8] wave_sim.py [setup=c3] [tile_step=1] [mode=0 ...]
-WAVE_UNIT: the pixels a wave traces, TWxTH (default 8x8, one tile; 16x8 or 8x16: the pair unit), at most 128 lanes."""
+WAVE_UNIT: the pixels a wave traces, TWxTH (default 8x8, one tile; 16x8 or 8x16: the pair unit), at most 128 lanes.
+WAVE_SIM_DIR: where the model's library is built (default: the system's temporary directory)."""
 import ctypes
 import os
 import subprocess
 import sys
+import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -16,21 +18,20 @@ sys.path.insert(0, os.path.join(REPO, "oracle"))
 import pyoracle  # noqa: E402
 
 TW, TH = (int(v) for v in os.environ.get("WAVE_UNIT", "8x8").split("x"))
-SO = f"/tmp/wave_sim_{TW}x{TH}.so"
+SO = os.path.join(os.environ.get("WAVE_SIM_DIR") or tempfile.gettempdir(), f"wave_sim_{TW}x{TH}.so")
 subprocess.check_call(["gcc", "-O2", "-mno-fma", "-ffp-contract=off", f"-DTW={TW}", f"-DTH={TH}", "-shared", "-fPIC", "-o", SO,
                        os.path.join(HERE, "wave_sim.c"), "-lm"])
 L = ctypes.CDLL(SO)
 NST = 32
 FIELDS = ["exp", "iter", "miss", "lodnone", "occlnone", "entered", "leaf", "push", "act", "hitl"]
 TAIL = ["tiles", "mismatch", "ties", "maxd"]
+EXTRA = ["cone_tested", "cone_culled", "skip_exp", "skip_lost", "cache_hit", "half_exp", "half_iter", "fold_exp", "fold_iter",
+         "root_a", "root_b", "root_d", "side_iter", "side_lod"]
 
 
 class Stats(ctypes.Structure):
     _fields_ = [(f, ctypes.c_longlong * NST) for f in FIELDS] + [(f, ctypes.c_longlong) for f in TAIL] + \
-               [("cone_tested", ctypes.c_longlong * NST), ("cone_culled", ctypes.c_longlong * NST),
-                ("skip_exp", ctypes.c_longlong * NST), ("skip_lost", ctypes.c_longlong * NST),
-                ("cache_hit", ctypes.c_longlong * NST), ("half_exp", ctypes.c_longlong * NST),
-                ("half_iter", ctypes.c_longlong * NST)]
+               [(f, ctypes.c_longlong * NST) for f in EXTRA]
 
 
 fp = ctypes.POINTER(ctypes.c_float)
@@ -70,7 +71,7 @@ def run(name="c3", tile_step=1, mode=0, check=True, split=(0, 0)):
                      ctypes.byref(parts[k]), split[0], split[1], works[k].ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
     with ThreadPoolExecutor(8) as ex:
         list(ex.map(work, range(len(trows))))
-    tot = {f: np.sum([np.array(getattr(p, f)[:]) for p in parts], 0) for f in FIELDS + ["cone_tested", "cone_culled", "skip_exp", "skip_lost", "cache_hit", "half_exp", "half_iter"]}
+    tot = {f: np.sum([np.array(getattr(p, f)[:]) for p in parts], 0) for f in FIELDS + EXTRA}
     for f in TAIL:
         tot[f] = max(getattr(p, f) for p in parts) if f == "maxd" else sum(getattr(p, f) for p in parts)
     tot["scale"] = tile_step
@@ -100,6 +101,24 @@ def report(t, label=""):
             if t["exp"][d]:
                 print(f"{d:2d} {t['half_exp'][d]*sc:9d} {t['exp'][d]*sc:9d} {t['half_iter'][d]*sc:11d} {t['iter'][d]*sc:9d}")
         print(f"all {tot('half_exp'):8d} {tot('exp'):9d} {tot('half_iter'):11d} {tot('iter'):9d}")
+    if (TW, TH) == (16, 8):   # the pair unit: what the kernel's one-ray loop takes, and what its two-ray loop still pays
+        print("pair unit: under nodes that no hardware lane visits with both tiles (one-tile nodes included)")
+        print(" d  exp-fold        of     iter-fold        of   roots: A-only  B-only disjoint")
+        for d in range(NST):
+            if t["exp"][d]:
+                print(f"{d:2d} {t['fold_exp'][d]*sc:9d} {t['exp'][d]*sc:9d} {t['fold_iter'][d]*sc:11d} {t['iter'][d]*sc:9d}"
+                      f"  {t['root_a'][d]*sc:13d} {t['root_b'][d]*sc:7d} {t['root_d'][d]*sc:8d}")
+        print(f"all {tot('fold_exp'):8d} {tot('exp'):9d} {tot('fold_iter'):11d} {tot('iter'):9d}"
+              f"  {tot('root_a'):13d} {tot('root_b'):7d} {tot('root_d'):8d}")
+        below = lambda f: int(t[f][1:].sum()) * sc
+        print(f"roots entered from a two-ray node (depth >= 1): A-only {below('root_a')} B-only {below('root_b')}"
+              f" disjoint {below('root_d')}")
+        print("pair unit: two-ray iterations whose bounding hits lie in one tile only")
+        print(" d  one-sided  passing-LOD  two-ray-iter")
+        for d in range(NST):
+            if t["exp"][d]:
+                print(f"{d:2d} {t['side_iter'][d]*sc:10d} {t['side_lod'][d]*sc:12d} {(t['iter'][d]-t['fold_iter'][d])*sc:13d}")
+        print(f"all {tot('side_iter'):9d} {tot('side_lod'):12d} {tot('iter')-tot('fold_iter'):13d}")
 
 
 if __name__ == "__main__":

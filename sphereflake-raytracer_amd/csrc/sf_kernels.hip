@@ -1446,9 +1446,14 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
 // lanes (actv, actbits), the ancestor mask -- is doubled (PairRay, ancm), and every per-ray float operation is exactly
 // the one traverse_ray does on that ray, so results are the single tile's bit for bit. A branch the one-ray loop takes
 // on a ballot is taken on the union of the two rays' ballots.
-// A child entered by lanes of one ray only stays that ray's for its whole subtree (a lane's activity only shrinks down
-// the tree): it runs the one-ray loop (dfs_one) on the "A" registers -- the two sets swapped around it for ray B --
-// until it pops back to the level it was entered from.
+// A child that no lane enters with both its rays stays so for its whole subtree (a lane's activity only shrinks down
+// the tree): every lane has at most one ray in it, so it runs the one-ray loop (dfs_one) on the "A" registers until it
+// pops back to the level it was entered from. Around it the lanes that enter with ray B exchange their two register
+// sets (one_ray_subtree): there A's set carries ray B, and B's set parks ray A, which does not visit the subtree. A
+// child of one tile only is the special case (no lane, or every entering lane, exchanged); the other is a node that
+// straddles the tiles' boundary with a footprint under 9 pixels, entered by A's right columns and B's left ones.
+// Nothing the one-ray loop reads is a tile's: the cone, kp (from the cone's axis), maxd, cull_t and status are the
+// unit's, and the overflow test at the deepest level takes both sets (the parked rays have actv -1).
 struct PairRay {
     float dx, dy, dz;
     HitState h;
@@ -1626,26 +1631,40 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
             ra.actv = ((ra.actbits >> d) & 1u) ? __builtin_inff() : -1.0f;
         }
     };
-    // the subtree of the open node (depth d) for the one ray that visits it: B's through A's registers
-    auto single_half = [&](bool isB) {
-        isB = __builtin_amdgcn_readfirstlane((int)isB) != 0;
-        auto swap = [&]() {
-            auto sw = [](auto& x, auto& y) {
-                const auto t = x;
-                x = y;
-                y = t;
-            };
-            sw(ra.dx, rb.dx), sw(ra.dy, rb.dy), sw(ra.dz, rb.dz);
-            sw(ra.h.minT, rb.h.minT), sw(ra.h.cx, rb.h.cx), sw(ra.h.cy, rb.h.cy), sw(ra.h.cz, rb.h.cz);
-            sw(ra.h.index, rb.h.index), sw(ra.h.depth, rb.h.depth);
-            sw(ra.actv, rb.actv), sw(ra.actbits, rb.actbits);
-            const uint64_t m = ancA;
-            ancA = ancB;
-            ancB = m;
+    // the subtree of the open node (depth d) when no lane visits it with both rays (mB: the lanes whose ray B does):
+    // the one-ray loop on A's registers, with the lanes of mB exchanged between the two sets around it -- there A's
+    // registers carry ray B and B's park ray A, which does not visit the node. v_swap_b32 under EXEC = mB: one VALU
+    // instruction per register, in place; the exchange is its own inverse.
+    auto one_ray_subtree = [&](const uint64_t mB) {
+        auto exchange = [&]() {
+            // (EXEC kept in VCC meanwhile: no SGPR pair of its own)
+            __asm__("s_mov_b64 vcc, exec\n\t"
+                    "s_mov_b64 exec, %22\n\t"
+                    "v_swap_b32 %0, %11\n\t"
+                    "v_swap_b32 %1, %12\n\t"
+                    "v_swap_b32 %2, %13\n\t"
+                    "v_swap_b32 %3, %14\n\t"
+                    "v_swap_b32 %4, %15\n\t"
+                    "v_swap_b32 %5, %16\n\t"
+                    "v_swap_b32 %6, %17\n\t"
+                    "v_swap_b32 %7, %18\n\t"
+                    "v_swap_b32 %8, %19\n\t"
+                    "v_swap_b32 %9, %20\n\t"
+                    "v_swap_b32 %10, %21\n\t"
+                    "s_mov_b64 exec, vcc"
+                    : "+v"(ra.dx), "+v"(ra.dy), "+v"(ra.dz), "+v"(ra.h.minT), "+v"(ra.h.cx), "+v"(ra.h.cy), "+v"(ra.h.cz),
+                      "+v"(ra.h.index), "+v"(ra.h.depth), "+v"(ra.actv), "+v"(ra.actbits), "+v"(rb.dx), "+v"(rb.dy),
+                      "+v"(rb.dz), "+v"(rb.h.minT), "+v"(rb.h.cx), "+v"(rb.h.cy), "+v"(rb.h.cz), "+v"(rb.h.index),
+                      "+v"(rb.h.depth), "+v"(rb.actv), "+v"(rb.actbits)
+                    : "s"(mB)
+                    : "vcc");
+            const uint64_t x = (ancA ^ ancB) & mB;
+            ancA ^= x;
+            ancB ^= x;
         };
-        if (isB) swap();
+        if (mB) exchange();
         dfs_one(d);
-        if (isB) swap();
+        if (mB) exchange();
     };
 
     {
@@ -1666,8 +1685,8 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
         if (!__builtin_amdgcn_readfirstlane((int)(pc.w > depth_leaf(K, 0u))))
             C = expand(pc, L.root() + 4u, 4u, tcur, kofs, readlane_f(tcaA, axl));
     }
-    if (ex0A == 0ull || ex0B == 0ull) {   // one half is empty or misses the root: a single tile from the start
-        single_half(ex0A == 0ull);
+    if ((ex0A & ex0B) == 0ull) {   // no lane expands the root with both rays (one half empty, or missing the root, is
+        one_ray_subtree(ex0B);     // the common case): the one-ray loop from the start
         C = 0u;
     }
 
@@ -1738,8 +1757,8 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
             kofs += 1u << 5;
             C = expand(pc, col, SF_LDS_COLS, tcur, kofs, readlane_f(tcaA, axl));
             R2c = depth_consts_at(K, kofs).x;
-            // entered by one ray only: its subtree on the one-ray loop, back here with the node finished
-            if (amxA == 0ull || amxB == 0ull) single_half(amxA == 0ull);
+            // entered by no lane with both rays: its subtree on the one-ray loop, back here with the node finished
+            if ((amxA & amxB) == 0ull) one_ray_subtree(amxB);
             continue;
         }
         ancA &= wave_ballot(ra.h.depth != (int32_t)d);
@@ -2214,7 +2233,8 @@ __device__ __forceinline__ TileStats trace_pair(const FrameArgs& a, float* __res
 {
     const DeviceConsts* __restrict__ K = a.consts;
     const FrameConsts fc = frame_consts(K);
-    const uint64_t c_start = COST ? __builtin_amdgcn_s_memtime() : 0ull;
+    // (the counter's low word only: one SGPR across the traversal; a unit's cycles are far below 2^32)
+    const uint32_t c_start = COST ? (uint32_t)__builtin_amdgcn_s_memtime() : 0u;
     const uint32_t pairs_x = (a.tiles_x + 1u) >> 1;
     uint32_t ty = __umulhi(unit, a.px_magic);   // (tile_of's divmod)
     uint32_t px = unit - ty * pairs_x;
@@ -2246,8 +2266,7 @@ __device__ __forceinline__ TileStats trace_pair(const FrameArgs& a, float* __res
     kernarg_frame(ae, a);
     if constexpr (COST) {
         if (ae.tile_cost && !(flags & SF_FLAG_REDO_PASS)) {   // (uniform values and addresses)
-            const uint64_t cyc = __builtin_amdgcn_s_memtime() - c_start;
-            const uint32_t cost = cyc > 0xffffffffull ? 0xffffffffu : (uint32_t)cyc;
+            const uint32_t cost = (uint32_t)__builtin_amdgcn_s_memtime() - c_start;
             ae.tile_cost[unit] = cost;
             if (ae.chunk_cnt) {
                 const uint32_t cs = __builtin_amdgcn_readfirstlane((unit >> 6) * SF_ORDER_BUCKETS + cost_bucket(cost));
