@@ -329,11 +329,12 @@ int sf_light_image_many(sf_ctx* ctx, const sf_shadows_params* params, float ambi
 /* --- the level of detail of the shadow traces -------------------------------- */
 /* THE LEVEL OF DETAIL IS THE LIGHT'S (above) because a shadow ray refines a node while sqrtf(t / r) < C with t measured
    from the ray's origin and C the variant's constant (70 AVX, 60 SSE). This sets C for the shadow traces -- and for
-   them only: sf_trace_shadow(_to), sf_trace_shadows(_to) and sf_trace_sun(_to). In their definitions "the reference's
-   ray" then reads "the reference's ray with C in place of the variant's constant in sqrtf(t / r) < C || t < 0
-   (Sphereflake.h:146, SSE :129)"; the oracle takes the same constant (sfo_set_lod_constant). C == 0 (the default) means
-   the variant's own, so a context that never calls this traces what it always traced. Renders, sf_trace_dirs_to,
-   sf_trace_rays_to, the frame-less mode and the multi-GPU paths keep the variant's constant whatever is set here.
+   them only: sf_trace_shadow(_to), sf_trace_shadows(_to), sf_trace_sun(_to) and sf_trace_suns(_to). In their
+   definitions "the reference's ray" then reads "the reference's ray with C in place of the variant's constant in
+   sqrtf(t / r) < C || t < 0 (Sphereflake.h:146, SSE :129)"; the oracle takes the same constant
+   (sfo_set_lod_constant). C == 0 (the default) means the variant's own, so a context that never calls this traces
+   what it always traced. Renders, sf_trace_dirs_to, sf_trace_rays_to, the frame-less mode and the multi-GPU paths keep
+   the variant's constant whatever is set here.
    A ray refined with C sees what a viewer (C / C_variant)^2 times nearer would: to give a light at distance D from a
    surface the detail the camera has at distance t_ref, C = C_variant sqrt(D / t_ref)
    (sphereflake_amd/lights.py: matched_lod). Synchronous (drains the context, as sf_set_variant does). SF_EINVAL for a
@@ -395,6 +396,54 @@ int sf_trace_sun(sf_ctx* ctx, const sf_sun_params* params);
    no light position, no division. params: dir, stream. sphereflake_amd/lights.py: light_model_sun. */
 int sf_light_image_sun(sf_ctx* ctx, const sf_sun_params* params, float ambient, const float* pos4, const float* nrm4,
                        const uint8_t* vis, uint8_t* rgba);
+
+/* --- many sun directions per pixel: a soft sun, a sky dome ------------------- */
+/* Extends sf_trace_sun_to from one direction to n <= SF_SUN_DIRS_MAX directions in ONE launch, as sf_trace_shadows_to
+   extends sf_trace_shadow_to: a sun with an angular size sampled at n directions inside its cone (a penumbra), or n
+   directions over the upper hemisphere as a sky-dome occlusion term of parallel rays. Each tile's wave loads its
+   positions once and loops over the directions; one 64-bit word per pixel comes out instead of n byte images. Against
+   a sky of point lights (sf_trace_shadows_to with lights.sky) every pixel and every direction gets THE SAME LEVEL OF
+   DETAIL, that of a viewer at distance tau, and with tau >= 4 no ray starts inside the radius-2 ball.
+   DEFINITION OF THE MASK (exact). Bit i (i < n) of mask[p] is 1 iff sf_trace_sun_to with dir = dirs[i] and the same
+   distance, bias, origin, sizes, position image and shadow LOD constant writes 255 at p, and 0 iff it writes 0: steps
+   1-6 of its definition apply per direction, unchanged, with f_i = s_i tau per component (one rounding, formed on the
+   host). Bits n..63 are 0. So a miss of the frame (P == 0) has its low n bits all set, and a direction that is zero
+   or not finite sets its own bit everywhere and leaves the other directions' bits alone. */
+#define SF_SUN_DIRS_MAX 64
+typedef struct sf_suns_params {
+    const float* dirs;        /* HOST, n x 3 floats, towards the sun, used as given; read before the call returns */
+    const float* weights;     /* HOST, n floats, or NULL = every weight (float)1 / (float)n; sf_light_image_suns only */
+    uint32_t n;               /* 1 .. SF_SUN_DIRS_MAX */
+    float distance;           /* tau, finite and > 0 (sf_suns_defaults: 4); one distance for all directions */
+    float bias;               /* as sf_sun_params.bias; one bias for all directions */
+    float origin[3];          /* as sf_sun_params.origin */
+    uint32_t use_origin;      /* as sf_sun_params.use_origin */
+    uint32_t width, height;   /* as sf_sun_params */
+    uint32_t max_depth;       /* 0 = 12, as sf_sun_params.max_depth */
+    void* stream;             /* NULL = the context stream */
+} sf_suns_params;
+
+/* Zeroed (n = 0, dirs NULL: the caller sets both), distance 4, the default bias of sf_shadow_defaults. */
+int sf_suns_defaults(const sf_ctx* ctx, sf_suns_params* params);
+/* As sf_trace_sun_to (pos4 DEVICE or NULL = the context's G-buffer; asynchronous and ordered as it is; no statistic and
+   none of the renders' state touched; re-traced tiles -- a tile flagged for any direction is re-traced once, for all
+   of them -- count in overflow_tiles). mask: DEVICE output, width * height uint64_t, row-major as pos4. Errors as
+   sf_trace_sun_to's, and SF_EINVAL for n == 0, n > SF_SUN_DIRS_MAX, a null dirs or a null mask. */
+int sf_trace_suns_to(sf_ctx* ctx, const sf_suns_params* params, const float* pos4, uint64_t* mask);
+/* The context's G-buffer into the context's mask buffer -- the one sf_trace_shadows writes: sf_download_shadow_masks
+   and sf_shadow_mask_buffer serve both, as the visibility buffer serves sf_trace_shadow and sf_trace_sun. */
+int sf_trace_suns(sf_ctx* ctx, const sf_suns_params* params);
+/* sf_light_image_many for sun directions: identical but for lam_i, which is sf_light_image_sun's for dirs[i]:
+   lam_i = max(0, (n.x s.x + n.y s.y) + n.z s.z) (0 where that is NaN) -- no light position, no division. Exact,
+   binary32, one rounding per operation, no fma: a frame miss is left untouched; else S = 0, then for i = 0 .. n-1 in
+   that order S = S + w_i (bit i of mask[p] ? lam_i : 0); k = ambient + (1 - ambient) S, and each of r, g, b becomes
+   (uint8) min(c k + 0.5f, 255); alpha stays. S is not clamped: with n = 1 and weight 1 the result is
+   sf_light_image_sun's, byte for byte. params: dirs, weights, n, stream. NULL pos4 / nrm4 / mask / rgba select the
+   context's G-buffer, mask buffer and image; SF_ESTATE where a context buffer selected that way was never written;
+   SF_EINVAL for an ambient outside [0, 1] or NaN, n or dirs as above, or a weight that is negative or NaN.
+   Asynchronous on the stream. sphereflake_amd/lights.py: light_model_suns; sun_cone and sky_dirs make directions. */
+int sf_light_image_suns(sf_ctx* ctx, const sf_suns_params* params, float ambient, const float* pos4,
+                        const float* nrm4, const uint64_t* mask, uint8_t* rgba);
 
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the

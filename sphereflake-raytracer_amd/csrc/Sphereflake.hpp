@@ -219,8 +219,9 @@ public:
         Check(sf_light_image_many(m_Ctx, &params, ambient, positions4, normals4, masks, rgba));
     }
 
-    // The LOD constant of the shadow traces (new; sf_set_shadow_lod, sf.h): TraceShadow, TraceShadows and TraceSun
-    // refine a node while sqrtf(t / r) < lodConstant; 0 = the variant's own (the default). Render() is not affected.
+    // The LOD constant of the shadow traces (new; sf_set_shadow_lod, sf.h): TraceShadow, TraceShadows, TraceSun and
+    // TraceSuns refine a node while sqrtf(t / r) < lodConstant; 0 = the variant's own (the default). Render() is not
+    // affected.
     void SetShadowLod(float lodConstant)
     {
         std::lock_guard<FairMutex> lk(m_Mutex);
@@ -246,6 +247,29 @@ public:
     {
         std::lock_guard<FairMutex> lk(m_Mutex);
         Check(sf_light_image_sun(m_Ctx, &params, ambient, positions4, normals4, visibility, rgba));
+    }
+    // Many sun directions per pixel in one launch (new; sf_trace_suns_to / sf_trace_suns, sf.h): a soft sun's samples
+    // or a sky dome of parallel rays. masks as TraceShadows': bit i = what TraceSun gives for params.dirs[i]. DEVICE
+    // pointers, asynchronous; positions4 null = this object's own frame.
+    void TraceSuns(const sf_suns_params& params, const float* positions4, uint64_t* masks)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_suns_to(m_Ctx, &params, positions4, masks));
+    }
+    // ... of this object's own device frame into its own mask buffer, the one TraceShadows writes
+    // (sf_download_shadow_masks, LightImageSuns)
+    void TraceSuns(const sf_suns_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_suns(m_Ctx, &params));
+    }
+    // The weighted sum of those directions' Lambert terms on the image of an SSAO::Render(), in place
+    // (sf_light_image_suns); null pointers select this object's own frame, mask buffer and image.
+    void LightImageSuns(const sf_suns_params& params, float ambient = 0.25f, const float* positions4 = nullptr,
+                        const float* normals4 = nullptr, const uint64_t* masks = nullptr, uint8_t* rgba = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_image_suns(m_Ctx, &params, ambient, positions4, normals4, masks, rgba));
     }
 
     // the device frame, downloaded into the vectors when it is newer than their contents (Refresh)

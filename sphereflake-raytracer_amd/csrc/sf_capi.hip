@@ -79,6 +79,12 @@ extern "C" __global__ void sf_trace_sun_fixup(FrameArgs a, const float* pos4, Su
 extern "C" __global__ void sf_light_image_sun_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
                                                  const uint8_t* vis, float sx, float sy, float sz, float ambient,
                                                  uint8_t* rgba);
+extern "C" __global__ void sf_trace_suns_wave(FrameArgs a, const float* pos4, SunDirs sd, uint64_t* mask,
+                                              uint32_t groups, uint32_t* overflow_list, uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_suns_fixup(FrameArgs a, const float* pos4, SunDirs sd, uint64_t* mask,
+                                               const uint32_t* overflow_list, uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_light_image_suns_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
+                                                  const uint64_t* mask, SunDirs sd, float ambient, uint8_t* rgba);
 extern "C" __global__ void sf_band_unpack(FrameArgs a, const float4* stage, uint32_t stage_rows, uint32_t band_rows,
                                            uint32_t n, uint32_t first, uint32_t members, uint32_t row0);
 extern "C" __global__ void sf_node_table(FrameArgs a, float4* table, uint32_t nodes);
@@ -1174,13 +1180,13 @@ int sf_render_to(sf_ctx* c, const sf_render_params* p, float* pos4, float* nrm4,
 }
 
 // ------------------------------------------------------------------------------------------
-// The five list traces (sf.h): sf_trace_dirs_to, sf_trace_rays_to, sf_trace_shadow_to,
-// sf_trace_shadows_to, sf_trace_sun_to. Each is a one-shot grid, one wave per group of 64 rays (an 8x8 tile of an
-// image, or 64 consecutive rays of a list), and a fixup launch behind it that re-traces the groups the waves flagged
-// (more levels needed, or a tie under the front-first order). They share one re-trace list and its counters (the
-// dirs_* fields; the calls are ordered on the context like any other pair of its calls), and read and write none of
-// the renders' state: not the overflow counters' parity, the tile order or costs, the depth hint, the timing ring or
-// the frame-less state.
+// The six list traces (sf.h): sf_trace_dirs_to, sf_trace_rays_to, sf_trace_shadow_to,
+// sf_trace_shadows_to, sf_trace_sun_to, sf_trace_suns_to. Each is a one-shot grid, one wave per group of 64 rays (an
+// 8x8 tile of an image, or 64 consecutive rays of a list), and a fixup launch behind it that re-traces the groups the
+// waves flagged (more levels needed, or a tie under the front-first order). They share one re-trace list and its
+// counters (the dirs_* fields; the calls are ordered on the context like any other pair of its calls), and read and
+// write none of the renders' state: not the overflow counters' parity, the tile order or costs, the depth hint, the
+// timing ring or the frame-less state.
 // ------------------------------------------------------------------------------------------
 
 extern "C++" {
@@ -1440,9 +1446,9 @@ int sf_probe_rays(sf_ctx* c, const float* origins3, const float* dirs3, uint32_t
     return probe_download(c, o, n, min_t, hidx, pos4, nrm4);
 }
 
-// ---- what the three shadow traces share (sf_trace_shadow_to, sf_trace_shadows_to, sf_trace_sun_to): one wave per 8x8
-// tile of a position image, the shadow traces' own constant block (sf_set_shadow_lod); they touch no statistic (not
-// the stats words, not the ray count).
+// ---- what the shadow traces share (sf_trace_shadow_to, sf_trace_shadows_to, sf_trace_sun_to, sf_trace_suns_to): one
+// wave per 8x8 tile of a position image, the shadow traces' own constant block (sf_set_shadow_lod); they touch no
+// statistic (not the stats words, not the ray count).
 
 // The position image of a shadow trace: width and height 0 mean the context's size, a null pos4 the context's own
 // G-buffer (at its size only). Checks bias and max_depth with them; every failure here is SF_EINVAL.
@@ -1699,7 +1705,8 @@ int sf_light_image_many(sf_ctx* c, const sf_shadows_params* p, float ambient, co
 }
 
 // The LOD constant of the shadow traces (sf.h): a second constant block, the context's own but for the
-// depth tables, which sf_trace_shadow_to, sf_trace_shadows_to and sf_trace_sun_to hand their kernels. No kernel knows.
+// depth tables, which sf_trace_shadow_to, sf_trace_shadows_to, sf_trace_sun_to and sf_trace_suns_to hand their
+// kernels. No kernel knows.
 int sf_set_shadow_lod(sf_ctx* c, float lod_constant)
 {
     if (!c || !(lod_constant >= 0.0f) || std::isinf(lod_constant)) return SF_EINVAL;   // (NaN fails the compare)
@@ -1760,6 +1767,85 @@ int sf_light_image_sun(sf_ctx* c, const sf_sun_params* p, float ambient, const f
     if (!c || !p) return SF_EINVAL;
     return light_image_pass(c, p->stream, ambient, pos4, nrm4, vis || c->shadow, rgba, sf_light_image_sun_px,
                             vis ? vis : (const uint8_t*)c->shadow, p->dir[0], p->dir[1], p->dir[2]);
+}
+
+// Many sun directions per pixel in one launch (kernels sf_trace_suns_wave / sf_trace_suns_fixup /
+// sf_light_image_suns_px). The launch of sf_trace_sun_to with the directions by value in the argument
+// segment; the mask buffer is sf_trace_shadows'.
+static_assert(SF_SUN_DIRS == SF_SUN_DIRS_MAX, "one mask bit per direction");
+static_assert(sizeof(FrameArgs) + sizeof(SunDirs) + 64 <= 4096, "kernel argument segment");
+
+int sf_suns_defaults(const sf_ctx* c, sf_suns_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->distance = 4.0f;
+    p->bias = kShadowBias;
+    return SF_OK;
+}
+
+// n and the directions' pointer (both calls), the weights (sf_light_image_suns)
+static int suns_check(const sf_suns_params* p, bool weights)
+{
+    if (p->n == 0u || p->n > SF_SUN_DIRS_MAX || !p->dirs) return SF_EINVAL;
+    if (weights && p->weights)
+        for (uint32_t i = 0; i < p->n; ++i)
+            if (!(p->weights[i] >= 0.0f)) return SF_EINVAL;   // (NaN fails)
+    return SF_OK;
+}
+
+// the launch's SunDirs from the parameters: read from the caller's host arrays here, before the call returns
+static void suns_args(const sf_ctx* c, const sf_suns_params* p, SunDirs* sd)
+{
+    std::memset(sd, 0, sizeof *sd);
+    shadow_origin(c, p->use_origin, p->origin, p->bias, sd->o, &sd->keep);
+    sd->n = p->n;
+    const float even = 1.0f / (float)p->n;
+    for (uint32_t i = 0; i < p->n; ++i) {
+        for (int k = 0; k < 3; ++k) {
+            sd->s[i][k] = p->dirs[3 * i + k];
+            sd->f[i][k] = p->dirs[3 * i + k] * p->distance;   // (one rounding: step 2 of sf_trace_sun_to's definition)
+        }
+        sd->w[i] = p->weights ? p->weights[i] : even;
+    }
+}
+
+int sf_trace_suns_to(sf_ctx* c, const sf_suns_params* p, const float* pos4, uint64_t* mask)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!mask) return SF_EINVAL;
+    if (int rc = suns_check(p, false)) return rc;
+    if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
+    ShadowImage im;
+    if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
+    SunDirs sd;
+    suns_args(c, p, &sd);
+    FrameArgs a = shadow_frame_args(c, im);
+    a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
+    return list_trace(
+        c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
+        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
+        [&](const ListLaunch& l) { l.wave(sf_trace_suns_wave, a, im.pos4, sd, mask); },
+        [&](const ListLaunch& l) { l.fixup(sf_trace_suns_fixup, a, im.pos4, sd, mask); });
+}
+
+int sf_trace_suns(sf_ctx* c, const sf_suns_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow_masks)) return rc;
+    return sf_trace_suns_to(c, p, nullptr, c->shadow_masks);
+}
+
+int sf_light_image_suns(sf_ctx* c, const sf_suns_params* p, float ambient, const float* pos4, const float* nrm4,
+                        const uint64_t* mask, uint8_t* rgba)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (int rc = suns_check(p, true)) return rc;
+    SunDirs sd;
+    suns_args(c, p, &sd);
+    return light_image_pass(c, p->stream, ambient, pos4, nrm4, mask || c->shadow_masks, rgba, sf_light_image_suns_px,
+                            mask ? mask : (const uint64_t*)c->shadow_masks, sd);
 }
 
 // Multi-frame persistent trace (sf.h; kernel sf_trace_frames1). One launch where every frame's own launch() would be

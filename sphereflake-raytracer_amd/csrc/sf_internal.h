@@ -220,6 +220,18 @@ struct ShadowLights {
     float w[SF_SHADOW_LIGHTS];        // their weights (sf_light_image_many; unused by the trace)
 };
 
+// Many sun directions per pixel in one launch (sf_trace_suns_to, sf_light_image_suns): the directions travel by value
+// in the kernel argument segment beside the FrameArgs (1812 B; indexed with a uniform index they are scalar loads)
+#define SF_SUN_DIRS 64u               // == SF_SUN_DIRS_MAX (sf.h): one bit of the mask word per direction
+struct SunDirs {
+    float o[3];                       // the origin the position image is relative to
+    float keep;                       // 1 - bias (sf_trace_suns_to; unused by sf_light_image_suns)
+    uint32_t n;                       // directions in use, 1..SF_SUN_DIRS
+    float f[SF_SUN_DIRS][3];          // s_i tau per component (sf_trace_suns_to; unused by sf_light_image_suns)
+    float s[SF_SUN_DIRS][3];          // the directions as given (sf_light_image_suns; unused by the trace)
+    float w[SF_SUN_DIRS];             // their weights (sf_light_image_suns; unused by the trace)
+};
+
 // Multi-frame persistent trace (round 6, sf_render_frames): the frames of one launch, passed by value in the kernel
 // argument segment (copied by the runtime at the launch, so the host may build the next batch at once; 4 KB at most:
 // 11 FrameArgs). Frame f is one slot context's view into that context's G-buffer and stats. All frames share one

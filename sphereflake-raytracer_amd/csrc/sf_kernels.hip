@@ -3454,7 +3454,7 @@ extern "C" __global__ __launch_bounds__(64) void sf_fixup_wave(FrameArgs a, cons
 // ------------------------------------------------------------------------------------------
 namespace {
 
-// ---- what the groups of the five list traces (this section and the four after it) share
+// ---- what the groups of the six list traces (this section and the five after it) share
 
 // The lane's ray of a group. A lane past the end of the list or off the image edge takes the nearest ray inside (a
 // real direction for the wave's cone) and traverses as an invalid lane: no load or store beyond the last ray.
@@ -3551,7 +3551,7 @@ __device__ __forceinline__ TileStats group_stats(int32_t maxd, float closest, bo
     return st;
 }
 
-// The shadow ray of the three shadow traces, from the surface point w and the ray's origin l (the
+// The shadow ray of the shadow traces, from the surface point w and the ray's origin l (the
 // light): d = (w - l) + 0, len = sqrt((d.x d.x + d.y d.y) + d.z d.z), bound = len keep, d normalised -- every
 // operation rounded on its own, in this order: the bits are the contract.
 // (__builtin_sqrtf is the correctly rounded square root under the build's -fhip-fp32-correctly-rounded-divide-sqrt,
@@ -3597,7 +3597,7 @@ enum class RootStage {
     InGroup,    // not at all: the group stages what it needs itself
 };
 
-// The body of the five fixup kernels (as sf_fixup_wave): re-trace counters[parity] groups of `overflow_list` with
+// The body of the six fixup kernels (as sf_fixup_wave): re-trace counters[parity] groups of `overflow_list` with
 // group_fn(group, bcol), one block at a time over the list; zero the next trace's counter and add this trace's to
 // counters[2], the re-traced groups sf_get_stats reports. STATS: group_fn returns the group's TileStats, published as
 // the renders' are (the shadow traces touch no statistic). (`a` by value: through a reference, sf_trace_rays_fixup
@@ -4295,6 +4295,90 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_sun_fixup(FrameArgs a,
                                          [&](uint32_t group, const float4 bcol) {
         trace_sun_group<true>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, bcol, group, SF_MAX_LEVELS,
                               nullptr, nullptr);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Many sun directions per pixel in one launch (sf_trace_suns_to): a soft sun, a sky dome of parallel
+// rays. Bit i of mask[p] is what sf_trace_sun_wave writes for direction i at p (1 = 255, 0 = 0), bits n..63 are 0. The
+// lane's position is loaded and w = o + P formed once; per direction (a uniform index, the f_i = s_i tau are scalar
+// loads from the argument segment) F, d, bound and the lane's root centre are formed as in trace_sun_group and
+// traverse_mixed runs in its any-hit mode, unchanged, on the axis columns staged once. A tile with no surface pixel
+// traces nothing; a direction that leaves no lane on (zero or not finite) is skipped and keeps its bit. A tile flagged
+// for any direction goes onto the overflow list once and is re-traced for all of them.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+template <bool FIXUP>
+__device__ __forceinline__ void trace_suns_group(const FrameArgs& a, const float4* __restrict__ pos4,
+                                                 const SunDirs& sd, uint64_t* __restrict__ mask,
+                                                 float* __restrict__ L, const float4 bcol, uint32_t group,
+                                                 uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const GroupLane g = tile_lane(a, group);
+    const float4 P = pos4[g.ray];
+    const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    const uint32_t n = sd.n;   // (uniform, 1..64)
+    uint64_t shadowed = 0ull;   // bit i: direction i's ray to the lane's pixel is stopped
+    uint32_t status = 0u;
+    if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss: every direction's bit is set)
+        const float wx = __fadd_rn(sd.o[0], P.x), wy = __fadd_rn(sd.o[1], P.y), wz = __fadd_rn(sd.o[2], P.z);
+        const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;   // (the mixed traversal has no cone and no order)
+        float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0u; i < n; ++i) {
+            const float Fx = __fadd_rn(wx, sd.f[i][0]), Fy = __fadd_rn(wy, sd.f[i][1]), Fz = __fadd_rn(wz, sd.f[i][2]);
+            float dx, dy, dz, bound;
+            shadow_ray(wx, wy, wz, Fx, Fy, Fz, sd.keep, K->lut, dx, dy, dz, bound);
+            // the lane's root centre (Sphereflake.cpp:83 at F)
+            const float rx = __fsub_rn(0.0f, Fx), ry = __fsub_rn(0.0f, Fy), rz = __fsub_rn(0.0f, Fz);
+            // finiteness depends on the direction: one that is zero or not finite leaves no lane on
+            const bool on = surface && finite3(dx, dy, dz);
+            if (wave_ballot(on) == 0ull) continue;   // (uniform)
+            HitState h;
+            h.hit = false;
+            int32_t md = -1;
+            uint32_t st = 0u;
+            lds_fence();   // (the direction before, or the re-trace's earlier tile, has read its tables)
+            traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, st, culls, bound);
+            status |= st;
+            shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
+        }
+    }
+    // (uniform) more levels needed for some direction: once on the list
+    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);
+    // a tile row is 64 contiguous bytes: one 8-byte vector store per valid lane
+    const uint64_t all = n >= 64u ? ~0ull : (1ull << n) - 1ull;
+    if (g.valid) mask[(size_t)g.y * a.W + g.x] = all & ~shadowed;
+}
+
+}  // namespace
+
+// One tile per one-wave workgroup, dynamic LDS SF_LDS_RAYS_FLOATS(a.max_depth) (the launch of sf_trace_sun_wave).
+// Touches none of the context's statistics.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_wave(FrameArgs a, const float* pos4, SunDirs sd,
+                                                                    uint64_t* mask, uint32_t groups,
+                                                                    uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    stage_root(lds, a.root);
+    trace_suns_group<false>(a, reinterpret_cast<const float4*>(pos4), sd, mask, lds, build_column(a.consts), blockIdx.x,
+                            a.max_depth, overflow_list, overflow_count);
+}
+
+// Re-trace of the flagged tiles, for every direction, at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and
+// counters). The mixed traversal reads the root image's columns and never writes it: staged once.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_fixup(FrameArgs a, const float* pos4, SunDirs sd,
+                                                                     uint64_t* mask, const uint32_t* overflow_list,
+                                                                     uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
+                                         [&](uint32_t group, const float4 bcol) {
+        trace_suns_group<true>(a, reinterpret_cast<const float4*>(pos4), sd, mask, lds, bcol, group, SF_MAX_LEVELS,
+                               nullptr, nullptr);
     });
 }
 

@@ -426,3 +426,33 @@ extern "C" __global__ void __launch_bounds__(256) sf_light_image_many_px(uint32_
     c.z = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.z, k), 0.5f), 255.0f);
     reinterpret_cast<uchar4*>(rgba)[px] = c;
 }
+
+// The same for many sun directions (sf_light_image_suns, sf.h): sf_light_image_many_px's sum with
+// lam_i sf_light_image_sun_px's lam for direction i -- no light position, no length, no division. The directions and
+// weights are scalar loads from the argument segment. sphereflake_amd/lights.py (light_model_suns) restates it
+// (tests/test_gpu_suns.py).
+extern "C" __global__ void __launch_bounds__(256) sf_light_image_suns_px(uint32_t W, uint32_t H, const float* pos4,
+                                                                      const float* nrm4, const uint64_t* mask,
+                                                                      SunDirs sd, float ambient, uint8_t* rgba)
+{
+    const uint32_t px = blockIdx.x * 256u + threadIdx.x;
+    if (px >= W * H) return;
+    const float4 P = ld4(pos4, px);
+    if (P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) return;   // a miss of the frame (post_final.glsl:20)
+    const float4 n = ld4(nrm4, px);
+    const uint64_t m = mask[px];
+    float S = 0.0f;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0u; i < sd.n; ++i) {
+        const float sx = sd.s[i][0], sy = sd.s[i][1], sz = sd.s[i][2];
+        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(n.x, sx), __fmul_rn(n.y, sy)), __fmul_rn(n.z, sz));
+        const float lam = fmaxf(0.0f, dot);   // (a NaN product gives 0)
+        S = __fadd_rn(S, __fmul_rn(sd.w[i], ((m >> i) & 1ull) ? lam : 0.0f));
+    }
+    const float k = __fadd_rn(ambient, __fmul_rn(__fsub_rn(1.0f, ambient), S));
+    uchar4 c = reinterpret_cast<uchar4*>(rgba)[px];
+    c.x = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.x, k), 0.5f), 255.0f);
+    c.y = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.y, k), 0.5f), 255.0f);
+    c.z = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.z, k), 0.5f), 255.0f);
+    reinterpret_cast<uchar4*>(rgba)[px] = c;
+}

@@ -88,6 +88,16 @@ class sf_sun_params(ctypes.Structure):
                 ("height", ctypes.c_uint32), ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
 
 
+SF_SUN_DIRS_MAX = 64
+
+
+class sf_suns_params(ctypes.Structure):
+    _fields_ = [("dirs", ctypes.POINTER(ctypes.c_float)), ("weights", ctypes.POINTER(ctypes.c_float)),
+                ("n", ctypes.c_uint32), ("distance", ctypes.c_float), ("bias", ctypes.c_float),
+                ("origin", ctypes.c_float * 3), ("use_origin", ctypes.c_uint32), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
 class sf_stats(ctypes.Structure):
     _fields_ = [("max_depth", ctypes.c_int32), ("closest", ctypes.c_float),
                 ("rays", ctypes.c_int64), ("overflow_tiles", ctypes.c_int64)]
@@ -149,6 +159,11 @@ SIGNATURES = {
     "sf_trace_sun": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_sun_params)]),
     "sf_light_image_sun": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_sun_params), ctypes.c_float, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_suns_defaults": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_suns_params)]),
+    "sf_trace_suns_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_suns_params), ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_suns": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_suns_params)]),
+    "sf_light_image_suns": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_suns_params), ctypes.c_float, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_render_frames": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
                                         ctypes.POINTER(sf_render_params)]),
     "sf_slab_rows": (ctypes.c_uint32, [ctypes.c_uint32] * 4),
@@ -843,10 +858,10 @@ class Sphereflake:
                                "sf_trace_shadow", pos, out)
 
     def _trace_vis(self, params, entry, pos, out, dtype=np.uint8):
-        """The `pos` / `out` forms of trace_shadow(), trace_shadows() and trace_sun(): params(width, height) makes the
-        call's parameter block, or (block, the host arrays it points into, kept alive until the call has returned);
-        `entry` names the call into the context's own buffer, `entry`_to the one into a caller's; `dtype` is the
-        result's per pixel."""
+        """The `pos` / `out` forms of trace_shadow(), trace_shadows(), trace_sun() and trace_suns(): params(width,
+        height) makes the call's parameter block, or (block, the host arrays it points into, kept alive until the call
+        has returned); `entry` names the call into the context's own buffer, `entry`_to the one into a caller's;
+        `dtype` is the result's per pixel."""
         to, own = getattr(lib(), entry + "_to"), getattr(lib(), entry)
 
         def make(W, H):
@@ -988,10 +1003,10 @@ class Sphereflake:
 
     # the shadow traces' level of detail, shadows from a directional light (sf_set_shadow_lod, sf_trace_sun_to) -------
     def set_shadow_lod(self, lod_constant):
-        """trace_shadow(), trace_shadows() and trace_sun() refine a node while sqrtf(t / r) < lod_constant instead of
-        the variant's 70 / 60; 0 restores the variant's own (the default). Nothing else is affected: Render(),
-        trace_dirs() and trace_rays() keep the variant's constant. sphereflake_amd.lights.matched_lod picks a value.
-        Synchronous."""
+        """trace_shadow(), trace_shadows(), trace_sun() and trace_suns() refine a node while sqrtf(t / r) < lod_constant
+        instead of the variant's 70 / 60; 0 restores the variant's own (the default). Nothing else is affected:
+        Render(), trace_dirs() and trace_rays() keep the variant's constant. sphereflake_amd.lights.matched_lod picks a
+        value. Synchronous."""
         with self._mutex:
             _check(lib().sf_set_shadow_lod(self._ctx, float(lod_constant)), "sf_set_shadow_lod", self._ctx)
 
@@ -1030,6 +1045,60 @@ class Sphereflake:
         with self._mutex:
             _check(lib().sf_light_image_sun(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
                                             vp(vis_ptr), vp(rgba_ptr)), "sf_light_image_sun", self._ctx)
+
+    # many sun directions per pixel in one launch (sf_trace_suns_to / sf_trace_suns / sf_light_image_suns) ----------
+    def suns_params(self, dirs, weights=None, distance=None, bias=None, origin=None, width=0, height=0, max_depth=0,
+                    stream=None):
+        """sf_suns_defaults, overridden: (params, keepalive). dirs [n, 3], weights [n] or None; distance and bias None
+        keep the library's defaults (4, 2^-10). The host arrays the params point into are in `keepalive` and must
+        outlive the call they are passed to."""
+        D = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
+        n = D.shape[0]
+        if not 1 <= n <= SF_SUN_DIRS_MAX:
+            raise ValueError(f"1..{SF_SUN_DIRS_MAX} directions per call, not {n}")
+        p = sf_suns_params()
+        _check(lib().sf_suns_defaults(self._ctx, ctypes.byref(p)), "sf_suns_defaults")
+        p.dirs = D.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        wts = None
+        if weights is not None:
+            wts = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+            if wts.shape[0] != n:
+                raise ValueError("one weight per direction")
+            p.weights = wts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        p.n = n
+        if distance is not None:
+            p.distance = float(distance)
+        if bias is not None:
+            p.bias = float(bias)
+        if origin is not None:
+            p.origin[:] = [float(x) for x in _f32(origin, 3)]
+            p.use_origin = 1
+        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
+        return p, (D, wts)
+
+    def trace_suns(self, dirs, distance=None, bias=None, pos=None, out=None, origin=None, max_depth=0, stream=None):
+        """Which of up to 64 sun directions `dirs` [n, 3] (each TOWARDS the sun, world, used as given) reach each pixel
+        of a position image, in one launch: a uint64 per pixel, bit i = 1 where trace_sun(dirs[i]) with the same
+        distance and bias gives 255 (lit, or a miss of the frame), 0 where it gives 0; bits n..63 are 0 (sf.h).
+        sphereflake_amd.lights.sun_cone samples a sun with an angular size, sky_dirs a sky dome. `pos`, `out` and
+        `origin` as trace_shadows'; the context's mask buffer is the one trace_shadows() writes
+        (download_shadow_masks(), light_image_suns() see it)."""
+        return self._trace_vis(
+            lambda W, H: self.suns_params(dirs, None, distance, bias, origin, W, H, max_depth, stream),
+            "sf_trace_suns", pos, out, np.uint64)
+
+    def light_image_suns(self, dirs, weights=None, ambient=0.25, pos_ptr=0, nrm_ptr=0, mask_ptr=0, rgba_ptr=0,
+                         stream=None):
+        """Scale the image of PostProcess() in place by ambient + (1 - ambient) x sum_i w_i (lit_i ? max(0, n . dirs[i])
+        : 0) over the directions (sf_light_image_suns; sphereflake_amd.lights.light_model_suns). weights None: 1 / n
+        each. Pointers are device addresses, 0 = the context's G-buffer, mask buffer (trace_suns()) and image.
+        Asynchronous."""
+        p, keep = self.suns_params(dirs, weights, None, None, None, 0, 0, 0, stream)
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        with self._mutex:
+            _check(lib().sf_light_image_suns(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
+                                             vp(mask_ptr), vp(rgba_ptr)), "sf_light_image_suns", self._ctx)
+        del keep
 
     def Synchronize(self):
         _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)

@@ -11,7 +11,9 @@ the light's: a node refines by its distance from the light, so a far light casts
 
 A directional light (``Sphereflake.trace_sun`` / ``light_image_sun``: sun_model, light_model_sun, sun_direction)
 starts every pixel's ray a fixed distance up the sun direction from its own surface point instead, and
-``Sphereflake.set_shadow_lod`` with matched_lod chooses the level of detail of all the shadow traces.
+``Sphereflake.set_shadow_lod`` with matched_lod chooses the level of detail of all the shadow traces. Many such
+directions in one launch (``Sphereflake.trace_suns`` / ``light_image_suns``: sun_cone, sky_dirs, suns_model,
+light_model_suns) make a sun with an angular size or a sky dome of parallel rays.
 """
 from __future__ import annotations
 
@@ -252,18 +254,106 @@ def sky(n, radius=4.0, up=(0.0, 0.0, 1.0)):
     In float64 z_i = (i + 0.5) / n along `up`, s_i = sqrt(1 - z_i^2), theta_i = i pi (3 - sqrt 5), point
     radius (s_i cos(theta_i) e1 + s_i sin(theta_i) e2 + z_i up) with e1, e2 completing `up` to a right-handed
     frame; float32 [n, 3]. Deterministic."""
-    n = _count(n)
-    w = np.asarray(up, np.float64).reshape(3)
-    if not np.linalg.norm(w) > 0:
-        raise ValueError("up must not be zero")
-    w = w / np.linalg.norm(w)
+    return (float(radius) * _hemisphere(n, up)).astype(_F)
+
+
+def _frame(axis, what):
+    """float64 (e1, e2, w): w along `axis`, e1 and e2 completing it to a right-handed frame."""
+    w = np.asarray(axis, np.float64).reshape(3)
+    norm = np.linalg.norm(w)
+    if not (np.isfinite(norm) and norm > 0):
+        raise ValueError(f"{what} must be finite and not zero")
+    w = w / norm
     t = np.array((1.0, 0.0, 0.0)) if abs(w[0]) < 0.9 else np.array((0.0, 1.0, 0.0))
     e1 = t - w * np.dot(t, w)
     e1 = e1 / np.linalg.norm(e1)
-    e2 = np.cross(w, e1)
+    return e1, np.cross(w, e1), w
+
+
+def _hemisphere(n, up):
+    """sky()'s points at radius 1, float64 [n, 3]."""
+    n = _count(n)
+    e1, e2, w = _frame(up, "up")
     i = np.arange(n, dtype=np.float64)
     z = (i + 0.5) / n
     s = np.sqrt(1.0 - z * z)
     th = i * _GOLDEN
-    pts = float(radius) * ((s * np.cos(th))[:, None] * e1 + (s * np.sin(th))[:, None] * e2 + z[:, None] * w)
-    return pts.astype(_F)
+    return (s * np.cos(th))[:, None] * e1 + (s * np.sin(th))[:, None] * e2 + z[:, None] * w
+
+
+# --- many sun directions per pixel (sf_trace_suns_to, sf_light_image_suns) ----------------------------------------
+def _unit32(v):
+    return (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(_F)
+
+
+def sun_cone(direction, half_angle, n):
+    """n unit directions inside the cone of `half_angle` (radians, 0 <= half_angle < pi / 2) about `direction`: the
+    samples of a sun with an angular size, the `dirs` of trace_suns. A Vogel disc on the cone's cap, in float64: with
+    (e1, e2, a) the frame of sky() about a = direction / |direction|, alpha_i = half_angle sqrt((i + 0.5) / n) (the
+    first directions are nearest the axis), theta_i = i pi (3 - sqrt 5), direction cos(alpha_i) a + sin(alpha_i)
+    (cos(theta_i) e1 + sin(theta_i) e2), normalised; float32 [n, 3]. Deterministic."""
+    n = _count(n)
+    half_angle = float(half_angle)
+    if not 0.0 <= half_angle < np.pi / 2:
+        raise ValueError("half_angle must be in [0, pi / 2) radians")
+    e1, e2, a = _frame(direction, "the sun direction")
+    i = np.arange(n, dtype=np.float64)
+    al = half_angle * np.sqrt((i + 0.5) / n)
+    th = i * _GOLDEN
+    v = np.cos(al)[:, None] * a + (np.sin(al) * np.cos(th))[:, None] * e1 + (np.sin(al) * np.sin(th))[:, None] * e2
+    return _unit32(v)
+
+
+def sky_dirs(n, up=(0.0, 0.0, 1.0)):
+    """n unit directions over the upper hemisphere about `up`: sky()'s points, normalised (in float64, then rounded);
+    float32 [n, 3]. The `dirs` of trace_suns for a sky dome of parallel rays: every pixel gets the same level of
+    detail, whereas a sky() point light refines by its own distance from each node. Deterministic."""
+    return _unit32(_hemisphere(n, up))
+
+
+def suns_model(pos4, origin, dirs, distance, bias):
+    """sun_model per direction, stacked: (F [n, ..., 3], d [n, ..., 3], bound [n, ...], is_surface [...]) for the
+    directions dirs [n, 3] -- slice i is sun_model(pos4, origin, dirs[i], distance, bias), bit for bit."""
+    D = np.asarray(dirs, _F).reshape(-1, 3)
+    parts = [sun_model(pos4, origin, D[i], distance, bias) for i in range(_count(D.shape[0]))]
+    return (np.stack([p[0] for p in parts]), np.stack([p[1] for p in parts]), np.stack([p[2] for p in parts]),
+            parts[0][3])
+
+
+def light_model_suns(rgba, pos4, nrm4, mask, dirs, weights=None, ambient=0.25):
+    """What sf_light_image_suns makes of the RGBA8 image `rgba` [..., 4]: a new uint8 array. mask [...] are the words
+    of trace_suns for the same directions dirs [n, 3]; weights [n] (None: float32(1) / float32(n) each).
+
+    light_model_many with light_model_sun's lam: a miss pixel stays; else S = 0, then for i = 0 .. n-1 in that order
+    S = S + w_i (bit i ? lam_i : 0) with lam_i = max(0, (n.x s.x + n.y s.y) + n.z s.z) (0 where that is NaN) for
+    s = dirs[i], k = ambient + (1 - ambient) S (S is not clamped), and each of r, g, b becomes
+    uint8(min(c k + 0.5, 255)); alpha stays."""
+    a = _F(ambient)
+    if not 0.0 <= float(a) <= 1.0:
+        raise ValueError("ambient must be in [0, 1]")
+    D = np.asarray(dirs, _F).reshape(-1, 3)
+    n = _count(D.shape[0])
+    if weights is None:
+        w = np.full(n, _F(1.0) / _F(n), _F)
+    else:
+        w = np.asarray(weights, _F).reshape(-1)
+        if w.shape[0] != n or not (w >= 0).all():
+            raise ValueError("one weight per direction, none negative or NaN")
+    out = np.array(rgba, np.uint8, copy=True)
+    P = np.asarray(pos4, _F)[..., :3]
+    nr = np.asarray(nrm4, _F)[..., :3]
+    mask = np.asarray(mask, np.uint64)
+    S = np.zeros(P.shape[:-1], _F)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in range(n):
+            s = D[i]
+            dot = (nr[..., 0] * s[0] + nr[..., 1] * s[1]) + nr[..., 2] * s[2]
+            lam = np.fmax(_F(0.0), dot)
+            bit = ((mask >> np.uint64(i)) & np.uint64(1)) != 0
+            S = S + w[i] * np.where(bit, lam, _F(0.0)).astype(_F)
+        k = a + (_F(1.0) - a) * S
+        rgb = np.fmin(out[..., :3].astype(_F) * k[..., None] + _F(0.5), _F(255.0))
+    assert S.dtype == _F and rgb.dtype == _F
+    surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
+    out[..., :3] = np.where(surface[..., None], rgb.astype(np.uint8), out[..., :3])
+    return out
