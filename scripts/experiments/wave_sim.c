@@ -113,6 +113,15 @@ typedef struct {
     long long fold_exp[NST], fold_iter[NST];   /* ... whose visiting lanes share no hardware lane between the two tiles */
     long long root_a[NST], root_b[NST], root_d[NST];   /* roots of such subtrees: tile A only, B only, both (disjoint) */
     long long side_iter[NST], side_lod[NST];   /* two-ray iterations with bounding hits in one tile only; passing LOD */
+    /* leaf-level nodes (every child the cone cull kept is an inline leaf; the kernel's leaf_children), by the node's
+     * depth: the nodes, their child iterations, those whose bounding sphere some visiting lane hits, those entered,
+     * those whose own sphere some visiting lane hits, those entered whose own sphere some entering lane hits; the
+     * nodes that keep the child loop -- their children's depth is not yet counted in the unit's max depth (the model
+     * has no depth seed: the kernel with the seed off), or their level is not provisioned (LEVELS, default all) --,
+     * the nodes entered from the two-ray loop by some hardware lane with both rays (they keep the child loop too), and
+     * the leaf children of nodes that are not leaf-level (mixed nodes) */
+    long long lf_node[NST], lf_iter[NST], lf_hit[NST], lf_ent[NST], lf_own[NST], lf_ent_own[NST];
+    long long lf_old[NST], lf_two[NST], lf_mixed[NST], lf_empty[NST];   /* (lf_empty: leaf-level nodes with no child kept) */
 } sim_stats_t;
 
 typedef struct {
@@ -318,6 +327,15 @@ static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, lmask_t
         if (skip && culled[i]) st->skip_lost[d]++;
         if (skip && (S->mode & 2)) culled[i] = 0;
     }
+    int leaf_level = 1, nleaf = 0, nkept = 0;
+    for (int i = 0; i < 9; ++i) if (!culled[i]) { nkept++; if (leaf[i]) nleaf++; else leaf_level = 0; }
+    if (leaf_level) {
+        st->lf_node[d]++;
+        st->lf_empty[d] += nkept == 0;   /* (no child kept: nothing that could raise the max depth) */
+        const int levels = getenv("LEVELS") ? atoi(getenv("LEVELS")) : NST;
+        if ((nkept && dc > S->maxd) || dc >= levels) st->lf_old[d]++;
+        else if (!fold && !saved_fold && d > 0) st->lf_two[d]++;
+    } else st->lf_mixed[d] += nleaf;
     int order[18], n = 0;
     for (int i = 0; i < 9; ++i) if (!culled[i] && front[i]) order[n++] = i;
     for (int i = 0; i < 9; ++i) if (!culled[i] && !front[i]) order[n++] = i;
@@ -331,18 +349,24 @@ static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, lmask_t
         st->fold_iter[d] += fold;
         SIM_WORK(1.0);
         st->act[d] += lm_pop(A);
-        lmask_t hb = 0, ex = 0;
+        lmask_t hb = 0, ex = 0, own = 0;
         for (int l = 0; l < NL; ++l) {
             if (!((A >> l) & 1)) continue;
             const float* D = S->D[l];
             float tca = (C[0] * D[0] + C[1] * D[1]) + C[2] * D[2];
             float d2 = cc[c] - tca * tca;
+            if (tca >= 0.0f && d2 <= S->r2s[dc]) own |= LM1 << l;
             if (!(tca >= 0.0f && d2 <= S->r2b[dc])) continue;
             hb |= LM1 << l;
             float t = near_root_f(tca, d2, S->r2b[dc]);
             if (t < S->T[dc]) ex |= LM1 << l;
         }
         st->hitl[d] += lm_pop(hb);
+        if (leaf_level) {
+            st->lf_iter[d]++;
+            st->lf_hit[d] += hb != 0;
+            st->lf_own[d] += own != 0;
+        }
 #if TW == 16 && TH == 8
         if (!fold && hb && (lm_tile_lanes(hb, 0) == 0 || lm_tile_lanes(hb, 1) == 0)) {
             st->side_iter[d]++;
@@ -363,6 +387,10 @@ static void expand_node(wsim_t* S, const float* M, int d, uint64_t node, lmask_t
         }
         if (!am) { st->occlnone[d]++; continue; }
         st->entered[d]++;
+        if (leaf_level) {
+            st->lf_ent[d]++;
+            st->lf_ent_own[d] += (own & am) != 0;
+        }
         const uint64_t id = 9 * node + 1 + (uint64_t)c;
         self_test(S, C, cc[c], dc, id, am);
         if (leaf[c]) { st->leaf[d]++; continue; }

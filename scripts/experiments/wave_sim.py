@@ -26,7 +26,8 @@ NST = 32
 FIELDS = ["exp", "iter", "miss", "lodnone", "occlnone", "entered", "leaf", "push", "act", "hitl"]
 TAIL = ["tiles", "mismatch", "ties", "maxd"]
 EXTRA = ["cone_tested", "cone_culled", "skip_exp", "skip_lost", "cache_hit", "half_exp", "half_iter", "fold_exp", "fold_iter",
-         "root_a", "root_b", "root_d", "side_iter", "side_lod"]
+         "root_a", "root_b", "root_d", "side_iter", "side_lod",
+         "lf_node", "lf_iter", "lf_hit", "lf_ent", "lf_own", "lf_ent_own", "lf_old", "lf_two", "lf_mixed", "lf_empty"]
 
 
 class Stats(ctypes.Structure):
@@ -94,6 +95,13 @@ def report(t, label=""):
     tot = lambda f: int(t[f].sum()) * sc
     print(f"all {tot('exp'):8d} {tot('iter'):8d} {tot('miss'):7d} {tot('lodnone'):7d} {tot('occlnone'):7d} {tot('entered'):7d}"
           f" {tot('leaf'):7d} {tot('push'):7d} {t['act'].sum()/max(t['iter'].sum(),1):6.1f}")
+    print("leaf-level nodes (every kept child an inline leaf), by the node's depth")
+    print(" d    nodes  of-exp   child-iter  of-iter  bound-hit  entered  own-hit  ent+own  old-path  two-ray  mixed-lvs  no-child")
+    lf = ["lf_node", "exp", "lf_iter", "iter", "lf_hit", "lf_ent", "lf_own", "lf_ent_own", "lf_old", "lf_two", "lf_mixed", "lf_empty"]
+    for d in range(NST):
+        if t["exp"][d]:
+            print(f"{d:2d} " + " ".join(f"{t[f][d]*sc:9d}" for f in lf))
+    print("all " + " ".join(f"{tot(f):9d}" for f in lf))
     if TW * TH > 64:   # a unit of more than one tile: what of it is visited by lanes of one 8x8 tile only
         print(f"unit {TW}x{TH}: visited by lanes of one 8x8 tile only")
         print(" d  exp-one-half    of     iter-one-half    of")

@@ -41,8 +41,8 @@ def main():
         print(f"  lane utilisation: active lanes/iteration {ph[5] / it:.2f} of 64, bounding-hit lanes/iteration "
               f"{ph[6] / it:.2f}; active lanes/expanded node {ph[7] / max(ph[0], 1):.2f}; inline leaf tests "
               f"{ph[8] / per:.0f} with {ph[9] / max(ph[8], 1):.2f} active lanes")
-        print(f"  iterations at depth >= 4: {ph[10] / it:.3f} of all, {ph[11] / max(ph[10], 1):.2f} active lanes; "
-              f"iterations with <= 32 active lanes: {ph[14] / it:.3f}; occlusion-checked entries {ph[13] / per:.0f}, "
+        print(f"  leaf-level nodes taken by leaf_children: {ph[10] / per:.0f} of the nodes tested, their children "
+              f"{ph[11] / per:.0f} (not among the child iterations); iterations with <= 32 active lanes: {ph[14] / it:.3f}; occlusion-checked entries {ph[13] / per:.0f}, "
               f"wholly culled {ph[12] / per:.0f}; waves {ph[15] / per:.0f}")
     elif ph.sum() > 0:
         # traverse_ray's stamps: 0 = back at the loop head (a child whose bounding/LOD test no lane passed, an inline

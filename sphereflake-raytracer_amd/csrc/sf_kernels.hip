@@ -388,8 +388,10 @@ __device__ __forceinline__ void wave_atomic_add_u64(uint64_t* p, uint64_t v)
 // phase_sums[k]: 0 nodes whose children are tested, 1 child-loop iterations, 2 iterations no lane
 // hits (bounding), 3 children entered, 4 leaf skips; lane utilisation: 5 active lanes summed over
 // child-loop iterations, 6 bounding-hit lanes summed over them, 7 active lanes summed over expanded
-// nodes, 8 inline leaf self tests, 9 their active lanes, 10 child-loop iterations at node depth >= 4,
-// 11 their active lanes, 12/13/14 iterations with <= 4 / <= 16 / <= 32 active lanes, 15 waves traced.
+// nodes, 8 inline leaf self tests, 9 their active lanes, 10 leaf-level nodes that took leaf_children (they are
+// among 0, and neither pushed nor popped), 11 their children (tested by leaf_children: not among 1),
+// 12 entries the occlusion cull left no lane for, 13 occlusion culls run, 14 iterations with <= 32 active lanes,
+// 15 waves traced.
 #define SF_STAMP_DECL uint64_t ph_sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
 #define SF_STAMP(k)
 #define SF_COUNT(k, v) (ph_sum[k] += (v))
@@ -668,13 +670,14 @@ __device__ __forceinline__ bool child_expands(float cx, float cy, float cz, floa
 // accepting lane only gets its finished flag (h.depth >= 0); a tie is not `<`: never accepted, never flagged.
 // INDEX_ORDER (traverse_mixed): the children are always entered in index order, nothing is ever flagged, and the tie
 // rule is applied without a branch of its own.
+// accept_hits: the accept part alone, for the lanes of hsm (not empty), which hit the sphere (leaf_children forms the
+// hit mask itself, before the LOD and occlusion tests).
 template <bool ANYHIT, bool INDEX_ORDER = false>
-__device__ __forceinline__ uint64_t accept_self(HitState& h, uint64_t& ancm, uint32_t& status, bool flag_ties,
-                                                const float4 pc, float tca, float d2, uint32_t dd, float actv,
+__device__ __forceinline__ uint64_t accept_hits(HitState& h, uint64_t& ancm, uint32_t& status, bool flag_ties,
+                                                const float4 pc, float tca, float d2, uint32_t dd, uint64_t hsm,
                                                 uint32_t idx, float R2s)
 {
-    const uint64_t hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);
-    if (hsm) {
+    {
         // (the general correctly rounded root only when a hitting lane's argument is tiny: a uniform branch)
         const float xs = R2s - d2;
         float ts;
@@ -705,6 +708,14 @@ __device__ __forceinline__ uint64_t accept_self(HitState& h, uint64_t& ancm, uin
         ancm |= accm;
         return accm;
     }
+}
+template <bool ANYHIT, bool INDEX_ORDER = false>
+__device__ __forceinline__ uint64_t accept_self(HitState& h, uint64_t& ancm, uint32_t& status, bool flag_ties,
+                                                const float4 pc, float tca, float d2, uint32_t dd, float actv,
+                                                uint32_t idx, float R2s)
+{
+    const uint64_t hsm = wave_ballot(__builtin_fminf(__builtin_fminf(tca, R2s - d2), actv) >= 0.0f);
+    if (hsm) return accept_hits<ANYHIT, INDEX_ORDER>(h, ancm, status, flag_ties, pc, tca, d2, dd, hsm, idx, R2s);
     return 0ull;
 }
 
@@ -728,6 +739,91 @@ __device__ __forceinline__ uint64_t occluded(float tca, float minT, float cull_t
     float v = tca - minT;
     if constexpr (!ANYHIT) v = __builtin_fminf(v, tca - cull_t);
     return wave_ballot(v - SF_OCCL_MARGIN * tca > cull_r);
+}
+
+// ---- The children of a leaf-level node: a node whose children (those the cone cull kept, entry order in Cl, their
+// {centre, cc} in table tb, depth dd, constants dc / dk = the depth's eight words, child 0's heap index idx0) are all
+// inline leaves (ChildBuild::leaf_level), for the lanes of avx (+inf on the lanes visiting the node, -1 elsewhere).
+// Three fifths of a frame's child iterations sit at such nodes. The only thing a leaf child can change is a lane's
+// hit, through its own sphere (radius r inside the bounding ball 2r), so the node is not opened: no push, no pop, the
+// depth's constants loaded once, and per child the own sphere first -- a child whose sphere no visiting lane hits ends
+// there (one compare), where the child loop takes it through LOD, the occlusion cull and the self test for its
+// bounding hit alone. Then LOD and the occlusion cull for the lanes that hit, and the accept.
+// Bit for bit the child loop's results:
+//  - An own hit is a bounding hit, exactly: R2s < R2b, and with denormals kept fl(a - b) >= 0 exactly when b <= a, so
+//    R2s - d2 >= 0 implies R2b - d2 >= 0 (tca >= 0 and the visiting lanes are the same operands in both compares).
+//  - lod_expands decides per lane: a lane's result is its reference decision t < T whichever other lanes are in the
+//    mask; the uniform shortcuts only choose how it is computed. So the lanes that hit the own sphere get here the
+//    decision they get there.
+//  - The occlusion cull is per lane too, and an occluded lane accepts nothing either way (its condition is strict).
+//  So a lane reaches the accept for a leaf child here exactly when it does in the child loop (own hit, bounding hit,
+//  LOD, not occluded), with the same tca, d2, root form (accept_hits) and tie rule; the children come in the same
+//  entry order, so the tie flags are the same; leaves never overflow, so status is.
+//  - ancm: a finished leaf clears the lanes whose best is at its depth. Lanes of ancm have their best at an ancestor
+//    of the open node, i.e. above the leaf's depth, except those that have just accepted the leaf: ancm &= ~accepted.
+//  - The max-depth statistic is the caller's part: the child loop raises maxd when some lane passes bounding + LOD,
+//    own hit or not. The caller takes this loop only where depth dd is already counted (dd <= max(maxd, seed)):
+//    then neither the statistic nor cull_t can change.
+__device__ __forceinline__ void leaf_children(HitState& h, uint64_t& ancm, uint32_t& status, bool flag_ties,
+                                              bool occl_cull, const float* tb, uint32_t Cl, float dx, float dy, float dz,
+                                              float avx, uint32_t idx0, uint32_t dd, const float4 dc, const float4 dk,
+                                              float cull_t)
+{
+    const float R2b = dc.x, R2s = dc.y, T = dc.w, Tfar = dk.z, cull_r = dk.y;
+    while (Cl) {
+        const uint32_t p = __builtin_ctz(Cl);
+        __asm__("s_bitset0_b32 %0, %1" : "+s"(Cl) : "s"(p));
+        const uint32_t c = p & 15u;
+        lds_fence();
+        const float4 pc = *reinterpret_cast<const float4*>(tb + c * 4u);
+        const float tca = (pc.x * dx + pc.y * dy) + pc.z * dz;
+        const float d2 = pc.w - tca * tca;
+        const bool hs = __builtin_fminf(__builtin_fminf(tca, R2s - d2), avx) >= 0.0f;
+        const uint64_t hsm = wave_ballot(hs);
+        if (hsm == 0ull) continue;
+        uint64_t amx = lod_expands(tca, d2, R2b - d2, hs, hsm, R2b, T, Tfar);
+        if (amx == 0ull) continue;
+        if (occl_cull) {
+            amx &= ~occluded<false>(tca, h.minT, cull_t, cull_r);
+            if (amx == 0ull) continue;
+        }
+        ancm &= ~accept_hits<false>(h, ancm, status, flag_ties, pc, tca, d2, dd, amx, idx0 + c, R2s);
+    }
+}
+
+// leaf_children for the two rays of a pair unit (traverse_pair's two-ray loop): per ray what the one-ray form does, a
+// branch taken on the union of the two rays' ballots.
+template <class Ray>
+__device__ __forceinline__ void leaf_children_pair(Ray& ra, Ray& rb, uint64_t& ancA, uint64_t& ancB, uint32_t& status,
+                                                   bool flag_ties, bool occl_cull, const float* tb, uint32_t Cl,
+                                                   float avxA, float avxB, uint32_t idx0, uint32_t dd, const float4 dc,
+                                                   const float4 dk, float cull_t)
+{
+    const float R2b = dc.x, R2s = dc.y, T = dc.w, Tfar = dk.z, cull_r = dk.y;
+    while (Cl) {
+        const uint32_t p = __builtin_ctz(Cl);
+        __asm__("s_bitset0_b32 %0, %1" : "+s"(Cl) : "s"(p));
+        const uint32_t c = p & 15u;
+        lds_fence();
+        const float4 pc = *reinterpret_cast<const float4*>(tb + c * 4u);
+        const float tcaA = (pc.x * ra.dx + pc.y * ra.dy) + pc.z * ra.dz;
+        const float tcaB = (pc.x * rb.dx + pc.y * rb.dy) + pc.z * rb.dz;
+        const float d2A = pc.w - tcaA * tcaA;
+        const float d2B = pc.w - tcaB * tcaB;
+        const bool hsA = __builtin_fminf(__builtin_fminf(tcaA, R2s - d2A), avxA) >= 0.0f;
+        const bool hsB = __builtin_fminf(__builtin_fminf(tcaB, R2s - d2B), avxB) >= 0.0f;
+        const uint64_t hsmA = wave_ballot(hsA), hsmB = wave_ballot(hsB);
+        if ((hsmA | hsmB) == 0ull) continue;
+        uint64_t amxA = hsmA ? lod_expands(tcaA, d2A, R2b - d2A, hsA, hsmA, R2b, T, Tfar) : 0ull;
+        uint64_t amxB = hsmB ? lod_expands(tcaB, d2B, R2b - d2B, hsB, hsmB, R2b, T, Tfar) : 0ull;
+        if ((amxA | amxB) == 0ull) continue;
+        if (occl_cull) {
+            amxA &= ~occluded<false>(tcaA, ra.h.minT, cull_t, cull_r);
+            amxB &= ~occluded<false>(tcaB, rb.h.minT, cull_t, cull_r);
+        }
+        if (amxA) ancA &= ~accept_hits<false>(ra.h, ancA, status, flag_ties, pc, tcaA, d2A, dd, amxA, idx0 + c, R2s);
+        if (amxB) ancB &= ~accept_hits<false>(rb.h, ancB, status, flag_ties, pc, tcaB, d2B, dd, amxB, idx0 + c, R2s);
+    }
 }
 
 // ---- Expand the node with centre/|c|^2 pc (its axis columns j = 0..2 at col + j cs: col = root image + 4, cs = 4
@@ -756,11 +852,20 @@ __device__ __forceinline__ uint64_t occluded(float tca, float minT, float cull_t
 // regime condition as w (1 - 2^-16) > 2 R^2, a slightly stronger one. 15 VALU per expansion. The four conditions
 // are compares of a v_min3 and a v_min (with denormals kept, a > b exactly when fl(a - b) > 0; every operand is
 // finite): the kept children come from one ballot. (w itself stays the reference's |c|^2: it is the table's cc.)
+struct LeafLevel {   // what a traversal's expand() tells its caller for leaf_children
+    float4 dc;       // the children's depth constants
+    bool on;         // uniform: the kept children are all inline leaves, and their table is stored
+};
 struct ChildBuild {
     float x, y, z, w;    // this lane's built column (BuildLane), w = its |.|^2: child i's centre and cc on lane 32 + i
     uint32_t M, front;   // uniform: the children the cone cull kept; the front children (all, in index order)
     float4 dtc;          // the children's depth constants
+    bool leaf_level;     // uniform: every child the cone cull kept is an inline leaf (see leaf_children)
 };
+// KP_CONE: kp is formed here, from the cone axis as read with the node -- the same operands, so the same float --
+// instead of being passed in (the pair unit's one-ray loop, whose ray registers may hold either ray: no uniform copy
+// of the axis is carried through the traversal)
+template <bool KP_CONE = false>
 __device__ __forceinline__ ChildBuild build_children(const DeviceConsts* K, const TraverseLds& L, const BuildLane& B,
                                                      const float4 pc, const float* col, uint32_t cs, uint32_t ko,
                                                      float kp, uint32_t index_order)
@@ -775,6 +880,7 @@ __device__ __forceinline__ ChildBuild build_children(const DeviceConsts* K, cons
     const float sinT = L.cone()[4];
     const float4 dtn = depth_consts_at(K, ko - (1u << 5));   // this node: (4/3) r
     const float4 dtc = depth_consts_at(K, ko);               // children: (2r)^2, T
+    const float leafw = depth_word_at(K, ko, 4u);            // children: leaf threshold
     // world = parent * child (SIMD_AVX.h:59-81), child translation scaled by (4/3) r (Sphereflake.h:162-172):
     // column 3 lanes multiply b0..b2 by s, the others by 1 (exact)
     const float sm = B.bc == 3u ? dtn.z : 1.0f;
@@ -796,8 +902,11 @@ __device__ __forceinline__ ChildBuild build_children(const DeviceConsts* K, cons
     // entry order as bit order: the front children (nearer than this node's centre along the cone axis) at bits 0..8,
     // the others at 16..24 -- one find-first-set per child picks the next, and its low 4 bits are the child's number
     // (index order: every child "front" -- an OR with a per-traversal mask, not a branch)
+    if constexpr (KP_CONE) kp = (pc.x * ax + pc.y * ay) + pc.z * az;
     const uint32_t front = ((uint32_t)(wave_ballot(ca < kp) >> 32) & 0x1ffu) | index_order;
-    return ChildBuild{ x, y, z, w, M, front, dtc };
+    // the inline leaves among the children (the child loop's own test, pc.w > leaf, on the value the table gets)
+    const uint32_t leafm = (uint32_t)(wave_ballot(w > leafw) >> 32);
+    return ChildBuild{ x, y, z, w, M, front, dtc, (M & ~leafm) == 0u };
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1136,7 +1245,8 @@ __device__ __forceinline__ uint32_t split_mask(uint32_t q, uint32_t idxB)
 // maintained past 0), and the traversal ends when no lane is live. On return h.depth >= 0 (h.hit) marks the finished
 // lanes; the other fields of h are not maintained. The visits are a subset of the closest-hit traversal's and every
 // sphere left out cannot be accepted below `bound`, so h.hit is exactly (the closest hit's min_t < bound).
-template <bool COMPACT = false, bool SPLIT = false, bool SHADOW = false>
+// LEAFNODES: leaf-level nodes take leaf_children (the plain traversal only; the fixup's deep re-trace keeps the child loop).
+template <bool COMPACT = false, bool SPLIT = false, bool SHADOW = false, bool LEAFNODES = !(COMPACT || SPLIT || SHADOW)>
 __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K, const float* root, float* __restrict__ Lbase,
                                              const float4 bcol, uint32_t levels, float dx, float dy, float dz, bool valid,
                                              HitState& h, int32_t& maxd, uint32_t& status, uint32_t K_flags,
@@ -1201,16 +1311,20 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
     // (expand_node for this traversal's ray. tb: table(d), ko: d + 1's constants offset -- the caller's carried values,
     // not formed here again; kp: the caller passes the axis lane's tca of the node, (pc.x ax + pc.y ay) + pc.z az on the
     // same operands -- the cone axis IS that lane's direction)
+    // (lf: the children's constants, and whether they are all inline leaves with their table stored -- leaf_children)
     auto expand = [&](const float4 pc, const float* col, uint32_t cs, uint32_t d, float actv,
-                      float* tb, uint32_t ko, float kp) -> uint32_t {
+                      float* tb, uint32_t ko, float kp, LeafLevel& lf) -> uint32_t {
         d = __builtin_amdgcn_readfirstlane(d);
         SF_COUNT(0, 1);
         SF_COUNT(7, __builtin_popcountll(wave_ballot(actv >= 0.0f)));   // (COUNTS builds: lanes visiting the node)
         const ChildBuild cb = build_children(K, L, B, pc, col, cs, ko, kp, index_order);
+        lf.dc = cb.dtc;
+        lf.on = false;
         // (one levels test for both outcomes: stored after the cull, the table is read only once this returns)
         if (ko < lv32) {   // (d + 1 < levels)
             *reinterpret_cast<float3*>(tb + B.slot) = make_float3(cb.x, cb.y, cb.z);
             *(B.bc == 3u ? tb + B.slot + 3u : L.cone() + 5u) = cb.w;
+            lf.on = cb.leaf_level;
             return (cb.M & cb.front) | ((cb.M & ~cb.front) << 16);
         }
         {   // (d + 1 >= levels)
@@ -1253,8 +1367,9 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
             sel_in_place(actbits, 0u, acc0);
             live = wave_ballot(actbits != 0u) != 0ull;
         }
+        LeafLevel lf0;   // (the root is opened as ever)
         if (live && !__builtin_amdgcn_readfirstlane((int)(pc.w > depth_leaf(K, 0u))))
-            C = expand(pc, L.root() + 4u, 4u, 0u, actv, tcur, kofs, readlane_f(tca, axl));
+            C = expand(pc, L.root() + 4u, 4u, 0u, actv, tcur, kofs, readlane_f(tca, axl), lf0);
         else SF_COUNT(4, 1);
         if constexpr (SPLIT) {
             if (split_depth == 1u) C &= split_mask(split_q, 1u);
@@ -1286,8 +1401,6 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
                 const uint32_t na = __builtin_popcountll(wave_ballot(actv >= 0.0f));
                 SF_COUNT(5, na);
                 SF_COUNT(6, __builtin_popcountll(hbm));
-                SF_COUNT(10, d >= 4u ? 1 : 0);
-                SF_COUNT(11, d >= 4u ? na : 0);
                 SF_COUNT(14, na <= 32u ? 1 : 0);
             }
 #endif
@@ -1345,27 +1458,52 @@ __device__ __forceinline__ void traverse_ray(const DeviceConsts* __restrict__ K,
                 ancm &= wave_ballot(h.depth != (int32_t)d + 1);   // the child is finished
                 continue;
             }
-            // push the open node, open child c
-            stk_pc = writelane_s(C, d, stk_pc);
-            stk_ix = writelane_s(idxB, d, stk_ix);
-            {
-                const uint32_t bit = 2u << d;   // level d + 1
-                uint32_t ab = actbits & ~bit;
-                sel_in_place(ab, ab | bit, amx);
-                actbits = ab;
-            }
-            idxB = 9u * (idxB + c) + 1u;
-            d += 1u;
-            actv = avx;
-            SF_STAMP(1);
             const float* const col = tcur + SF_LDS_PLANE + 3u * c;   // the entered child's axis columns
-            tcur += SF_LDS_LEVEL;
-            kofs += 1u << 5;
-            C = expand(pc, col, SF_LDS_COLS, d, avx, tcur, kofs, readlane_f(tca, axl));
+            // push the open node, open child c
+            auto push = [&]() {
+                stk_pc = writelane_s(C, d, stk_pc);
+                stk_ix = writelane_s(idxB, d, stk_ix);
+                {
+                    const uint32_t bit = 2u << d;   // level d + 1
+                    uint32_t ab = actbits & ~bit;
+                    sel_in_place(ab, ab | bit, amx);
+                    actbits = ab;
+                }
+                idxB = 9u * (idxB + c) + 1u;
+                d += 1u;
+                actv = avx;
+                tcur += SF_LDS_LEVEL;
+                kofs += 1u << 5;
+            };
+            LeafLevel lf;
+            if constexpr (LEAFNODES) {
+                // child c's children are built first: if they are all inline leaves (at depth d + 2, already counted
+                // in the max-depth statistic), leaf_children tests them from here and the open node stays open
+                SF_STAMP(1);
+                const uint32_t Cn = expand(pc, col, SF_LDS_COLS, d + 1u, avx, tcur + SF_LDS_LEVEL, kofs + (1u << 5),
+                                           readlane_f(tca, axl), lf);
+                if (lf.on && (Cn == 0u || (int32_t)d + 2 <= (maxd > seed ? maxd : seed))) {   // (no child kept: nothing to count)
+                    SF_COUNT(10, 1);
+                    SF_COUNT(11, __builtin_popcount(Cn));
+                    leaf_children(h, ancm, status, front_first, occl_cull, tcur + SF_LDS_LEVEL, Cn, dx, dy, dz, avx,
+                                  9u * (idxB + c) + 1u, d + 2u, lf.dc, depth_consts_at(K, kofs + (1u << 5) + 16u), cull_t);
+                    ancm &= wave_ballot(h.depth != (int32_t)d + 1);   // child c is finished
+                    SF_STAMP(6);
+                    continue;
+                }
+                push();
+                C = Cn;
+            } else {
+                push();
+                SF_STAMP(1);
+                C = expand(pc, col, SF_LDS_COLS, d, avx, tcur, kofs, readlane_f(tca, axl), lf);
+            }
             if constexpr (SPLIT) {   // (the children are at depth d + 1)
                 if (d + 1u == split_depth) C &= split_mask(split_q, idxB);
             }
-            R2c = depth_consts_at(K, kofs).x;
+            // (depth d + 1's bounding radius^2, the open node's children's: with LEAFNODES the expansion has it)
+            if constexpr (LEAFNODES) R2c = lf.dc.x;
+            else R2c = depth_consts_at(K, kofs).x;
             if (COMPACT && C != 0u) {
                 // ---- Active-ray compaction of sparse nodes (north star: "wavefront ballot / prefix-sum active-ray
                 // compaction down the recursion"; sf_trace_queue2c, opt-in). Deep in the tree a node is often visited
@@ -1499,7 +1637,7 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
     maxd = 0;
 
     // ---- one cone for both rays
-    // (uniform; kept for the one-ray loop's kp: there ray A's registers may hold ray B)
+    // (the axis: ray A of the axis lane; the one-ray loop's kp reads it back from the cone block, see build_children)
     const float ax = readlane_f(ra.dx, axl), ay = readlane_f(ra.dy, axl), az = readlane_f(ra.dz, axl);
     {
         // (cone_s2m's text on a ray held by reference: called as a function, the compiler commutes two of its additions)
@@ -1509,7 +1647,11 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
             const bool fwd = (r.dx * ax + r.dy * ay) + r.dz * az > 0.0f;
             return fwd ? s2 : 1.0f;
         };
-        stage_cone(L, lane, cone_cull, ax, ay, az, [&] { return __builtin_fmaxf(s2m_of(ra), s2m_of(rb)); });
+        // (the lane as an opaque value: its compares in stage_cone are then formed here, per unit -- hoisted out of the
+        // unit loop they were carried through the whole traversal as 64-bit masks, and spilled)
+        uint32_t ln = lane;
+        __asm__ volatile("" : "+v"(ln));
+        stage_cone(L, ln, cone_cull, ax, ay, az, [&] { return __builtin_fmaxf(s2m_of(ra), s2m_of(rb)); });
     }
 
     float cull_t = depth_consts(K, (uint32_t)(seed > 0 ? seed : 0) + 1u).w;
@@ -1527,12 +1669,17 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
     const uint32_t lv32 = __builtin_amdgcn_readfirstlane(levels << 5);
     const uint32_t index_order = front_first ? 0u : 0x1ffu;
     // (expand_node for both rays: at the deepest provisioned level a ray that does not visit the node has actv -1 and
-    // passes nothing)
-    auto expand = [&](const float4 pc, const float* col, uint32_t cs, float* tb, uint32_t ko, float kp) -> uint32_t {
-        const ChildBuild cb = build_children(K, L, B, pc, col, cs, ko, kp, index_order);
+    // passes nothing. actvA / actvB: the two rays' lanes visiting the node, which is not open yet; lf: as traverse_ray's)
+    // (kp_cone: BoolC<true> -- kp from the cone axis, see build_children)
+    auto expand = [&](const float4 pc, const float* col, uint32_t cs, float* tb, uint32_t ko, float kp, auto kp_cone,
+                      float actvA, float actvB, LeafLevel& lf) -> uint32_t {
+        const ChildBuild cb = build_children<decltype(kp_cone)::value>(K, L, B, pc, col, cs, ko, kp, index_order);
+        lf.dc = cb.dtc;
+        lf.on = false;
         if (ko < lv32) {
             *reinterpret_cast<float3*>(tb + B.slot) = make_float3(cb.x, cb.y, cb.z);
             *(B.bc == 3u ? tb + B.slot + 3u : L.cone() + 5u) = cb.w;
+            lf.on = cb.leaf_level;
             return (cb.M & cb.front) | ((cb.M & ~cb.front) << 16);
         }
         {
@@ -1543,10 +1690,10 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
                 M &= ~(1u << i);
                 const float cx = readlane_f(cb.x, 32u + i), cy = readlane_f(cb.y, 32u + i);
                 const float cz = readlane_f(cb.z, 32u + i), cc = readlane_f(cb.w, 32u + i);
-                auto passes = [&](const PairRay& r) -> bool {
-                    return child_expands(cx, cy, cz, cc, r.dx, r.dy, r.dz, r.actv, R2b, T, Tfar);
+                auto passes = [&](const PairRay& r, float actv) -> bool {
+                    return child_expands(cx, cy, cz, cc, r.dx, r.dy, r.dz, actv, R2b, T, Tfar);
                 };
-                if (passes(ra) || passes(rb)) {
+                if (passes(ra, actvA) || passes(rb, actvB)) {
                     status |= SF_STATUS_OVERFLOW;
                     break;
                 }
@@ -1599,6 +1746,17 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
                     ancA &= wave_ballot(ra.h.depth != (int32_t)d + 1);
                     continue;
                 }
+                // child c's children first (traverse_ray): a leaf-level node is not opened
+                // (kp from the axis itself: the axis lane's tca of the node, whichever ray these registers hold)
+                LeafLevel lf;
+                const uint32_t Cn = expand(pc, tcur + SF_LDS_PLANE + 3u * c, SF_LDS_COLS, tcur + SF_LDS_LEVEL,
+                                           kofs + (1u << 5), 0.0f, BoolC<true>(), avx, rb.actv, lf);
+                if (lf.on && (Cn == 0u || (int32_t)d + 2 <= (maxd > seed ? maxd : seed))) {   // (no child kept: nothing to count)
+                    leaf_children(ra.h, ancA, status, front_first, occl_cull, tcur + SF_LDS_LEVEL, Cn, ra.dx, ra.dy, ra.dz,
+                                  avx, 9u * (idxB + c) + 1u, d + 2u, lf.dc, depth_consts_at(K, kofs + (1u << 5) + 16u), cull_t);
+                    ancA &= wave_ballot(ra.h.depth != (int32_t)d + 1);
+                    continue;
+                }
                 stk_pc = writelane_s(C, d, stk_pc);
                 stk_ix = writelane_s(idxB, d, stk_ix);
                 {
@@ -1610,14 +1768,10 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
                 idxB = 9u * (idxB + c) + 1u;
                 d += 1u;
                 ra.actv = avx;
-                const float* const col = tcur + SF_LDS_PLANE + 3u * c;
                 tcur += SF_LDS_LEVEL;
                 kofs += 1u << 5;
-                // (kp from the axis itself: the axis lane's tca of the node, whichever ray these registers hold)
-                C = expand(pc, col, SF_LDS_COLS, tcur, kofs,
-                           __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(
-                               __builtin_bit_cast(int, (pc.x * ax + pc.y * ay) + pc.z * az))));
-                R2c = depth_consts_at(K, kofs).x;
+                C = Cn;
+                R2c = lf.dc.x;
                 continue;
             }
             ancA &= wave_ballot(ra.h.depth != (int32_t)d);
@@ -1635,8 +1789,8 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
     // the one-ray loop on A's registers, with the lanes of mB exchanged between the two sets around it -- there A's
     // registers carry ray B and B's park ray A, which does not visit the node. v_swap_b32 under EXEC = mB: one VALU
     // instruction per register, in place; the exchange is its own inverse.
-    auto one_ray_subtree = [&](const uint64_t mB) {
-        auto exchange = [&]() {
+    auto exchange = [&](const uint64_t mB) {
+        {
             // (EXEC kept in VCC meanwhile: no SGPR pair of its own)
             __asm__("s_mov_b64 vcc, exec\n\t"
                     "s_mov_b64 exec, %22\n\t"
@@ -1661,10 +1815,21 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
             const uint64_t x = (ancA ^ ancB) & mB;
             ancA ^= x;
             ancB ^= x;
-        };
-        if (mB) exchange();
+        }
+    };
+    auto one_ray_subtree = [&](const uint64_t mB) {
+        if (mB) exchange(mB);
         dfs_one(d);
-        if (mB) exchange();
+        if (mB) exchange(mB);
+    };
+    // likewise the children of a leaf-level node that no lane enters with both rays (mB: the lanes entering with ray
+    // B; avx: the entering lanes of either ray): the one-ray leaf_children between the two exchanges
+    auto one_ray_leaves = [&](const uint64_t mB, const float* tb, uint32_t Cl, float avx, uint32_t idx0, uint32_t dd,
+                              const LeafLevel& lf) {
+        if (mB) exchange(mB);
+        leaf_children(ra.h, ancA, status, front_first, occl_cull, tb, Cl, ra.dx, ra.dy, ra.dz, avx, idx0, dd, lf.dc, depth_consts_at(K, kofs + (1u << 5) + 16u),
+                      cull_t);
+        if (mB) exchange(mB);
     };
 
     {
@@ -1682,8 +1847,9 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
         };
         const float tcaA = enter_root(ra, ancA, ex0A);
         enter_root(rb, ancB, ex0B);
+        LeafLevel lf0;   // (the root is opened as ever)
         if (!__builtin_amdgcn_readfirstlane((int)(pc.w > depth_leaf(K, 0u))))
-            C = expand(pc, L.root() + 4u, 4u, tcur, kofs, readlane_f(tcaA, axl));
+            C = expand(pc, L.root() + 4u, 4u, tcur, kofs, readlane_f(tcaA, axl), BoolC<false>(), ra.actv, rb.actv, lf0);
     }
     if ((ex0A & ex0B) == 0ull) {   // no lane expands the root with both rays (one half empty, or missing the root, is
         one_ray_subtree(ex0B);     // the common case): the one-ray loop from the start
@@ -1738,6 +1904,21 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
                 ancB &= wave_ballot(rb.h.depth != (int32_t)d + 1);
                 continue;
             }
+            // child c's children first (traverse_ray): a leaf-level node is not opened
+            LeafLevel lf;
+            const uint32_t Cn = expand(pc, tcur + SF_LDS_PLANE + 3u * c, SF_LDS_COLS, tcur + SF_LDS_LEVEL, kofs + (1u << 5),
+                                       readlane_f(tcaA, axl), BoolC<false>(), avxA, avxB, lf);
+            if (lf.on && (Cn == 0u || (int32_t)d + 2 <= (maxd > seed ? maxd : seed))) {   // (no child kept: nothing to count)
+                if ((amxA & amxB) == 0ull)
+                    one_ray_leaves(amxB, tcur + SF_LDS_LEVEL, Cn, sel_mask(avxA, __builtin_inff(), amxB),
+                                   9u * (idxB + c) + 1u, d + 2u, lf);
+                else
+                    leaf_children_pair(ra, rb, ancA, ancB, status, front_first, occl_cull, tcur + SF_LDS_LEVEL, Cn, avxA,
+                                       avxB, 9u * (idxB + c) + 1u, d + 2u, lf.dc, depth_consts_at(K, kofs + (1u << 5) + 16u), cull_t);
+                ancA &= wave_ballot(ra.h.depth != (int32_t)d + 1);
+                ancB &= wave_ballot(rb.h.depth != (int32_t)d + 1);
+                continue;
+            }
             stk_pc = writelane_s(C, d, stk_pc);
             stk_ix = writelane_s(idxB, d, stk_ix);
             {
@@ -1752,11 +1933,10 @@ __device__ __forceinline__ void traverse_pair(const DeviceConsts* __restrict__ K
             d += 1u;
             ra.actv = avxA;
             rb.actv = avxB;
-            const float* const col = tcur + SF_LDS_PLANE + 3u * c;
             tcur += SF_LDS_LEVEL;
             kofs += 1u << 5;
-            C = expand(pc, col, SF_LDS_COLS, tcur, kofs, readlane_f(tcaA, axl));
-            R2c = depth_consts_at(K, kofs).x;
+            C = Cn;
+            R2c = lf.dc.x;
             // entered by no lane with both rays: its subtree on the one-ray loop, back here with the node finished
             if ((amxA & amxB) == 0ull) one_ray_subtree(amxB);
             continue;
@@ -2076,7 +2256,7 @@ __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __res
                                     FIXUP ? nullptr : a.phase_sums, part_axis_lane(sub ? 0u : part), &tile_counts,
                                     sub ? part - SF_PART_QUARTER0 : 0u, sub ? a.split_depth : 0xffffffffu, seed);
     else
-        traverse_ray<COMPACT>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status,
+        traverse_ray<COMPACT, false, false, !FIXUP && !COMPACT>(K, a.root, L, bcol, levels, dx, dy, dz, t.valid, h, maxd, status,
                               FIXUP ? (flags | SF_FLAG_NO_FRONT_FIRST) : flags,
                               FIXUP ? nullptr : a.phase_sums, part_axis_lane(part), &tile_counts, 0u, 0u, seed);
     if (!FIXUP && (flags & (SF_FLAG_DIAG_FORCE_RETRACE | SF_FLAG_REDO_PASS)) == SF_FLAG_DIAG_FORCE_RETRACE)
