@@ -329,8 +329,8 @@ int sf_light_image_many(sf_ctx* ctx, const sf_shadows_params* params, float ambi
 /* --- the level of detail of the shadow traces -------------------------------- */
 /* THE LEVEL OF DETAIL IS THE LIGHT'S (above) because a shadow ray refines a node while sqrtf(t / r) < C with t measured
    from the ray's origin and C the variant's constant (70 AVX, 60 SSE). This sets C for the shadow traces -- and for
-   them only: sf_trace_shadow(_to), sf_trace_shadows(_to), sf_trace_sun(_to) and sf_trace_suns(_to). In their
-   definitions "the reference's ray" then reads "the reference's ray with C in place of the variant's constant in
+   them only: sf_trace_shadow(_to), sf_trace_shadows(_to), sf_trace_sun(_to), sf_trace_suns(_to) and
+   sf_trace_shafts(_to). In their definitions "the reference's ray" then reads "the reference's ray with C in place of the variant's constant in
    sqrtf(t / r) < C || t < 0 (Sphereflake.h:146, SSE :129)"; the oracle takes the same constant
    (sfo_set_lod_constant). C == 0 (the default) means the variant's own, so a context that never calls this traces
    what it always traced. Renders, sf_trace_dirs_to, sf_trace_rays_to, the frame-less mode and the multi-GPU paths keep
@@ -444,6 +444,75 @@ int sf_trace_suns(sf_ctx* ctx, const sf_suns_params* params);
    Asynchronous on the stream. sphereflake_amd/lights.py: light_model_suns; sun_cone and sky_dirs make directions. */
 int sf_light_image_suns(sf_ctx* ctx, const sf_suns_params* params, float ambient, const float* pos4,
                         const float* nrm4, const uint64_t* mask, uint8_t* rgba);
+
+/* --- light shafts: sun visibility along each pixel's view ray ----------------- */
+/* The calls above all ask "is this surface point lit?". This one asks it of the air between the camera and the
+   surface: n <= SF_SHAFT_SAMPLES_MAX points along each pixel's view ray, from the position image's origin to the
+   pixel's surface point (or, for a miss of the frame, to a point `far` along a caller's direction), each tested against
+   the sun in ONE launch. Light that passes the gaps of the flake leaves shafts in front of it and on the background.
+   Each tile's wave loads its pixel once and loops over the samples; one 64-bit word per pixel comes out.
+   DEFINITION OF THE MASK (exact; binary32, round to nearest, every operation rounded on its own, no fused
+   multiply-add). Inputs: a position image pos4 and its origin o as for sf_trace_sun_to; the sun s = dir (as given),
+   tau = distance, the bias and the shadow LOD constant (sf_set_shadow_lod); the march fractions sigma_0 .. sigma_{n-1};
+   optionally a direction image dirs and a distance far. For pixel p with P = pos4[p].xyz:
+     1. The march end E = P where P != (0, 0, 0); where P == 0, dirs is not NULL and far > 0,
+        E = (dirs[p].x far, dirs[p].y far, dirs[p].z far), one rounding each; otherwise E = 0.
+     2. For i < n the sample Q_i = (E.x sigma_i, E.y sigma_i, E.z sigma_i), one rounding each.
+     3. Bit i of mask[p] is 1 iff sf_trace_sun_to with the same dir, distance, bias, origin and shadow LOD constant
+        writes 255 at a pixel whose position is Q_i, and 0 iff it writes 0: steps 1-6 of its definition apply
+        unchanged. So Q_i == 0 (E == 0, or a product that underflows) sets the bit without a ray, and a zero or
+        non-finite dir sets every bit.
+     4. Bits n..63 are 0.
+   CONSEQUENCES:
+   - A sample with sigma_i == 1 is the surface point itself: its bit is exactly sf_trace_sun_to's byte.
+   - THE REFERENCE'S QUIRK cannot bite when every ray's origin o + Q_i + s tau lies outside the radius-2 ball;
+     tau >= 2 + max |o + E| guarantees that (for |s| = 1 and fractions <= 1; sphereflake_amd/lights.py: shaft_distance).
+   - THE LEVEL OF DETAIL IS THAT OF A VIEWER AT DISTANCE tau, so a larger tau is coarser; sf_set_shadow_lod with
+     matched_lod corrects this, as for sf_trace_sun_to.
+   sphereflake_amd/lights.py states steps 1-2 on the host (shaft_ends, shafts_model). */
+#define SF_SHAFT_SAMPLES_MAX 64
+typedef struct sf_shafts_params {
+    float dir[3];             /* s, towards the sun, world space, as given */
+    float distance;           /* tau, finite and > 0 (sf_shafts_defaults: 4) */
+    float bias;               /* as sf_sun_params.bias */
+    const float* fractions;   /* HOST, n floats, each finite and > 0; read before the call returns */
+    const float* weights;     /* HOST, n floats, or NULL = every weight (float)1 / (float)n; the image pass only */
+    uint32_t n;               /* 1 .. SF_SHAFT_SAMPLES_MAX */
+    const float* dirs;        /* DEVICE, width * height directions for the frame's misses, used as given (not
+                                 normalised), or NULL = a miss is not marched */
+    uint32_t dirs_stride;     /* floats per pixel of dirs: 3 or 4 */
+    float far;                /* how far a miss is marched along its direction; finite and >= 0, 0 = not marched */
+    float origin[3];          /* as sf_sun_params.origin */
+    uint32_t use_origin;      /* as sf_sun_params.use_origin */
+    uint32_t width, height;   /* as sf_sun_params */
+    uint32_t max_depth;       /* 0 = 12, as sf_sun_params.max_depth */
+    void* stream;             /* NULL = the context stream */
+} sf_shafts_params;
+
+/* dir (0, 0, 1), distance 4, the default bias of sf_shadow_defaults, the rest zero (n = 0, fractions NULL: the caller
+   sets both). */
+int sf_shafts_defaults(const sf_ctx* ctx, sf_shafts_params* params);
+/* As sf_trace_suns_to (pos4 DEVICE or NULL = the context's G-buffer; asynchronous and ordered as it is; no statistic
+   and none of the renders' state touched; re-traced tiles -- a tile flagged for any sample is re-traced once, for all of
+   them -- count in overflow_tiles). mask: DEVICE output, width * height uint64_t, row-major as pos4. Errors as
+   sf_trace_suns_to's, and SF_EINVAL for n == 0, n > SF_SHAFT_SAMPLES_MAX, a null fractions, a fraction that is not
+   finite and > 0, a far that is negative, infinite or NaN, or a dirs_stride other than 3 or 4 with a non-null dirs. */
+int sf_trace_shafts_to(sf_ctx* ctx, const sf_shafts_params* params, const float* pos4, uint64_t* mask);
+/* The context's G-buffer into the context's mask buffer -- the one sf_trace_shadows and sf_trace_suns write:
+   sf_download_shadow_masks and sf_shadow_mask_buffer serve it. */
+int sf_trace_shafts(sf_ctx* ctx, const sf_shafts_params* params);
+/* The in-scatter pass: blends the image of sf_post towards `colour` (r, g, b in [0, 255]) where the march was lit.
+   Exact, binary32, one rounding per operation, no fma. Per pixel, with E as in step 1 above: a pixel with E == 0 is
+   left untouched; else len = sqrt((E.x E.x + E.y E.y) + E.z E.z), correctly rounded; S = 0, then for i = 0 .. n-1 in
+   that order S = S + (bit i of mask[p] ? w_i : 0); a = min((gain len) S, 1), and 0 where that is NaN; each of r, g,
+   b with float value c becomes (uint8) min((c + (colour_c - c) a) + 0.5f, 255); alpha stays. Unlike the other image
+   passes it does touch the frame's misses, where they were marched. params: fractions (for n only), weights, n, dirs,
+   dirs_stride, far, stream. NULL pos4 / mask / rgba select the context's G-buffer, mask buffer and image; SF_ESTATE
+   where a context buffer selected that way was never written; SF_EINVAL for n, fractions, far or dirs_stride as
+   above, a gain that is negative, infinite or NaN, a colour component outside [0, 255] or NaN, or a weight that is
+   negative or NaN. Asynchronous on the stream. sphereflake_amd/lights.py: light_model_shafts. */
+int sf_light_image_shafts(sf_ctx* ctx, const sf_shafts_params* params, float gain, const float colour[3],
+                          const float* pos4, const uint64_t* mask, uint8_t* rgba);
 
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the

@@ -219,8 +219,8 @@ public:
         Check(sf_light_image_many(m_Ctx, &params, ambient, positions4, normals4, masks, rgba));
     }
 
-    // The LOD constant of the shadow traces (new; sf_set_shadow_lod, sf.h): TraceShadow, TraceShadows, TraceSun and
-    // TraceSuns refine a node while sqrtf(t / r) < lodConstant; 0 = the variant's own (the default). Render() is not
+    // The LOD constant of the shadow traces (new; sf_set_shadow_lod, sf.h): TraceShadow, TraceShadows, TraceSun,
+    // TraceSuns and TraceShafts refine a node while sqrtf(t / r) < lodConstant; 0 = the variant's own (the default). Render() is not
     // affected.
     void SetShadowLod(float lodConstant)
     {
@@ -270,6 +270,31 @@ public:
     {
         std::lock_guard<FairMutex> lk(m_Mutex);
         Check(sf_light_image_suns(m_Ctx, &params, ambient, positions4, normals4, masks, rgba));
+    }
+    // Light shafts (new; sf_trace_shafts_to / sf_trace_shafts, sf.h): the sun's visibility at params.n points along
+    // each pixel's view ray in one launch. masks as TraceSuns': bit i = what TraceSun gives at the point
+    // params.fractions[i] of the way from the origin to the pixel's surface point (or, for a miss of the frame, to
+    // params.far along params.dirs). DEVICE pointers, asynchronous; positions4 null = this object's own frame.
+    void TraceShafts(const sf_shafts_params& params, const float* positions4, uint64_t* masks)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_shafts_to(m_Ctx, &params, positions4, masks));
+    }
+    // ... of this object's own device frame into its own mask buffer, the one TraceShadows and TraceSuns write
+    // (sf_download_shadow_masks, LightImageShafts)
+    void TraceShafts(const sf_shafts_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_shafts(m_Ctx, &params));
+    }
+    // The in-scatter of those samples on the image of an SSAO::Render(), in place (sf_light_image_shafts): each marched
+    // pixel blends towards colour (r, g, b in [0, 255]) by min(gain x march length x the lit samples' weights, 1);
+    // null pointers select this object's own frame, mask buffer and image.
+    void LightImageShafts(const sf_shafts_params& params, float gain, const float colour[3],
+                          const float* positions4 = nullptr, const uint64_t* masks = nullptr, uint8_t* rgba = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_image_shafts(m_Ctx, &params, gain, colour, positions4, masks, rgba));
     }
 
     // the device frame, downloaded into the vectors when it is newer than their contents (Refresh)

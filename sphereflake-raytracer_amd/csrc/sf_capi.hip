@@ -85,6 +85,13 @@ extern "C" __global__ void sf_trace_suns_fixup(FrameArgs a, const float* pos4, S
                                                const uint32_t* overflow_list, uint32_t* counters, uint32_t parity);
 extern "C" __global__ void sf_light_image_suns_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
                                                   const uint64_t* mask, SunDirs sd, float ambient, uint8_t* rgba);
+extern "C" __global__ void sf_trace_shafts_wave(FrameArgs a, const float* pos4, ShaftArgs sh, uint64_t* mask,
+                                                uint32_t groups, uint32_t* overflow_list, uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_shafts_fixup(FrameArgs a, const float* pos4, ShaftArgs sh, uint64_t* mask,
+                                                 const uint32_t* overflow_list, uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_light_image_shafts_px(uint32_t W, uint32_t H, const float* pos4, const uint64_t* mask,
+                                                    ShaftArgs sh, float gain, float cr, float cg, float cb,
+                                                    uint8_t* rgba);
 extern "C" __global__ void sf_band_unpack(FrameArgs a, const float4* stage, uint32_t stage_rows, uint32_t band_rows,
                                            uint32_t n, uint32_t first, uint32_t members, uint32_t row0);
 extern "C" __global__ void sf_node_table(FrameArgs a, float4* table, uint32_t nodes);
@@ -1180,13 +1187,13 @@ int sf_render_to(sf_ctx* c, const sf_render_params* p, float* pos4, float* nrm4,
 }
 
 // ------------------------------------------------------------------------------------------
-// The six list traces (sf.h): sf_trace_dirs_to, sf_trace_rays_to, sf_trace_shadow_to,
-// sf_trace_shadows_to, sf_trace_sun_to, sf_trace_suns_to. Each is a one-shot grid, one wave per group of 64 rays (an
-// 8x8 tile of an image, or 64 consecutive rays of a list), and a fixup launch behind it that re-traces the groups the
-// waves flagged (more levels needed, or a tie under the front-first order). They share one re-trace list and its
-// counters (the dirs_* fields; the calls are ordered on the context like any other pair of its calls), and read and
-// write none of the renders' state: not the overflow counters' parity, the tile order or costs, the depth hint, the
-// timing ring or the frame-less state.
+// The seven list traces (sf.h): sf_trace_dirs_to, sf_trace_rays_to, sf_trace_shadow_to,
+// sf_trace_shadows_to, sf_trace_sun_to, sf_trace_suns_to, sf_trace_shafts_to. Each is a one-shot grid, one wave per
+// group of 64 rays (an 8x8 tile of an image, or 64 consecutive rays of a list), and a fixup launch behind it that
+// re-traces the groups the waves flagged (more levels needed, or a tie under the front-first order). They share one
+// re-trace list and its counters (the dirs_* fields; the calls are ordered on the context like any other pair of its
+// calls), and read and write none of the renders' state: not the overflow counters' parity, the tile order or costs,
+// the depth hint, the timing ring or the frame-less state.
 // ------------------------------------------------------------------------------------------
 
 extern "C++" {
@@ -1446,9 +1453,9 @@ int sf_probe_rays(sf_ctx* c, const float* origins3, const float* dirs3, uint32_t
     return probe_download(c, o, n, min_t, hidx, pos4, nrm4);
 }
 
-// ---- what the shadow traces share (sf_trace_shadow_to, sf_trace_shadows_to, sf_trace_sun_to, sf_trace_suns_to): one
-// wave per 8x8 tile of a position image, the shadow traces' own constant block (sf_set_shadow_lod); they touch no
-// statistic (not the stats words, not the ray count).
+// ---- what the shadow traces share (sf_trace_shadow_to, sf_trace_shadows_to, sf_trace_sun_to, sf_trace_suns_to,
+// sf_trace_shafts_to): one wave per 8x8 tile of a position image, the shadow traces' own constant block
+// (sf_set_shadow_lod); they touch no statistic (not the stats words, not the ray count).
 
 // The position image of a shadow trace: width and height 0 mean the context's size, a null pos4 the context's own
 // G-buffer (at its size only). Checks bias and max_depth with them; every failure here is SF_EINVAL.
@@ -1705,8 +1712,8 @@ int sf_light_image_many(sf_ctx* c, const sf_shadows_params* p, float ambient, co
 }
 
 // The LOD constant of the shadow traces (sf.h): a second constant block, the context's own but for the
-// depth tables, which sf_trace_shadow_to, sf_trace_shadows_to, sf_trace_sun_to and sf_trace_suns_to hand their
-// kernels. No kernel knows.
+// depth tables, which sf_trace_shadow_to, sf_trace_shadows_to, sf_trace_sun_to, sf_trace_suns_to and
+// sf_trace_shafts_to hand their kernels. No kernel knows.
 int sf_set_shadow_lod(sf_ctx* c, float lod_constant)
 {
     if (!c || !(lod_constant >= 0.0f) || std::isinf(lod_constant)) return SF_EINVAL;   // (NaN fails the compare)
@@ -1846,6 +1853,108 @@ int sf_light_image_suns(sf_ctx* c, const sf_suns_params* p, float ambient, const
     suns_args(c, p, &sd);
     return light_image_pass(c, p->stream, ambient, pos4, nrm4, mask || c->shadow_masks, rgba, sf_light_image_suns_px,
                             mask ? mask : (const uint64_t*)c->shadow_masks, sd);
+}
+
+// Light shafts: sun visibility along each pixel's view ray in one launch (kernels sf_trace_shafts_wave /
+// sf_trace_shafts_fixup / sf_light_image_shafts_px). The launch of sf_trace_suns_to with the march
+// fractions by value in the argument segment; the mask buffer is sf_trace_shadows'.
+static_assert(SF_SHAFT_SAMPLES == SF_SHAFT_SAMPLES_MAX, "one mask bit per sample");
+static_assert(sizeof(FrameArgs) + sizeof(ShaftArgs) + 64 <= 4096, "kernel argument segment");
+
+int sf_shafts_defaults(const sf_ctx* c, sf_shafts_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->dir[2] = 1.0f;
+    p->distance = 4.0f;
+    p->bias = kShadowBias;
+    return SF_OK;
+}
+
+// n, the fractions, far and the direction image's stride (both calls), the weights (sf_light_image_shafts)
+static int shafts_check(const sf_shafts_params* p, bool weights)
+{
+    if (p->n == 0u || p->n > SF_SHAFT_SAMPLES_MAX || !p->fractions) return SF_EINVAL;
+    for (uint32_t i = 0; i < p->n; ++i)
+        if (!(p->fractions[i] > 0.0f) || std::isinf(p->fractions[i])) return SF_EINVAL;   // (NaN fails the compare)
+    if (!(p->far >= 0.0f) || std::isinf(p->far)) return SF_EINVAL;
+    if (p->dirs && p->dirs_stride != 3u && p->dirs_stride != 4u) return SF_EINVAL;
+    if (weights && p->weights)
+        for (uint32_t i = 0; i < p->n; ++i)
+            if (!(p->weights[i] >= 0.0f)) return SF_EINVAL;   // (NaN fails)
+    return SF_OK;
+}
+
+// the launch's ShaftArgs from the parameters: read from the caller's host arrays here, before the call returns
+static void shafts_args(const sf_ctx* c, const sf_shafts_params* p, ShaftArgs* sh)
+{
+    std::memset(sh, 0, sizeof *sh);
+    shadow_origin(c, p->use_origin, p->origin, p->bias, sh->o, &sh->keep);
+    for (int k = 0; k < 3; ++k) sh->f[k] = p->dir[k] * p->distance;   // (one rounding: step 2 of sf_trace_sun_to's)
+    if (p->dirs && p->far > 0.0f) {   // (else a miss of the frame is not marched: the kernels never look)
+        sh->dirs = p->dirs;
+        sh->dirs_stride = p->dirs_stride;
+        sh->far = p->far;
+    }
+    sh->n = p->n;
+    const float even = 1.0f / (float)p->n;
+    for (uint32_t i = 0; i < p->n; ++i) {
+        sh->sigma[i] = p->fractions[i];
+        sh->w[i] = p->weights ? p->weights[i] : even;
+    }
+}
+
+int sf_trace_shafts_to(sf_ctx* c, const sf_shafts_params* p, const float* pos4, uint64_t* mask)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!mask) return SF_EINVAL;
+    if (int rc = shafts_check(p, false)) return rc;
+    if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
+    ShadowImage im;
+    if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
+    ShaftArgs sh;
+    shafts_args(c, p, &sh);
+    FrameArgs a = shadow_frame_args(c, im);
+    a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
+    return list_trace(
+        c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
+        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
+        [&](const ListLaunch& l) { l.wave(sf_trace_shafts_wave, a, im.pos4, sh, mask); },
+        [&](const ListLaunch& l) { l.fixup(sf_trace_shafts_fixup, a, im.pos4, sh, mask); });
+}
+
+int sf_trace_shafts(sf_ctx* c, const sf_shafts_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow_masks)) return rc;
+    return sf_trace_shafts_to(c, p, nullptr, c->shadow_masks);
+}
+
+// One thread per pixel of the context's frame, the buffers defaulted to the context's (as light_image_pass, without a
+// normal image or an ambient term).
+int sf_light_image_shafts(sf_ctx* c, const sf_shafts_params* p, float gain, const float colour[3], const float* pos4,
+                          const uint64_t* mask, uint8_t* rgba)
+{
+    if (!c || !p || !colour) return SF_EINVAL;
+    if (int rc = shafts_check(p, true)) return rc;
+    if (!(gain >= 0.0f) || std::isinf(gain)) return SF_EINVAL;   // (NaN fails the compare)
+    for (int k = 0; k < 3; ++k)
+        if (!(colour[k] >= 0.0f && colour[k] <= 255.0f)) return SF_EINVAL;
+    if (!rgba && !c->image) return SF_ESTATE;
+    if (!mask && !c->shadow_masks) return SF_ESTATE;
+    ShaftArgs sh;
+    shafts_args(c, p, &sh);
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
+    hipLaunchKernelGGL(sf_light_image_shafts_px, grid, dim3(256), 0, s, c->W, c->H,
+                       pos4 ? pos4 : (const float*)c->pos, mask ? mask : (const uint64_t*)c->shadow_masks, sh, gain,
+                       colour[0], colour[1], colour[2], rgba ? rgba : c->image);
+    SF_HIP(c, hipGetLastError());
+    return SF_OK;
 }
 
 // Multi-frame persistent trace (sf.h; kernel sf_trace_frames1). One launch where every frame's own launch() would be

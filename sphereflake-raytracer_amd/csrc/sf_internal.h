@@ -232,6 +232,22 @@ struct SunDirs {
     float w[SF_SUN_DIRS];             // their weights (sf_light_image_suns; unused by the trace)
 };
 
+// Light shafts: sun visibility along each pixel's view ray in one launch (sf_trace_shafts_to, sf_light_image_shafts):
+// the march fractions travel by value in the kernel argument segment beside the FrameArgs (560 B; indexed with a
+// uniform index they are scalar loads)
+#define SF_SHAFT_SAMPLES 64u          // == SF_SHAFT_SAMPLES_MAX (sf.h): one bit of the mask word per sample
+struct ShaftArgs {
+    float o[3];                       // the origin the position image is relative to
+    float keep;                       // 1 - bias (sf_trace_shafts_to; unused by sf_light_image_shafts)
+    float f[3];                       // s tau per component (sf_trace_shafts_to; unused by sf_light_image_shafts)
+    float far;                        // what a frame miss's direction is scaled by (> 0 wherever dirs is not null)
+    const float* dirs;                // DEVICE direction image for the frame's misses, or null: a miss is not marched
+    uint32_t dirs_stride;             // floats per pixel of dirs: 3 or 4
+    uint32_t n;                       // samples in use, 1..SF_SHAFT_SAMPLES
+    float sigma[SF_SHAFT_SAMPLES];    // the march fractions
+    float w[SF_SHAFT_SAMPLES];        // their weights (sf_light_image_shafts; unused by the trace)
+};
+
 // Multi-frame persistent trace (round 6, sf_render_frames): the frames of one launch, passed by value in the kernel
 // argument segment (copied by the runtime at the launch, so the host may build the next batch at once; 4 KB at most:
 // 11 FrameArgs). Frame f is one slot context's view into that context's G-buffer and stats. All frames share one

@@ -3634,7 +3634,7 @@ extern "C" __global__ __launch_bounds__(64) void sf_fixup_wave(FrameArgs a, cons
 // ------------------------------------------------------------------------------------------
 namespace {
 
-// ---- what the groups of the six list traces (this section and the five after it) share
+// ---- what the groups of the seven list traces (this section and the six after it) share
 
 // The lane's ray of a group. A lane past the end of the list or off the image edge takes the nearest ray inside (a
 // real direction for the wave's cone) and traverses as an invalid lane: no load or store beyond the last ray.
@@ -3777,7 +3777,7 @@ enum class RootStage {
     InGroup,    // not at all: the group stages what it needs itself
 };
 
-// The body of the six fixup kernels (as sf_fixup_wave): re-trace counters[parity] groups of `overflow_list` with
+// The body of the seven fixup kernels (as sf_fixup_wave): re-trace counters[parity] groups of `overflow_list` with
 // group_fn(group, bcol), one block at a time over the list; zero the next trace's counter and add this trace's to
 // counters[2], the re-traced groups sf_get_stats reports. STATS: group_fn returns the group's TileStats, published as
 // the renders' are (the shadow traces touch no statistic). (`a` by value: through a reference, sf_trace_rays_fixup
@@ -4559,6 +4559,103 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_fixup(FrameArgs a
                                          [&](uint32_t group, const float4 bcol) {
         trace_suns_group<true>(a, reinterpret_cast<const float4*>(pos4), sd, mask, lds, bcol, group, SF_MAX_LEVELS,
                                nullptr, nullptr);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Light shafts: sun visibility along each pixel's view ray in one launch (sf_trace_shafts_to). Bit i
+// of mask[p] is what sf_trace_sun_wave writes at a pixel whose position is Q_i = E sigma_i (1 = 255, 0 = 0), bits
+// n..63 are 0. The lane's position is loaded and its march end E formed once -- P, or where P == 0 and a direction
+// image was given, dirs[p] far (loaded in those lanes only). Per sample (a uniform index, the sigma_i are scalar loads
+// from the argument segment) Q_i, w = o + Q_i, F = w + f, d, bound and the lane's root centre 0 - F are formed as in
+// trace_sun_group -- all of them per sample: d is nearly -f every time, but its roundings follow w -- and
+// traverse_mixed runs in its any-hit mode, unchanged, on the axis columns staged once. A tile whose E are all zero
+// traces nothing; a sample that leaves no lane on (a zero or non-finite sun, products that all underflow) is skipped
+// and keeps its bit. A tile flagged for any sample goes onto the overflow list once and is re-traced for all of them.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+template <bool FIXUP>
+__device__ __forceinline__ void trace_shafts_group(const FrameArgs& a, const float4* __restrict__ pos4,
+                                                   const ShaftArgs& sh, uint64_t* __restrict__ mask,
+                                                   float* __restrict__ L, const float4 bcol, uint32_t group,
+                                                   uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const GroupLane g = tile_lane(a, group);
+    const float4 P = pos4[g.ray];
+    float Ex = P.x, Ey = P.y, Ez = P.z;
+    if (sh.dirs != nullptr && P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) {   // a miss of the frame: marched to far
+        const float* __restrict__ dp = sh.dirs + (size_t)g.ray * sh.dirs_stride;
+        Ex = __fmul_rn(dp[0], sh.far);
+        Ey = __fmul_rn(dp[1], sh.far);
+        Ez = __fmul_rn(dp[2], sh.far);
+    }
+    const bool marched = g.valid && !(Ex == 0.0f && Ey == 0.0f && Ez == 0.0f);
+    const uint32_t n = sh.n;   // (uniform, 1..64)
+    uint64_t shadowed = 0ull;   // bit i: the sun's ray to the lane's sample i is stopped
+    uint32_t status = 0u;
+    if (wave_ballot(marched) != 0ull) {   // (uniform; else no pixel of the tile is marched: every sample's bit is set)
+        const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;   // (the mixed traversal has no cone and no order)
+        float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0u; i < n; ++i) {
+            const float sg = sh.sigma[i];
+            const float Qx = __fmul_rn(Ex, sg), Qy = __fmul_rn(Ey, sg), Qz = __fmul_rn(Ez, sg);
+            // (a sample at 0 is a frame miss to sf_trace_sun_to: no ray)
+            const bool surface = marched && !(Qx == 0.0f && Qy == 0.0f && Qz == 0.0f);
+            const float wx = __fadd_rn(sh.o[0], Qx), wy = __fadd_rn(sh.o[1], Qy), wz = __fadd_rn(sh.o[2], Qz);
+            const float Fx = __fadd_rn(wx, sh.f[0]), Fy = __fadd_rn(wy, sh.f[1]), Fz = __fadd_rn(wz, sh.f[2]);
+            float dx, dy, dz, bound;
+            shadow_ray(wx, wy, wz, Fx, Fy, Fz, sh.keep, K->lut, dx, dy, dz, bound);
+            // the lane's root centre (Sphereflake.cpp:83 at F)
+            const float rx = __fsub_rn(0.0f, Fx), ry = __fsub_rn(0.0f, Fy), rz = __fsub_rn(0.0f, Fz);
+            const bool on = surface && finite3(dx, dy, dz);
+            if (wave_ballot(on) == 0ull) continue;   // (uniform)
+            HitState h;
+            h.hit = false;
+            int32_t md = -1;
+            uint32_t st = 0u;
+            lds_fence();   // (the sample before, or the re-trace's earlier tile, has read its tables)
+            traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, st, culls, bound);
+            status |= st;
+            shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
+        }
+    }
+    // (uniform) more levels needed for some sample: once on the list
+    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);
+    // a tile row is 64 contiguous bytes: one 8-byte vector store per valid lane
+    const uint64_t all = n >= 64u ? ~0ull : (1ull << n) - 1ull;
+    if (g.valid) mask[(size_t)g.y * a.W + g.x] = all & ~shadowed;
+}
+
+}  // namespace
+
+// One tile per one-wave workgroup, dynamic LDS SF_LDS_RAYS_FLOATS(a.max_depth) (the launch of sf_trace_suns_wave).
+// Touches none of the context's statistics.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_shafts_wave(FrameArgs a, const float* pos4, ShaftArgs sh,
+                                                                      uint64_t* mask, uint32_t groups,
+                                                                      uint32_t* overflow_list,
+                                                                      uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    stage_root(lds, a.root);
+    trace_shafts_group<false>(a, reinterpret_cast<const float4*>(pos4), sh, mask, lds, build_column(a.consts),
+                              blockIdx.x, a.max_depth, overflow_list, overflow_count);
+}
+
+// Re-trace of the flagged tiles, for every sample, at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and
+// counters). The mixed traversal reads the root image's columns and never writes it: staged once.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_shafts_fixup(FrameArgs a, const float* pos4, ShaftArgs sh,
+                                                                       uint64_t* mask, const uint32_t* overflow_list,
+                                                                       uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
+                                         [&](uint32_t group, const float4 bcol) {
+        trace_shafts_group<true>(a, reinterpret_cast<const float4*>(pos4), sh, mask, lds, bcol, group, SF_MAX_LEVELS,
+                                 nullptr, nullptr);
     });
 }
 

@@ -456,3 +456,40 @@ extern "C" __global__ void __launch_bounds__(256) sf_light_image_suns_px(uint32_
     c.z = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.z, k), 0.5f), 255.0f);
     reinterpret_cast<uchar4*>(rgba)[px] = c;
 }
+
+// The in-scatter pass of the light shafts (sf_light_image_shafts, sf.h): blend each marched pixel
+// towards `colour` by a = min((gain len) S, 1), len the length of its march end E (sf_trace_shafts_wave forms E the
+// same way) and S the weights of its lit samples summed in index order. Unlike the passes above it has no normal and
+// does touch the frame's misses, where they were marched. sphereflake_amd/lights.py (light_model_shafts) restates it
+// (tests/test_gpu_shafts.py).
+extern "C" __global__ void __launch_bounds__(256) sf_light_image_shafts_px(uint32_t W, uint32_t H, const float* pos4,
+                                                                        const uint64_t* mask, ShaftArgs sh,
+                                                                        float gain, float cr, float cg, float cb,
+                                                                        uint8_t* rgba)
+{
+    const uint32_t px = blockIdx.x * 256u + threadIdx.x;
+    if (px >= W * H) return;
+    const float4 P = ld4(pos4, px);
+    float Ex = P.x, Ey = P.y, Ez = P.z;
+    if (sh.dirs != nullptr && P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) {
+        const float* dp = sh.dirs + (size_t)px * sh.dirs_stride;
+        Ex = __fmul_rn(dp[0], sh.far);
+        Ey = __fmul_rn(dp[1], sh.far);
+        Ez = __fmul_rn(dp[2], sh.far);
+    }
+    if (Ex == 0.0f && Ey == 0.0f && Ez == 0.0f) return;   // not marched
+    // (sqrtf is correctly rounded under the build's -fhip-fp32-correctly-rounded-divide-sqrt; __fsqrt_rn is not)
+    const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(Ex, Ex), __fmul_rn(Ey, Ey)), __fmul_rn(Ez, Ez)));
+    const uint64_t m = mask[px];
+    float S = 0.0f;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0u; i < sh.n; ++i) S = __fadd_rn(S, ((m >> i) & 1ull) ? sh.w[i] : 0.0f);
+    const float t = __fmul_rn(__fmul_rn(gain, len), S);
+    const float k = t != t ? 0.0f : fminf(t, 1.0f);   // (NaN: an infinite length times a zero sum)
+    uchar4 c = reinterpret_cast<uchar4*>(rgba)[px];
+    const float r = (float)c.x, gr = (float)c.y, b = (float)c.z;
+    c.x = (uint8_t)fminf(__fadd_rn(__fadd_rn(r, __fmul_rn(__fsub_rn(cr, r), k)), 0.5f), 255.0f);
+    c.y = (uint8_t)fminf(__fadd_rn(__fadd_rn(gr, __fmul_rn(__fsub_rn(cg, gr), k)), 0.5f), 255.0f);
+    c.z = (uint8_t)fminf(__fadd_rn(__fadd_rn(b, __fmul_rn(__fsub_rn(cb, b), k)), 0.5f), 255.0f);
+    reinterpret_cast<uchar4*>(rgba)[px] = c;
+}

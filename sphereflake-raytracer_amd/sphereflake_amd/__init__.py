@@ -98,6 +98,18 @@ class sf_suns_params(ctypes.Structure):
                 ("height", ctypes.c_uint32), ("max_depth", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
 
 
+SF_SHAFT_SAMPLES_MAX = 64
+
+
+class sf_shafts_params(ctypes.Structure):
+    _fields_ = [("dir", ctypes.c_float * 3), ("distance", ctypes.c_float), ("bias", ctypes.c_float),
+                ("fractions", ctypes.POINTER(ctypes.c_float)), ("weights", ctypes.POINTER(ctypes.c_float)),
+                ("n", ctypes.c_uint32), ("dirs", ctypes.POINTER(ctypes.c_float)), ("dirs_stride", ctypes.c_uint32),
+                ("far", ctypes.c_float), ("origin", ctypes.c_float * 3), ("use_origin", ctypes.c_uint32),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("max_depth", ctypes.c_uint32),
+                ("stream", ctypes.c_void_p)]
+
+
 class sf_stats(ctypes.Structure):
     _fields_ = [("max_depth", ctypes.c_int32), ("closest", ctypes.c_float),
                 ("rays", ctypes.c_int64), ("overflow_tiles", ctypes.c_int64)]
@@ -164,6 +176,12 @@ SIGNATURES = {
     "sf_trace_suns": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_suns_params)]),
     "sf_light_image_suns": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_suns_params), ctypes.c_float, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_shafts_defaults": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shafts_params)]),
+    "sf_trace_shafts_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shafts_params), ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_shafts": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shafts_params)]),
+    "sf_light_image_shafts": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shafts_params), ctypes.c_float,
+                                             ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
     "sf_render_frames": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
                                         ctypes.POINTER(sf_render_params)]),
     "sf_slab_rows": (ctypes.c_uint32, [ctypes.c_uint32] * 4),
@@ -858,10 +876,10 @@ class Sphereflake:
                                "sf_trace_shadow", pos, out)
 
     def _trace_vis(self, params, entry, pos, out, dtype=np.uint8):
-        """The `pos` / `out` forms of trace_shadow(), trace_shadows(), trace_sun() and trace_suns(): params(width,
-        height) makes the call's parameter block, or (block, the host arrays it points into, kept alive until the call
-        has returned); `entry` names the call into the context's own buffer, `entry`_to the one into a caller's;
-        `dtype` is the result's per pixel."""
+        """The `pos` / `out` forms of trace_shadow(), trace_shadows(), trace_sun(), trace_suns() and trace_shafts():
+        params(width, height) makes the call's parameter block, or (block, the host arrays it points into, kept alive
+        until the call has returned); `entry` names the call into the context's own buffer, `entry`_to the one into a
+        caller's; `dtype` is the result's per pixel."""
         to, own = getattr(lib(), entry + "_to"), getattr(lib(), entry)
 
         def make(W, H):
@@ -1003,10 +1021,10 @@ class Sphereflake:
 
     # the shadow traces' level of detail, shadows from a directional light (sf_set_shadow_lod, sf_trace_sun_to) -------
     def set_shadow_lod(self, lod_constant):
-        """trace_shadow(), trace_shadows(), trace_sun() and trace_suns() refine a node while sqrtf(t / r) < lod_constant
-        instead of the variant's 70 / 60; 0 restores the variant's own (the default). Nothing else is affected:
-        Render(), trace_dirs() and trace_rays() keep the variant's constant. sphereflake_amd.lights.matched_lod picks a
-        value. Synchronous."""
+        """trace_shadow(), trace_shadows(), trace_sun(), trace_suns() and trace_shafts() refine a node while
+        sqrtf(t / r) < lod_constant instead of the variant's 70 / 60; 0 restores the variant's own (the default).
+        Nothing else is affected: Render(), trace_dirs() and trace_rays() keep the variant's constant.
+        sphereflake_amd.lights.matched_lod picks a value. Synchronous."""
         with self._mutex:
             _check(lib().sf_set_shadow_lod(self._ctx, float(lod_constant)), "sf_set_shadow_lod", self._ctx)
 
@@ -1098,6 +1116,115 @@ class Sphereflake:
         with self._mutex:
             _check(lib().sf_light_image_suns(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
                                              vp(mask_ptr), vp(rgba_ptr)), "sf_light_image_suns", self._ctx)
+        del keep
+
+    # light shafts: sun visibility along each pixel's view ray (sf_trace_shafts_to / sf_trace_shafts /
+    # sf_light_image_shafts) -------------------------------------------------------------------------------------------
+    def shafts_params(self, direction, fractions, weights=None, distance=None, bias=None, dirs_ptr=0, dirs_stride=0,
+                      far=0.0, origin=None, width=0, height=0, max_depth=0, stream=None):
+        """sf_shafts_defaults, overridden: (params, keepalive). fractions [n], weights [n] or None; distance and bias
+        None keep the library's defaults (4, 2^-10); dirs_ptr is a device address (0 = none) of dirs_stride floats per
+        pixel. The host arrays the params point into are in `keepalive` and must outlive the call they are passed to."""
+        F = np.ascontiguousarray(np.asarray(fractions, np.float32).reshape(-1))
+        n = F.shape[0]
+        if not 1 <= n <= SF_SHAFT_SAMPLES_MAX:
+            raise ValueError(f"1..{SF_SHAFT_SAMPLES_MAX} samples per call, not {n}")
+        p = sf_shafts_params()
+        _check(lib().sf_shafts_defaults(self._ctx, ctypes.byref(p)), "sf_shafts_defaults")
+        p.dir[:] = [float(x) for x in _f32(direction, 3)]
+        p.fractions = F.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        wts = None
+        if weights is not None:
+            wts = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+            if wts.shape[0] != n:
+                raise ValueError("one weight per sample")
+            p.weights = wts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        p.n = n
+        if distance is not None:
+            p.distance = float(distance)
+        if bias is not None:
+            p.bias = float(bias)
+        p.dirs = ctypes.cast(ctypes.c_void_p(int(dirs_ptr) or None), ctypes.POINTER(ctypes.c_float))
+        p.dirs_stride, p.far = int(dirs_stride), float(far)
+        if origin is not None:
+            p.origin[:] = [float(x) for x in _f32(origin, 3)]
+            p.use_origin = 1
+        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
+        return p, (F, wts)
+
+    @staticmethod
+    def _dirs_image(dirs):
+        """(device address, floats per pixel) of a direction image given as a torch CUDA tensor [H, W, 3 or 4], a
+        device address (3 floats per pixel) or (address, stride); (0, 0) for None."""
+        if dirs is None:
+            return 0, 0
+        if hasattr(dirs, "data_ptr"):
+            shape = tuple(dirs.shape)
+            if len(shape) != 3 or shape[-1] not in (3, 4) or not (dirs.is_cuda and dirs.is_contiguous()
+                                                                   and dirs.element_size() == 4
+                                                                   and dirs.dtype.is_floating_point):
+                raise ValueError("dirs must be a contiguous float32 CUDA tensor [H, W, 3] or [H, W, 4]")
+            return dirs.data_ptr(), shape[-1]
+        if isinstance(dirs, (tuple, list)):
+            return int(dirs[0]), int(dirs[1])
+        return int(dirs), 3
+
+    def trace_shafts(self, direction, fractions, distance=None, bias=None, pos=None, dirs=None, far=0.0, out=None,
+                     origin=None, max_depth=0, stream=None):
+        """Which of up to 64 points along each pixel's view ray does the sun reach, in one launch: a uint64 per pixel,
+        bit i = 1 where trace_sun(direction) with the same distance and bias gives 255 at the point fractions[i] of
+        the way from the image's origin to the pixel's march end, 0 where it gives 0; bits n..63 are 0 (sf.h). The
+        march end is the pixel's surface point, or for a miss of the frame `far` along its direction in `dirs`
+        ([H, W, 3 or 4], used as given; None or far = 0: a miss is not marched and has its low n bits set).
+        sphereflake_amd.lights.shaft_fractions makes fractions, shaft_distance a safe `distance`. `pos`, `out` and
+        `origin` as trace_suns'; `dirs` a numpy array (uploaded beside `pos`), a torch CUDA tensor, a device address
+        (3 floats per pixel) or (address, stride). The context's mask buffer is the one trace_shadows() and
+        trace_suns() write (download_shadow_masks(), light_image_shafts() see it)."""
+        def run(dptr, dstride):
+            return self._trace_vis(
+                lambda W, H: self.shafts_params(direction, fractions, None, distance, bias, dptr, dstride, far, origin,
+                                                W, H, max_depth, stream),
+                "sf_trace_shafts", pos, out, np.uint64)
+        if pos is None:
+            size = (self.height, self.width)
+        elif hasattr(pos, "shape"):
+            size = tuple(pos.shape[:2])
+        else:
+            size = (int(pos[2]), int(pos[1]))
+        if hasattr(dirs, "shape") and tuple(dirs.shape[:2]) != size:
+            raise ValueError("dirs and pos must have the same height and width")
+        if not isinstance(dirs, np.ndarray):
+            return run(*self._dirs_image(dirs))
+        D = np.ascontiguousarray(dirs, np.float32)
+        if D.ndim != 3 or D.shape[-1] not in (3, 4):
+            raise ValueError("dirs must be [H, W, 3] or [H, W, 4]")
+        if D.size == 0:
+            return run(0, 0)
+        with _DeviceScratch(self.device, D.nbytes) as d:
+            d.upload(0, D)
+            res = run(d.ptr, D.shape[-1])
+            # (the scratch is freed on leaving: the trace that reads it must be done)
+            _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
+        return res
+
+    def light_image_shafts(self, fractions, weights=None, gain=1.0, colour=(255.0, 255.0, 255.0), dirs=None, far=0.0,
+                           pos_ptr=0, mask_ptr=0, rgba_ptr=0, stream=None):
+        """Blend the image of PostProcess() in place towards `colour` (r, g, b in [0, 255]) by
+        min(gain x |march end| x sum_i (bit i ? w_i : 0), 1) (sf_light_image_shafts;
+        sphereflake_amd.lights.light_model_shafts): the in-scatter of the samples of trace_shafts(). weights None:
+        1 / n each. `dirs` (a torch CUDA tensor, a device address or (address, stride); not a numpy array) and `far`
+        as given to trace_shafts(). Pointers are device addresses, 0 = the context's G-buffer, mask buffer and image.
+        Asynchronous."""
+        if isinstance(dirs, np.ndarray):
+            raise ValueError("light_image_shafts is asynchronous: dirs must be on the device")
+        dptr, dstride = self._dirs_image(dirs)
+        p, keep = self.shafts_params((0.0, 0.0, 1.0), fractions, weights, None, None, dptr, dstride, far, None, 0, 0, 0,
+                                     stream)
+        col = (ctypes.c_float * 3)(*[float(x) for x in _f32(colour, 3)])
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        with self._mutex:
+            _check(lib().sf_light_image_shafts(self._ctx, ctypes.byref(p), float(gain), col, vp(pos_ptr), vp(mask_ptr),
+                                               vp(rgba_ptr)), "sf_light_image_shafts", self._ctx)
         del keep
 
     def Synchronize(self):

@@ -13,7 +13,9 @@ A directional light (``Sphereflake.trace_sun`` / ``light_image_sun``: sun_model,
 starts every pixel's ray a fixed distance up the sun direction from its own surface point instead, and
 ``Sphereflake.set_shadow_lod`` with matched_lod chooses the level of detail of all the shadow traces. Many such
 directions in one launch (``Sphereflake.trace_suns`` / ``light_image_suns``: sun_cone, sky_dirs, suns_model,
-light_model_suns) make a sun with an angular size or a sky dome of parallel rays.
+light_model_suns) make a sun with an angular size or a sky dome of parallel rays. Light shafts
+(``Sphereflake.trace_shafts`` / ``light_image_shafts``: shaft_fractions, shaft_ends, shaft_samples, shafts_model,
+shaft_distance, light_model_shafts) ask the sun's question of points along each pixel's view ray.
 """
 from __future__ import annotations
 
@@ -356,4 +358,121 @@ def light_model_suns(rgba, pos4, nrm4, mask, dirs, weights=None, ambient=0.25):
     assert S.dtype == _F and rgb.dtype == _F
     surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
     out[..., :3] = np.where(surface[..., None], rgb.astype(np.uint8), out[..., :3])
+    return out
+
+
+# --- light shafts: sun visibility along each pixel's view ray (sf_trace_shafts_to, sf_light_image_shafts) ----------
+SHAFT_SAMPLES_MAX = 64   # SF_SHAFT_SAMPLES_MAX: one bit of the mask word per sample
+
+
+def shaft_fractions(n):
+    """n march fractions at the midpoints of n equal steps from the origin to the march end: (i + 0.5) / n, formed in
+    float64 and rounded; float32 [n]. The `fractions` of trace_shafts; their even weights are 1 / n."""
+    n = _count(n)
+    return ((np.arange(n, dtype=np.float64) + 0.5) / n).astype(_F)
+
+
+def shaft_ends(pos4, dirs=None, far=0.0):
+    """Step 1 of sf_trace_shafts_to's definition: the march ends E [..., 3] of a position image pos4 [..., 3 | 4].
+    E = P where P != (0, 0, 0); at a miss of the frame E = dirs[p] far per component (dirs [..., 3 | 4], used as
+    given) where dirs is not None and far > 0, else 0."""
+    P = np.asarray(pos4, _F)[..., :3]
+    far = _F(far)
+    if not (np.isfinite(far) and far >= 0):
+        raise ValueError("far must be finite and >= 0")
+    E = np.array(P, _F, copy=True)
+    if dirs is not None and far > 0:
+        D = np.asarray(dirs, _F)[..., :3]
+        if D.shape != P.shape:
+            raise ValueError("dirs and pos4 must have the same height and width")
+        miss = (P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0)
+        with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+            E = np.where(miss[..., None], D * far, P).astype(_F)
+    return E
+
+
+def _fractions(fractions):
+    sg = np.asarray(fractions, _F).reshape(-1)
+    if not 1 <= sg.shape[0] <= SHAFT_SAMPLES_MAX:
+        raise ValueError(f"1..{SHAFT_SAMPLES_MAX} samples, not {sg.shape[0]}")
+    if not (np.isfinite(sg) & (sg > 0)).all():
+        raise ValueError("every fraction must be finite and > 0")
+    return sg
+
+
+def shaft_samples(ends, fractions):
+    """Step 2: the samples Q [n, ..., 3], Q_i = E sigma_i per component, one rounding each. Q_i is the position image
+    whose trace_sun byte is bit i of trace_shafts' word."""
+    E = np.asarray(ends, _F)[..., :3]
+    sg = _fractions(fractions)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        Q = np.stack([E * s for s in sg])
+    assert Q.dtype == _F
+    return Q
+
+
+def shafts_model(pos4, origin, direction, distance, bias, fractions, dirs=None, far=0.0):
+    """Steps 1-2, then sun_model per sample, stacked: (F [n, ..., 3], d [n, ..., 3], bound [n, ...],
+    is_surface [n, ...]) -- slice i is sun_model(Q_i, origin, direction, distance, bias), bit for bit, with Q_i the
+    i-th image of shaft_samples(shaft_ends(pos4, dirs, far), fractions). is_surface[i] is False where Q_i == 0: no
+    ray, the bit is set."""
+    Q = shaft_samples(shaft_ends(pos4, dirs, far), fractions)
+    parts = [sun_model(Q[i], origin, direction, distance, bias) for i in range(Q.shape[0])]
+    return tuple(np.stack([p[k] for p in parts]) for k in range(4))
+
+
+def shaft_distance(origin, ends):
+    """A `distance` for trace_shafts that keeps the reference's quirk out: 2 + max |origin + E| over the march ends
+    E [..., 3], float32, rounded up. With a unit sun direction and fractions <= 1 every sample origin + E sigma lies
+    within max(|origin|, |origin + E|) of the flake's centre, so every ray starts outside the radius-2 ball. Ends
+    that are not finite are ignored."""
+    o = np.asarray(origin, np.float64).reshape(3)
+    E = np.asarray(ends, np.float64)[..., :3].reshape(-1, 3)
+    r = np.linalg.norm(np.concatenate([o[None, :], o + E]), axis=-1)
+    r = r[np.isfinite(r)]
+    tau = 2.0 + float(r.max())
+    t32 = _F(tau)
+    if float(t32) < tau:
+        t32 = np.nextafter(t32, _F(np.inf))
+    return t32
+
+
+def light_model_shafts(rgba, pos4, mask, fractions, weights=None, gain=1.0, colour=(255.0, 255.0, 255.0), dirs=None,
+                       far=0.0):
+    """What sf_light_image_shafts makes of the RGBA8 image `rgba` [..., 4]: a new uint8 array. mask [...] are the
+    words of trace_shafts for the same fractions [n] (used for n only); weights [n] (None: float32(1) / float32(n)
+    each); dirs and far as given to trace_shafts.
+
+    With E = shaft_ends(pos4, dirs, far): a pixel with E == 0 stays; else len = sqrt((E.x E.x + E.y E.y) + E.z E.z),
+    S = 0, then for i = 0 .. n-1 in that order S = S + (bit i ? w_i : 0), a = min((gain len) S, 1) (0 where that is
+    NaN), and each of r, g, b becomes uint8(min((c + (colour_c - c) a) + 0.5, 255)); alpha stays."""
+    g = _F(gain)
+    if not (np.isfinite(g) and g >= 0):
+        raise ValueError("gain must be finite and >= 0")
+    col = np.asarray(colour, _F).reshape(3)
+    if not ((col >= 0) & (col <= 255)).all():
+        raise ValueError("colour components must be in [0, 255]")
+    n = _fractions(fractions).shape[0]
+    if weights is None:
+        w = np.full(n, _F(1.0) / _F(n), _F)
+    else:
+        w = np.asarray(weights, _F).reshape(-1)
+        if w.shape[0] != n or not (w >= 0).all():
+            raise ValueError("one weight per sample, none negative or NaN")
+    out = np.array(rgba, np.uint8, copy=True)
+    E = shaft_ends(pos4, dirs, far)
+    mask = np.asarray(mask, np.uint64)
+    S = np.zeros(E.shape[:-1], _F)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        length = _length(E)
+        for i in range(n):
+            bit = ((mask >> np.uint64(i)) & np.uint64(1)) != 0
+            S = S + np.where(bit, w[i], _F(0.0)).astype(_F)
+        t = (g * length) * S
+        a = np.where(np.isnan(t), _F(0.0), np.fmin(t, _F(1.0))).astype(_F)
+        c = out[..., :3].astype(_F)
+        rgb = np.fmin((c + (col - c) * a[..., None]) + _F(0.5), _F(255.0))
+    assert S.dtype == _F and length.dtype == _F and rgb.dtype == _F
+    marched = ~((E[..., 0] == 0) & (E[..., 1] == 0) & (E[..., 2] == 0))
+    out[..., :3] = np.where(marched[..., None], rgb.astype(np.uint8), out[..., :3])
     return out

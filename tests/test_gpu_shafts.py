@@ -1,0 +1,401 @@
+"""Light shafts on the GPU (sf_trace_shafts_to / sf_trace_shafts / sf_light_image_shafts): bit i of every pixel's mask
+word equals the visibility byte of sf_trace_sun_to at the sample Q_i = E sigma_i -- the CPU oracle's
+(tests/shaftscheck.py) on a sample of the surface pixels and of the marched misses, the single-position kernel's
+(trace_sun on the host-scaled images) for all 64 bits -- and the in-scatter pass equals
+sphereflake_amd.lights.light_model_shafts byte for byte."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import sphereflake_amd as sf
+from sphereflake_amd import lights
+from dirscheck import same_bits
+from oracle import pyoracle
+from rayscheck import frame
+import shaftscheck as sc
+import suncheck as su
+
+pytestmark = pytest.mark.gpu
+
+BIASES = (0.0, su.B10)
+F8 = lights.shaft_fractions(8)
+COLOUR = (255.0, 240.0, 200.0)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def device():
+    sf.build()
+    assert sf.device_count() >= 1, "no HIP device visible: GPU tests must run on an MI355X"
+
+
+def flake(name, variant="avx"):
+    S = pyoracle.load_setup(name)
+    s = sf.Sphereflake(S["W"], S["H"])
+    s.SetVariant(variant)
+    s.SetView(S["origin"], S["tl"], S["tr"], S["bl"])
+    return s
+
+
+def shafts(s, name, fractions, pos, bias=su.B10, **kw):
+    """trace_shafts under the fixture's case (shaftscheck.CASES): its sun, tau, and far with its direction image."""
+    kw.setdefault("dirs", sc.dirs_of(name))
+    kw.setdefault("far", sc.CASES[name][2])
+    return s.trace_shafts(sc.sun(name), fractions, sc.CASES[name][1], bias=bias, pos=pos, **kw)
+
+
+def assert_mask(got, want, what, where=None):
+    assert got.dtype == np.uint64 and got.shape == want.shape, what
+    differ = got != want
+    if where is not None:
+        differ &= where
+    bad = np.argwhere(differ)
+    assert bad.size == 0, f"{what}: {len(bad)} pixels differ, first {bad[:4]}: " \
+                          f"{[hex(int(got[tuple(b)])) for b in bad[:4]]} != {[hex(int(want[tuple(b)])) for b in bad[:4]]}"
+
+
+def assert_high_bits_clear(got, n, what):
+    if n < 64:
+        assert (got >> np.uint64(n) == 0).all(), what
+
+
+# 1 ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,variant", [("t1", "avx"), ("t3", "avx"), ("t1", "sse")])
+def test_eight_samples_equal_the_oracle(name, variant):
+    """The oracle's own frame, uploaded; 8 samples; both biases. t1: sun (4, 7, 2), tau 16, the misses marched to 13
+    along the unit pinhole directions -- every 4th surface pixel (208) and every 8th miss (185); t3: sun (0, 0, 1),
+    tau 4 -- every 12th surface pixel (300)."""
+    pos = frame(name, variant)["pos4"]
+    with flake(name, variant) as s:
+        for bias in BIASES:
+            got = shafts(s, name, F8, pos, bias)
+            assert_high_bits_clear(got, 8, f"{name} {variant} bias {bias}")
+            for part, every, traced in sc.PARITY[name]:
+                want, pick = sc.oracle_mask(name, F8, bias, variant, every, part)
+                assert int(pick.sum()) == traced
+                if variant == "avx":   # a constant mask cannot pass
+                    bits, count = sc.BOTH[(name, part)]
+                    for i in bits:
+                        assert min(sc.outcomes(want, pick, i)) >= count, (part, i)
+                assert_mask(got, want, f"{name} {variant} bias {bias} {part}", pick)
+            if sc.dirs_of(name) is None:
+                assert (got[~sc.surface_of(pos)] == sc.low(8)).all()
+
+
+# 2 ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["t1", "t3"])
+def test_all_64_bits_equal_the_single_position_kernel(name):
+    """64 samples, whole images: bit i is trace_sun's byte on the host-scaled image Q_i. Prefixes of the fractions:
+    n = 1 and 33. On t1 every 8th surface pixel also equals the oracle, where bits 32..55 have both outcomes in
+    quantity (tests/test_shafts_host.py): a 32-bit shift cannot pass."""
+    pos = frame(name)["pos4"]
+    fr = lights.shaft_fractions(64)
+    Q = sc.samples(name, fr)
+    pad = np.zeros(pos.shape[:2] + (1,), np.float32)
+    with flake(name) as s:
+        vis = [s.trace_sun(sc.sun(name), sc.CASES[name][1], bias=su.B10, pos=np.concatenate([Q[i], pad], axis=-1))
+               for i in range(64)]
+        for n in (64, 1, 33):
+            got = shafts(s, name, fr[:n], pos)
+            assert_mask(got, lights.masks_from_vis(vis[:n]), f"{name} n = {n}")
+            assert_high_bits_clear(got, n, f"{name} n = {n}")
+            if n == 64:
+                m64 = got
+    print(name, "bits >= 32 with 20 shadowed pixels:", len([i for i in range(32, 64) if (vis[i] == 0).sum() >= 20]))
+    if name == "t1":
+        want, pick = sc.oracle_mask("t1", fr, su.B10, "avx", sc.ALL64_EVERY, "surface")
+        assert int(pick.sum()) == 104
+        assert min(min(sc.outcomes(want, pick, i)) for i in range(32, 56)) >= 20
+        assert_mask(m64, want, "t1 64 samples against the oracle", pick)
+
+
+# 3 ---------------------------------------------------------------------------------------------------
+def test_identities_and_special_inputs():
+    """sigma = 1 is trace_sun itself; a permutation of the fractions permutes the bits; a NaN, infinite or zero sun
+    sets the low n bits everywhere; without a direction image, or with far = 0, every miss has exactly its low n bits
+    set and the surface pixels' words are those of the run with one; bits n..63 are 0."""
+    pos = frame("t1")["pos4"]
+    surf = sc.surface_of(pos)
+    sun, tau = sc.sun("t1"), sc.CASES["t1"][1]
+    perm = np.array([5, 2, 7, 0, 3, 6, 1, 4])
+    with flake("t1") as s:
+        base = shafts(s, "t1", F8, pos)
+        assert len(np.unique(base[surf])) >= 4 and len(np.unique(base[~surf])) >= 4   # the bits differ between samples
+        assert_high_bits_clear(base, 8, "base")
+        got = shafts(s, "t1", F8[perm], pos)
+        for j in range(8):
+            assert np.array_equal(sc.bit(got, j), sc.bit(base, perm[j])), j
+        for kw in ({"dirs": None}, {"far": 0.0}, {"dirs": None, "far": 0.0}):
+            plain = shafts(s, "t1", F8, pos, **kw)
+            assert (plain[~surf] == sc.low(8)).all(), kw
+            assert_mask(plain, base, f"surface pixels, {kw}", surf)
+        # the surface point itself, among other samples: whole image without a direction image, the surface with one
+        byte = s.trace_sun(sun, tau, bias=su.B10, pos=pos)
+        assert (byte[surf] == 0).sum() >= 20 and (byte[surf] == 255).sum() >= 20   # (back-lit: 809 and 21)
+        fr = np.array([0.5, 1.0, 0.25], np.float32)
+        got = shafts(s, "t1", fr, pos, dirs=None)
+        assert np.array_equal(sc.bit(got, 1), byte != 0)
+        assert_high_bits_clear(got, 3, "sigma = 1")
+        got = shafts(s, "t1", fr, pos)
+        assert np.array_equal(sc.bit(got, 1)[surf], byte[surf] != 0)
+        only = shafts(s, "t1", [1.0], pos, bias=0.0, dirs=None)
+        assert np.array_equal(only, np.where(s.trace_sun(sun, tau, bias=0.0, pos=pos) != 0, 1, 0).astype(np.uint64))
+        for bad in ((np.nan, 0.0, 1.0), (np.inf, 0.0, 0.0), (0.0, 0.0, 0.0), (0.0, -np.inf, 3.0)):
+            for n in (8, 64):
+                got = s.trace_shafts(bad, lights.shaft_fractions(n), tau, bias=su.B10, pos=pos,
+                                     dirs=sc.unit_dirs("t1"), far=13.0)
+                assert (got == sc.low(n)).all(), (bad, n)
+        # a 4-float direction image
+        d4 = np.concatenate([sc.unit_dirs("t1"), np.full(pos.shape[:2] + (1,), np.nan, np.float32)], axis=-1)
+        assert_mask(shafts(s, "t1", F8, pos, dirs=d4), base, "dirs_stride 4")
+    # the surface point itself under t3's overhead sun, where both outcomes are common
+    pos = frame("t3")["pos4"]
+    surf = sc.surface_of(pos)
+    with flake("t3") as s:
+        byte = s.trace_sun(sc.sun("t3"), sc.CASES["t3"][1], bias=su.B10, pos=pos)
+        assert (byte[surf] == 0).sum() >= 100 and (byte[surf] == 255).sum() >= 100
+        got = shafts(s, "t3", [0.75, 1.0], pos)
+        assert np.array_equal(sc.bit(got, 1), byte != 0) and (sc.bit(got, 0) != sc.bit(got, 1)).sum() >= 100
+
+
+# 4 ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,tiles", [("t3", 60), ("t1", 40)])
+def test_overflow_tiles_are_retraced_once_for_all_samples(name, tiles):
+    """max_depth = 4 provisions too few levels (the rays reach depth 6): same bits, the oracle's on its sample, and the
+    re-trace counter moved by tiles, not by tiles x samples."""
+    pos = frame(name)["pos4"]
+    with flake(name) as s:
+        base = shafts(s, name, F8, pos)
+        o0 = s.stats().overflow_tiles
+        got = shafts(s, name, F8, pos, max_depth=4)
+        moved = s.stats().overflow_tiles - o0
+    print(name, "flagged tiles", moved)
+    assert_mask(got, base, f"{name} max_depth = 4")
+    for part, every, _ in sc.PARITY[name]:
+        want, pick = sc.oracle_mask(name, F8, su.B10, "avx", every, part)
+        assert_mask(got, want, f"{name} max_depth = 4 against the oracle, {part}", pick)
+    assert 1 <= moved <= tiles
+
+
+# 5 ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,y0,x0", [("t3", 17, 30), ("t1", 9, 20)])
+def test_partial_tiles(name, y0, x0):
+    """A 13 x 11 crop (partial tiles in both directions; t1's with its direction image) equals the crop of the whole;
+    the guard words before the first and past the last mask are untouched."""
+    import torch
+    pos = frame(name)["pos4"]
+    h, w = 11, 13
+    crop = np.ascontiguousarray(pos[y0:y0 + h, x0:x0 + w])
+    D = sc.dirs_of(name)
+    dcrop = None if D is None else np.ascontiguousarray(D[y0:y0 + h, x0:x0 + w])
+    guard, sentinel = 8, 0x5a5a5a5a5a5a5a5a
+    with flake(name) as s:
+        sub = shafts(s, name, F8, pos)[y0:y0 + h, x0:x0 + w]
+        assert len(np.unique(sub)) >= 3
+        if D is not None:   # the crop holds surface pixels and marched misses
+            assert 10 <= int(sc.surface_of(crop).sum()) <= h * w - 10
+        assert_mask(shafts(s, name, F8, crop, dirs=dcrop), sub, "numpy crop")
+        pt = torch.from_numpy(crop).cuda()
+        dt = None if dcrop is None else torch.from_numpy(dcrop).cuda()
+        out = torch.full((guard + h * w + guard,), sentinel, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        shafts(s, name, F8, pt, dirs=dt, out=out.data_ptr() + 8 * guard)
+        s.Synchronize()
+        o = out.cpu().numpy().view(np.uint64)
+        assert (o[:guard] == np.uint64(sentinel)).all(), "wrote before the first pixel"
+        assert (o[guard + h * w:] == np.uint64(sentinel)).all(), "wrote past the last pixel"
+        assert_mask(o[guard:guard + h * w].reshape(h, w), sub, "torch crop")
+
+
+# 6 ---------------------------------------------------------------------------------------------------
+def test_callers_stream_between_renders_and_the_shared_mask_buffer():
+    """Render, trace_shafts on a caller's torch stream twice (the caller's buffers, the context's), Render -- no host
+    synchronisation in between; the statistics are what the renders alone leave and the later render's bits are the
+    oracle frame's. download_shadow_masks() serves trace_shafts, and a following trace_suns overwrites the buffer."""
+    import torch
+    S = pyoracle.load_setup("t1")
+    W, H = S["W"], S["H"]
+    ref = frame("t1")
+    sun, tau, far = sc.sun("t1"), sc.CASES["t1"][1], sc.CASES["t1"][2]
+    with flake("t1") as s:   # what two renders alone leave
+        s.Render(emit_aux=True)
+        s.Render(emit_aux=True)
+        s.Synchronize()
+        st0 = s.stats()
+        alone = (st0.max_depth, np.float32(st0.closest), st0.rays, st0.overflow_tiles)
+    pt = torch.from_numpy(np.ascontiguousarray(ref["pos4"])).cuda()
+    dt = torch.from_numpy(np.array(sc.unit_dirs("t1"))).cuda()
+    out = torch.full((H, W), 7, dtype=torch.int64, device="cuda")
+    ts = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    host = np.empty((H, W), np.uint64)
+    with flake("t1") as s:
+        s.Render(emit_aux=True)
+        assert s.shadow_mask_buffer() == 0
+        assert sf.lib().sf_download_shadow_masks(s.ctx, host.ctypes.data_as(ctypes.c_void_p)) == sf.SF_ESTATE
+        s.trace_shafts(sun, F8, tau, bias=su.B10, pos=pt, dirs=dt, far=far, out=out, stream=ts.cuda_stream)
+        # the context's frame, its buffer
+        assert s.trace_shafts(sun, F8[::-1], tau, dirs=dt, far=far, stream=ts.cuda_stream) is None
+        s.Render(emit_aux=True)
+        pos, nrm, mint, idx = s.download(aux=True)   # (synchronises the context, whatever stream its work ran on)
+        st = s.stats()
+        assert (st.max_depth, np.float32(st.closest), st.rays, st.overflow_tiles) == alone
+        for k, a in (("pos4", pos), ("nrm4", nrm), ("minT", mint), ("index", idx)):
+            assert same_bits(a, ref[k]), f"Render after the shaft traces: {k} differs"
+        theirs = out.cpu().numpy().view(np.uint64)
+        for part, every, _ in sc.PARITY["t1"]:
+            want, pick = sc.oracle_mask("t1", F8, su.B10, "avx", every, part)
+            assert_mask(theirs, want, f"caller's tensors, {part}", pick)
+        own = s.download_shadow_masks()
+        assert s.shadow_mask_buffer() != 0
+        for j in range(8):
+            assert np.array_equal(sc.bit(own, j), sc.bit(theirs, 7 - j)), j
+        p, keep = s.shafts_params(sun, F8)
+        assert (p.n, p.distance, p.bias, p.far, p.dirs_stride, bool(p.dirs)) == (8, 4.0, 2.0 ** -10, 0.0, 0, False)
+        # the buffer is trace_suns' too
+        D = lights.sky_dirs(3)
+        s.trace_suns(D, su.TAU, bias=su.B10)
+        assert_mask(s.download_shadow_masks(), s.trace_suns(D, su.TAU, bias=su.B10, pos=ref["pos4"]),
+                    "trace_suns after")
+
+
+# 7 ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("gain", [0.03, 0.25])
+@pytest.mark.parametrize("explicit", [False, True])
+def test_light_image_shafts_equals_the_model(gain, explicit):
+    import torch
+    n = 16
+    fr = lights.shaft_fractions(n)
+    weights = (np.arange(n, dtype=np.float32) + np.float32(1.0)) / np.float32(136.0) if explicit else None
+    sun, tau, far = sc.sun("t1"), sc.CASES["t1"][1], sc.CASES["t1"][2]
+    D = sc.unit_dirs("t1")
+    dt = torch.from_numpy(np.array(D)).cuda()
+    torch.cuda.synchronize()
+    with flake("t1") as s:
+        s.Render()
+        s.PostProcess()
+        p, keep = s.shafts_params(sun, fr)
+        col = (ctypes.c_float * 3)(*COLOUR)
+        assert sf.lib().sf_light_image_shafts(s.ctx, ctypes.byref(p), 0.25, col, None, None, None) == sf.SF_ESTATE
+        s.trace_shafts(sun, fr, tau, bias=su.B10, dirs=dt, far=far)
+        img = s.download_image()
+        pos, _, _, _ = s.download()
+        mask = s.download_shadow_masks()
+        s.light_image_shafts(fr, weights, gain, COLOUR, dirs=dt, far=far)
+        got = s.download_image()
+        # without the direction image the misses are left alone
+        s.PostProcess()
+        assert np.array_equal(s.download_image(), img)
+        s.light_image_shafts(fr, weights, gain, COLOUR)
+        plain = s.download_image()
+    want = lights.light_model_shafts(img, pos, mask, fr, weights, gain, COLOUR, D, far)
+    surf = sc.surface_of(pos)
+    assert np.array_equal(got[..., 3], img[..., 3])
+    bad = np.argwhere((got != want).any(axis=-1))
+    assert bad.size == 0, f"{len(bad)} pixels differ, first {bad[:4]}: {got[tuple(bad[0])]} != {want[tuple(bad[0])]}"
+    assert (want[surf] != img[surf]).any() and len(np.unique(want[..., :3])) > 16   # the pass did something
+    assert (want[~surf] != img[~surf]).any()                                          # ... to the marched misses too
+    assert len(np.unique(mask[surf])) >= 8 and len(np.unique(mask[~surf])) >= 8
+    assert np.array_equal(plain[~surf], img[~surf]) and np.array_equal(plain[surf], want[surf])
+    assert np.array_equal(plain, lights.light_model_shafts(img, pos, mask, fr, weights, gain, COLOUR))
+
+
+# 8 ---------------------------------------------------------------------------------------------------
+def test_error_codes():
+    import torch
+    Lb = sf.lib()
+    pos = torch.zeros((36, 64, 4), dtype=torch.float32, device="cuda")
+    dirs = torch.zeros((36, 64, 4), dtype=torch.float32, device="cuda")
+    out = torch.full((36 * 64,), 9, dtype=torch.int64, device="cuda")
+    img = torch.full((36 * 64 * 4,), 9, dtype=torch.uint8, device="cuda")
+    pp, op, ip = (ctypes.c_void_p(t.data_ptr()) for t in (pos, out, img))
+    fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    three = np.array([0.25, 0.5, 1.0], np.float32)
+    col = (ctypes.c_float * 3)(*COLOUR)
+    keep = []
+
+    def P(w=0, h=0, bias=su.B10, max_depth=0, n=3, fractions=three, weights=None, distance=4.0, far=0.0, stride=None):
+        p = sf.sf_shafts_params()
+        p.dir[:] = [0.0, 0.6, 0.8]
+        if fractions is not None:
+            fa = np.ascontiguousarray(fractions, np.float32)
+            keep.append(fa)
+            p.fractions = fp(fa)
+        if weights is not None:
+            wa = np.asarray(weights, np.float32)
+            keep.append(wa)
+            p.weights = fp(wa)
+        if stride is not None:
+            p.dirs = ctypes.cast(ctypes.c_void_p(dirs.data_ptr()), ctypes.POINTER(ctypes.c_float))
+            p.dirs_stride = stride
+        p.n, p.distance, p.bias, p.width, p.height, p.max_depth, p.far = n, distance, bias, w, h, max_depth, far
+        return ctypes.byref(p)
+
+    many = np.full(65, 0.5, np.float32)
+    with sf.Sphereflake(64, 36) as s:
+        d = sf.sf_shafts_params()
+        d.n = 5
+        assert Lb.sf_shafts_defaults(s.ctx, ctypes.byref(d)) == sf.SF_OK
+        assert Lb.sf_shafts_defaults(s.ctx, None) == sf.SF_EINVAL
+        assert (tuple(d.dir), d.distance, d.bias) == ((0.0, 0.0, 1.0), 4.0, 2.0 ** -10)
+        assert (bool(d.fractions), bool(d.weights), d.n, bool(d.dirs), d.dirs_stride, d.far) \
+            == (False, False, 0, False, 0, 0.0)
+        assert (tuple(d.origin), d.use_origin, d.width, d.height, d.max_depth, d.stream) \
+            == ((0.0, 0.0, 0.0), 0, 0, 0, 0, None)
+        assert Lb.sf_trace_shafts_to(s.ctx, P(64, 36), pp, op) == sf.SF_ENOVIEW
+        assert Lb.sf_trace_shafts(s.ctx, P()) == sf.SF_ENOVIEW
+        S = pyoracle.load_setup("t1")
+        s.SetView(S["origin"], S["tl"], S["tr"], S["bl"])
+        assert Lb.sf_light_image_shafts(s.ctx, P(), 0.25, col, pp, None, ip) == sf.SF_ESTATE   # no masks yet
+        for call in (lambda p: Lb.sf_trace_shafts_to(s.ctx, p, pp, op),
+                     lambda p: Lb.sf_light_image_shafts(s.ctx, p, 0.25, col, pp, op, ip)):
+            assert call(P(64, 36, n=0)) == sf.SF_EINVAL
+            assert call(P(64, 36, n=65, fractions=many)) == sf.SF_EINVAL
+            assert call(P(64, 36, fractions=None)) == sf.SF_EINVAL
+            for fr in ((0.25, 0.0, 1.0), (0.25, -0.5, 1.0), (0.25, 0.5, float("inf")), (float("nan"), 0.5, 1.0)):
+                assert call(P(64, 36, fractions=fr)) == sf.SF_EINVAL
+            for far in (-1.0, float("inf"), float("nan")):
+                assert call(P(64, 36, far=far)) == sf.SF_EINVAL
+                assert call(P(64, 36, far=far, stride=3)) == sf.SF_EINVAL
+            for stride in (0, 2, 5):
+                assert call(P(64, 36, far=13.0, stride=stride)) == sf.SF_EINVAL
+        assert Lb.sf_trace_shafts_to(s.ctx, P(64, 36), pp, None) == sf.SF_EINVAL
+        for bias in (-0.25, 1.0, 2.0, float("nan")):
+            assert Lb.sf_trace_shafts_to(s.ctx, P(64, 36, bias=bias), pp, op) == sf.SF_EINVAL
+        for distance in (0.0, -4.0, float("inf"), float("nan")):
+            assert Lb.sf_trace_shafts_to(s.ctx, P(64, 36, distance=distance), pp, op) == sf.SF_EINVAL
+            assert Lb.sf_trace_shafts(s.ctx, P(distance=distance)) == sf.SF_EINVAL
+        assert Lb.sf_trace_shafts_to(s.ctx, P(64, 36, max_depth=32), pp, op) == sf.SF_EINVAL
+        assert Lb.sf_trace_shafts_to(s.ctx, P(32, 16), None, op) == sf.SF_EINVAL   # sizes against a NULL pos4
+        assert Lb.sf_trace_shafts_to(s.ctx, P(64, 0), pp, op) == sf.SF_EINVAL
+        assert Lb.sf_trace_shafts(s.ctx, P(32, 16)) == sf.SF_EINVAL
+        assert Lb.sf_trace_shafts_to(None, P(64, 36), pp, op) == sf.SF_EINVAL
+        assert Lb.sf_trace_shafts_to(s.ctx, None, pp, op) == sf.SF_EINVAL
+        assert Lb.sf_light_image_shafts(s.ctx, None, 0.25, col, pp, op, ip) == sf.SF_EINVAL
+        assert Lb.sf_light_image_shafts(s.ctx, P(), 0.25, None, pp, op, ip) == sf.SF_EINVAL
+        for wts in ((0.5, -0.5, 0.5), (float("nan"), 1.0, 1.0)):
+            assert Lb.sf_light_image_shafts(s.ctx, P(weights=wts), 0.25, col, pp, op, ip) == sf.SF_EINVAL
+        for gain in (-0.1, float("inf"), float("nan")):
+            assert Lb.sf_light_image_shafts(s.ctx, P(), gain, col, pp, op, ip) == sf.SF_EINVAL
+        for bad in ((256.0, 0.0, 0.0), (0.0, -1.0, 0.0), (0.0, 0.0, float("nan"))):
+            assert Lb.sf_light_image_shafts(s.ctx, P(), 0.25, (ctypes.c_float * 3)(*bad), pp, op, ip) == sf.SF_EINVAL
+        assert Lb.sf_light_image_shafts(s.ctx, P(), 0.25, col, None, None, None) == sf.SF_ESTATE   # no image, no masks
+        assert Lb.sf_light_image_shafts(s.ctx, P(), 0.25, col, pp, op, None) == sf.SF_ESTATE       # no image
+        s.Synchronize()
+        assert (out == 9).all() and (img == 9).all()   # none of them wrote
+        # a negative weight does not bother the trace, which ignores the weights; an all-miss position image with a
+        # zero direction image: every mask has exactly its low n bits set, no ray
+        assert Lb.sf_trace_shafts_to(s.ctx, P(64, 36, weights=(0.5, -0.5, 0.5), far=13.0, stride=4), pp, op) == sf.SF_OK
+        s.Synchronize()
+        assert (out == 7).all()
+        assert s.stats().rays == 0
+        # ... and the image pass leaves every such pixel alone
+        assert Lb.sf_light_image_shafts(s.ctx, P(far=13.0, stride=4), 0.25, col, pp, op, ip) == sf.SF_OK
+        s.Synchronize()
+        assert (img == 9).all()
+        with pytest.raises(ValueError):
+            s.trace_shafts((0.0, 0.6, 0.8), many, pos=(pos.data_ptr(), 64, 36), out=out)
+        with pytest.raises(ValueError):
+            s.trace_shafts((0.0, 0.6, 0.8), np.zeros(0, np.float32), pos=(pos.data_ptr(), 64, 36), out=out)
+        with pytest.raises(ValueError):   # a direction image of another size
+            s.trace_shafts((0.0, 0.6, 0.8), three, pos=(pos.data_ptr(), 64, 36), dirs=dirs[:35], far=13.0, out=out)
