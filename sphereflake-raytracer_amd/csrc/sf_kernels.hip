@@ -50,6 +50,9 @@
 
 namespace {
 
+// Wave64 ballot straight on the compare mask (no bool -> int -> compare round trip).
+__device__ __forceinline__ uint64_t wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 // x86 rsqrtps (SIMD_AVX.h:173), reproduced exactly from the measured table.
 __device__ __forceinline__ float rsqrtps_x86(float x, const uint32_t* __restrict__ lut)
 {
@@ -78,8 +81,61 @@ __device__ __forceinline__ void normalize3(float& x, float& y, float& z, const u
     z = z * s;
 }
 
+// rsqrtps_x86 for a positive, normal, finite x: the table entry of (exponent parity, mantissa >> 13) less the
+// exponent's half -- ((E - E0) / 2) << 23 with E0 = 127 or 128 of E's parity is (E + (E & 1) - 128) << 22
+__device__ __forceinline__ float rsqrtps_pos(float x, const uint32_t* __restrict__ lut)
+{
+    const uint32_t b = __float_as_uint(x);
+    const uint32_t E = b >> 23;
+    return __uint_as_float(lut[(b >> 13) & 0x7ffu] - ((E + (E & 1u) - 128u) << 22));
+}
+
+// normalize3 (SIMD::Normalize) with rsqrtps_pos, falling back to rsqrtps_x86 for the whole wave when a live lane's
+// length is zero, denormal, negative, infinite or NaN
+__device__ __forceinline__ void normalize3_fast(float& x, float& y, float& z, const uint32_t* __restrict__ lut, bool live)
+{
+    const float len = (x * x + y * y) + z * z;
+    float nr;
+    if (wave_ballot(live && !(__float_as_uint(len) - 0x00800000u < 0x7f000000u)) != 0ull) nr = rsqrtps_x86(len, lut);
+    else nr = rsqrtps_pos(len, lut);
+    const float muls = (len * nr) * nr;
+    const float s = (0.5f * nr) * (3.0f - muls);
+    x = x * s;
+    y = y * s;
+    z = z * s;
+}
+
+// normalize3_fast for the two rays of a pair unit: one wave-uniform test over both rays' live lanes -- both rays take
+// rsqrtps_x86 if any fails it --, and otherwise both table gathers in flight before either is used (one wait)
+__device__ __forceinline__ void normalize3_fast2(float& ax, float& ay, float& az, bool liveA, float& bx, float& by, float& bz,
+                                                 bool liveB, const uint32_t* __restrict__ lut)
+{
+    const float lenA = (ax * ax + ay * ay) + az * az;
+    const float lenB = (bx * bx + by * by) + bz * bz;
+    float nrA, nrB;
+    const bool plainA = __float_as_uint(lenA) - 0x00800000u < 0x7f000000u;
+    const bool plainB = __float_as_uint(lenB) - 0x00800000u < 0x7f000000u;
+    if (__builtin_expect((wave_ballot(liveA && !plainA) | wave_ballot(liveB && !plainB)) != 0ull, 0)) {
+        nrA = rsqrtps_x86(lenA, lut);
+        nrB = rsqrtps_x86(lenB, lut);
+    } else {
+        nrA = rsqrtps_pos(lenA, lut);
+        nrB = rsqrtps_pos(lenB, lut);
+    }
+    const float sA = (0.5f * nrA) * (3.0f - (lenA * nrA) * nrA);
+    const float sB = (0.5f * nrB) * (3.0f - (lenB * nrB) * nrB);
+    ax = ax * sA;
+    ay = ay * sA;
+    az = az * sA;
+    bx = bx * sB;
+    by = by * sB;
+    bz = bz * sB;
+}
+
 // Ray direction (Sphereflake.cpp:149-150, 162-167): u = x/W, v = y/H at the pixel corner.
 // The per-context words of the constant block {rw, rh, fast_div, tx_magic} (DeviceConsts) as one scalar load
+// (the pair loop gets one vector load: forcing the scalar form there cost more scalar instructions than the vector
+// ones it saved and no fewer wave cycles, profiles/unit_path/)
 struct FrameConsts {
     float rw, rh;
     uint32_t fast_div, tx_magic;
@@ -98,8 +154,10 @@ __device__ __forceinline__ FrameConsts frame_consts(const DeviceConsts* K)
 }
 
 __device__ __forceinline__ void ray_dir(const FrameArgs& a, float x, float y, float& dx, float& dy, float& dz,
-                                        const uint32_t* __restrict__ lut, const FrameConsts* fc = nullptr)
+                                        const uint32_t* __restrict__ lut, const FrameConsts* fc = nullptr,
+                                        const bool* live = nullptr)
 {
+    // (live: the lean loops -- the lane traces this ray; the direction by normalize3_fast, in wave-uniform code)
     float u, v;
     // (uniform) RN(x / W) as one product and one fma correction (sfhost::division_by_reciprocal_exact); the
     // context's reciprocals by scalar loads from the constant block (fc: already loaded, with tile_of's word)
@@ -127,7 +185,36 @@ __device__ __forceinline__ void ray_dir(const FrameArgs& a, float x, float y, fl
     dx = ((a.tl[0] + a.dh[0] * u) + a.dv[0] * v) - a.o[0];
     dy = ((a.tl[1] + a.dh[1] * u) + a.dv[1] * v) - a.o[1];
     dz = ((a.tl[2] + a.dh[2] * u) + a.dv[2] * v) - a.o[2];
-    normalize3(dx, dy, dz, lut);
+    if (live) normalize3_fast(dx, dy, dz, lut, *live);
+    else normalize3(dx, dy, dz, lut);
+}
+
+// ray_dir for the two rays of a pair unit (pixels (xa, y) and (xb, y), the lean loop's constants): v and the three
+// dv x v products once -- the same operands, so the same floats for both --, u and the dh x u sums per ray, and the
+// two directions normalised together (normalize3_fast2)
+__device__ __forceinline__ void ray_dir_pair(const FrameArgs& a, const FrameConsts& fc, float xa, float xb, float y,
+                                             bool liveA, bool liveB, float& ax, float& ay, float& az, float& bx, float& by,
+                                             float& bz, const uint32_t* __restrict__ lut)
+{
+    float ua, ub, v;
+    if (fc.fast_div) {   // (uniform)
+        const float qa = xa * fc.rw, qb = xb * fc.rw, qv = y * fc.rh;
+        ua = __builtin_fmaf(__builtin_fmaf(-qa, a.fw, xa), fc.rw, qa);
+        ub = __builtin_fmaf(__builtin_fmaf(-qb, a.fw, xb), fc.rw, qb);
+        v = __builtin_fmaf(__builtin_fmaf(-qv, a.fh, y), fc.rh, qv);
+    } else {
+        ua = xa / a.fw;
+        ub = xb / a.fw;
+        v = y / a.fh;
+    }
+    const float vx = a.dv[0] * v, vy = a.dv[1] * v, vz = a.dv[2] * v;
+    ax = ((a.tl[0] + a.dh[0] * ua) + vx) - a.o[0];
+    ay = ((a.tl[1] + a.dh[1] * ua) + vy) - a.o[1];
+    az = ((a.tl[2] + a.dh[2] * ua) + vz) - a.o[2];
+    bx = ((a.tl[0] + a.dh[0] * ub) + vx) - a.o[0];
+    by = ((a.tl[1] + a.dh[1] * ub) + vy) - a.o[1];
+    bz = ((a.tl[2] + a.dh[2] * ub) + vz) - a.o[2];
+    normalize3_fast2(ax, ay, az, liveA, bx, by, bz, liveB, lut);
 }
 
 // Near root of RaySphereIntersection (SIMD_AVX.h:260-267); NaN when R2 < d2 (lanes that missed).
@@ -197,6 +284,19 @@ __device__ __forceinline__ void shade(float dx, float dy, float dz, const HitSta
     }
 }
 
+// shade's position and its normal before normalisation, for every lane (the lean loops shade in wave-uniform code:
+// normalize3_fast / normalize3_fast2 on the normal, then the zeros of the lanes that missed)
+__device__ __forceinline__ void hit_point(float dx, float dy, float dz, const HitState& h, float& px, float& py, float& pz,
+                                          float& nx, float& ny, float& nz)
+{
+    px = dx * h.minT;
+    py = dy * h.minT;
+    pz = dz * h.minT;
+    nx = px - h.cx;
+    ny = py - h.cy;
+    nz = pz - h.cz;
+}
+
 // max over the wave of a non-negative float (ordered as its bit pattern), all 64 lanes active.
 // DPP row operations (six v_max_u32_dpp and one v_readlane, no LDS round trip): within each row of 16 lanes by
 // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror and row_mirror -- every lane then holds its row's
@@ -220,9 +320,6 @@ __device__ __forceinline__ float wave_min(float v)
     for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, 64));
     return v;
 }
-
-// Wave64 ballot straight on the compare mask (no bool -> int -> compare round trip).
-__device__ __forceinline__ uint64_t wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
 // (lane in m) ? b : a -- one v_cndmask on an SGPR lane mask (a wave ballot), no per-lane bool
 __device__ __forceinline__ float sel_mask(float a, float b, uint64_t m)
@@ -2026,13 +2123,18 @@ __device__ __forceinline__ void write_pixel(const FrameArgs& a, const Tile& t, f
                                             const HitState& h, const uint32_t* __restrict__ lut)
 {
     float px, py, pz, nx, ny, nz;
-    shade(dx, dy, dz, h, lut, px, py, pz, nx, ny, nz);
     const size_t o = (size_t)t.orow * a.W + t.x;
-    if constexpr (LEAN) {
-        reinterpret_cast<float4*>(a.pos)[o] = make_float4(px, py, pz, 1.0f);
-        reinterpret_cast<float4*>(a.nrm)[o] = make_float4(nx, ny, nz, 1.0f);
+    if constexpr (LEAN) {   // (called by every lane, in wave-uniform code; the lanes of the frame store)
+        const bool live = t.valid && h.hit;
+        hit_point(dx, dy, dz, h, px, py, pz, nx, ny, nz);
+        normalize3_fast(nx, ny, nz, lut, live);
+        if (t.valid) {
+            reinterpret_cast<float4*>(a.pos)[o] = make_float4(live ? px : 0.f, live ? py : 0.f, live ? pz : 0.f, 1.0f);
+            reinterpret_cast<float4*>(a.nrm)[o] = make_float4(live ? nx : 0.f, live ? ny : 0.f, live ? nz : 0.f, 1.0f);
+        }
         return;
     }
+    shade(dx, dy, dz, h, lut, px, py, pz, nx, ny, nz);
     if (a.packed) {   // (uniform)
         if (a.packed >= SF_PACKED_INDEX) {
             // 4 B: the hit's heap index; the receiver rebuilds the rest. (The host selects this format only where
@@ -2054,6 +2156,28 @@ __device__ __forceinline__ void write_pixel(const FrameArgs& a, const Tile& t, f
     if (a.emit_aux) {
         if (a.min_t) a.min_t[o] = h.minT;
         if (a.hit_index) a.hit_index[o] = h.hit ? h.index : 0xffffffffu;
+    }
+}
+
+// write_pixel<true> for the two tiles of a pair unit (every lane, in wave-uniform code): both rays shaded first --
+// the two table gathers in flight together behind one wait (normalize3_fast2) --, then the misses' zeros, then the
+// four 16-byte stores: no store precedes the gathers' wait and nothing waits for a store.
+__device__ __forceinline__ void write_pair(const FrameArgs& a, const Tile& tA, const Tile& tB, const PairRay& ra,
+                                           const PairRay& rb, const uint32_t* __restrict__ lut)
+{
+    const bool liveA = tA.valid && ra.h.hit, liveB = tB.valid && rb.h.hit;
+    float pax, pay, paz, nax, nay, naz, pbx, pby, pbz, nbx, nby, nbz;
+    hit_point(ra.dx, ra.dy, ra.dz, ra.h, pax, pay, paz, nax, nay, naz);
+    hit_point(rb.dx, rb.dy, rb.dz, rb.h, pbx, pby, pbz, nbx, nby, nbz);
+    normalize3_fast2(nax, nay, naz, liveA, nbx, nby, nbz, liveB, lut);
+    const size_t o = (size_t)tA.orow * a.W + tA.x;   // (tile B: the same row, SF_TILE pixels on)
+    if (tA.valid) {
+        reinterpret_cast<float4*>(a.pos)[o] = make_float4(liveA ? pax : 0.f, liveA ? pay : 0.f, liveA ? paz : 0.f, 1.0f);
+        reinterpret_cast<float4*>(a.nrm)[o] = make_float4(liveA ? nax : 0.f, liveA ? nay : 0.f, liveA ? naz : 0.f, 1.0f);
+    }
+    if (tB.valid) {
+        reinterpret_cast<float4*>(a.pos)[o + SF_TILE] = make_float4(liveB ? pbx : 0.f, liveB ? pby : 0.f, liveB ? pbz : 0.f, 1.0f);
+        reinterpret_cast<float4*>(a.nrm)[o + SF_TILE] = make_float4(liveB ? nbx : 0.f, liveB ? nby : 0.f, liveB ? nbz : 0.f, 1.0f);
     }
 }
 
@@ -2208,7 +2332,7 @@ __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __res
         const FrameConsts fc = frame_consts(K);
         const Tile t = tile_of<true>(a, tile, lane, 0u, fc.tx_magic);
         float dx, dy, dz;
-        ray_dir(a, (float)t.x, (float)t.y, dx, dy, dz, K->lut, &fc);
+        ray_dir(a, (float)t.x, (float)t.y, dx, dy, dz, K->lut, &fc, &t.valid);
         const int32_t seed = seen.depth(flags);
         HitState h;
         int32_t maxd = -1;
@@ -2224,7 +2348,7 @@ __device__ __forceinline__ TileStats trace_tile(const FrameArgs& a, float* __res
             const uint32_t slot = wave_fetch_add(ae.counters + ae.parity, 1u);
             ae.overflow_list[slot] = tile;   // uniform value and address
         }
-        if (t.valid) write_pixel<true>(ae, t, dx, dy, dz, h, K->lut);
+        write_pixel<true>(ae, t, dx, dy, dz, h, K->lut);
         TileStats st;
         st.maxd = maxd;
         st.seed = seed;
@@ -2432,8 +2556,8 @@ __device__ __forceinline__ TileStats trace_pair(const FrameArgs& a, float* __res
     tA.valid = tA.x < a.W && tA.y < a.H;
     tB.valid = tB.x < a.W && tA.y < a.H;
     PairRay ra, rb;
-    ray_dir(a, (float)tA.x, (float)tA.y, ra.dx, ra.dy, ra.dz, K->lut, &fc);
-    ray_dir(a, (float)tB.x, (float)tB.y, rb.dx, rb.dy, rb.dz, K->lut, &fc);
+    ray_dir_pair(a, fc, (float)tA.x, (float)tB.x, (float)tA.y, tA.valid, tB.valid, ra.dx, ra.dy, ra.dz, rb.dx, rb.dy, rb.dz,
+                 K->lut);
     const int32_t seed = seen.depth(flags);
     int32_t maxd = -1;
     uint32_t status = 0u;
@@ -2462,8 +2586,7 @@ __device__ __forceinline__ TileStats trace_pair(const FrameArgs& a, float* __res
         ae.overflow_list[slot] = tile;   // uniform values and addresses
         if (n == 2u) ae.overflow_list[slot + 1u] = tile + 1u;
     }
-    if (tA.valid) write_pixel<true>(ae, tA, ra.dx, ra.dy, ra.dz, ra.h, K->lut);
-    if (tB.valid) write_pixel<true>(ae, tB, rb.dx, rb.dy, rb.dz, rb.h, K->lut);
+    write_pair(ae, tA, tB, ra, rb, K->lut);
     TileStats st;
     st.maxd = maxd;
     st.seed = seed;
@@ -3421,30 +3544,6 @@ struct UnpackLds {
     float r2_self[SF_DEPTH_TABLE];
     uint32_t first[12];   // first[c] = (9^(c+1) - 1) / 8: the first heap index of depth c + 1 (first[11]: none)
 };
-
-// rsqrtps_x86 for a positive, normal, finite x: the table entry of (exponent parity, mantissa >> 13) less the
-// exponent's half -- ((E - E0) / 2) << 23 with E0 = 127 or 128 of E's parity is (E + (E & 1) - 128) << 22
-__device__ __forceinline__ float rsqrtps_pos(float x, const uint32_t* __restrict__ lut)
-{
-    const uint32_t b = __float_as_uint(x);
-    const uint32_t E = b >> 23;
-    return __uint_as_float(lut[(b >> 13) & 0x7ffu] - ((E + (E & 1u) - 128u) << 22));
-}
-
-// normalize3 (SIMD::Normalize) with rsqrtps_pos, falling back to rsqrtps_x86 for the whole wave when a live lane's
-// length is zero, denormal, negative, infinite or NaN
-__device__ __forceinline__ void normalize3_fast(float& x, float& y, float& z, const uint32_t* __restrict__ lut, bool live)
-{
-    const float len = (x * x + y * y) + z * z;
-    float nr;
-    if (wave_ballot(live && !(__float_as_uint(len) - 0x00800000u < 0x7f000000u)) != 0ull) nr = rsqrtps_x86(len, lut);
-    else nr = rsqrtps_pos(len, lut);
-    const float muls = (len * nr) * nr;
-    const float s = (0.5f * nr) * (3.0f - muls);
-    x = x * s;
-    y = y * s;
-    z = z * s;
-}
 
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void sf_slab_unpack4(
     FrameArgs a, const uint32_t* __restrict__ stage, const float4* __restrict__ table, uint32_t table_depth,
