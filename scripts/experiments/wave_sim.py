@@ -44,7 +44,7 @@ L.wsim_depth8.argtypes = [ctypes.c_float, fp]
 
 
 def run(name="c3", tile_step=1, mode=0, check=True, split=(0, 0)):
-    s = pyoracle.load_setup(name)
+    s = name if isinstance(name, dict) else pyoracle.load_setup(name)   # (a setup of the caller's own, or a fixture's)
     W, H = int(s["W"]), int(s["H"])
     lut = np.ascontiguousarray(pyoracle.load_lut(), np.uint32)
     f32 = lambda a: np.ascontiguousarray(a, np.float32)

@@ -23,7 +23,7 @@ from test_gpu_lean_tile import (MISS, SCHEDULES, assert_golden, assert_oracle, a
 
 PAIR_SCHEDULES = ["rowmajor", "ordered"]
 ENV_KEYS = SCHEDULES["rowmajor"].keys() | SCHEDULES["ordered"].keys() | {"SF_LEAN", "SF_FLAGS", "SF_PAIR", "SF_LEVELS",
-                                                                        "SF_TIE_INLINE"}
+                                                                        "SF_TIE_INLINE", "SF_MAX_BLOCKS"}
 EDGE_W, EDGE_H, EDGE_YAW = 128, 72, 0.2   # the view whose flake ends inside the frame (edge_view)
 
 
@@ -33,9 +33,10 @@ def device():
     assert sf.device_count() >= 1, "no HIP device visible: GPU tests must run on an MI355X"
 
 
-def render_frames(view, size, env, monkeypatch, n, pair, **kw):
-    """n renders after a reset (no aux channels) in a fresh context under `env` and SF_PAIR=`pair`:
-    [((pos, nrm), stats)], the launches that took the pair loop, and those that took a lean loop."""
+def render_frames(view, size, env, monkeypatch, n, pair, variant=None, **kw):
+    """n renders after a reset (no aux channels) in a fresh context under `env` and SF_PAIR=`pair` (in the reference
+    variant `variant` where given): [((pos, nrm), stats)], the launches that took the pair loop, and those that took
+    a lean loop."""
     for k in ENV_KEYS:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
@@ -43,6 +44,8 @@ def render_frames(view, size, env, monkeypatch, n, pair, **kw):
     monkeypatch.setenv("SF_PAIR", pair)
     frames = []
     with sf.Sphereflake(*size) as s:
+        if variant is not None:
+            s.SetVariant(variant)
         s.SetView(*view)
         s.reset_stats()
         for _ in range(n):
