@@ -514,6 +514,84 @@ int sf_trace_shafts(sf_ctx* ctx, const sf_shafts_params* params);
 int sf_light_image_shafts(sf_ctx* ctx, const sf_shafts_params* params, float gain, const float colour[3],
                           const float* pos4, const uint64_t* mask, uint8_t* rgba);
 
+/* --- the colour light buffer: sum any number of suns and lights while tracing -- */
+/* The image passes above each MULTIPLY the 8-bit image in place, so a second call cannot add a light, a launch stops at
+   64 entries, and a weight is one grey float. The light buffer removes all three limits: a width x height image of
+   float4 (row-major as the G-buffer; .xyz the RGB irradiance factor, .w reserved: written 0 by an overwriting call and
+   carried through by an accumulating one) that the two summing traces below ADD into while they trace, each entry with
+   its own RGB colour, and that sf_light_image_buffer applies to the image once, at the end. The context owns one,
+   allocated on first use; a caller's DEVICE buffer of width * height * 4 floats (16-byte aligned) serves as well.
+   DEFINITION OF THE SUM (exact; binary32, round to nearest, every operation rounded on its own, no fused
+   multiply-add). For pixel p with P = pos4[p].xyz and N = nrm4[p].xyz:
+     1. base = accumulate ? out[p] : (0, 0, 0, 0).
+     2. P == (0, 0, 0) is a miss of the frame: an accumulating call does not write out[p], an overwriting call writes
+        (0, 0, 0, 0).
+     3. Otherwise S = base.xyz, and then for i = 0 .. n-1 IN THAT ORDER, per channel c,
+        S.c = S.c + colours[i].c (lit_i ? lam_i : 0). lit_i is bit i as sf_trace_suns_to (sf_trace_shadows_to) defines
+        it for entry i alone, with the same distance, bias, origin, position image and shadow LOD constant: an entry
+        that traces no ray -- a zero or non-finite direction or light -- is lit. lam_i is exactly the term of
+        sf_light_image_suns, max(0, (N.x s.x + N.y s.y) + N.z s.z), or of sf_light_image_many, max(0, dot / len) with
+        dot and len as sf_light_image forms them; 0 where that is NaN.
+     4. out[p] = (S, base.w).
+   CONSEQUENCES, both bit for bit:
+   - A call with n entries equals an overwriting call with the first k followed by an accumulating call with the rest,
+     for every k. That is how n > 64 is carried out: one launch per 64 entries on the stream.
+   - The result equals the host sum over the masks that sf_trace_suns_to (sf_trace_shadows_to) gives for consecutive
+     chunks of 64 entries (sphereflake_amd/lights.py: sum_model).
+   With one overwriting sf_trace_suns_sum of n <= 64 directions and colours (w_i, w_i, w_i), sf_light_image_buffer makes
+   the image of sf_light_image_suns with ambient 0, byte for byte (0 + (1 - 0) S is S); likewise the point lights and
+   sf_light_image_many. */
+#define SF_LIGHT_SUM_MAX 65536
+typedef struct sf_light_sum_params {
+    const float* points;      /* HOST, n x 3 floats: directions towards the sun (the suns call) or light positions (the
+                                 shadows call), world space, used as given; read before the call returns */
+    const float* colours;     /* HOST, n x 3 floats (r, g, b per entry), each finite and >= 0, or NULL = every
+                                 component (float)1 / (float)n; read before the call returns */
+    uint32_t n;               /* 1 .. SF_LIGHT_SUM_MAX */
+    uint32_t accumulate;      /* 0 = overwrite the output, 1 = add to what it holds */
+    float distance;           /* tau, the suns call only: as sf_suns_params.distance (sf_light_sum_defaults: 4) */
+    float bias;               /* as sf_suns_params.bias / sf_shadows_params.bias */
+    float origin[3];          /* as sf_sun_params.origin */
+    uint32_t use_origin;      /* as sf_sun_params.use_origin */
+    uint32_t width, height;   /* as sf_sun_params */
+    uint32_t max_depth;       /* as sf_suns_params.max_depth / sf_shadows_params.max_depth */
+    void* stream;             /* NULL = the context stream */
+} sf_light_sum_params;
+
+/* Zeroed (n = 0, points NULL: the caller sets both; overwriting), distance 4, the default bias of sf_shadow_defaults. */
+int sf_light_sum_defaults(const sf_ctx* ctx, sf_light_sum_params* params);
+/* The sum over sun directions. pos4, nrm4 and out are DEVICE pointers; NULL selects the context's G-buffer (positions,
+   normals) and light buffer, at the context's size only. Asynchronous on the stream and ordered with the context's
+   other calls; one launch pair per 64 entries; no statistic and none of the renders' state touched; re-traced tiles
+   count in overflow_tiles once per launch that re-traced them. SF_EINVAL for n == 0, n > SF_LIGHT_SUM_MAX, a null
+   points, a colour component that is negative, infinite or NaN, and everything sf_trace_suns_to rejects; SF_ESTATE
+   for a null out before anything has written the context's light buffer. A failing call writes nothing. */
+int sf_trace_suns_sum_to(sf_ctx* ctx, const sf_light_sum_params* params, const float* pos4, const float* nrm4,
+                         float* out);
+/* The context's G-buffer into the context's light buffer, which an overwriting call allocates on first use
+   (SF_ESTATE for an accumulating call before anything has written it). */
+int sf_trace_suns_sum(sf_ctx* ctx, const sf_light_sum_params* params);
+/* The same for point lights: points are light positions, lit_i and lam_i those of sf_trace_shadows_to and
+   sf_light_image_many; distance is not used. Errors as above, with sf_trace_shadows_to's in place of
+   sf_trace_suns_to's. */
+int sf_trace_shadows_sum_to(sf_ctx* ctx, const sf_light_sum_params* params, const float* pos4, const float* nrm4,
+                            float* out);
+int sf_trace_shadows_sum(sf_ctx* ctx, const sf_light_sum_params* params);
+/* The ambient term: every pixel of buf (DEVICE, NULL = the context's light buffer, allocated here on first use) becomes
+   (r, g, b, 0). Asynchronous on the stream (NULL = the context stream). SF_EINVAL for a component that is negative,
+   infinite or NaN. */
+int sf_light_fill(sf_ctx* ctx, const float rgb[3], float* buf, void* stream);
+/* The context's light buffer (DEVICE), and a synchronous copy of it to width * height * 4 HOST floats. SF_ESTATE before
+   anything has written it. */
+int sf_light_buffer(sf_ctx* ctx, float** buf);
+int sf_download_light(sf_ctx* ctx, float* buf4);
+/* The resolve pass: what the sf_light_image passes are to a mask, for the buffer. A frame miss (P == 0) is left
+   untouched; else with E = buf[p] each of r, g, b with float value c becomes (uint8) min(c E.c + 0.5f, 255), one
+   rounding per operation; alpha stays. NULL pos4 / buf / rgba select the context's G-buffer, light buffer and image;
+   SF_ESTATE where a context buffer selected that way was never written. Asynchronous on the stream (NULL = the
+   context stream). sphereflake_amd/lights.py: light_model_buffer. */
+int sf_light_image_buffer(sf_ctx* ctx, void* stream, const float* pos4, const float* buf, uint8_t* rgba);
+
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the
    work units of all n frames from one set of tile queues -- a wave whose frame runs dry goes on with the next

@@ -296,6 +296,45 @@ public:
         std::lock_guard<FairMutex> lk(m_Mutex);
         Check(sf_light_image_shafts(m_Ctx, &params, gain, colour, positions4, masks, rgba));
     }
+    // The colour light buffer (new; sf_trace_suns_sum_to / sf_trace_shadows_sum_to, sf.h): any number of sun directions
+    // or point lights, each with an RGB colour, ADDED per pixel into a float4 image while they are traced (params.accumulate:
+    // onto what it holds). DEVICE pointers, asynchronous; null pointers select this object's own frame and light buffer.
+    void TraceSunsSum(const sf_light_sum_params& params, const float* positions4, const float* normals4, float* light4)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_suns_sum_to(m_Ctx, &params, positions4, normals4, light4));
+    }
+    // ... of this object's own device frame into its own light buffer (sf_download_light, LightImageBuffer)
+    void TraceSunsSum(const sf_light_sum_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_suns_sum(m_Ctx, &params));
+    }
+    void TraceShadowsSum(const sf_light_sum_params& params, const float* positions4, const float* normals4,
+                         float* light4)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_shadows_sum_to(m_Ctx, &params, positions4, normals4, light4));
+    }
+    void TraceShadowsSum(const sf_light_sum_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_shadows_sum(m_Ctx, &params));
+    }
+    // The ambient term: every pixel of the light buffer becomes (r, g, b, 0) (sf_light_fill); null = this object's own.
+    void LightFill(const float rgb[3], float* light4 = nullptr, void* stream = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_fill(m_Ctx, rgb, light4, stream));
+    }
+    // The light buffer on the image of an SSAO::Render(), in place (sf_light_image_buffer); null pointers select this
+    // object's own frame, light buffer and image.
+    void LightImageBuffer(void* stream = nullptr, const float* positions4 = nullptr, const float* light4 = nullptr,
+                          uint8_t* rgba = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_image_buffer(m_Ctx, stream, positions4, light4, rgba));
+    }
 
     // the device frame, downloaded into the vectors when it is newer than their contents (Refresh)
     const GBuffer& GetGBuffer() const

@@ -92,6 +92,21 @@ extern "C" __global__ void sf_trace_shafts_fixup(FrameArgs a, const float* pos4,
 extern "C" __global__ void sf_light_image_shafts_px(uint32_t W, uint32_t H, const float* pos4, const uint64_t* mask,
                                                     ShaftArgs sh, float gain, float cr, float cg, float cb,
                                                     uint8_t* rgba);
+extern "C" __global__ void sf_trace_suns_sum_wave(FrameArgs a, const float* pos4, const float* nrm4, SunSum ss,
+                                                  float* out, uint32_t groups, uint32_t* overflow_list,
+                                                  uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_suns_sum_fixup(FrameArgs a, const float* pos4, const float* nrm4, SunSum ss,
+                                                   float* out, const uint32_t* overflow_list, uint32_t* counters,
+                                                   uint32_t parity);
+extern "C" __global__ void sf_trace_shadows_sum_wave(FrameArgs a, const float* pos4, const float* nrm4, ShadowSum ss,
+                                                     float* out, uint32_t groups, uint32_t* overflow_list,
+                                                     uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_shadows_sum_fixup(FrameArgs a, const float* pos4, const float* nrm4, ShadowSum ss,
+                                                      float* out, const uint32_t* overflow_list, uint32_t* counters,
+                                                      uint32_t parity);
+extern "C" __global__ void sf_light_fill_px(uint32_t n, float r, float g, float b, float* buf);
+extern "C" __global__ void sf_light_image_buffer_px(uint32_t W, uint32_t H, const float* pos4, const float* buf,
+                                                    uint8_t* rgba);
 extern "C" __global__ void sf_band_unpack(FrameArgs a, const float4* stage, uint32_t stage_rows, uint32_t band_rows,
                                            uint32_t n, uint32_t first, uint32_t members, uint32_t row0);
 extern "C" __global__ void sf_node_table(FrameArgs a, float4* table, uint32_t nodes);
@@ -394,6 +409,7 @@ struct sf_ctx {
     uint8_t* image = nullptr;          // W x H RGBA8
     uint8_t* shadow = nullptr;         // W x H visibility bytes (sf_trace_shadow): lazily allocated
     uint64_t* shadow_masks = nullptr;  // W x H visibility masks (sf_trace_shadows): lazily allocated
+    float* light = nullptr;            // W x H float4 light buffer (sf_light_fill, sf_trace_suns_sum): lazily allocated
     int centre_exact = -1;             // sfhost::post_centre_exact(W) && (H), cached
 };
 
@@ -509,6 +525,7 @@ static void free_ctx(sf_ctx* c)
     (void)hipFree(c->image);
     (void)hipFree(c->shadow);
     (void)hipFree(c->shadow_masks);
+    (void)hipFree(c->light);
     for (int i = 0; i < sf_ctx::kTimed; ++i)
         for (int j = 0; j < 2; ++j)
             if (c->ev[i][j]) (void)hipEventDestroy(c->ev[i][j]);
@@ -1953,6 +1970,204 @@ int sf_light_image_shafts(sf_ctx* c, const sf_shafts_params* p, float gain, cons
     hipLaunchKernelGGL(sf_light_image_shafts_px, grid, dim3(256), 0, s, c->W, c->H,
                        pos4 ? pos4 : (const float*)c->pos, mask ? mask : (const uint64_t*)c->shadow_masks, sh, gain,
                        colour[0], colour[1], colour[2], rgba ? rgba : c->image);
+    SF_HIP(c, hipGetLastError());
+    return SF_OK;
+}
+
+// The colour light buffer and the traces that add into it (kernels sf_trace_suns_sum_wave / _fixup,
+// sf_trace_shadows_sum_wave / _fixup, sf_light_fill_px, sf_light_image_buffer_px). The launches of
+// sf_trace_suns_to / sf_trace_shadows_to, once per chunk of SF_LIGHT_SUM_CHUNK entries: the first chunk with the
+// caller's accumulate, the rest accumulating, all on one stream.
+static_assert(sizeof(FrameArgs) + sizeof(SunSum) + 64 <= 4096, "kernel argument segment");
+static_assert(sizeof(FrameArgs) + sizeof(ShadowSum) + 64 <= 4096, "kernel argument segment");
+
+int sf_light_sum_defaults(const sf_ctx* c, sf_light_sum_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->distance = 4.0f;
+    p->bias = kShadowBias;
+    return SF_OK;
+}
+
+// a colour component: finite and not negative (NaN fails the compare)
+static bool light_component(float v) { return v >= 0.0f && !std::isinf(v); }
+
+// The context's light buffer, allocated on first use (every call that allocates it writes all of it).
+static int own_light_buffer(sf_ctx* c)
+{
+    if (c->light) return SF_OK;
+    DevGuard g(c->device);
+    SF_HIP(c, hipMalloc(&c->light, (size_t)c->W * c->H * 16));
+    return SF_OK;
+}
+
+// Everything both summing traces check, in one place; the images' sizes come back in `im`.
+static int light_sum_check(const sf_ctx* c, const sf_light_sum_params* p, bool suns, const float* pos4,
+                           bool ctx_buffer, ShadowImage* im)
+{
+    if (p->n == 0u || p->n > SF_LIGHT_SUM_MAX || !p->points) return SF_EINVAL;
+    if (p->colours)
+        for (uint32_t i = 0; i < 3u * p->n; ++i)
+            if (!light_component(p->colours[i])) return SF_EINVAL;
+    if (suns && (!(p->distance > 0.0f) || std::isinf(p->distance))) return SF_EINVAL;   // (NaN fails the compare)
+    if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, im)) return rc;
+    if (ctx_buffer && (im->W != c->W || im->H != c->H)) return SF_EINVAL;   // (a context buffer, at its size only)
+    return SF_OK;
+}
+
+static int trace_sum_to(sf_ctx* c, const sf_light_sum_params* p, bool suns, const float* pos4, const float* nrm4,
+                        float* out)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    ShadowImage im;
+    if (int rc = light_sum_check(c, p, suns, pos4, !nrm4 || !out, &im)) return rc;
+    if (!out && !c->light) return SF_ESTATE;
+    float* const dst = out ? out : c->light;
+    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
+    FrameArgs a = shadow_frame_args(c, im);
+    float o[3], keep;
+    shadow_origin(c, p->use_origin, p->origin, p->bias, o, &keep);
+    const float even = 1.0f / (float)p->n;
+    for (uint32_t first = 0; first < p->n; first += SF_LIGHT_SUM_CHUNK) {
+        const uint32_t m = p->n - first < SF_LIGHT_SUM_CHUNK ? p->n - first : SF_LIGHT_SUM_CHUNK;
+        const uint32_t accumulate = (first || p->accumulate) ? 1u : 0u;
+        const float* const pts = p->points + (size_t)3 * first;
+        const float* const col = p->colours ? p->colours + (size_t)3 * first : nullptr;
+        int rc;
+        if (suns) {
+            SunSum ss;
+            std::memset(&ss, 0, sizeof ss);
+            for (int k = 0; k < 3; ++k) ss.o[k] = o[k];
+            ss.keep = keep;
+            ss.n = m;
+            ss.accumulate = accumulate;
+            for (uint32_t i = 0; i < m; ++i)
+                for (int k = 0; k < 3; ++k) {
+                    ss.s[i][k] = pts[3 * i + k];
+                    ss.f[i][k] = pts[3 * i + k] * p->distance;   // (one rounding: step 2 of sf_trace_sun_to's definition)
+                    ss.c[i][k] = col ? col[3 * i + k] : even;
+                }
+            a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
+            rc = list_trace(
+                c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
+                (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
+                [&](const ListLaunch& l) { l.wave(sf_trace_suns_sum_wave, a, im.pos4, nrm, ss, dst); },
+                [&](const ListLaunch& l) { l.fixup(sf_trace_suns_sum_fixup, a, im.pos4, nrm, ss, dst); });
+        } else {
+            ShadowSum ss;
+            std::memset(&ss, 0, sizeof ss);
+            for (int k = 0; k < 3; ++k) ss.o[k] = o[k];
+            ss.keep = keep;
+            ss.n = m;
+            ss.accumulate = accumulate;
+            uint32_t levels = p->max_depth;
+            for (uint32_t i = 0; i < m; ++i) {
+                for (int k = 0; k < 3; ++k) {
+                    ss.l[i][k] = pts[3 * i + k];
+                    ss.c[i][k] = col ? col[3 * i + k] : even;
+                }
+                if (p->max_depth) continue;   // (else the largest geometric bound over the chunk, as sf_trace_shadows_to)
+                const float centre[3] = { 0.0f - ss.l[i][0], 0.0f - ss.l[i][1], 0.0f - ss.l[i][2] };
+                if (!std::isfinite(centre[0] + centre[1] + centre[2])) continue;   // (traces nothing)
+                bool bounded = false;
+                const uint32_t li = geometric_levels(c->host_shadow_consts.dt, centre, &bounded);
+                if (li > levels) levels = li;
+            }
+            for (int k = 0; k < 3; ++k) a.root[9 + k] = 0.0f;   // (the kernel stages each light's own translation)
+            a.max_depth = clamp_levels(levels);
+            rc = list_trace(
+                c, p->stream, im.groups, (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4,
+                (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, SF_PROG_FIXUP_BLOCKS,
+                [&](const ListLaunch& l) { l.wave(sf_trace_shadows_sum_wave, a, im.pos4, nrm, ss, dst); },
+                [&](const ListLaunch& l) { l.fixup(sf_trace_shadows_sum_fixup, a, im.pos4, nrm, ss, dst); });
+        }
+        if (rc != SF_OK) return rc;
+    }
+    return SF_OK;
+}
+
+// The context's G-buffer into the context's light buffer: an overwriting call makes the buffer, an accumulating one
+// needs it written.
+static int trace_sum_own(sf_ctx* c, const sf_light_sum_params* p, bool suns)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!c->light) {
+        ShadowImage im;   // (the parameters' errors come before the buffer's state)
+        if (int rc = light_sum_check(c, p, suns, nullptr, true, &im)) return rc;
+        if (p->accumulate) return SF_ESTATE;
+        if (int rc = own_light_buffer(c)) return rc;
+    }
+    return trace_sum_to(c, p, suns, nullptr, nullptr, nullptr);
+}
+
+int sf_trace_suns_sum_to(sf_ctx* c, const sf_light_sum_params* p, const float* pos4, const float* nrm4, float* out)
+{
+    return trace_sum_to(c, p, true, pos4, nrm4, out);
+}
+
+int sf_trace_suns_sum(sf_ctx* c, const sf_light_sum_params* p) { return trace_sum_own(c, p, true); }
+
+int sf_trace_shadows_sum_to(sf_ctx* c, const sf_light_sum_params* p, const float* pos4, const float* nrm4, float* out)
+{
+    return trace_sum_to(c, p, false, pos4, nrm4, out);
+}
+
+int sf_trace_shadows_sum(sf_ctx* c, const sf_light_sum_params* p) { return trace_sum_own(c, p, false); }
+
+int sf_light_buffer(sf_ctx* c, float** buf)
+{
+    if (!c || !buf) return SF_EINVAL;
+    if (!c->light) return SF_ESTATE;
+    *buf = c->light;
+    return SF_OK;
+}
+
+int sf_download_light(sf_ctx* c, float* buf4)
+{
+    if (!c || !buf4) return SF_EINVAL;
+    if (!c->light) return SF_ESTATE;
+    int rc = sf_synchronize(c);
+    if (rc != SF_OK) return rc;
+    DevGuard g(c->device);
+    SF_HIP(c, hipMemcpy(buf4, c->light, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
+    return SF_OK;
+}
+
+// One thread per pixel of the context's frame; a null buf is the context's buffer, made here if need be.
+int sf_light_fill(sf_ctx* c, const float rgb[3], float* buf, void* stream)
+{
+    if (!c || !rgb) return SF_EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (!light_component(rgb[k])) return SF_EINVAL;
+    if (!buf)
+        if (int rc = own_light_buffer(c)) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    const uint32_t n = c->W * c->H;
+    hipLaunchKernelGGL(sf_light_fill_px, dim3((n + 255u) / 256u), dim3(256), 0, s, n, rgb[0], rgb[1], rgb[2],
+                       buf ? buf : c->light);
+    SF_HIP(c, hipGetLastError());
+    return SF_OK;
+}
+
+// The resolve pass: one thread per pixel of the context's frame, the buffers defaulted to the context's.
+int sf_light_image_buffer(sf_ctx* c, void* stream, const float* pos4, const float* buf, uint8_t* rgba)
+{
+    if (!c) return SF_EINVAL;
+    if (!rgba && !c->image) return SF_ESTATE;
+    if (!buf && !c->light) return SF_ESTATE;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
+    hipLaunchKernelGGL(sf_light_image_buffer_px, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
+                       buf ? buf : (const float*)c->light, rgba ? rgba : c->image);
     SF_HIP(c, hipGetLastError());
     return SF_OK;
 }

@@ -248,6 +248,28 @@ struct ShaftArgs {
     float w[SF_SHAFT_SAMPLES];        // their weights (sf_light_image_shafts; unused by the trace)
 };
 
+// The summing traces (sf_trace_suns_sum_to, sf_trace_shadows_sum_to): one chunk of up to SF_LIGHT_SUM_CHUNK entries of
+// the call travels by value in the kernel argument segment beside the FrameArgs (2328 B / 1560 B; indexed with a
+// uniform index they are scalar loads). The C entry point launches once per chunk.
+#define SF_LIGHT_SUM_CHUNK 64u        // one bit of the traversal's 64-bit word per entry
+struct SunSum {
+    float o[3];                       // the origin the position image is relative to
+    float keep;                       // 1 - bias
+    uint32_t n;                       // directions of this chunk, 1..SF_LIGHT_SUM_CHUNK
+    uint32_t accumulate;              // 0: the base is 0, 1: the base is what the output holds
+    float f[SF_LIGHT_SUM_CHUNK][3];   // s_i tau per component (the trace)
+    float s[SF_LIGHT_SUM_CHUNK][3];   // the directions as given (the Lambert term)
+    float c[SF_LIGHT_SUM_CHUNK][3];   // their colours
+};
+struct ShadowSum {
+    float o[3];
+    float keep;
+    uint32_t n;                       // lights of this chunk, 1..SF_LIGHT_SUM_CHUNK
+    uint32_t accumulate;
+    float l[SF_LIGHT_SUM_CHUNK][3];   // the lights (world)
+    float c[SF_LIGHT_SUM_CHUNK][3];   // their colours
+};
+
 // Multi-frame persistent trace (round 6, sf_render_frames): the frames of one launch, passed by value in the kernel
 // argument segment (copied by the runtime at the launch, so the host may build the next batch at once; 4 KB at most:
 // 11 FrameArgs). Frame f is one slot context's view into that context's G-buffer and stats. All frames share one

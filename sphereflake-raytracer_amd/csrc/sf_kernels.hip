@@ -4632,7 +4632,209 @@ __device__ __forceinline__ void trace_suns_group(const FrameArgs& a, const float
     if (g.valid) mask[(size_t)g.y * a.W + g.x] = all & ~shadowed;
 }
 
+// ---- the summing traces (sf_trace_suns_sum_to, sf_trace_shadows_sum_to): the loops of
+// trace_suns_group and trace_shadows_group with another ending. Across the traversals a lane carries what it carries
+// there -- its position, the 64-bit `shadowed` word, the surface flag; the normal, the base and the three sums exist
+// only in the ending (light_sum_store), which adds colour_i (lit_i ? lam_i : 0) per channel in index order onto the
+// base and makes one 16-byte vector store. A tile flagged for more levels is re-traced for ALL of the chunk's entries,
+// so its first pass stores nothing (the flag is uniform and known when the loop ends): an accumulating call would
+// otherwise add the chunk twice. The fixup kernel reads the base, sums and stores.
+
+// The ending for a lane of a tile that is not flagged. lam(i) is the Lambert term of entry i at the lane's pixel.
+template <class Sum, class Lam>
+__device__ __forceinline__ void light_sum_store(const FrameArgs& a, const GroupLane& g, bool surface, uint64_t shadowed,
+                                                const Sum& ss, float4* __restrict__ out, Lam lam)
+{
+    if (!g.valid) return;   // (a partial tile: nothing outside the image)
+    float4* const o = out + ((size_t)g.y * a.W + g.x);
+    if (!surface) {   // a miss of the frame: an accumulating call leaves it, an overwriting one zeroes it
+        if (!ss.accumulate) *o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    float4 S = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (ss.accumulate) S = *o;   // (uniform)
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0u; i < ss.n; ++i) {
+        const float k = ((shadowed >> i) & 1ull) ? 0.0f : lam(i);
+        S.x = __fadd_rn(S.x, __fmul_rn(ss.c[i][0], k));
+        S.y = __fadd_rn(S.y, __fmul_rn(ss.c[i][1], k));
+        S.z = __fadd_rn(S.z, __fmul_rn(ss.c[i][2], k));
+    }
+    *o = S;   // (.w: the base's)
+}
+
+template <bool FIXUP>
+__device__ __forceinline__ void trace_suns_sum_group(const FrameArgs& a, const float4* __restrict__ pos4,
+                                                     const float4* __restrict__ nrm4, const SunSum& ss,
+                                                     float4* __restrict__ out, float* __restrict__ L,
+                                                     const float4 bcol, uint32_t group, uint32_t levels,
+                                                     uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const GroupLane g = tile_lane(a, group);
+    const float4 P = pos4[g.ray];
+    const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    const uint32_t n = ss.n;   // (uniform, 1..64)
+    uint64_t shadowed = 0ull;   // bit i: direction i's ray to the lane's pixel is stopped
+    uint32_t status = 0u;
+    if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss)
+        const float wx = __fadd_rn(ss.o[0], P.x), wy = __fadd_rn(ss.o[1], P.y), wz = __fadd_rn(ss.o[2], P.z);
+        const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;
+        float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0u; i < n; ++i) {   // (trace_suns_group's loop)
+            const float Fx = __fadd_rn(wx, ss.f[i][0]), Fy = __fadd_rn(wy, ss.f[i][1]), Fz = __fadd_rn(wz, ss.f[i][2]);
+            float dx, dy, dz, bound;
+            shadow_ray(wx, wy, wz, Fx, Fy, Fz, ss.keep, K->lut, dx, dy, dz, bound);
+            const float rx = __fsub_rn(0.0f, Fx), ry = __fsub_rn(0.0f, Fy), rz = __fsub_rn(0.0f, Fz);
+            const bool on = surface && finite3(dx, dy, dz);
+            if (wave_ballot(on) == 0ull) continue;   // (uniform: the entry traces no ray and is lit)
+            HitState h;
+            h.hit = false;
+            int32_t md = -1;
+            uint32_t st = 0u;
+            lds_fence();
+            traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, st, culls, bound);
+            status |= st;
+            shadowed |= h.hit ? (1ull << i) : 0ull;
+        }
+    }
+    if (!FIXUP && status != 0u) {   // (uniform) more levels needed: the fixup kernel sums and stores this tile
+        flag_group(overflow_list, overflow_count, group);
+        return;
+    }
+    float4 N = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (surface) N = nrm4[g.ray];
+    // sf_light_image_suns_px's lam
+    light_sum_store(a, g, surface, shadowed, ss, out, [&](uint32_t i) {
+        const float sx = ss.s[i][0], sy = ss.s[i][1], sz = ss.s[i][2];
+        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(N.x, sx), __fmul_rn(N.y, sy)), __fmul_rn(N.z, sz));
+        return fmaxf(0.0f, dot);   // (a NaN product gives 0)
+    });
+}
+
+template <bool FIXUP>
+__device__ __forceinline__ void trace_shadows_sum_group(const FrameArgs& a, const float4* __restrict__ pos4,
+                                                        const float4* __restrict__ nrm4, const ShadowSum& ss,
+                                                        float4* __restrict__ out, float* __restrict__ L,
+                                                        const float4 bcol, uint32_t group, uint32_t levels,
+                                                        uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const GroupLane g = tile_lane(a, group);
+    const float4 P = pos4[g.ray];
+    const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    const uint32_t n = ss.n;   // (uniform, 1..64)
+    const float wx = __fadd_rn(ss.o[0], P.x), wy = __fadd_rn(ss.o[1], P.y), wz = __fadd_rn(ss.o[2], P.z);
+    uint64_t shadowed = 0ull;   // bit i: light i does not reach the lane's pixel
+    uint32_t status = 0u;
+    if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss)
+        const uint32_t culls = a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST);
+        lds_fence();
+        stage_root(L, a.root);   // the columns, once per tile; each light restages its translation
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0u; i < n; ++i) {   // (trace_shadows_group's loop)
+            const float lx = ss.l[i][0], ly = ss.l[i][1], lz = ss.l[i][2];
+            float dx, dy, dz, bound;
+            shadow_ray(wx, wy, wz, lx, ly, lz, ss.keep, K->lut, dx, dy, dz, bound);
+            const bool on = surface && finite3(dx, dy, dz);
+            const uint64_t onm = wave_ballot(on);
+            if (onm == 0ull) continue;   // (uniform: the entry traces no ray and is lit)
+            const uint32_t axl = axis_lane(onm, g.mid);
+            const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
+            float r[12];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) r[k] = 0.0f;
+            r[9] = __fsub_rn(0.0f, lx);
+            r[10] = __fsub_rn(0.0f, ly);
+            r[11] = __fsub_rn(0.0f, lz);
+            lds_fence();
+            stage_root_translation(L, r[9], r[10], r[11]);
+            HitState h;
+            h.hit = false;
+            int32_t md = -1;
+            uint32_t st = 0u;
+            traverse_ray<false, false, true>(K, r, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az, on, h,
+                                                    md, st, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
+            status |= st;
+            shadowed |= h.hit ? (1ull << i) : 0ull;
+        }
+    }
+    if (!FIXUP && status != 0u) {   // (uniform) more levels needed: the fixup kernel sums and stores this tile
+        flag_group(overflow_list, overflow_count, group);
+        return;
+    }
+    float4 N = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (surface) N = nrm4[g.ray];
+    // sf_light_image_many_px's lam, operation for operation
+    light_sum_store(a, g, surface, shadowed, ss, out, [&](uint32_t i) {
+        const float lx = ss.l[i][0], ly = ss.l[i][1], lz = ss.l[i][2];
+        const float dx = __fadd_rn(__fsub_rn(wx, lx), 0.0f);
+        const float dy = __fadd_rn(__fsub_rn(wy, ly), 0.0f);
+        const float dz = __fadd_rn(__fsub_rn(wz, lz), 0.0f);
+        const float len =
+            __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+        const float ex = __fsub_rn(lx, wx), ey = __fsub_rn(ly, wy), ez = __fsub_rn(lz, wz);
+        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(N.x, ex), __fmul_rn(N.y, ey)), __fmul_rn(N.z, ez));
+        return fmaxf(0.0f, dot / len);   // (a NaN quotient gives 0)
+    });
+}
+
 }  // namespace
+
+// The launches of sf_trace_suns_wave / sf_trace_suns_fixup and of sf_trace_shadows_wave / sf_trace_shadows_fixup, one
+// chunk of the call's entries each. Plain vector stores only; no statistic and none of the renders' state is touched.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_sum_wave(FrameArgs a, const float* pos4,
+                                                                        const float* nrm4, SunSum ss, float* out,
+                                                                        uint32_t groups, uint32_t* overflow_list,
+                                                                        uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    stage_root(lds, a.root);
+    trace_suns_sum_group<false>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ss,
+                                reinterpret_cast<float4*>(out), lds, build_column(a.consts), blockIdx.x, a.max_depth,
+                                overflow_list, overflow_count);
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_sum_fixup(FrameArgs a, const float* pos4,
+                                                                         const float* nrm4, SunSum ss, float* out,
+                                                                         const uint32_t* overflow_list,
+                                                                         uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
+                                         [&](uint32_t group, const float4 bcol) {
+        trace_suns_sum_group<true>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ss,
+                                   reinterpret_cast<float4*>(out), lds, bcol, group, SF_MAX_LEVELS, nullptr, nullptr);
+    });
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_sum_wave(FrameArgs a, const float* pos4,
+                                                                           const float* nrm4, ShadowSum ss, float* out,
+                                                                           uint32_t groups, uint32_t* overflow_list,
+                                                                           uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    trace_shadows_sum_group<false>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ss,
+                                   reinterpret_cast<float4*>(out), lds, build_column(a.consts), blockIdx.x,
+                                   a.max_depth, overflow_list, overflow_count);
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_sum_fixup(FrameArgs a, const float* pos4,
+                                                                            const float* nrm4, ShadowSum ss, float* out,
+                                                                            const uint32_t* overflow_list,
+                                                                            uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    fixup_groups<RootStage::InGroup, false>(a, lds, overflow_list, counters, parity,
+                                            [&](uint32_t group, const float4 bcol) {
+        trace_shadows_sum_group<true>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4),
+                                      ss, reinterpret_cast<float4*>(out), lds, bcol, group, SF_MAX_LEVELS, nullptr,
+                                      nullptr);
+    });
+}
 
 // One tile per one-wave workgroup, dynamic LDS SF_LDS_RAYS_FLOATS(a.max_depth) (the launch of sf_trace_sun_wave).
 // Touches none of the context's statistics.

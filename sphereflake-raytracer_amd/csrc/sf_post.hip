@@ -493,3 +493,29 @@ extern "C" __global__ void __launch_bounds__(256) sf_light_image_shafts_px(uint3
     c.z = (uint8_t)fminf(__fadd_rn(__fadd_rn(b, __fmul_rn(__fsub_rn(cb, b), k)), 0.5f), 255.0f);
     reinterpret_cast<uchar4*>(rgba)[px] = c;
 }
+
+// The light buffer (sf_light_fill, sf_light_image_buffer, sf.h): a float4 per pixel, .xyz the RGB
+// irradiance factor the summing traces add into. The fill is the ambient term: every pixel becomes (r, g, b, 0).
+extern "C" __global__ void __launch_bounds__(256) sf_light_fill_px(uint32_t n, float r, float g, float b, float* buf)
+{
+    const uint32_t px = blockIdx.x * 256u + threadIdx.x;
+    if (px >= n) return;
+    reinterpret_cast<float4*>(buf)[px] = make_float4(r, g, b, 0.0f);
+}
+
+// The resolve pass: the image passes above with the factor per channel read from the buffer instead of formed from a
+// mask. sphereflake_amd/lights.py (light_model_buffer) restates it (tests/test_gpu_light_sum.py).
+extern "C" __global__ void __launch_bounds__(256) sf_light_image_buffer_px(uint32_t W, uint32_t H, const float* pos4,
+                                                                        const float* buf, uint8_t* rgba)
+{
+    const uint32_t px = blockIdx.x * 256u + threadIdx.x;
+    if (px >= W * H) return;
+    const float4 P = ld4(pos4, px);
+    if (P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) return;   // a miss of the frame (post_final.glsl:20)
+    const float4 E = ld4(buf, px);
+    uchar4 c = reinterpret_cast<uchar4*>(rgba)[px];
+    c.x = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.x, E.x), 0.5f), 255.0f);
+    c.y = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.y, E.y), 0.5f), 255.0f);
+    c.z = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.z, E.z), 0.5f), 255.0f);
+    reinterpret_cast<uchar4*>(rgba)[px] = c;
+}

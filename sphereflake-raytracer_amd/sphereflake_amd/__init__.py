@@ -110,6 +110,17 @@ class sf_shafts_params(ctypes.Structure):
                 ("stream", ctypes.c_void_p)]
 
 
+SF_LIGHT_SUM_MAX = 65536
+
+
+class sf_light_sum_params(ctypes.Structure):
+    _fields_ = [("points", ctypes.POINTER(ctypes.c_float)), ("colours", ctypes.POINTER(ctypes.c_float)),
+                ("n", ctypes.c_uint32), ("accumulate", ctypes.c_uint32), ("distance", ctypes.c_float),
+                ("bias", ctypes.c_float), ("origin", ctypes.c_float * 3), ("use_origin", ctypes.c_uint32),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("max_depth", ctypes.c_uint32),
+                ("stream", ctypes.c_void_p)]
+
+
 class sf_stats(ctypes.Structure):
     _fields_ = [("max_depth", ctypes.c_int32), ("closest", ctypes.c_float),
                 ("rays", ctypes.c_int64), ("overflow_tiles", ctypes.c_int64)]
@@ -181,6 +192,18 @@ SIGNATURES = {
     "sf_trace_shafts": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shafts_params)]),
     "sf_light_image_shafts": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_shafts_params), ctypes.c_float,
                                              ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
+    "sf_light_sum_defaults": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_sum_params)]),
+    "sf_trace_suns_sum_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_sum_params), ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_suns_sum": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_sum_params)]),
+    "sf_trace_shadows_sum_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_sum_params), ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_shadows_sum": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_sum_params)]),
+    "sf_light_fill": (ctypes.c_int, [_CTX, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_light_buffer": (ctypes.c_int, [_CTX, ctypes.POINTER(ctypes.c_void_p)]),
+    "sf_download_light": (ctypes.c_int, [_CTX, ctypes.c_void_p]),
+    "sf_light_image_buffer": (ctypes.c_int, [_CTX, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p]),
     "sf_render_frames": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
                                         ctypes.POINTER(sf_render_params)]),
@@ -1226,6 +1249,172 @@ class Sphereflake:
             _check(lib().sf_light_image_shafts(self._ctx, ctypes.byref(p), float(gain), col, vp(pos_ptr), vp(mask_ptr),
                                                vp(rgba_ptr)), "sf_light_image_shafts", self._ctx)
         del keep
+
+    # the colour light buffer: sum any number of suns and lights while tracing (sf_trace_suns_sum_to /
+    # sf_trace_shadows_sum_to / sf_light_fill / sf_light_image_buffer) ------------------------------------------------
+    def light_sum_params(self, points, colours=None, accumulate=False, distance=None, bias=None, origin=None, width=0,
+                         height=0, max_depth=0, stream=None):
+        """sf_light_sum_defaults, overridden: (params, keepalive). points [n, 3] (sun directions or light positions),
+        colours [n, 3] or None (1 / n per component); distance and bias None keep the library's defaults (4, 2^-10).
+        The host arrays the params point into are in `keepalive` and must outlive the call they are passed to."""
+        pts = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+        n = pts.shape[0]
+        if not 1 <= n <= SF_LIGHT_SUM_MAX:
+            raise ValueError(f"1..{SF_LIGHT_SUM_MAX} entries per call, not {n}")
+        p = sf_light_sum_params()
+        _check(lib().sf_light_sum_defaults(self._ctx, ctypes.byref(p)), "sf_light_sum_defaults")
+        p.points = pts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        col = None
+        if colours is not None:
+            col = np.ascontiguousarray(np.asarray(colours, np.float32).reshape(-1, 3))
+            if col.shape[0] != n:
+                raise ValueError("one colour per entry")
+            p.colours = col.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        p.n, p.accumulate = n, 1 if accumulate else 0
+        if distance is not None:
+            p.distance = float(distance)
+        if bias is not None:
+            p.bias = float(bias)
+        if origin is not None:
+            p.origin[:] = [float(x) for x in _f32(origin, 3)]
+            p.use_origin = 1
+        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
+        return p, (pts, col)
+
+    @staticmethod
+    def _image4(a, what):
+        """(device address, width, height) of a contiguous float32 CUDA tensor [H, W, 4] or such a tuple."""
+        if hasattr(a, "data_ptr"):
+            shape = tuple(a.shape)
+            if len(shape) != 3 or shape[-1] != 4 or not (a.is_cuda and a.is_contiguous() and a.element_size() == 4
+                                                         and a.dtype.is_floating_point):
+                raise ValueError(f"{what} must be a contiguous float32 CUDA tensor [H, W, 4]")
+            return a.data_ptr(), shape[1], shape[0]
+        ptr, W, H = (int(x) for x in a)
+        return ptr, W, H
+
+    def _trace_sum(self, params, entry, pos, nrm, out, accumulate):
+        """The `pos` / `nrm` / `out` forms of trace_suns_sum() and trace_shadows_sum(): params(width, height) makes
+        (block, keepalive); `entry` names the call into the context's own buffers, `entry`_to the one into a
+        caller's."""
+        to, own = getattr(lib(), entry + "_to"), getattr(lib(), entry)
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        if isinstance(pos, np.ndarray):
+            pos = np.ascontiguousarray(pos, np.float32)
+            if pos.ndim != 3 or pos.shape[-1] != 4:
+                raise ValueError("pos must be [H, W, 4]")
+            if not isinstance(nrm, np.ndarray):
+                raise ValueError("a host position image needs a host normal image")
+            nrm = np.ascontiguousarray(nrm, np.float32)
+            if nrm.shape != pos.shape:
+                raise ValueError("nrm and pos must have the same shape")
+            if accumulate:
+                if not isinstance(out, np.ndarray) or out.shape != pos.shape:
+                    raise ValueError("an accumulating call on host images needs the base as `out` [H, W, 4]")
+                buf = np.array(out, np.float32, copy=True, order="C")
+            elif out is not None:
+                raise ValueError("a host position image returns a host array: out must be None")
+            else:
+                buf = np.empty(pos.shape, np.float32)
+            H, W = pos.shape[:2]
+            p, keep = params(W, H)
+            if H * W == 0:
+                return buf
+            with _DeviceScratch(self.device, 3 * pos.nbytes) as d:
+                d.upload(0, pos)
+                d.upload(pos.nbytes, nrm)
+                if accumulate:
+                    d.upload(2 * pos.nbytes, buf)
+                with self._mutex:
+                    _check(to(self._ctx, ctypes.byref(p), vp(d.ptr), vp(d.ptr + pos.nbytes), vp(d.ptr + 2 * pos.nbytes)),
+                           entry + "_to", self._ctx)
+                    # (the scratch is freed on leaving: the trace that reads and writes it must be done)
+                    _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
+                d.download(2 * pos.nbytes, buf)
+            del keep
+            return buf
+        optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
+        if pos is None:
+            if nrm is not None:
+                raise ValueError("nrm goes with pos: None selects the context's G-buffer for both")
+            p, keep = params(0, 0)
+            with self._mutex:
+                if optr:
+                    _check(to(self._ctx, ctypes.byref(p), None, None, vp(optr)), entry + "_to", self._ctx)
+                else:
+                    _check(own(self._ctx, ctypes.byref(p)), entry, self._ctx)
+            del keep
+            return None
+        pptr, W, H = self._image4(pos, "pos")
+        if nrm is None or isinstance(nrm, np.ndarray):
+            raise ValueError("a device position image needs a device normal image")
+        nptr = self._image4(nrm, "nrm")[0] if hasattr(nrm, "data_ptr") or isinstance(nrm, (tuple, list)) else int(nrm)
+        if not optr:
+            raise ValueError("a device position image needs an `out` buffer")
+        p, keep = params(W, H)
+        with self._mutex:
+            _check(to(self._ctx, ctypes.byref(p), vp(pptr), vp(nptr), vp(optr)), entry + "_to", self._ctx)
+        del keep
+        return None
+
+    def trace_suns_sum(self, dirs, colours=None, accumulate=False, distance=None, bias=None, pos=None, nrm=None,
+                       out=None, origin=None, max_depth=0, stream=None):
+        """Add the light of any number (1..65536) of sun directions `dirs` [n, 3] (each TOWARDS the sun, used as given),
+        each with an RGB colour `colours` [n, 3] (None: 1 / n per component), into a float4 light buffer while tracing
+        them: per surface pixel and channel, in index order, S += colour_i x (lit_i ? max(0, n . dirs[i]) : 0) with
+        lit_i trace_suns()' bit (sf.h; sphereflake_amd.lights.sum_model). accumulate False starts from 0 and zeroes
+        the frame's misses, True adds to what the buffer holds and leaves the misses alone.
+          - pos None: the context's own G-buffer (after Render()) into the context's light buffer (download_light(),
+            light_image_buffer() see it) or, with `out`, into that buffer -- asynchronous;
+          - pos, nrm numpy arrays [H, W, 4]: uploaded, traced, and a numpy [H, W, 4] float32 returned (an accumulating
+            call takes its base as `out`, a numpy array it does not change) -- synchronous;
+          - pos, nrm torch CUDA tensors [H, W, 4] (contiguous float32) or (device address, width, height) tuples: zero
+            copy, asynchronous; `out` a torch CUDA tensor [H, W, 4] or a device address."""
+        return self._trace_sum(
+            lambda W, H: self.light_sum_params(dirs, colours, accumulate, distance, bias, origin, W, H, max_depth, stream),
+            "sf_trace_suns_sum", pos, nrm, out, accumulate)
+
+    def trace_shadows_sum(self, lights, colours=None, accumulate=False, bias=None, pos=None, nrm=None, out=None,
+                          origin=None, max_depth=0, stream=None):
+        """trace_suns_sum() for point lights `lights` [n, 3] (world): lit_i is trace_shadows()' bit and the Lambert term
+        light_image_many()'s."""
+        return self._trace_sum(
+            lambda W, H: self.light_sum_params(lights, colours, accumulate, None, bias, origin, W, H, max_depth, stream),
+            "sf_trace_shadows_sum", pos, nrm, out, accumulate)
+
+    def light_fill(self, rgb, buf_ptr=0, stream=None):
+        """Every pixel of the light buffer becomes (r, g, b, 0): the ambient term (sf_light_fill). buf_ptr 0 = the
+        context's buffer, allocated on first use. Asynchronous."""
+        col = (ctypes.c_float * 3)(*[float(x) for x in _f32(rgb, 3)])
+        with self._mutex:
+            _check(lib().sf_light_fill(self._ctx, col, ctypes.c_void_p(buf_ptr) if buf_ptr else None, stream),
+                   "sf_light_fill", self._ctx)
+
+    def light_buffer(self) -> int:
+        """Device address of the context's light buffer (0 before anything has written it)."""
+        ptr = ctypes.c_void_p()
+        rc = lib().sf_light_buffer(self._ctx, ctypes.byref(ptr))
+        if rc == SF_ESTATE:
+            return 0
+        _check(rc, "sf_light_buffer")
+        return ptr.value or 0
+
+    def download_light(self) -> np.ndarray:
+        """[H, W, 4] float32 of the context's light buffer (synchronous)."""
+        buf = np.empty((self.height, self.width, 4), np.float32)
+        with self._mutex:
+            _check(lib().sf_download_light(self._ctx, buf.ctypes.data_as(ctypes.c_void_p)), "sf_download_light",
+                   self._ctx)
+        return buf
+
+    def light_image_buffer(self, pos_ptr=0, buf_ptr=0, rgba_ptr=0, stream=None):
+        """Scale the image of PostProcess() in place, per channel, by the light buffer (sf_light_image_buffer;
+        sphereflake_amd.lights.light_model_buffer). Pointers are device addresses, 0 = the context's G-buffer, light
+        buffer and image. Asynchronous."""
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        with self._mutex:
+            _check(lib().sf_light_image_buffer(self._ctx, stream, vp(pos_ptr), vp(buf_ptr), vp(rgba_ptr)),
+                   "sf_light_image_buffer", self._ctx)
 
     def Synchronize(self):
         _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)

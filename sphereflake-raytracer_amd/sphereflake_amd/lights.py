@@ -15,7 +15,10 @@ starts every pixel's ray a fixed distance up the sun direction from its own surf
 directions in one launch (``Sphereflake.trace_suns`` / ``light_image_suns``: sun_cone, sky_dirs, suns_model,
 light_model_suns) make a sun with an angular size or a sky dome of parallel rays. Light shafts
 (``Sphereflake.trace_shafts`` / ``light_image_shafts``: shaft_fractions, shaft_ends, shaft_samples, shafts_model,
-shaft_distance, light_model_shafts) ask the sun's question of points along each pixel's view ray.
+shaft_distance, light_model_shafts) ask the sun's question of points along each pixel's view ray. The colour light
+buffer (``Sphereflake.trace_suns_sum`` / ``trace_shadows_sum`` / ``light_fill`` / ``light_image_buffer``: sum_model,
+light_model_buffer, sky_colours) adds any number of coloured suns and lights per pixel instead of multiplying the
+image once per call.
 """
 from __future__ import annotations
 
@@ -164,10 +167,10 @@ LIGHTS_MAX = 64          # SF_SHADOW_LIGHTS_MAX: one bit of the mask word per li
 _GOLDEN = np.pi * (3.0 - np.sqrt(5.0))   # the golden angle
 
 
-def _count(n):
+def _count(n, limit=LIGHTS_MAX):
     n = int(n)
-    if not 1 <= n <= LIGHTS_MAX:
-        raise ValueError(f"1..{LIGHTS_MAX} lights, not {n}")
+    if not 1 <= n <= limit:
+        raise ValueError(f"1..{limit} lights, not {n}")
     return n
 
 
@@ -227,12 +230,13 @@ def light_model_many(rgba, pos4, nrm4, mask, origin, lights, weights=None, ambie
     return out
 
 
-def disc(centre, radius, n):
+def disc(centre, radius, n, limit=LIGHTS_MAX):
     """n points of a sunflower disc of `radius` about `centre` that faces the flake's centre (the world origin): an
-    area light's samples. In float64 a = -c / |c|, u = normalize(a x (0, 0, 1)), v = a x u, r_i = radius
+    area light's samples (limit: the most the caller's trace takes -- SUM_MAX for trace_shadows_sum). In float64
+    a = -c / |c|, u = normalize(a x (0, 0, 1)), v = a x u, r_i = radius
     sqrt((i + 0.5) / n), theta_i = i pi (3 - sqrt 5), point c + r_i cos(theta_i) u + r_i sin(theta_i) v; float32
     [n, 3]. Deterministic. (A centre on the z axis has no such u: ValueError.)"""
-    n = _count(n)
+    n = _count(n, limit)
     c = np.asarray(centre, np.float64).reshape(3)
     norm = np.linalg.norm(c)
     if not norm > 0:
@@ -250,13 +254,13 @@ def disc(centre, radius, n):
     return pts.astype(_F)
 
 
-def sky(n, radius=4.0, up=(0.0, 0.0, 1.0)):
+def sky(n, radius=4.0, up=(0.0, 0.0, 1.0), limit=LIGHTS_MAX):
     """n points of a Fibonacci upper hemisphere of `radius` about the flake's centre (the world origin), the pole
     along `up`: the lights of a ray-traced sky occlusion term (keep radius > 2: outside the flake's bounding ball).
     In float64 z_i = (i + 0.5) / n along `up`, s_i = sqrt(1 - z_i^2), theta_i = i pi (3 - sqrt 5), point
     radius (s_i cos(theta_i) e1 + s_i sin(theta_i) e2 + z_i up) with e1, e2 completing `up` to a right-handed
-    frame; float32 [n, 3]. Deterministic."""
-    return (float(radius) * _hemisphere(n, up)).astype(_F)
+    frame; float32 [n, 3]. Deterministic. limit as disc's."""
+    return (float(radius) * _hemisphere(n, up, limit)).astype(_F)
 
 
 def _frame(axis, what):
@@ -272,9 +276,9 @@ def _frame(axis, what):
     return e1, np.cross(w, e1), w
 
 
-def _hemisphere(n, up):
+def _hemisphere(n, up, limit=LIGHTS_MAX):
     """sky()'s points at radius 1, float64 [n, 3]."""
-    n = _count(n)
+    n = _count(n, limit)
     e1, e2, w = _frame(up, "up")
     i = np.arange(n, dtype=np.float64)
     z = (i + 0.5) / n
@@ -288,13 +292,14 @@ def _unit32(v):
     return (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(_F)
 
 
-def sun_cone(direction, half_angle, n):
+def sun_cone(direction, half_angle, n, limit=LIGHTS_MAX):
     """n unit directions inside the cone of `half_angle` (radians, 0 <= half_angle < pi / 2) about `direction`: the
     samples of a sun with an angular size, the `dirs` of trace_suns. A Vogel disc on the cone's cap, in float64: with
     (e1, e2, a) the frame of sky() about a = direction / |direction|, alpha_i = half_angle sqrt((i + 0.5) / n) (the
     first directions are nearest the axis), theta_i = i pi (3 - sqrt 5), direction cos(alpha_i) a + sin(alpha_i)
-    (cos(theta_i) e1 + sin(theta_i) e2), normalised; float32 [n, 3]. Deterministic."""
-    n = _count(n)
+    (cos(theta_i) e1 + sin(theta_i) e2), normalised; float32 [n, 3]. Deterministic. limit: the most the caller's
+    trace takes (SUM_MAX for trace_suns_sum)."""
+    n = _count(n, limit)
     half_angle = float(half_angle)
     if not 0.0 <= half_angle < np.pi / 2:
         raise ValueError("half_angle must be in [0, pi / 2) radians")
@@ -306,11 +311,12 @@ def sun_cone(direction, half_angle, n):
     return _unit32(v)
 
 
-def sky_dirs(n, up=(0.0, 0.0, 1.0)):
+def sky_dirs(n, up=(0.0, 0.0, 1.0), limit=LIGHTS_MAX):
     """n unit directions over the upper hemisphere about `up`: sky()'s points, normalised (in float64, then rounded);
     float32 [n, 3]. The `dirs` of trace_suns for a sky dome of parallel rays: every pixel gets the same level of
-    detail, whereas a sky() point light refines by its own distance from each node. Deterministic."""
-    return _unit32(_hemisphere(n, up))
+    detail, whereas a sky() point light refines by its own distance from each node. Deterministic. limit as
+    sun_cone's."""
+    return _unit32(_hemisphere(n, up, limit))
 
 
 def suns_model(pos4, origin, dirs, distance, bias):
@@ -476,3 +482,91 @@ def light_model_shafts(rgba, pos4, mask, fractions, weights=None, gain=1.0, colo
     marched = ~((E[..., 0] == 0) & (E[..., 1] == 0) & (E[..., 2] == 0))
     out[..., :3] = np.where(marched[..., None], rgb.astype(np.uint8), out[..., :3])
     return out
+
+
+# --- the colour light buffer (sf_trace_suns_sum_to, sf_trace_shadows_sum_to, sf_light_fill, sf_light_image_buffer) ---
+SUM_MAX = 65536          # SF_LIGHT_SUM_MAX: entries per summing call
+SUM_CHUNK = 64           # entries per launch, and per mask of trace_suns / trace_shadows
+
+
+def sum_model(base, pos4, nrm4, masks, points, colours=None, kind="suns", origin=(0.0, 0.0, 0.0)):
+    """Steps 1-4 of sf.h's definition of the sum, on the host: a new float32 array [..., 4].
+
+    base [..., 4] is what the output held (an accumulating call), or None (an overwriting call: the base is 0).
+    masks is a list of uint64 images [...]: the words of trace_suns (kind "suns") or trace_shadows (kind "shadows")
+    for consecutive chunks of 64 of the points [n, 3] -- entry i is bit i % 64 of masks[i // 64]. colours [n, 3]
+    (None: float32(1) / float32(n) per component). origin is what pos4 is relative to (the point lights only).
+
+    A miss pixel (P == 0) keeps the base (None: becomes 0). Else S = base.xyz, then for i = 0 .. n-1 in that order
+    and per channel S = S + colours[i] (bit i ? lam_i : 0), lam_i being light_model_suns' / light_model_many's; the
+    result is (S, base.w)."""
+    if kind not in ("suns", "shadows"):
+        raise ValueError("kind is 'suns' or 'shadows'")
+    pts = np.asarray(points, _F).reshape(-1, 3)
+    n = _count(pts.shape[0], SUM_MAX)
+    if colours is None:
+        col = np.full((n, 3), _F(1.0) / _F(n), _F)
+    else:
+        col = np.asarray(colours, _F).reshape(-1, 3)
+        if col.shape[0] != n or not (np.isfinite(col) & (col >= 0)).all():
+            raise ValueError("one colour per entry, every component finite and not negative")
+    masks = [np.asarray(m, np.uint64) for m in masks]
+    if len(masks) != (n + SUM_CHUNK - 1) // SUM_CHUNK:
+        raise ValueError("one mask image per chunk of 64 entries")
+    P, wpos = _world(pos4, origin)
+    nr = np.asarray(nrm4, _F)[..., :3]
+    out = np.zeros(P.shape[:-1] + (4,), _F) if base is None else np.array(base, _F, copy=True)
+    if out.shape != P.shape[:-1] + (4,):
+        raise ValueError("base must be [..., 4] over the images' pixels")
+    S = out[..., :3].copy()
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for i in range(n):
+            if kind == "suns":
+                s = pts[i]
+                dot = (nr[..., 0] * s[0] + nr[..., 1] * s[1]) + nr[..., 2] * s[2]
+                lam = np.fmax(_F(0.0), dot)
+            else:
+                l = pts[i]
+                length = _length((wpos - l) + _F(0.0))
+                e = l - wpos
+                dot = (nr[..., 0] * e[..., 0] + nr[..., 1] * e[..., 1]) + nr[..., 2] * e[..., 2]
+                lam = np.fmax(_F(0.0), dot / length)
+            bit = ((masks[i // SUM_CHUNK] >> np.uint64(i % SUM_CHUNK)) & np.uint64(1)) != 0
+            k = np.where(bit, lam, _F(0.0)).astype(_F)
+            S = S + col[i] * k[..., None]
+    assert S.dtype == _F
+    surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
+    out[..., :3] = np.where(surface[..., None], S, out[..., :3])
+    return out
+
+
+def light_model_buffer(rgba, pos4, buf):
+    """What sf_light_image_buffer makes of the RGBA8 image `rgba` [..., 4]: a new uint8 array. buf [..., 4] is the
+    light buffer. A miss pixel stays; else each of r, g, b becomes uint8(min(c buf.c + 0.5, 255)); alpha stays."""
+    out = np.array(rgba, np.uint8, copy=True)
+    P = np.asarray(pos4, _F)[..., :3]
+    E = np.asarray(buf, _F)[..., :3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        rgb = np.fmin(out[..., :3].astype(_F) * E + _F(0.5), _F(255.0))
+    assert rgb.dtype == _F
+    surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
+    out[..., :3] = np.where(surface[..., None], rgb.astype(np.uint8), out[..., :3])
+    return out
+
+
+def sky_colours(dirs, zenith=(0.25, 0.45, 1.0), horizon=(1.0, 0.8, 0.6), up=(0.0, 0.0, 1.0)):
+    """Colours [n, 3] float32 for the sky directions dirs [n, 3]: a two-colour gradient by elevation, pre-divided by
+    n, so the colours of a whole dome sum to about one sky. In float64 t_i = clip(dirs[i] . up / (|dirs[i]| |up|), 0, 1)
+    (0 at the horizon, 1 at the zenith) and colour_i = (horizon + (zenith - horizon) t_i) / n, then rounded."""
+    D = np.asarray(dirs, np.float64).reshape(-1, 3)
+    n = _count(D.shape[0], SUM_MAX)
+    z = np.asarray(zenith, np.float64).reshape(3)
+    h = np.asarray(horizon, np.float64).reshape(3)
+    if not ((np.isfinite(z) & (z >= 0)).all() and (np.isfinite(h) & (h >= 0)).all()):
+        raise ValueError("colour components must be finite and not negative")
+    _, _, w = _frame(up, "up")
+    norm = np.linalg.norm(D, axis=-1)
+    if not (np.isfinite(norm) & (norm > 0)).all():
+        raise ValueError("every direction must be finite and not zero")
+    t = np.clip((D @ w) / norm, 0.0, 1.0)
+    return ((h + (z - h) * t[:, None]) / n).astype(_F)
