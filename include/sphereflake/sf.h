@@ -592,6 +592,83 @@ int sf_download_light(sf_ctx* ctx, float* buf4);
    context stream). sphereflake_amd/lights.py: light_model_buffer. */
 int sf_light_image_buffer(sf_ctx* ctx, void* stream, const float* pos4, const float* buf, uint8_t* rgba);
 
+/* --- ambient occlusion about each pixel's normal ------------------------------ */
+/* The directions of sf_trace_suns_to are fixed in the world: under a sky dome a surface that faces down or sideways
+   spends half its samples behind its own tangent plane, and no pixel gets the cosine weighting of its own normal.
+   Here the n <= SF_AO_SAMPLES_MAX directions are given in a LOCAL frame and each pixel turns them about its own
+   normal: n rays over the hemisphere about N, in ONE launch. Each tile's wave loads its positions and normals once,
+   forms each lane's frame once (one division per pixel) and loops over the samples; one 64-bit word per pixel comes
+   out, or, from the summing call, a sum in the light buffer. The rays are posed as the sun's are: from a point tau up
+   the direction, down to the surface point.
+   DEFINITION OF THE MASK (exact; binary32, round to nearest, every operation rounded on its own, no fused
+   multiply-add). Inputs: a position image pos4 and a normal image nrm4, and the origin o as for sf_trace_sun_to; n
+   local-frame samples h_i = (h.x, h.y, h.z), given on the host and used AS GIVEN (sphereflake_amd/lights.py
+   ao_samples makes unit ones with h.z > 0); tau = distance, the bias b and the shadow LOD constant
+   (sf_set_shadow_lod). For pixel p with P = pos4[p].xyz and N = nrm4[p].xyz (as given, not normalised):
+     1. P == (0, 0, 0) is a miss of the frame: no ray is traced and every bit i < n is set.
+     2. The frame about N is the branch-free one of Duff et al. ("Building an Orthonormal Basis, Revisited", 2017):
+        sg = copysignf(1, N.z); a = -1 / (sg + N.z), a correctly rounded division; b = (N.x N.y) a;
+        T = (1 + sg ((N.x N.x) a), sg b, -sg N.x); B = (b, sg + (N.y N.y) a, -N.y). Products by sg and negations are
+        exact, so only the order written matters.
+     3. Per component c, s_i.c = ((T.c h_i.x) + (B.c h_i.y)) + (N.c h_i.z); per component, f_i.c = s_i.c tau.
+     4. Steps 2-6 of sf_trace_sun_to's definition follow with this f_i: w = o + P, F = w + f_i, d = (w - F) + 0.0f,
+        bound = |d| (1.0f - b); the ray is sf_trace_rays_to's ray from F along Normalize(d); bit i is 0 iff its
+        min_t < bound. A d or an F that is not finite sets the bit without a ray: a NaN or infinite sample or normal
+        component is such a case, and so is a zero sample.
+     5. Bits n..63 are 0.
+   CONSEQUENCES:
+   - h = (0, 0, 1) gives s = N exactly.
+   - A normal image that holds one constant N0 gives, bit for bit, sf_trace_suns_to with dirs[i] = s_i(N0): the one
+     product s tau is formed on the host there and on the device here, and is the same rounding
+     (sphereflake_amd/lights.py: ao_directions).
+   - tau >= 4 keeps every ray's origin outside the flake's radius-2 ball for |N| = |h| = 1, where THE REFERENCE'S QUIRK
+     cannot bite.
+   - THE LEVEL OF DETAIL IS THAT OF A VIEWER AT DISTANCE tau, the caller's through sf_set_shadow_lod, as for
+     sf_trace_sun_to.
+   sphereflake_amd/lights.py states steps 1-4 on the host (ao_basis, ao_directions, ao_model). */
+#define SF_AO_SAMPLES_MAX 64
+typedef struct sf_ao_params {
+    const float* samples;     /* HOST, n x 3 floats: the samples in the frame about the normal (z along it), used as
+                                 given; read before the call returns */
+    const float* colours;     /* HOST, n x 3 floats (r, g, b per sample), each finite and >= 0, or NULL = every
+                                 component (float)1 / (float)n; the summing call only; read before the call returns */
+    uint32_t n;               /* 1 .. SF_AO_SAMPLES_MAX */
+    uint32_t accumulate;      /* the summing call only: 0 = overwrite the output, 1 = add to what it holds */
+    float distance;           /* tau, finite and > 0 (sf_ao_defaults: 4); one distance for all samples */
+    float bias;               /* as sf_sun_params.bias; one bias for all samples */
+    float origin[3];          /* as sf_sun_params.origin */
+    uint32_t use_origin;      /* as sf_sun_params.use_origin */
+    uint32_t width, height;   /* as sf_sun_params */
+    uint32_t max_depth;       /* 0 = 12, as sf_sun_params.max_depth */
+    void* stream;             /* NULL = the context stream */
+} sf_ao_params;
+
+/* Zeroed (n = 0, samples NULL: the caller sets both; overwriting), distance 4, the default bias of
+   sf_shadow_defaults. */
+int sf_ao_defaults(const sf_ctx* ctx, sf_ao_params* params);
+/* As sf_trace_suns_to (asynchronous on the stream and ordered as it is; no statistic and none of the renders' state
+   touched; re-traced tiles -- a tile flagged for any sample is re-traced once, for all of them -- count in
+   overflow_tiles). pos4 and nrm4 are DEVICE images of width * height float4; NULL selects the context's G-buffer, at
+   the context's size only. mask: DEVICE output, width * height uint64_t, row-major as pos4. Errors as
+   sf_trace_suns_to's, and SF_EINVAL for n == 0, n > SF_AO_SAMPLES_MAX, a null samples or a null mask. A failing call
+   writes nothing. */
+int sf_trace_ao_to(sf_ctx* ctx, const sf_ao_params* params, const float* pos4, const float* nrm4, uint64_t* mask);
+/* The context's G-buffer into the context's mask buffer -- the one sf_trace_shadows, sf_trace_suns and sf_trace_shafts
+   write: sf_download_shadow_masks and sf_shadow_mask_buffer serve it. */
+int sf_trace_ao(sf_ctx* ctx, const sf_ao_params* params);
+/* The sum into the light buffer: steps 1-4 of the DEFINITION OF THE SUM above, unchanged, with lit_i the bit defined
+   here and lam_i = 1: S.c = S.c + colours[i].c (lit_i ? 1.0f : 0.0f) in index order -- the weighting lives in the
+   sample set and the colours (sphereflake_amd/lights.py: ao_colours, ao_sum_model). It overwrites or accumulates,
+   handles a miss of the frame and carries .w exactly as sf_trace_suns_sum_to does, and a call equals its split into an
+   overwriting and an accumulating call at any k. n <= SF_AO_SAMPLES_MAX per call: more samples are further
+   accumulating calls. pos4, nrm4 and out as sf_trace_suns_sum_to's; errors as sf_trace_ao_to's and
+   sf_trace_suns_sum_to's (a colour component that is negative, infinite or NaN: SF_EINVAL; a null out before anything
+   has written the context's light buffer: SF_ESTATE). A failing call writes nothing. */
+int sf_trace_ao_sum_to(sf_ctx* ctx, const sf_ao_params* params, const float* pos4, const float* nrm4, float* out);
+/* The context's G-buffer into the context's light buffer, which an overwriting call allocates on first use
+   (SF_ESTATE for an accumulating call before anything has written it). */
+int sf_trace_ao_sum(sf_ctx* ctx, const sf_ao_params* params);
+
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the
    work units of all n frames from one set of tile queues -- a wave whose frame runs dry goes on with the next

@@ -335,6 +335,31 @@ public:
         std::lock_guard<FairMutex> lk(m_Mutex);
         Check(sf_light_image_buffer(m_Ctx, stream, positions4, light4, rgba));
     }
+    // Ambient occlusion about each pixel's normal (new; sf_trace_ao_to / sf_trace_ao_sum_to, sf.h): up to 64 local-frame
+    // samples turned about every pixel's own normal and traced in one launch, into a uint64 mask per pixel ...
+    void TraceAO(const sf_ao_params& params, const float* positions4, const float* normals4, uint64_t* masks)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_ao_to(m_Ctx, &params, positions4, normals4, masks));
+    }
+    // ... of this object's own device frame into its own mask buffer (sf_download_shadow_masks)
+    void TraceAO(const sf_ao_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_ao(m_Ctx, &params));
+    }
+    // ... or ADDED, each sample with its RGB colour, into a float4 light buffer (params.accumulate: onto what it holds);
+    // null pointers select this object's own frame and light buffer.
+    void TraceAOSum(const sf_ao_params& params, const float* positions4, const float* normals4, float* light4)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_ao_sum_to(m_Ctx, &params, positions4, normals4, light4));
+    }
+    void TraceAOSum(const sf_ao_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_ao_sum(m_Ctx, &params));
+    }
 
     // the device frame, downloaded into the vectors when it is newer than their contents (Refresh)
     const GBuffer& GetGBuffer() const

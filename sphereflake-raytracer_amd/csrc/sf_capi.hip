@@ -104,6 +104,16 @@ extern "C" __global__ void sf_trace_shadows_sum_wave(FrameArgs a, const float* p
 extern "C" __global__ void sf_trace_shadows_sum_fixup(FrameArgs a, const float* pos4, const float* nrm4, ShadowSum ss,
                                                       float* out, const uint32_t* overflow_list, uint32_t* counters,
                                                       uint32_t parity);
+extern "C" __global__ void sf_trace_ao_wave(FrameArgs a, const float* pos4, const float* nrm4, AoArgs ao, uint64_t* mask,
+                                            uint32_t groups, uint32_t* overflow_list, uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_ao_fixup(FrameArgs a, const float* pos4, const float* nrm4, AoArgs ao,
+                                             uint64_t* mask, const uint32_t* overflow_list, uint32_t* counters,
+                                             uint32_t parity);
+extern "C" __global__ void sf_trace_ao_sum_wave(FrameArgs a, const float* pos4, const float* nrm4, AoSum ao, float* out,
+                                                uint32_t groups, uint32_t* overflow_list, uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_ao_sum_fixup(FrameArgs a, const float* pos4, const float* nrm4, AoSum ao,
+                                                 float* out, const uint32_t* overflow_list, uint32_t* counters,
+                                                 uint32_t parity);
 extern "C" __global__ void sf_light_fill_px(uint32_t n, float r, float g, float b, float* buf);
 extern "C" __global__ void sf_light_image_buffer_px(uint32_t W, uint32_t H, const float* pos4, const float* buf,
                                                     uint8_t* rgba);
@@ -2116,6 +2126,121 @@ int sf_trace_shadows_sum_to(sf_ctx* c, const sf_light_sum_params* p, const float
 }
 
 int sf_trace_shadows_sum(sf_ctx* c, const sf_light_sum_params* p) { return trace_sum_own(c, p, false); }
+
+// Ambient occlusion about each pixel's normal (kernels sf_trace_ao_wave / _fixup, sf_trace_ao_sum_wave / _fixup,
+// DESIGN.md §6.17). The launches of sf_trace_suns_to and sf_trace_suns_sum_to with the local-frame samples by value in
+// the argument segment and the normal image beside the position image; the mask buffer is sf_trace_shadows', the
+// light buffer sf_trace_suns_sum's. The argument block stays under the 4 KB kernel-argument limit:
+static_assert(SF_AO_SAMPLES == SF_AO_SAMPLES_MAX, "one mask bit per sample");
+static_assert(sizeof(FrameArgs) + sizeof(AoArgs) + 64 <= 4096, "kernel argument segment");
+static_assert(sizeof(FrameArgs) + sizeof(AoSum) + 64 <= 4096, "kernel argument segment");
+
+int sf_ao_defaults(const sf_ctx* c, sf_ao_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->distance = 4.0f;
+    p->bias = kShadowBias;
+    return SF_OK;
+}
+
+// Everything the calls check, in one place (the colours: the summing calls only); the images' sizes come back in `im`.
+static int ao_check(const sf_ctx* c, const sf_ao_params* p, bool sum, const float* pos4, bool ctx_buffer,
+                    ShadowImage* im)
+{
+    if (p->n == 0u || p->n > SF_AO_SAMPLES_MAX || !p->samples) return SF_EINVAL;
+    if (sum && p->colours)
+        for (uint32_t i = 0; i < 3u * p->n; ++i)
+            if (!light_component(p->colours[i])) return SF_EINVAL;
+    if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
+    if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, im)) return rc;
+    if (ctx_buffer && (im->W != c->W || im->H != c->H)) return SF_EINVAL;   // (a context buffer, at its size only)
+    return SF_OK;
+}
+
+extern "C++" {
+// what AoArgs and AoSum share, from the parameters: read from the caller's host array here, before the call returns
+template <class AO>
+static void ao_args(const sf_ctx* c, const sf_ao_params* p, AO* ao)
+{
+    std::memset(ao, 0, sizeof *ao);
+    shadow_origin(c, p->use_origin, p->origin, p->bias, ao->o, &ao->keep);
+    ao->tau = p->distance;
+    ao->n = p->n;
+    for (uint32_t i = 0; i < p->n; ++i)
+        for (int k = 0; k < 3; ++k) ao->h[i][k] = p->samples[3 * i + k];
+}
+}  // extern "C++"
+
+int sf_trace_ao_to(sf_ctx* c, const sf_ao_params* p, const float* pos4, const float* nrm4, uint64_t* mask)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!mask) return SF_EINVAL;
+    ShadowImage im;
+    if (int rc = ao_check(c, p, false, pos4, !nrm4, &im)) return rc;
+    AoArgs ao;
+    ao_args(c, p, &ao);
+    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
+    FrameArgs a = shadow_frame_args(c, im);
+    a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
+    return list_trace(
+        c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
+        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
+        [&](const ListLaunch& l) { l.wave(sf_trace_ao_wave, a, im.pos4, nrm, ao, mask); },
+        [&](const ListLaunch& l) { l.fixup(sf_trace_ao_fixup, a, im.pos4, nrm, ao, mask); });
+}
+
+int sf_trace_ao(sf_ctx* c, const sf_ao_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!c->shadow_masks) {
+        ShadowImage im;   // (the parameters' errors come before the buffer is made)
+        if (int rc = ao_check(c, p, false, nullptr, true, &im)) return rc;
+    }
+    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow_masks)) return rc;
+    return sf_trace_ao_to(c, p, nullptr, nullptr, c->shadow_masks);
+}
+
+int sf_trace_ao_sum_to(sf_ctx* c, const sf_ao_params* p, const float* pos4, const float* nrm4, float* out)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    ShadowImage im;
+    if (int rc = ao_check(c, p, true, pos4, !nrm4 || !out, &im)) return rc;
+    if (!out && !c->light) return SF_ESTATE;
+    AoSum ao;
+    ao_args(c, p, &ao);
+    ao.accumulate = p->accumulate ? 1u : 0u;
+    const float even = 1.0f / (float)p->n;
+    for (uint32_t i = 0; i < p->n; ++i)
+        for (int k = 0; k < 3; ++k) ao.c[i][k] = p->colours ? p->colours[3 * i + k] : even;
+    float* const dst = out ? out : c->light;
+    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
+    FrameArgs a = shadow_frame_args(c, im);
+    a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
+    return list_trace(
+        c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
+        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
+        [&](const ListLaunch& l) { l.wave(sf_trace_ao_sum_wave, a, im.pos4, nrm, ao, dst); },
+        [&](const ListLaunch& l) { l.fixup(sf_trace_ao_sum_fixup, a, im.pos4, nrm, ao, dst); });
+}
+
+// The context's G-buffer into the context's light buffer: an overwriting call makes the buffer, an accumulating one
+// needs it written (trace_sum_own).
+int sf_trace_ao_sum(sf_ctx* c, const sf_ao_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!c->light) {
+        ShadowImage im;   // (the parameters' errors come before the buffer's state)
+        if (int rc = ao_check(c, p, true, nullptr, true, &im)) return rc;
+        if (p->accumulate) return SF_ESTATE;
+        if (int rc = own_light_buffer(c)) return rc;
+    }
+    return sf_trace_ao_sum_to(c, p, nullptr, nullptr, nullptr);
+}
 
 int sf_light_buffer(sf_ctx* c, float** buf)
 {

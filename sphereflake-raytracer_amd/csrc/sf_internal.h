@@ -270,6 +270,28 @@ struct ShadowSum {
     float c[SF_LIGHT_SUM_CHUNK][3];   // their colours
 };
 
+// Ambient occlusion about each pixel's normal (sf_trace_ao_to, sf_trace_ao_sum_to): the local-frame samples travel by
+// value in the kernel argument segment beside the FrameArgs and the two image pointers (792 B / 1564 B, under the 4 KB
+// limit with them: sf_capi.hip asserts it; indexed with a uniform index they are scalar loads). tau travels too: the
+// product s_i tau is formed per lane, where s_i is.
+#define SF_AO_SAMPLES 64u             // == SF_AO_SAMPLES_MAX (sf.h): one bit of the mask word per sample
+struct AoArgs {
+    float o[3];                       // the origin the position image is relative to
+    float keep;                       // 1 - bias
+    float tau;                        // the distance from a surface point up each direction to its ray's origin
+    uint32_t n;                       // samples in use, 1..SF_AO_SAMPLES
+    float h[SF_AO_SAMPLES][3];        // the samples in the frame about the normal, as given
+};
+struct AoSum {
+    float o[3];
+    float keep;
+    float tau;
+    uint32_t n;
+    uint32_t accumulate;              // 0: the base is 0, 1: the base is what the output holds
+    float h[SF_AO_SAMPLES][3];
+    float c[SF_AO_SAMPLES][3];        // the samples' colours
+};
+
 // Multi-frame persistent trace (round 6, sf_render_frames): the frames of one launch, passed by value in the kernel
 // argument segment (copied by the runtime at the launch, so the host may build the next batch at once; 4 KB at most:
 // 11 FrameArgs). Frame f is one slot context's view into that context's G-buffer and stats. All frames share one

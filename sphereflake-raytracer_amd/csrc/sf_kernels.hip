@@ -4864,6 +4864,179 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_fixup(FrameArgs a
 }
 
 // ------------------------------------------------------------------------------------------
+// Ambient occlusion about each pixel's normal in one launch (sf_trace_ao_to / sf_trace_ao_sum_to).
+// trace_suns_group with a direction that depends on the lane: the lane's position AND normal are loaded once, and
+// w = o + P and the frame (T, B) about N (the branch-free frame of Duff et al.: one division per pixel) are formed
+// once; per sample (a uniform index, the local-frame samples h_i are scalar loads from the argument segment)
+// s_i = ((T h.x) + (B h.y)) + (N h.z), f_i = s_i tau, F, d, bound and the lane's root centre are formed as in
+// trace_sun_group and traverse_mixed runs in its any-hit mode, unchanged, on the axis columns staged once. Every
+// operation is its own rounding (sf.h), so a constant normal image gives trace_suns_group's bits for the directions
+// s_i. A tile with no surface pixel traces nothing; a sample that leaves no lane on is skipped and keeps its bit. A
+// tile flagged for any sample goes onto the overflow list once and is re-traced for all of them.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// The lane's frame about N: T and B of sf.h's step 2, in the order written there.
+__device__ __forceinline__ void ao_frame(const float4 N, float T[3], float B[3])
+{
+    const float sg = __builtin_copysignf(1.0f, N.z);
+    const float a = __fdiv_rn(-1.0f, __fadd_rn(sg, N.z));   // (sg + N.z is +-(1 + |N.z|): never zero)
+    const float b = __fmul_rn(__fmul_rn(N.x, N.y), a);
+    T[0] = __fadd_rn(1.0f, __fmul_rn(sg, __fmul_rn(__fmul_rn(N.x, N.x), a)));
+    T[1] = __fmul_rn(sg, b);
+    T[2] = -__fmul_rn(sg, N.x);
+    B[0] = b;
+    B[1] = __fadd_rn(sg, __fmul_rn(__fmul_rn(N.y, N.y), a));
+    B[2] = -N.y;
+}
+
+// The loop both endings share: bit i of the result is set where sample i's ray to the lane's pixel is stopped.
+// AO is AoArgs or AoSum (o, keep, tau, n, h).
+template <class AO>
+__device__ __forceinline__ uint64_t trace_ao_samples(const FrameArgs& a, const float4 P, const float4 N, bool surface,
+                                                     const AO& ao, float* __restrict__ L, const float4 bcol,
+                                                     uint32_t levels, uint32_t& status)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const uint32_t n = ao.n;   // (uniform, 1..64)
+    uint64_t shadowed = 0ull;
+    const float wx = __fadd_rn(ao.o[0], P.x), wy = __fadd_rn(ao.o[1], P.y), wz = __fadd_rn(ao.o[2], P.z);
+    float T[3], B[3];
+    ao_frame(N, T, B);
+    const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;   // (the mixed traversal has no cone and no order)
+    float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0u; i < n; ++i) {
+        const float hx = ao.h[i][0], hy = ao.h[i][1], hz = ao.h[i][2];
+        const float sx = __fadd_rn(__fadd_rn(__fmul_rn(T[0], hx), __fmul_rn(B[0], hy)), __fmul_rn(N.x, hz));
+        const float sy = __fadd_rn(__fadd_rn(__fmul_rn(T[1], hx), __fmul_rn(B[1], hy)), __fmul_rn(N.y, hz));
+        const float sz = __fadd_rn(__fadd_rn(__fmul_rn(T[2], hx), __fmul_rn(B[2], hy)), __fmul_rn(N.z, hz));
+        const float Fx = __fadd_rn(wx, __fmul_rn(sx, ao.tau)), Fy = __fadd_rn(wy, __fmul_rn(sy, ao.tau)),
+                    Fz = __fadd_rn(wz, __fmul_rn(sz, ao.tau));
+        float dx, dy, dz, bound;
+        shadow_ray(wx, wy, wz, Fx, Fy, Fz, ao.keep, K->lut, dx, dy, dz, bound);
+        // the lane's root centre (Sphereflake.cpp:83 at F)
+        const float rx = __fsub_rn(0.0f, Fx), ry = __fsub_rn(0.0f, Fy), rz = __fsub_rn(0.0f, Fz);
+        // finiteness depends on the sample and the lane's normal: a NaN, infinite or zero one leaves the lane off
+        const bool on = surface && finite3(dx, dy, dz);
+        if (wave_ballot(on) == 0ull) continue;   // (uniform)
+        HitState h;
+        h.hit = false;
+        int32_t md = -1;
+        uint32_t st = 0u;
+        lds_fence();   // (the sample before, or the re-trace's earlier tile, has read its tables)
+        traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, st, culls, bound);
+        status |= st;
+        shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
+    }
+    return shadowed;
+}
+
+template <bool FIXUP>
+__device__ __forceinline__ void trace_ao_group(const FrameArgs& a, const float4* __restrict__ pos4,
+                                               const float4* __restrict__ nrm4, const AoArgs& ao,
+                                               uint64_t* __restrict__ mask, float* __restrict__ L, const float4 bcol,
+                                               uint32_t group, uint32_t levels, uint32_t* overflow_list,
+                                               uint32_t* overflow_count)
+{
+    const GroupLane g = tile_lane(a, group);
+    const float4 P = pos4[g.ray];
+    const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    uint64_t shadowed = 0ull;   // bit i: sample i's ray to the lane's pixel is stopped
+    uint32_t status = 0u;
+    if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss: every sample's bit is set)
+        const float4 N = nrm4[g.ray];   // (g.ray is clamped into the image)
+        shadowed = trace_ao_samples(a, P, N, surface, ao, L, bcol, levels, status);
+    }
+    // (uniform) more levels needed for some sample: once on the list
+    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);
+    // a tile row is 64 contiguous bytes: one 8-byte vector store per valid lane
+    const uint64_t all = ao.n >= 64u ? ~0ull : (1ull << ao.n) - 1ull;
+    if (g.valid) mask[(size_t)g.y * a.W + g.x] = all & ~shadowed;
+}
+
+// The summing ending (trace_suns_sum_group's, with lam == 1: the weighting lives in the sample set and the colours).
+// A flagged tile stores nothing in its first pass; the fixup kernel reads the base, sums and stores.
+template <bool FIXUP>
+__device__ __forceinline__ void trace_ao_sum_group(const FrameArgs& a, const float4* __restrict__ pos4,
+                                                   const float4* __restrict__ nrm4, const AoSum& ao,
+                                                   float4* __restrict__ out, float* __restrict__ L, const float4 bcol,
+                                                   uint32_t group, uint32_t levels, uint32_t* overflow_list,
+                                                   uint32_t* overflow_count)
+{
+    const GroupLane g = tile_lane(a, group);
+    const float4 P = pos4[g.ray];
+    const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    uint64_t shadowed = 0ull;
+    uint32_t status = 0u;
+    if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss)
+        const float4 N = nrm4[g.ray];
+        shadowed = trace_ao_samples(a, P, N, surface, ao, L, bcol, levels, status);
+    }
+    if (!FIXUP && status != 0u) {   // (uniform) more levels needed: the fixup kernel sums and stores this tile
+        flag_group(overflow_list, overflow_count, group);
+        return;
+    }
+    light_sum_store(a, g, surface, shadowed, ao, out, [](uint32_t) { return 1.0f; });
+}
+
+}  // namespace
+
+// One tile per one-wave workgroup, dynamic LDS SF_LDS_RAYS_FLOATS(a.max_depth) (the launch of sf_trace_suns_wave).
+// Plain vector stores only; no statistic and none of the renders' state is touched.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_wave(FrameArgs a, const float* pos4, const float* nrm4,
+                                                                  AoArgs ao, uint64_t* mask, uint32_t groups,
+                                                                  uint32_t* overflow_list, uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    stage_root(lds, a.root);
+    trace_ao_group<false>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ao, mask,
+                          lds, build_column(a.consts), blockIdx.x, a.max_depth, overflow_list, overflow_count);
+}
+
+// Re-trace of the flagged tiles, for every sample, at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and
+// counters). The mixed traversal reads the root image's columns and never writes it: staged once.
+extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_fixup(FrameArgs a, const float* pos4, const float* nrm4,
+                                                                   AoArgs ao, uint64_t* mask,
+                                                                   const uint32_t* overflow_list, uint32_t* counters,
+                                                                   uint32_t parity)
+{
+    extern __shared__ float lds[];
+    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
+                                         [&](uint32_t group, const float4 bcol) {
+        trace_ao_group<true>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ao, mask,
+                             lds, bcol, group, SF_MAX_LEVELS, nullptr, nullptr);
+    });
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_sum_wave(FrameArgs a, const float* pos4,
+                                                                      const float* nrm4, AoSum ao, float* out,
+                                                                      uint32_t groups, uint32_t* overflow_list,
+                                                                      uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    if (blockIdx.x >= groups) return;
+    stage_root(lds, a.root);
+    trace_ao_sum_group<false>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ao,
+                              reinterpret_cast<float4*>(out), lds, build_column(a.consts), blockIdx.x, a.max_depth,
+                              overflow_list, overflow_count);
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_sum_fixup(FrameArgs a, const float* pos4,
+                                                                       const float* nrm4, AoSum ao, float* out,
+                                                                       const uint32_t* overflow_list,
+                                                                       uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
+                                         [&](uint32_t group, const float4 bcol) {
+        trace_ao_sum_group<true>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ao,
+                                 reinterpret_cast<float4*>(out), lds, bcol, group, SF_MAX_LEVELS, nullptr, nullptr);
+    });
+}
+
+// ------------------------------------------------------------------------------------------
 // Light shafts: sun visibility along each pixel's view ray in one launch (sf_trace_shafts_to). Bit i
 // of mask[p] is what sf_trace_sun_wave writes at a pixel whose position is Q_i = E sigma_i (1 = 255, 0 = 0), bits
 // n..63 are 0. The lane's position is loaded and its march end E formed once -- P, or where P == 0 and a direction

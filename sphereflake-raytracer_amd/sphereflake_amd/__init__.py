@@ -121,6 +121,17 @@ class sf_light_sum_params(ctypes.Structure):
                 ("stream", ctypes.c_void_p)]
 
 
+SF_AO_SAMPLES_MAX = 64
+
+
+class sf_ao_params(ctypes.Structure):
+    _fields_ = [("samples", ctypes.POINTER(ctypes.c_float)), ("colours", ctypes.POINTER(ctypes.c_float)),
+                ("n", ctypes.c_uint32), ("accumulate", ctypes.c_uint32), ("distance", ctypes.c_float),
+                ("bias", ctypes.c_float), ("origin", ctypes.c_float * 3), ("use_origin", ctypes.c_uint32),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("max_depth", ctypes.c_uint32),
+                ("stream", ctypes.c_void_p)]
+
+
 class sf_stats(ctypes.Structure):
     _fields_ = [("max_depth", ctypes.c_int32), ("closest", ctypes.c_float),
                 ("rays", ctypes.c_int64), ("overflow_tiles", ctypes.c_int64)]
@@ -200,6 +211,13 @@ SIGNATURES = {
     "sf_trace_shadows_sum_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_sum_params), ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p]),
     "sf_trace_shadows_sum": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_sum_params)]),
+    "sf_ao_defaults": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_ao_params)]),
+    "sf_trace_ao_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_ao_params), ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p]),
+    "sf_trace_ao": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_ao_params)]),
+    "sf_trace_ao_sum_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_ao_params), ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
+    "sf_trace_ao_sum": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_ao_params)]),
     "sf_light_fill": (ctypes.c_int, [_CTX, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]),
     "sf_light_buffer": (ctypes.c_int, [_CTX, ctypes.POINTER(ctypes.c_void_p)]),
     "sf_download_light": (ctypes.c_int, [_CTX, ctypes.c_void_p]),
@@ -1044,7 +1062,8 @@ class Sphereflake:
 
     # the shadow traces' level of detail, shadows from a directional light (sf_set_shadow_lod, sf_trace_sun_to) -------
     def set_shadow_lod(self, lod_constant):
-        """trace_shadow(), trace_shadows(), trace_sun(), trace_suns() and trace_shafts() refine a node while
+        """trace_shadow(), trace_shadows(), trace_sun(), trace_suns(), trace_shafts(), trace_ao() and their summing
+        forms refine a node while
         sqrtf(t / r) < lod_constant instead of the variant's 70 / 60; 0 restores the variant's own (the default).
         Nothing else is affected: Render(), trace_dirs() and trace_rays() keep the variant's constant.
         sphereflake_amd.lights.matched_lod picks a value. Synchronous."""
@@ -1415,6 +1434,116 @@ class Sphereflake:
         with self._mutex:
             _check(lib().sf_light_image_buffer(self._ctx, stream, vp(pos_ptr), vp(buf_ptr), vp(rgba_ptr)),
                    "sf_light_image_buffer", self._ctx)
+
+    # ambient occlusion about each pixel's normal (sf_trace_ao_to / sf_trace_ao / sf_trace_ao_sum_to / sf_trace_ao_sum) --
+    def ao_params(self, samples, colours=None, accumulate=False, distance=None, bias=None, origin=None, width=0,
+                  height=0, max_depth=0, stream=None):
+        """sf_ao_defaults, overridden: (params, keepalive). samples [n, 3] in the frame about the normal, colours
+        [n, 3] or None (1 / n per component; the summing call only); distance and bias None keep the library's
+        defaults (4, 2^-10). The host arrays the params point into are in `keepalive` and must outlive the call they are
+        passed to."""
+        h = np.ascontiguousarray(np.asarray(samples, np.float32).reshape(-1, 3))
+        n = h.shape[0]
+        if not 1 <= n <= SF_AO_SAMPLES_MAX:
+            raise ValueError(f"1..{SF_AO_SAMPLES_MAX} samples per call, not {n}")
+        p = sf_ao_params()
+        _check(lib().sf_ao_defaults(self._ctx, ctypes.byref(p)), "sf_ao_defaults")
+        p.samples = h.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        col = None
+        if colours is not None:
+            col = np.ascontiguousarray(np.asarray(colours, np.float32).reshape(-1, 3))
+            if col.shape[0] != n:
+                raise ValueError("one colour per sample")
+            p.colours = col.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        p.n, p.accumulate = n, 1 if accumulate else 0
+        if distance is not None:
+            p.distance = float(distance)
+        if bias is not None:
+            p.bias = float(bias)
+        if origin is not None:
+            p.origin[:] = [float(x) for x in _f32(origin, 3)]
+            p.use_origin = 1
+        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
+        return p, (h, col)
+
+    def trace_ao(self, samples, distance=4.0, bias=2.0 ** -10, pos=None, nrm=None, out=None, max_depth=0, stream=None,
+                 origin=None):
+        """Ray-traced ambient occlusion: which of up to 64 directions over the hemisphere about EACH PIXEL'S OWN normal
+        are open, in one launch. `samples` [n, 3] are directions in the local frame whose z axis is the normal
+        (sphereflake_amd.lights.ao_samples), used as given; each pixel turns them about its normal (the frame of Duff
+        et al.) and traces them as trace_suns() traces its directions: a uint64 per pixel, bit i = 1 where sample i's
+        ray from `distance` up its direction reaches the pixel (or the pixel is a miss of the frame), 0 where it is
+        stopped; bits n..63 are 0 (sf.h; sphereflake_amd.lights.ao_model).
+          - pos None: the context's own G-buffer (after Render()) into the context's mask buffer, the one
+            trace_suns() writes (download_shadow_masks() sees it), or, with `out`, into that buffer -- asynchronous;
+          - pos, nrm numpy arrays [H, W, 4]: uploaded, traced, and a numpy [H, W] uint64 returned -- synchronous;
+          - pos, nrm torch CUDA tensors [H, W, 4] (contiguous float32) or (device address, width, height) tuples: zero
+            copy, asynchronous; `out` a torch CUDA tensor of H x W 8-byte elements or a device address.
+        `origin` is what pos is relative to (None: the context's view origin)."""
+        params = lambda W, H: self.ao_params(samples, None, False, distance, bias, origin, W, H, max_depth, stream)
+        to, own = lib().sf_trace_ao_to, lib().sf_trace_ao
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        if isinstance(pos, np.ndarray):
+            pos = np.ascontiguousarray(pos, np.float32)
+            if pos.ndim != 3 or pos.shape[-1] != 4:
+                raise ValueError("pos must be [H, W, 4]")
+            if not isinstance(nrm, np.ndarray):
+                raise ValueError("a host position image needs a host normal image")
+            nrm = np.ascontiguousarray(nrm, np.float32)
+            if nrm.shape != pos.shape:
+                raise ValueError("nrm and pos must have the same shape")
+            if out is not None:
+                raise ValueError("a host position image returns a host array: out must be None")
+            H, W = pos.shape[:2]
+            mask = np.empty((H, W), np.uint64)
+            p, keep = params(W, H)
+            if H * W == 0:
+                return mask
+            with _DeviceScratch(self.device, 2 * pos.nbytes + mask.nbytes) as d:
+                d.upload(0, pos)
+                d.upload(pos.nbytes, nrm)
+                with self._mutex:
+                    _check(to(self._ctx, ctypes.byref(p), vp(d.ptr), vp(d.ptr + pos.nbytes), vp(d.ptr + 2 * pos.nbytes)),
+                           "sf_trace_ao_to", self._ctx)
+                    # (the scratch is freed on leaving: the trace that reads and writes it must be done)
+                    _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
+                d.download(2 * pos.nbytes, mask)
+            del keep
+            return mask
+        optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
+        if pos is None:
+            if nrm is not None:
+                raise ValueError("nrm goes with pos: None selects the context's G-buffer for both")
+            p, keep = params(0, 0)
+            with self._mutex:
+                if optr:
+                    _check(to(self._ctx, ctypes.byref(p), None, None, vp(optr)), "sf_trace_ao_to", self._ctx)
+                else:
+                    _check(own(self._ctx, ctypes.byref(p)), "sf_trace_ao", self._ctx)
+            del keep
+            return None
+        pptr, W, H = self._image4(pos, "pos")
+        if nrm is None or isinstance(nrm, np.ndarray):
+            raise ValueError("a device position image needs a device normal image")
+        nptr = self._image4(nrm, "nrm")[0] if hasattr(nrm, "data_ptr") or isinstance(nrm, (tuple, list)) else int(nrm)
+        if not optr:
+            raise ValueError("a device position image needs an `out` buffer")
+        p, keep = params(W, H)
+        with self._mutex:
+            _check(to(self._ctx, ctypes.byref(p), vp(pptr), vp(nptr), vp(optr)), "sf_trace_ao_to", self._ctx)
+        del keep
+        return None
+
+    def trace_ao_sum(self, samples, colours=None, accumulate=False, distance=4.0, bias=2.0 ** -10, pos=None, nrm=None,
+                     out=None, max_depth=0, stream=None, origin=None):
+        """trace_ao() with trace_suns_sum()'s ending: per surface pixel and channel, in index order,
+        S += colour_i x (open_i ? 1 : 0) into a float4 light buffer -- no Lambert term: the cosine weighting lives in the
+        sample set and the colours (sphereflake_amd.lights.ao_samples, ao_colours, ao_sum_model). colours [n, 3] (None:
+        1 / n per component); accumulate, pos, nrm and out as trace_suns_sum()'s. At most 64 samples per call: more are
+        further accumulating calls."""
+        return self._trace_sum(
+            lambda W, H: self.ao_params(samples, colours, accumulate, distance, bias, origin, W, H, max_depth, stream),
+            "sf_trace_ao_sum", pos, nrm, out, accumulate)
 
     def Synchronize(self):
         _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)

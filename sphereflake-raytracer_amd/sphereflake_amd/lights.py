@@ -18,7 +18,8 @@ light_model_suns) make a sun with an angular size or a sky dome of parallel rays
 shaft_distance, light_model_shafts) ask the sun's question of points along each pixel's view ray. The colour light
 buffer (``Sphereflake.trace_suns_sum`` / ``trace_shadows_sum`` / ``light_fill`` / ``light_image_buffer``: sum_model,
 light_model_buffer, sky_colours) adds any number of coloured suns and lights per pixel instead of multiplying the
-image once per call.
+image once per call. Ambient occlusion (``Sphereflake.trace_ao`` / ``trace_ao_sum``: ao_samples, ao_colours, ao_basis,
+ao_directions, ao_model, ao_sum_model) traces a hemisphere of such sun rays about each pixel's own normal.
 """
 from __future__ import annotations
 
@@ -570,3 +571,132 @@ def sky_colours(dirs, zenith=(0.25, 0.45, 1.0), horizon=(1.0, 0.8, 0.6), up=(0.0
         raise ValueError("every direction must be finite and not zero")
     t = np.clip((D @ w) / norm, 0.0, 1.0)
     return ((h + (z - h) * t[:, None]) / n).astype(_F)
+
+
+# --- ambient occlusion about each pixel's normal (sf_trace_ao_to, sf_trace_ao_sum_to) ------------------------------
+AO_SAMPLES_MAX = 64      # SF_AO_SAMPLES_MAX: one bit of the mask word per sample
+
+
+def ao_samples(n, kind="cosine"):
+    """n local-frame unit samples h [n, 3] over the hemisphere h.z > 0, the `samples` of trace_ao: a golden-angle
+    spiral, made in float64 and rounded to float32. Deterministic. With u_i = (i + 0.5) / n and
+    theta_i = i pi (3 - sqrt 5): kind "cosine" (density proportional to h.z) has radius sqrt(u_i) and
+    h.z = sqrt(1 - u_i); kind "uniform" (equal solid angle) has h.z = u_i and radius sqrt(1 - u_i^2);
+    h = (radius cos(theta_i), radius sin(theta_i), h.z)."""
+    n = _count(n, AO_SAMPLES_MAX)
+    if kind not in ("cosine", "uniform"):
+        raise ValueError("kind is 'cosine' or 'uniform'")
+    i = np.arange(n, dtype=np.float64)
+    u = (i + 0.5) / n
+    th = i * _GOLDEN
+    if kind == "cosine":
+        r, z = np.sqrt(u), np.sqrt(1.0 - u)
+    else:
+        r, z = np.sqrt(1.0 - u * u), u
+    return np.stack([r * np.cos(th), r * np.sin(th), z], axis=-1).astype(_F)
+
+
+def ao_colours(samples, colour=(1.0, 1.0, 1.0), kind="cosine"):
+    """Colours [n, 3] float32 for trace_ao_sum that make the sum the cosine-weighted mean of the sky `colour` over the
+    open part of the hemisphere: colour / n for a "cosine" sample set (the weighting is in the samples' density),
+    colour 2 h.z / n for a "uniform" one. Formed in float64, then rounded."""
+    h = np.asarray(samples, np.float64).reshape(-1, 3)
+    n = _count(h.shape[0], AO_SAMPLES_MAX)
+    if kind not in ("cosine", "uniform"):
+        raise ValueError("kind is 'cosine' or 'uniform'")
+    c = np.asarray(colour, np.float64).reshape(3)
+    if not (np.isfinite(c) & (c >= 0)).all():
+        raise ValueError("colour components must be finite and not negative")
+    wgt = np.full(n, 1.0 / n) if kind == "cosine" else 2.0 * h[:, 2] / n
+    if not (np.isfinite(wgt) & (wgt >= 0)).all():
+        raise ValueError("a uniform sample set needs finite h.z >= 0")
+    return (wgt[:, None] * c).astype(_F)
+
+
+def ao_basis(nrm4):
+    """Step 2 of sf_trace_ao_to's definition: the frame (T, B, N), each [..., 3] float32, about the normals
+    nrm4 [..., 3 | 4], used as given (not normalised). The branch-free frame of Duff et al., one rounding per
+    operation in the order written: sg = copysign(1, N.z), a = -1 / (sg + N.z), b = (N.x N.y) a,
+    T = (1 + sg ((N.x N.x) a), sg b, -sg N.x), B = (b, sg + (N.y N.y) a, -N.y). Orthonormal, to rounding, for a
+    unit N; sg + N.z is never zero."""
+    N = np.array(np.asarray(nrm4, _F)[..., :3], _F, copy=True)
+    x, y, z = N[..., 0], N[..., 1], N[..., 2]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
+        sg = np.copysign(_F(1.0), z)
+        a = _F(-1.0) / (sg + z)
+        b = (x * y) * a
+        T = np.stack([_F(1.0) + sg * ((x * x) * a), sg * b, -(sg * x)], axis=-1)
+        B = np.stack([b, sg + (y * y) * a, -y], axis=-1)
+    assert T.dtype == _F and B.dtype == _F
+    return T, B, N
+
+
+def ao_directions(nrm4, samples):
+    """Step 3: the world directions s [n, ..., 3] of the local-frame samples h [n, 3] about the normals
+    nrm4 [..., 3 | 4]: per component c, s_i.c = ((T.c h_i.x) + (B.c h_i.y)) + (N.c h_i.z) with (T, B, N) of ao_basis,
+    one rounding per operation. For one normal [3 | 4] the result [n, 3] is the `dirs` of trace_suns that trace_ao
+    equals on a constant normal image."""
+    T, B, N = ao_basis(nrm4)
+    h = np.asarray(samples, _F).reshape(-1, 3)
+    _count(h.shape[0], AO_SAMPLES_MAX)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        s = np.stack([((T * hi[0]) + (B * hi[1])) + (N * hi[2]) for hi in h])
+    assert s.dtype == _F
+    return s
+
+
+def ao_model(pos4, nrm4, origin, samples, distance, bias):
+    """Steps 1-4 of sf_trace_ao_to's definition up to the ray, stacked per sample as suns_model stacks them:
+    (F [n, ..., 3], d [n, ..., 3], bound [n, ...], is_surface [...]) for a position image pos4 [..., 3 | 4] relative
+    to `origin`, its normal image nrm4 and the samples [n, 3]. With s_i = ao_directions(nrm4, samples)[i] (a
+    direction per pixel): w = origin + P, f_i = s_i tau, F_i = w + f_i the ray's origin, d_i = (w - F_i) + 0 its
+    unnormalised direction, bound_i = |d_i| (1 - bias). is_surface is False where P == (0, 0, 0): no ray, every bit
+    set."""
+    if not 0.0 <= float(bias) < 1.0:
+        raise ValueError("bias must be in [0, 1)")
+    tau = _F(distance)
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError("distance must be finite and > 0")
+    P, w = _world(pos4, origin)
+    s = ao_directions(nrm4, samples)
+    if s.shape[1:] != P.shape:
+        raise ValueError("nrm4 and pos4 must have the same height and width")
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        f = s * tau
+        Fo = w + f
+        d = (w - Fo) + _F(0.0)
+        bound = _length(d) * (_F(1.0) - _F(bias))
+    is_surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
+    assert Fo.dtype == _F and d.dtype == _F and bound.dtype == _F
+    return Fo, d, bound, is_surface
+
+
+def ao_sum_model(base, pos4, masks, colours, accumulate=False):
+    """What trace_ao_sum leaves in the light buffer: a new float32 array [..., 4]. sum_model with lam_i = 1: base
+    [..., 4] is what the output held (read by an accumulating call only; None otherwise), masks [...] the uint64 words
+    of trace_ao for the same samples, colours [n, 3] the call's (its default is float32(1) / float32(n) per
+    component). A miss pixel (P == 0) keeps the base (an overwriting call: becomes 0). Else S = base.xyz (or 0), then
+    for i = 0 .. n-1 in that order and per channel S = S + colours[i] (bit i ? 1 : 0); the result is (S, base.w)."""
+    col = np.asarray(colours, _F).reshape(-1, 3)
+    n = _count(col.shape[0], AO_SAMPLES_MAX)
+    if not (np.isfinite(col) & (col >= 0)).all():
+        raise ValueError("every colour component must be finite and not negative")
+    P = np.asarray(pos4, _F)[..., :3]
+    mask = np.asarray(masks, np.uint64)
+    if accumulate:
+        if base is None:
+            raise ValueError("an accumulating call needs its base")
+        out = np.array(base, _F, copy=True)
+    else:
+        out = np.zeros(P.shape[:-1] + (4,), _F)
+    if out.shape != P.shape[:-1] + (4,) or mask.shape != P.shape[:-1]:
+        raise ValueError("base must be [..., 4] and masks [...] over the images' pixels")
+    S = out[..., :3].copy()
+    for i in range(n):
+        bit = ((mask >> np.uint64(i)) & np.uint64(1)) != 0
+        k = np.where(bit, _F(1.0), _F(0.0)).astype(_F)
+        S = S + col[i] * k[..., None]
+    assert S.dtype == _F
+    surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
+    out[..., :3] = np.where(surface[..., None], S, out[..., :3])
+    return out
