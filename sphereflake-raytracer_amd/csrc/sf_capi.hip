@@ -1480,9 +1480,11 @@ int sf_probe_rays(sf_ctx* c, const float* origins3, const float* dirs3, uint32_t
     return probe_download(c, o, n, min_t, hidx, pos4, nrm4);
 }
 
-// ---- what the shadow traces share (sf_trace_shadow_to, sf_trace_shadows_to, sf_trace_sun_to, sf_trace_suns_to,
-// sf_trace_shafts_to): one wave per 8x8 tile of a position image, the shadow traces' own constant block
-// (sf_set_shadow_lod); they touch no statistic (not the stats words, not the ray count).
+// ---- what the light traces share (sf_trace_shadow_to, sf_trace_shadows_to, sf_trace_sun_to, sf_trace_suns_to,
+// sf_trace_shafts_to, the summing traces and the AO pair): one wave per 8x8 tile of a position image,
+// the shadow traces' own constant block (sf_set_shadow_lod); they touch no statistic (not the stats words, not the ray
+// count). The image and its FrameArgs, the checks and fillers of a list of entries, the two launch shapes, the
+// context's own buffers and the one-thread-per-pixel pass.
 
 // The position image of a shadow trace: width and height 0 mean the context's size, a null pos4 the context's own
 // G-buffer (at its size only). Checks bias and max_depth with them; every failure here is SF_EINVAL.
@@ -1526,7 +1528,98 @@ static void shadow_origin(const sf_ctx* c, uint32_t use_origin, const float orig
     *keep = 1.0f - bias;
 }
 
+// a colour component: finite and not negative (NaN fails the compare)
+static bool light_component(float v) { return v >= 0.0f && !std::isinf(v); }
+
+// What every trace of a list of entries (lights, directions, march fractions, samples) checks of the list: n in
+// 1..max and the entries' pointer; then the optional `count` values beside them -- colour components, or weights, which
+// are not negative (NaN fails the compare) and may be infinite.
+static int entries_check(uint32_t n, uint32_t max, const float* entries, const float* values, uint32_t count,
+                         bool colours)
+{
+    if (n == 0u || n > max || !entries) return SF_EINVAL;
+    if (values)
+        for (uint32_t i = 0; i < count; ++i)
+            if (colours ? !light_component(values[i]) : !(values[i] >= 0.0f)) return SF_EINVAL;
+    return SF_OK;
+}
+
+// An argument block's triples from the caller's host array (read here, before the call returns): as given, and where
+// the block has them, times `scale` (one rounding: step 2 of sf_trace_sun_to's definition).
+static void entry_triples(uint32_t n, const float* src, float (*given)[3], float (*scaled)[3] = nullptr,
+                          float scale = 0.0f)
+{
+    for (uint32_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) {
+            given[i][k] = src[3 * i + k];
+            if (scaled) scaled[i][k] = src[3 * i + k] * scale;
+        }
+}
+
+// Its weights or colour components: the caller's, or `even` each.
+static void entry_values(uint32_t count, const float* src, float even, float* dst)
+{
+    for (uint32_t i = 0; i < count; ++i) dst[i] = src ? src[i] : even;
+}
+
+// The levels of a launch over point lights, one value for all of them: max_depth where given, else the largest
+// geometric bound over the finite lights (one that is not finite traces nothing).
+static uint32_t light_levels(const sf_ctx* c, uint32_t max_depth, const float (*l)[3], uint32_t n)
+{
+    uint32_t levels = max_depth;
+    if (!levels)
+        for (uint32_t i = 0; i < n; ++i) {
+            const float centre[3] = { 0.0f - l[i][0], 0.0f - l[i][1], 0.0f - l[i][2] };
+            if (!std::isfinite(centre[0] + centre[1] + centre[2])) continue;
+            bool bounded = false;
+            const uint32_t li = geometric_levels(c->host_shadow_consts.dt, centre, &bounded);
+            if (li > levels) levels = li;
+        }
+    return levels;
+}
+
 extern "C++" {
+// The head of an argument block of entries: zeroed, then the origin, 1 - bias and n.
+template <class Args>
+static void entry_args(const sf_ctx* c, uint32_t use_origin, const float origin[3], float bias, uint32_t n, Args* x)
+{
+    std::memset(x, 0, sizeof *x);
+    shadow_origin(c, use_origin, origin, bias, x->o, &x->keep);
+    x->n = n;
+}
+
+// The two launches of the light traces over the tiles of `im`: wave(a, im.pos4, args...) and fixup(a, im.pos4, args...).
+// Rays from one point per entry (traverse_ray): the root translation 0 - that point, or 0 where the kernel stages each
+// entry's own; the levels are the caller's bound.
+template <class Wave, class Fixup, class... Args>
+static int fixed_origin_trace(sf_ctx* c, void* stream, const ShadowImage& im, const float centre[3], uint32_t levels,
+                              Wave wave, Fixup fixup, Args... args)
+{
+    FrameArgs a = shadow_frame_args(c, im);
+    for (int k = 0; k < 3; ++k) a.root[9 + k] = centre[k];
+    a.max_depth = clamp_levels(levels);
+    return list_trace(
+        c, stream, im.groups, (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4,
+        (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, SF_PROG_FIXUP_BLOCKS,
+        [&](const ListLaunch& l) { l.wave(wave, a, im.pos4, args...); },
+        [&](const ListLaunch& l) { l.fixup(fixup, a, im.pos4, args...); });
+}
+
+// Rays with an origin per lane (traverse_mixed): the context's own root columns, the default levels of
+// sf_trace_rays_to, the mixed traversal's LDS and sf_trace_rays_to's fixup grid.
+template <class Wave, class Fixup, class... Args>
+static int mixed_origin_trace(sf_ctx* c, void* stream, const ShadowImage& im, uint32_t max_depth, Wave wave,
+                              Fixup fixup, Args... args)
+{
+    FrameArgs a = shadow_frame_args(c, im);
+    a.max_depth = clamp_levels(max_depth ? max_depth : kDefaultLevels);
+    return list_trace(
+        c, stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
+        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
+        [&](const ListLaunch& l) { l.wave(wave, a, im.pos4, args...); },
+        [&](const ListLaunch& l) { l.fixup(fixup, a, im.pos4, args...); });
+}
+
 // The calls into the context's own result buffer (*buf, W x H elements, allocated on first use).
 template <class T>
 static int own_result_buffer(sf_ctx* c, uint32_t width, uint32_t height, T** buf)
@@ -1540,8 +1633,37 @@ static int own_result_buffer(sf_ctx* c, uint32_t width, uint32_t height, T** buf
     return SF_OK;
 }
 
-// The three lighting passes: kernel(W, H, pos4, nrm4, mid..., ambient, rgba), one thread per pixel of the context's
-// frame, the buffers defaulted to the context's. have_vis: there is a visibility buffer to read.
+// The same for the calls that come with a check of their own (check(): the trace's parameters against the context's
+// images): where the buffer (`bytes` per pixel) is yet to be made, the parameters' errors come before the buffer's
+// state, and an accumulating call needs it written.
+template <class T, class Check>
+static int own_buffer_checked(sf_ctx* c, T** buf, size_t bytes, bool accumulate, Check check)
+{
+    if (*buf) return SF_OK;
+    if (int rc = check()) return rc;
+    if (accumulate) return SF_ESTATE;
+    DevGuard g(c->device);
+    SF_HIP(c, hipMalloc(buf, (size_t)c->W * c->H * bytes));
+    return SF_OK;
+}
+
+// One thread per pixel of the context's frame: kernel(args...) on `stream` (null: the context's), ordered after the
+// context's earlier work.
+template <class Kernel, class... Args>
+static int pixel_pass(sf_ctx* c, void* stream, Kernel kernel, Args... args)
+{
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...);
+    SF_HIP(c, hipGetLastError());
+    return SF_OK;
+}
+
+// The lighting passes that shade by a normal: kernel(W, H, pos4, nrm4, mid..., ambient, rgba), the buffers defaulted to
+// the context's. have_vis: there is a visibility buffer to read.
 template <class Kernel, class... Mid>
 static int light_image_pass(sf_ctx* c, void* stream, float ambient, const float* pos4, const float* nrm4, bool have_vis,
                             uint8_t* rgba, Kernel kernel, Mid... mid)
@@ -1549,15 +1671,8 @@ static int light_image_pass(sf_ctx* c, void* stream, float ambient, const float*
     if (!(ambient >= 0.0f && ambient <= 1.0f)) return SF_EINVAL;
     if (!rgba && !c->image) return SF_ESTATE;
     if (!have_vis) return SF_ESTATE;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
-    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
-                       nrm4 ? nrm4 : (const float*)c->nrm, mid..., ambient, rgba ? rgba : c->image);
-    SF_HIP(c, hipGetLastError());
-    return SF_OK;
+    return pixel_pass(c, stream, kernel, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
+                      nrm4 ? nrm4 : (const float*)c->nrm, mid..., ambient, rgba ? rgba : c->image);
 }
 }  // extern "C++"
 
@@ -1588,17 +1703,11 @@ int sf_trace_shadow_to(sf_ctx* c, const sf_shadow_params* p, const float* pos4, 
     ShadowImage im;
     if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
     const ShadowArgs sa = shadow_args(c, p);
-    FrameArgs a = shadow_frame_args(c, im);
     const float centre[3] = { 0.0f - sa.l[0], 0.0f - sa.l[1], 0.0f - sa.l[2] };   // (Sphereflake.cpp:83 at the light)
-    for (int k = 0; k < 3; ++k) a.root[9 + k] = centre[k];
     bool bounded = false;
-    a.max_depth =
-        clamp_levels(p->max_depth ? p->max_depth : geometric_levels(c->host_shadow_consts.dt, centre, &bounded));
-    return list_trace(
-        c, p->stream, im.groups, (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4,
-        (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, SF_PROG_FIXUP_BLOCKS,
-        [&](const ListLaunch& l) { l.wave(sf_trace_shadow_wave, a, im.pos4, sa, vis); },
-        [&](const ListLaunch& l) { l.fixup(sf_trace_shadow_fixup, a, im.pos4, sa, vis); });
+    const uint32_t levels =
+        p->max_depth ? p->max_depth : geometric_levels(c->host_shadow_consts.dt, centre, &bounded);
+    return fixed_origin_trace(c, p->stream, im, centre, levels, sf_trace_shadow_wave, sf_trace_shadow_fixup, sa, vis);
 }
 
 int sf_trace_shadow(sf_ctx* c, const sf_shadow_params* p)
@@ -1649,56 +1758,28 @@ int sf_shadows_defaults(const sf_ctx* c, sf_shadows_params* p)
     return SF_OK;
 }
 
-// n and the lights' pointer (both calls), the weights (sf_light_image_many)
-static int shadows_check(const sf_shadows_params* p, bool weights)
-{
-    if (p->n == 0u || p->n > SF_SHADOW_LIGHTS_MAX || !p->lights) return SF_EINVAL;
-    if (weights && p->weights)
-        for (uint32_t i = 0; i < p->n; ++i)
-            if (!(p->weights[i] >= 0.0f)) return SF_EINVAL;   // (NaN fails)
-    return SF_OK;
-}
-
-// the launch's ShadowLights from the parameters: read from the caller's host arrays here, before the call returns
+// the launch's ShadowLights from the parameters (the weights: sf_light_image_many's)
 static void shadows_args(const sf_ctx* c, const sf_shadows_params* p, ShadowLights* sl)
 {
-    std::memset(sl, 0, sizeof *sl);
-    shadow_origin(c, p->use_origin, p->origin, p->bias, sl->o, &sl->keep);
-    sl->n = p->n;
-    const float even = 1.0f / (float)p->n;
-    for (uint32_t i = 0; i < p->n; ++i) {
-        for (int k = 0; k < 3; ++k) sl->l[i][k] = p->lights[3 * i + k];
-        sl->w[i] = p->weights ? p->weights[i] : even;
-    }
+    entry_args(c, p->use_origin, p->origin, p->bias, p->n, sl);
+    entry_triples(p->n, p->lights, sl->l);
+    entry_values(p->n, p->weights, 1.0f / (float)p->n, sl->w);
 }
+
+static const float kNoCentre[3] = { 0.0f, 0.0f, 0.0f };   // (the kernel stages each light's own translation)
 
 int sf_trace_shadows_to(sf_ctx* c, const sf_shadows_params* p, const float* pos4, uint64_t* mask)
 {
     if (!c || !p) return SF_EINVAL;
     if (!c->has_view) return SF_ENOVIEW;
     if (!mask) return SF_EINVAL;
-    if (int rc = shadows_check(p, false)) return rc;
+    if (int rc = entries_check(p->n, SF_SHADOW_LIGHTS_MAX, p->lights, nullptr, 0u, false)) return rc;
     ShadowImage im;
     if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
     ShadowLights sl;
     shadows_args(c, p, &sl);
-    FrameArgs a = shadow_frame_args(c, im);
-    for (int k = 0; k < 3; ++k) a.root[9 + k] = 0.0f;   // (the kernel stages each light's own translation)
-    uint32_t levels = p->max_depth;
-    if (!levels)
-        for (uint32_t i = 0; i < sl.n; ++i) {
-            const float centre[3] = { 0.0f - sl.l[i][0], 0.0f - sl.l[i][1], 0.0f - sl.l[i][2] };
-            if (!std::isfinite(centre[0] + centre[1] + centre[2])) continue;   // (traces nothing)
-            bool bounded = false;
-            const uint32_t li = geometric_levels(c->host_shadow_consts.dt, centre, &bounded);
-            if (li > levels) levels = li;
-        }
-    a.max_depth = clamp_levels(levels);
-    return list_trace(
-        c, p->stream, im.groups, (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4,
-        (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, SF_PROG_FIXUP_BLOCKS,
-        [&](const ListLaunch& l) { l.wave(sf_trace_shadows_wave, a, im.pos4, sl, mask); },
-        [&](const ListLaunch& l) { l.fixup(sf_trace_shadows_fixup, a, im.pos4, sl, mask); });
+    return fixed_origin_trace(c, p->stream, im, kNoCentre, light_levels(c, p->max_depth, sl.l, sl.n),
+                              sf_trace_shadows_wave, sf_trace_shadows_fixup, sl, mask);
 }
 
 int sf_trace_shadows(sf_ctx* c, const sf_shadows_params* p)
@@ -1731,7 +1812,7 @@ int sf_light_image_many(sf_ctx* c, const sf_shadows_params* p, float ambient, co
 {
     if (!c || !p) return SF_EINVAL;
     if (!c->has_view && !p->use_origin) return SF_ENOVIEW;
-    if (int rc = shadows_check(p, true)) return rc;
+    if (int rc = entries_check(p->n, SF_SHADOW_LIGHTS_MAX, p->lights, p->weights, p->n, false)) return rc;
     ShadowLights sl;
     shadows_args(c, p, &sl);
     return light_image_pass(c, p->stream, ambient, pos4, nrm4, mask || c->shadow_masks, rgba, sf_light_image_many_px,
@@ -1779,13 +1860,7 @@ int sf_trace_sun_to(sf_ctx* c, const sf_sun_params* p, const float* pos4, uint8_
     SunArgs sa;
     shadow_origin(c, p->use_origin, p->origin, p->bias, sa.o, &sa.keep);
     for (int k = 0; k < 3; ++k) sa.f[k] = p->dir[k] * p->distance;   // (one rounding: step 2 of the definition)
-    FrameArgs a = shadow_frame_args(c, im);
-    a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
-    return list_trace(
-        c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
-        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
-        [&](const ListLaunch& l) { l.wave(sf_trace_sun_wave, a, im.pos4, sa, vis); },
-        [&](const ListLaunch& l) { l.fixup(sf_trace_sun_fixup, a, im.pos4, sa, vis); });
+    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_sun_wave, sf_trace_sun_fixup, sa, vis);
 }
 
 int sf_trace_sun(sf_ctx* c, const sf_sun_params* p)
@@ -1818,30 +1893,12 @@ int sf_suns_defaults(const sf_ctx* c, sf_suns_params* p)
     return SF_OK;
 }
 
-// n and the directions' pointer (both calls), the weights (sf_light_image_suns)
-static int suns_check(const sf_suns_params* p, bool weights)
-{
-    if (p->n == 0u || p->n > SF_SUN_DIRS_MAX || !p->dirs) return SF_EINVAL;
-    if (weights && p->weights)
-        for (uint32_t i = 0; i < p->n; ++i)
-            if (!(p->weights[i] >= 0.0f)) return SF_EINVAL;   // (NaN fails)
-    return SF_OK;
-}
-
-// the launch's SunDirs from the parameters: read from the caller's host arrays here, before the call returns
+// the launch's SunDirs from the parameters (the directions as given and the weights: sf_light_image_suns's)
 static void suns_args(const sf_ctx* c, const sf_suns_params* p, SunDirs* sd)
 {
-    std::memset(sd, 0, sizeof *sd);
-    shadow_origin(c, p->use_origin, p->origin, p->bias, sd->o, &sd->keep);
-    sd->n = p->n;
-    const float even = 1.0f / (float)p->n;
-    for (uint32_t i = 0; i < p->n; ++i) {
-        for (int k = 0; k < 3; ++k) {
-            sd->s[i][k] = p->dirs[3 * i + k];
-            sd->f[i][k] = p->dirs[3 * i + k] * p->distance;   // (one rounding: step 2 of sf_trace_sun_to's definition)
-        }
-        sd->w[i] = p->weights ? p->weights[i] : even;
-    }
+    entry_args(c, p->use_origin, p->origin, p->bias, p->n, sd);
+    entry_triples(p->n, p->dirs, sd->s, sd->f, p->distance);
+    entry_values(p->n, p->weights, 1.0f / (float)p->n, sd->w);
 }
 
 int sf_trace_suns_to(sf_ctx* c, const sf_suns_params* p, const float* pos4, uint64_t* mask)
@@ -1849,19 +1906,13 @@ int sf_trace_suns_to(sf_ctx* c, const sf_suns_params* p, const float* pos4, uint
     if (!c || !p) return SF_EINVAL;
     if (!c->has_view) return SF_ENOVIEW;
     if (!mask) return SF_EINVAL;
-    if (int rc = suns_check(p, false)) return rc;
+    if (int rc = entries_check(p->n, SF_SUN_DIRS_MAX, p->dirs, nullptr, 0u, false)) return rc;
     if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
     ShadowImage im;
     if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
     SunDirs sd;
     suns_args(c, p, &sd);
-    FrameArgs a = shadow_frame_args(c, im);
-    a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
-    return list_trace(
-        c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
-        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
-        [&](const ListLaunch& l) { l.wave(sf_trace_suns_wave, a, im.pos4, sd, mask); },
-        [&](const ListLaunch& l) { l.fixup(sf_trace_suns_fixup, a, im.pos4, sd, mask); });
+    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_suns_wave, sf_trace_suns_fixup, sd, mask);
 }
 
 int sf_trace_suns(sf_ctx* c, const sf_suns_params* p)
@@ -1875,7 +1926,7 @@ int sf_light_image_suns(sf_ctx* c, const sf_suns_params* p, float ambient, const
                         const uint64_t* mask, uint8_t* rgba)
 {
     if (!c || !p) return SF_EINVAL;
-    if (int rc = suns_check(p, true)) return rc;
+    if (int rc = entries_check(p->n, SF_SUN_DIRS_MAX, p->dirs, p->weights, p->n, false)) return rc;
     SunDirs sd;
     suns_args(c, p, &sd);
     return light_image_pass(c, p->stream, ambient, pos4, nrm4, mask || c->shadow_masks, rgba, sf_light_image_suns_px,
@@ -1898,37 +1949,31 @@ int sf_shafts_defaults(const sf_ctx* c, sf_shafts_params* p)
     return SF_OK;
 }
 
-// n, the fractions, far and the direction image's stride (both calls), the weights (sf_light_image_shafts)
+// n, the fractions, far and the direction image's stride (both calls), the weights (sf_light_image_shafts): the list
+// first, as everywhere, then what is shafts' own; every failure is SF_EINVAL, so the order shows in no return code
 static int shafts_check(const sf_shafts_params* p, bool weights)
 {
-    if (p->n == 0u || p->n > SF_SHAFT_SAMPLES_MAX || !p->fractions) return SF_EINVAL;
+    if (int rc = entries_check(p->n, SF_SHAFT_SAMPLES_MAX, p->fractions, weights ? p->weights : nullptr, p->n, false))
+        return rc;
     for (uint32_t i = 0; i < p->n; ++i)
         if (!(p->fractions[i] > 0.0f) || std::isinf(p->fractions[i])) return SF_EINVAL;   // (NaN fails the compare)
     if (!(p->far >= 0.0f) || std::isinf(p->far)) return SF_EINVAL;
     if (p->dirs && p->dirs_stride != 3u && p->dirs_stride != 4u) return SF_EINVAL;
-    if (weights && p->weights)
-        for (uint32_t i = 0; i < p->n; ++i)
-            if (!(p->weights[i] >= 0.0f)) return SF_EINVAL;   // (NaN fails)
     return SF_OK;
 }
 
-// the launch's ShaftArgs from the parameters: read from the caller's host arrays here, before the call returns
+// the launch's ShaftArgs from the parameters (the weights: sf_light_image_shafts's)
 static void shafts_args(const sf_ctx* c, const sf_shafts_params* p, ShaftArgs* sh)
 {
-    std::memset(sh, 0, sizeof *sh);
-    shadow_origin(c, p->use_origin, p->origin, p->bias, sh->o, &sh->keep);
+    entry_args(c, p->use_origin, p->origin, p->bias, p->n, sh);
     for (int k = 0; k < 3; ++k) sh->f[k] = p->dir[k] * p->distance;   // (one rounding: step 2 of sf_trace_sun_to's)
     if (p->dirs && p->far > 0.0f) {   // (else a miss of the frame is not marched: the kernels never look)
         sh->dirs = p->dirs;
         sh->dirs_stride = p->dirs_stride;
         sh->far = p->far;
     }
-    sh->n = p->n;
-    const float even = 1.0f / (float)p->n;
-    for (uint32_t i = 0; i < p->n; ++i) {
-        sh->sigma[i] = p->fractions[i];
-        sh->w[i] = p->weights ? p->weights[i] : even;
-    }
+    for (uint32_t i = 0; i < p->n; ++i) sh->sigma[i] = p->fractions[i];
+    entry_values(p->n, p->weights, 1.0f / (float)p->n, sh->w);
 }
 
 int sf_trace_shafts_to(sf_ctx* c, const sf_shafts_params* p, const float* pos4, uint64_t* mask)
@@ -1942,13 +1987,7 @@ int sf_trace_shafts_to(sf_ctx* c, const sf_shafts_params* p, const float* pos4, 
     if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
     ShaftArgs sh;
     shafts_args(c, p, &sh);
-    FrameArgs a = shadow_frame_args(c, im);
-    a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
-    return list_trace(
-        c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
-        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
-        [&](const ListLaunch& l) { l.wave(sf_trace_shafts_wave, a, im.pos4, sh, mask); },
-        [&](const ListLaunch& l) { l.fixup(sf_trace_shafts_fixup, a, im.pos4, sh, mask); });
+    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_shafts_wave, sf_trace_shafts_fixup, sh, mask);
 }
 
 int sf_trace_shafts(sf_ctx* c, const sf_shafts_params* p)
@@ -1958,8 +1997,7 @@ int sf_trace_shafts(sf_ctx* c, const sf_shafts_params* p)
     return sf_trace_shafts_to(c, p, nullptr, c->shadow_masks);
 }
 
-// One thread per pixel of the context's frame, the buffers defaulted to the context's (as light_image_pass, without a
-// normal image or an ambient term).
+// The buffers defaulted to the context's (as light_image_pass, without a normal image or an ambient term).
 int sf_light_image_shafts(sf_ctx* c, const sf_shafts_params* p, float gain, const float colour[3], const float* pos4,
                           const uint64_t* mask, uint8_t* rgba)
 {
@@ -1972,16 +2010,9 @@ int sf_light_image_shafts(sf_ctx* c, const sf_shafts_params* p, float gain, cons
     if (!mask && !c->shadow_masks) return SF_ESTATE;
     ShaftArgs sh;
     shafts_args(c, p, &sh);
-    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
-    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
-    hipLaunchKernelGGL(sf_light_image_shafts_px, grid, dim3(256), 0, s, c->W, c->H,
-                       pos4 ? pos4 : (const float*)c->pos, mask ? mask : (const uint64_t*)c->shadow_masks, sh, gain,
-                       colour[0], colour[1], colour[2], rgba ? rgba : c->image);
-    SF_HIP(c, hipGetLastError());
-    return SF_OK;
+    return pixel_pass(c, p->stream, sf_light_image_shafts_px, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
+                      mask ? mask : (const uint64_t*)c->shadow_masks, sh, gain, colour[0], colour[1], colour[2],
+                      rgba ? rgba : c->image);
 }
 
 // The colour light buffer and the traces that add into it (kernels sf_trace_suns_sum_wave / _fixup,
@@ -2000,26 +2031,11 @@ int sf_light_sum_defaults(const sf_ctx* c, sf_light_sum_params* p)
     return SF_OK;
 }
 
-// a colour component: finite and not negative (NaN fails the compare)
-static bool light_component(float v) { return v >= 0.0f && !std::isinf(v); }
-
-// The context's light buffer, allocated on first use (every call that allocates it writes all of it).
-static int own_light_buffer(sf_ctx* c)
-{
-    if (c->light) return SF_OK;
-    DevGuard g(c->device);
-    SF_HIP(c, hipMalloc(&c->light, (size_t)c->W * c->H * 16));
-    return SF_OK;
-}
-
 // Everything both summing traces check, in one place; the images' sizes come back in `im`.
 static int light_sum_check(const sf_ctx* c, const sf_light_sum_params* p, bool suns, const float* pos4,
                            bool ctx_buffer, ShadowImage* im)
 {
-    if (p->n == 0u || p->n > SF_LIGHT_SUM_MAX || !p->points) return SF_EINVAL;
-    if (p->colours)
-        for (uint32_t i = 0; i < 3u * p->n; ++i)
-            if (!light_component(p->colours[i])) return SF_EINVAL;
+    if (int rc = entries_check(p->n, SF_LIGHT_SUM_MAX, p->points, p->colours, 3u * p->n, true)) return rc;
     if (suns && (!(p->distance > 0.0f) || std::isinf(p->distance))) return SF_EINVAL;   // (NaN fails the compare)
     if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, im)) return rc;
     if (ctx_buffer && (im->W != c->W || im->H != c->H)) return SF_EINVAL;   // (a context buffer, at its size only)
@@ -2036,9 +2052,6 @@ static int trace_sum_to(sf_ctx* c, const sf_light_sum_params* p, bool suns, cons
     if (!out && !c->light) return SF_ESTATE;
     float* const dst = out ? out : c->light;
     const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
-    FrameArgs a = shadow_frame_args(c, im);
-    float o[3], keep;
-    shadow_origin(c, p->use_origin, p->origin, p->bias, o, &keep);
     const float even = 1.0f / (float)p->n;
     for (uint32_t first = 0; first < p->n; first += SF_LIGHT_SUM_CHUNK) {
         const uint32_t m = p->n - first < SF_LIGHT_SUM_CHUNK ? p->n - first : SF_LIGHT_SUM_CHUNK;
@@ -2048,50 +2061,20 @@ static int trace_sum_to(sf_ctx* c, const sf_light_sum_params* p, bool suns, cons
         int rc;
         if (suns) {
             SunSum ss;
-            std::memset(&ss, 0, sizeof ss);
-            for (int k = 0; k < 3; ++k) ss.o[k] = o[k];
-            ss.keep = keep;
-            ss.n = m;
+            entry_args(c, p->use_origin, p->origin, p->bias, m, &ss);
             ss.accumulate = accumulate;
-            for (uint32_t i = 0; i < m; ++i)
-                for (int k = 0; k < 3; ++k) {
-                    ss.s[i][k] = pts[3 * i + k];
-                    ss.f[i][k] = pts[3 * i + k] * p->distance;   // (one rounding: step 2 of sf_trace_sun_to's definition)
-                    ss.c[i][k] = col ? col[3 * i + k] : even;
-                }
-            a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
-            rc = list_trace(
-                c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
-                (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
-                [&](const ListLaunch& l) { l.wave(sf_trace_suns_sum_wave, a, im.pos4, nrm, ss, dst); },
-                [&](const ListLaunch& l) { l.fixup(sf_trace_suns_sum_fixup, a, im.pos4, nrm, ss, dst); });
-        } else {
+            entry_triples(m, pts, ss.s, ss.f, p->distance);
+            entry_values(3u * m, col, even, &ss.c[0][0]);
+            rc = mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_suns_sum_wave, sf_trace_suns_sum_fixup,
+                                    nrm, ss, dst);
+        } else {   // (the levels: the largest geometric bound over the chunk, as sf_trace_shadows_to)
             ShadowSum ss;
-            std::memset(&ss, 0, sizeof ss);
-            for (int k = 0; k < 3; ++k) ss.o[k] = o[k];
-            ss.keep = keep;
-            ss.n = m;
+            entry_args(c, p->use_origin, p->origin, p->bias, m, &ss);
             ss.accumulate = accumulate;
-            uint32_t levels = p->max_depth;
-            for (uint32_t i = 0; i < m; ++i) {
-                for (int k = 0; k < 3; ++k) {
-                    ss.l[i][k] = pts[3 * i + k];
-                    ss.c[i][k] = col ? col[3 * i + k] : even;
-                }
-                if (p->max_depth) continue;   // (else the largest geometric bound over the chunk, as sf_trace_shadows_to)
-                const float centre[3] = { 0.0f - ss.l[i][0], 0.0f - ss.l[i][1], 0.0f - ss.l[i][2] };
-                if (!std::isfinite(centre[0] + centre[1] + centre[2])) continue;   // (traces nothing)
-                bool bounded = false;
-                const uint32_t li = geometric_levels(c->host_shadow_consts.dt, centre, &bounded);
-                if (li > levels) levels = li;
-            }
-            for (int k = 0; k < 3; ++k) a.root[9 + k] = 0.0f;   // (the kernel stages each light's own translation)
-            a.max_depth = clamp_levels(levels);
-            rc = list_trace(
-                c, p->stream, im.groups, (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4,
-                (size_t)SF_LDS_WAVE_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, SF_PROG_FIXUP_BLOCKS,
-                [&](const ListLaunch& l) { l.wave(sf_trace_shadows_sum_wave, a, im.pos4, nrm, ss, dst); },
-                [&](const ListLaunch& l) { l.fixup(sf_trace_shadows_sum_fixup, a, im.pos4, nrm, ss, dst); });
+            entry_triples(m, pts, ss.l);
+            entry_values(3u * m, col, even, &ss.c[0][0]);
+            rc = fixed_origin_trace(c, p->stream, im, kNoCentre, light_levels(c, p->max_depth, ss.l, m),
+                                    sf_trace_shadows_sum_wave, sf_trace_shadows_sum_fixup, nrm, ss, dst);
         }
         if (rc != SF_OK) return rc;
     }
@@ -2104,12 +2087,10 @@ static int trace_sum_own(sf_ctx* c, const sf_light_sum_params* p, bool suns)
 {
     if (!c || !p) return SF_EINVAL;
     if (!c->has_view) return SF_ENOVIEW;
-    if (!c->light) {
-        ShadowImage im;   // (the parameters' errors come before the buffer's state)
-        if (int rc = light_sum_check(c, p, suns, nullptr, true, &im)) return rc;
-        if (p->accumulate) return SF_ESTATE;
-        if (int rc = own_light_buffer(c)) return rc;
-    }
+    ShadowImage im;
+    if (int rc = own_buffer_checked(c, &c->light, 16, p->accumulate != 0u,
+                                    [&] { return light_sum_check(c, p, suns, nullptr, true, &im); }))
+        return rc;
     return trace_sum_to(c, p, suns, nullptr, nullptr, nullptr);
 }
 
@@ -2148,10 +2129,8 @@ int sf_ao_defaults(const sf_ctx* c, sf_ao_params* p)
 static int ao_check(const sf_ctx* c, const sf_ao_params* p, bool sum, const float* pos4, bool ctx_buffer,
                     ShadowImage* im)
 {
-    if (p->n == 0u || p->n > SF_AO_SAMPLES_MAX || !p->samples) return SF_EINVAL;
-    if (sum && p->colours)
-        for (uint32_t i = 0; i < 3u * p->n; ++i)
-            if (!light_component(p->colours[i])) return SF_EINVAL;
+    if (int rc = entries_check(p->n, SF_AO_SAMPLES_MAX, p->samples, sum ? p->colours : nullptr, 3u * p->n, true))
+        return rc;
     if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
     if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, im)) return rc;
     if (ctx_buffer && (im->W != c->W || im->H != c->H)) return SF_EINVAL;   // (a context buffer, at its size only)
@@ -2159,16 +2138,13 @@ static int ao_check(const sf_ctx* c, const sf_ao_params* p, bool sum, const floa
 }
 
 extern "C++" {
-// what AoArgs and AoSum share, from the parameters: read from the caller's host array here, before the call returns
+// what AoArgs and AoSum share, from the parameters
 template <class AO>
 static void ao_args(const sf_ctx* c, const sf_ao_params* p, AO* ao)
 {
-    std::memset(ao, 0, sizeof *ao);
-    shadow_origin(c, p->use_origin, p->origin, p->bias, ao->o, &ao->keep);
+    entry_args(c, p->use_origin, p->origin, p->bias, p->n, ao);
     ao->tau = p->distance;
-    ao->n = p->n;
-    for (uint32_t i = 0; i < p->n; ++i)
-        for (int k = 0; k < 3; ++k) ao->h[i][k] = p->samples[3 * i + k];
+    entry_triples(p->n, p->samples, ao->h);
 }
 }  // extern "C++"
 
@@ -2182,24 +2158,17 @@ int sf_trace_ao_to(sf_ctx* c, const sf_ao_params* p, const float* pos4, const fl
     AoArgs ao;
     ao_args(c, p, &ao);
     const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
-    FrameArgs a = shadow_frame_args(c, im);
-    a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
-    return list_trace(
-        c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
-        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
-        [&](const ListLaunch& l) { l.wave(sf_trace_ao_wave, a, im.pos4, nrm, ao, mask); },
-        [&](const ListLaunch& l) { l.fixup(sf_trace_ao_fixup, a, im.pos4, nrm, ao, mask); });
+    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_ao_wave, sf_trace_ao_fixup, nrm, ao, mask);
 }
 
 int sf_trace_ao(sf_ctx* c, const sf_ao_params* p)
 {
     if (!c || !p) return SF_EINVAL;
     if (!c->has_view) return SF_ENOVIEW;
-    if (!c->shadow_masks) {
-        ShadowImage im;   // (the parameters' errors come before the buffer is made)
-        if (int rc = ao_check(c, p, false, nullptr, true, &im)) return rc;
-    }
-    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow_masks)) return rc;
+    ShadowImage im;
+    if (int rc = own_buffer_checked(c, &c->shadow_masks, 8, false,
+                                    [&] { return ao_check(c, p, false, nullptr, true, &im); }))
+        return rc;
     return sf_trace_ao_to(c, p, nullptr, nullptr, c->shadow_masks);
 }
 
@@ -2213,18 +2182,11 @@ int sf_trace_ao_sum_to(sf_ctx* c, const sf_ao_params* p, const float* pos4, cons
     AoSum ao;
     ao_args(c, p, &ao);
     ao.accumulate = p->accumulate ? 1u : 0u;
-    const float even = 1.0f / (float)p->n;
-    for (uint32_t i = 0; i < p->n; ++i)
-        for (int k = 0; k < 3; ++k) ao.c[i][k] = p->colours ? p->colours[3 * i + k] : even;
+    entry_values(3u * p->n, p->colours, 1.0f / (float)p->n, &ao.c[0][0]);
     float* const dst = out ? out : c->light;
     const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
-    FrameArgs a = shadow_frame_args(c, im);
-    a.max_depth = clamp_levels(p->max_depth ? p->max_depth : kDefaultLevels);
-    return list_trace(
-        c, p->stream, im.groups, (size_t)SF_LDS_RAYS_FLOATS(a.max_depth) * 4,
-        (size_t)SF_LDS_RAYS_FLOATS(SF_MAX_DEPTH_LIMIT) * 4, kRaysFixupBlocks,
-        [&](const ListLaunch& l) { l.wave(sf_trace_ao_sum_wave, a, im.pos4, nrm, ao, dst); },
-        [&](const ListLaunch& l) { l.fixup(sf_trace_ao_sum_fixup, a, im.pos4, nrm, ao, dst); });
+    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_ao_sum_wave, sf_trace_ao_sum_fixup, nrm, ao,
+                              dst);
 }
 
 // The context's G-buffer into the context's light buffer: an overwriting call makes the buffer, an accumulating one
@@ -2233,12 +2195,10 @@ int sf_trace_ao_sum(sf_ctx* c, const sf_ao_params* p)
 {
     if (!c || !p) return SF_EINVAL;
     if (!c->has_view) return SF_ENOVIEW;
-    if (!c->light) {
-        ShadowImage im;   // (the parameters' errors come before the buffer's state)
-        if (int rc = ao_check(c, p, true, nullptr, true, &im)) return rc;
-        if (p->accumulate) return SF_ESTATE;
-        if (int rc = own_light_buffer(c)) return rc;
-    }
+    ShadowImage im;
+    if (int rc = own_buffer_checked(c, &c->light, 16, p->accumulate != 0u,
+                                    [&] { return ao_check(c, p, true, nullptr, true, &im); }))
+        return rc;
     return sf_trace_ao_sum_to(c, p, nullptr, nullptr, nullptr);
 }
 
@@ -2267,34 +2227,19 @@ int sf_light_fill(sf_ctx* c, const float rgb[3], float* buf, void* stream)
     if (!c || !rgb) return SF_EINVAL;
     for (int k = 0; k < 3; ++k)
         if (!light_component(rgb[k])) return SF_EINVAL;
-    if (!buf)
-        if (int rc = own_light_buffer(c)) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
-    const uint32_t n = c->W * c->H;
-    hipLaunchKernelGGL(sf_light_fill_px, dim3((n + 255u) / 256u), dim3(256), 0, s, n, rgb[0], rgb[1], rgb[2],
-                       buf ? buf : c->light);
-    SF_HIP(c, hipGetLastError());
-    return SF_OK;
+    if (!buf)   // (the traces' path for the buffer; the colour is checked above, so nothing is left for its check)
+        if (int rc = own_buffer_checked(c, &c->light, 16, false, [] { return SF_OK; })) return rc;
+    return pixel_pass(c, stream, sf_light_fill_px, c->W * c->H, rgb[0], rgb[1], rgb[2], buf ? buf : c->light);
 }
 
-// The resolve pass: one thread per pixel of the context's frame, the buffers defaulted to the context's.
+// The resolve pass: the buffers defaulted to the context's.
 int sf_light_image_buffer(sf_ctx* c, void* stream, const float* pos4, const float* buf, uint8_t* rgba)
 {
     if (!c) return SF_EINVAL;
     if (!rgba && !c->image) return SF_ESTATE;
     if (!buf && !c->light) return SF_ESTATE;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    DevGuard g(c->device);
-    if (int rc = ctx_join(c, s)) return rc;
-    StreamMark mark_(c, s);
-    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
-    hipLaunchKernelGGL(sf_light_image_buffer_px, grid, dim3(256), 0, s, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
-                       buf ? buf : (const float*)c->light, rgba ? rgba : c->image);
-    SF_HIP(c, hipGetLastError());
-    return SF_OK;
+    return pixel_pass(c, stream, sf_light_image_buffer_px, c->W, c->H, pos4 ? pos4 : (const float*)c->pos,
+                      buf ? buf : (const float*)c->light, rgba ? rgba : c->image);
 }
 
 // Multi-frame persistent trace (sf.h; kernel sf_trace_frames1). One launch where every frame's own launch() would be

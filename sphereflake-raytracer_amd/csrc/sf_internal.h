@@ -292,6 +292,32 @@ struct AoSum {
     float c[SF_AO_SAMPLES][3];        // the samples' colours
 };
 
+#if defined(__HIPCC__) || defined(__HIP__)
+// The two Lambert terms at a pixel of normal n, shared by the image passes (sf_post.hip) and the summing traces
+// (sf_kernels.hip): every operation rounded on its own, in this order -- the bits are the contract
+// (sphereflake_amd/lights.py restates them).
+// A directional light: max(0, n . s) with s the direction towards the sun as given (a NaN product gives 0).
+__device__ __forceinline__ float sf_lambert_sun(const float4 n, float sx, float sy, float sz)
+{
+    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(n.x, sx), __fmul_rn(n.y, sy)), __fmul_rn(n.z, sz));
+    return fmaxf(0.0f, dot);
+}
+// A point light l seen from the surface point w: max(0, n . (l - w) / len), len the shadow ray's length (a NaN
+// quotient gives 0). (sqrtf and / are correctly rounded under the build's -fhip-fp32-correctly-rounded-divide-sqrt;
+// __fsqrt_rn is not)
+__device__ __forceinline__ float sf_lambert_point(const float4 n, float wx, float wy, float wz, float lx, float ly,
+                                                  float lz)
+{
+    const float dx = __fadd_rn(__fsub_rn(wx, lx), 0.0f);
+    const float dy = __fadd_rn(__fsub_rn(wy, ly), 0.0f);
+    const float dz = __fadd_rn(__fsub_rn(wz, lz), 0.0f);
+    const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float ex = __fsub_rn(lx, wx), ey = __fsub_rn(ly, wy), ez = __fsub_rn(lz, wz);
+    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(n.x, ex), __fmul_rn(n.y, ey)), __fmul_rn(n.z, ez));
+    return fmaxf(0.0f, dot / len);
+}
+#endif
+
 // Multi-frame persistent trace (round 6, sf_render_frames): the frames of one launch, passed by value in the kernel
 // argument segment (copied by the runtime at the launch, so the host may build the next batch at once; 4 KB at most:
 // 11 FrameArgs). Frame f is one slot context's view into that context's G-buffer and stats. All frames share one

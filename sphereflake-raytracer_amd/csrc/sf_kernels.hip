@@ -4320,6 +4320,205 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_rays_fixup(FrameArgs a
 }
 
 // ------------------------------------------------------------------------------------------
+// The light traces: nine traces over the 8x8 tiles of a position image, one _wave and one
+// _fixup kernel each. A trace is a pose -- where the ray of entry i to the lane's pixel starts and ends -- run through
+// one of two entry loops (trace_parallel_entries: a ray origin per lane, traverse_mixed; trace_point_entries: one
+// origin per entry, traverse_ray) and closed by one of two endings (light_mask_end, light_sum_end). The two kernel
+// bodies and what they hand a group come first.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// What a kernel body hands a group: the wave's LDS image, the builder column, the tile, the levels provisioned, and
+// where a first pass flags the tile (null in the re-trace, which flags nothing).
+template <bool FIXUP>
+struct LightTile {
+    float* L;
+    float4 bcol;
+    uint32_t group, levels;
+    uint32_t* overflow_list;
+    uint32_t* overflow_count;
+};
+using WaveTile = LightTile<false>;
+using FixupTile = LightTile<true>;
+
+// The body of a _wave kernel: one tile per one-wave workgroup; `lds` is the dynamic LDS for a.max_depth levels,
+// SF_LDS_WAVE_FLOATS for the traces of trace_point_entries and SF_LDS_RAYS_FLOATS (the mixed traversal's tables and
+// centre stack) for those of trace_parallel_entries. STAGE: Once where the group reads the root image and never writes
+// it, InGroup where it stages what it needs itself (and a tile without a surface pixel stages nothing). Plain vector
+// stores only; no statistic and none of the renders' state is touched.
+template <RootStage STAGE, class GroupFn>
+__device__ __forceinline__ void light_wave(const FrameArgs& a, float* lds, uint32_t groups, uint32_t* overflow_list,
+                                           uint32_t* overflow_count, GroupFn group_fn)
+{
+    if (blockIdx.x >= groups) return;
+    if constexpr (STAGE == RootStage::Once) stage_root(lds, a.root);
+    group_fn(WaveTile{lds, build_column(a.consts), blockIdx.x, a.max_depth, overflow_list, overflow_count});
+}
+
+// The body of a _fixup kernel: the re-trace of the flagged tiles, for every entry, at SF_MAX_LEVELS (fixup_groups;
+// sf_trace_dirs_fixup's list and counters).
+template <RootStage STAGE, class GroupFn>
+__device__ __forceinline__ void light_fixup(const FrameArgs& a, float* lds, const uint32_t* overflow_list,
+                                            uint32_t* counters, uint32_t parity, GroupFn group_fn)
+{
+    fixup_groups<STAGE, false>(a, lds, overflow_list, counters, parity, [&](uint32_t group, const float4 bcol) {
+        group_fn(FixupTile{lds, bcol, group, SF_MAX_LEVELS, nullptr, nullptr});
+    });
+}
+
+// a pixel's float4 of a position or normal image
+__device__ __forceinline__ float4 px4(const float* __restrict__ image, uint32_t px)
+{
+    return reinterpret_cast<const float4*>(image)[px];
+}
+
+// The lane's ray of one entry: from F to the surface point w, where there is one.
+struct RayPose {
+    float wx, wy, wz, Fx, Fy, Fz;
+    bool ray;
+};
+
+// The entry loop of the traces whose rays have an origin per lane: suns, shafts, AO and its sum.
+// A FIX MADE HERE IS MADE IN trace_suns_sum_group TOO: it keeps this loop written out (the reason is given there).
+// pose(i) is the lane's RayPose of entry i (a uniform index: what the pose reads of the argument segment are scalar
+// loads). Per entry d, len and bound are formed by shadow_ray and the lane's root centre is 0 - F (Sphereflake.cpp:83
+// at F); an entry that leaves no lane on (no ray, or a d that is zero or not finite) is skipped and keeps its bit; else
+// traverse_mixed runs in its any-hit mode, unchanged, on the axis columns staged once. Returns the word whose bit i is
+// set where entry i's ray to the lane's pixel is stopped, and ORs the traversals' status into `status`.
+template <bool FIXUP, class Pose>
+__device__ __forceinline__ uint64_t trace_parallel_entries(const FrameArgs& a, uint32_t n, float keep,
+                                                           const LightTile<FIXUP>& t, uint32_t& status, Pose pose)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;   // (the mixed traversal has no cone and no order)
+    float* const cstk = t.L + SF_LDS_WAVE_FLOATS(t.levels + 1u);
+    uint64_t shadowed = 0ull;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0u; i < n; ++i) {
+        const RayPose p = pose(i);
+        float dx, dy, dz, bound;
+        shadow_ray(p.wx, p.wy, p.wz, p.Fx, p.Fy, p.Fz, keep, K->lut, dx, dy, dz, bound);
+        const float rx = __fsub_rn(0.0f, p.Fx), ry = __fsub_rn(0.0f, p.Fy), rz = __fsub_rn(0.0f, p.Fz);
+        const bool on = p.ray && finite3(dx, dy, dz);
+        if (wave_ballot(on) == 0ull) continue;   // (uniform)
+        HitState h;
+        h.hit = false;
+        int32_t md = -1;
+        uint32_t st = 0u;
+        lds_fence();   // (the entry before, or the re-trace's earlier tile, has read its tables)
+        traverse_mixed<true>(K, t.L, cstk, t.bcol, t.levels, dx, dy, dz, rx, ry, rz, on, h, md, st, culls, bound);
+        status |= st;
+        shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
+    }
+    return shadowed;
+}
+
+// The part of stage_root's image that depends on the light: words 0..2 the translation, word 3 its squared length
+// (the columns stay). Without a branch on the lane, as stage_root_all_lanes: lane l writes word l & 3. (stage_root
+// itself inside the loop over the lights had its 16 lane compares hoisted into 32 SGPRs: occupancy 7.)
+__device__ __forceinline__ void stage_root_translation(float* __restrict__ Lbase, float tx, float ty, float tz)
+{
+    const uint32_t l = threadIdx.x & 3u;
+    const float tcc = (tx * tx + ty * ty) + tz * tz;
+    Lbase[l] = l == 0u ? tx : l == 1u ? ty : l == 2u ? tz : tcc;   // TraverseLds::root()
+}
+
+// The entry loop of the traces whose rays start at one point per entry (shadows and its sum): entry i is the light
+// ls.l[i] (a uniform index, scalar loads from the argument segment), (wx, wy, wz) the lane's surface point. The
+// context's columns are staged once per tile; per light d, len and bound are formed by shadow_ray, the root image's
+// translation is restaged as 0 - l_i (as trace_ray_group does per origin) and traverse_ray runs in its shadow mode,
+// unchanged. A light that leaves no lane on (one that is not finite) is skipped and keeps its bit. The result and
+// `status` are trace_parallel_entries'.
+template <bool FIXUP, class Lights>
+__device__ __forceinline__ uint64_t trace_point_entries(const FrameArgs& a, const GroupLane& g, bool surface, float wx,
+                                                        float wy, float wz, const Lights& ls, const LightTile<FIXUP>& t,
+                                                        uint32_t& status)
+{
+    const DeviceConsts* __restrict__ K = a.consts;
+    const uint32_t culls = a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST);
+    const uint32_t n = ls.n;   // (uniform, 1..64)
+    uint64_t shadowed = 0ull;
+    lds_fence();
+    stage_root(t.L, a.root);   // the columns, once per tile; each light restages its translation
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0u; i < n; ++i) {
+        const float lx = ls.l[i][0], ly = ls.l[i][1], lz = ls.l[i][2];
+        float dx, dy, dz, bound;
+        shadow_ray(wx, wy, wz, lx, ly, lz, ls.keep, K->lut, dx, dy, dz, bound);
+        const bool on = surface && finite3(dx, dy, dz);
+        const uint64_t onm = wave_ballot(on);
+        if (onm == 0ull) continue;   // (uniform)
+        const uint32_t axl = axis_lane(onm, g.mid);
+        const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
+        float r[12];   // (traverse_ray reads the translation only; the columns are in the staged image)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) r[k] = 0.0f;
+        r[9] = __fsub_rn(0.0f, lx);   // (Sphereflake.cpp:83 at the light)
+        r[10] = __fsub_rn(0.0f, ly);
+        r[11] = __fsub_rn(0.0f, lz);
+        lds_fence();
+        stage_root_translation(t.L, r[9], r[10], r[11]);   // (the light before left its own)
+        HitState h;
+        h.hit = false;
+        int32_t md = -1;
+        uint32_t st = 0u;
+        traverse_ray<false, false, true>(K, r, t.L, t.bcol, t.levels, on ? dx : ax, on ? dy : ay, on ? dz : az, on, h,
+                                         md, st, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
+        status |= st;
+        shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
+    }
+    return shadowed;
+}
+
+// The mask ending: bit i of mask[p] is set where entry i reaches the pixel (what the single-entry trace writes as
+// 255), bits n..63 are 0. A tile flagged for any entry (uniform: more levels needed) goes onto the overflow list once
+// and is re-traced for all of them. A tile row is 64 contiguous bytes: one 8-byte vector store per valid lane.
+template <bool FIXUP>
+__device__ __forceinline__ void light_mask_end(const FrameArgs& a, const GroupLane& g, uint32_t n, uint64_t shadowed,
+                                               uint32_t status, uint64_t* __restrict__ mask, const LightTile<FIXUP>& t)
+{
+    if (!FIXUP && status != 0u) flag_group(t.overflow_list, t.overflow_count, t.group);
+    const uint64_t all = n >= 64u ? ~0ull : (1ull << n) - 1ull;
+    if (g.valid) mask[(size_t)g.y * a.W + g.x] = all & ~shadowed;
+}
+
+// The summing ending. Across the traversals a lane carries what it carries under the mask ending --
+// its position, the 64-bit `shadowed` word, the surface flag; the normal N, the base and the three sums exist only
+// here: colour_i (lit_i ? lam(N, i) : 0) is added per channel in index order onto the base, then one 16-byte vector
+// store. lam(N, i) is the Lambert term of entry i at the lane's pixel. A tile flagged for more levels is re-traced for
+// ALL of the chunk's entries, so its first pass stores nothing (the flag is uniform and known when the loop ends): an
+// accumulating call would otherwise add the chunk twice. The fixup kernel reads the base, sums and stores.
+template <bool FIXUP, class Sum, class Lam>
+__device__ __forceinline__ void light_sum_end(const FrameArgs& a, const GroupLane& g, bool surface, uint64_t shadowed,
+                                              uint32_t status, const Sum& ss, const float* __restrict__ nrm4,
+                                              float* __restrict__ out, const LightTile<FIXUP>& t, Lam lam)
+{
+    if (!FIXUP && status != 0u) {
+        flag_group(t.overflow_list, t.overflow_count, t.group);
+        return;
+    }
+    if (!g.valid) return;   // (a partial tile: nothing outside the image)
+    float4* const o = reinterpret_cast<float4*>(out) + ((size_t)g.y * a.W + g.x);
+    if (!surface) {   // a miss of the frame: an accumulating call leaves it, an overwriting one zeroes it
+        if (!ss.accumulate) *o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const float4 N = px4(nrm4, g.ray);   // (AO's lam ignores N: there the load is dead and the compiler drops it)
+    float4 S = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (ss.accumulate) S = *o;   // (uniform)
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0u; i < ss.n; ++i) {
+        const float k = ((shadowed >> i) & 1ull) ? 0.0f : lam(N, i);
+        S.x = __fadd_rn(S.x, __fmul_rn(ss.c[i][0], k));
+        S.y = __fadd_rn(S.y, __fmul_rn(ss.c[i][1], k));
+        S.z = __fadd_rn(S.z, __fmul_rn(ss.c[i][2], k));
+    }
+    *o = S;   // (.w: the base's)
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
 // Shadows from a point light (sf_trace_shadow_to). Pixel p of a view-space position image (float4,
 // as the renders write it; origin o) is a frame miss where P == (0, 0, 0) (Shaders/post_final.glsl:20): vis = 255, no
 // ray. Else w = o + P, d = (w - l) + 0, len = sqrt((d.x d.x + d.y d.y) + d.z d.z), bound = len (1 - bias), every
@@ -4332,14 +4531,13 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_rays_fixup(FrameArgs a
 namespace {
 
 template <bool FIXUP>
-__device__ __forceinline__ void trace_shadow_group(const FrameArgs& a, const float4* __restrict__ pos4,
+__device__ __forceinline__ void trace_shadow_group(const FrameArgs& a, const float* __restrict__ pos4,
                                                    const ShadowArgs& sa, uint8_t* __restrict__ vis,
-                                                   float* __restrict__ L, const float4 bcol, uint32_t group,
-                                                   uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
+                                                   const LightTile<FIXUP>& t)
 {
     const DeviceConsts* __restrict__ K = a.consts;
-    const GroupLane g = tile_lane(a, group);
-    const float4 P = pos4[g.ray];
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
     const bool surface = !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
     float dx, dy, dz, bound;
     shadow_ray(__fadd_rn(sa.o[0], P.x), __fadd_rn(sa.o[1], P.y), __fadd_rn(sa.o[2], P.z), sa.l[0], sa.l[1], sa.l[2],
@@ -4359,149 +4557,85 @@ __device__ __forceinline__ void trace_shadow_group(const FrameArgs& a, const flo
 #ifdef SF_SHADOW_CLOSEST
         // measurement builds only: the closest-hit traversal and the comparison afterwards (no early exit, no bound
         // seed) -- what the any-hit mode is measured against
-        traverse_ray<>(K, a.root, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az, on, h, md, status,
+        traverse_ray<>(K, a.root, t.L, t.bcol, t.levels, on ? dx : ax, on ? dy : ay, on ? dz : az, on, h, md, status,
                        culls | (FIXUP ? SF_FLAG_NO_FRONT_FIRST : 0u), nullptr, axl);
         h.hit = on && h.minT < bound;
 #else
         // (a tie never flags in the shadow mode, so the re-trace keeps the front-first order)
-        traverse_ray<false, false, true>(K, a.root, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az,
-                                                on, h, md, status, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
+        traverse_ray<false, false, true>(K, a.root, t.L, t.bcol, t.levels, on ? dx : ax, on ? dy : ay, on ? dz : az,
+                                         on, h, md, status, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
 #endif
     }
-    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);   // (uniform) more levels needed
+    // (uniform) more levels needed
+    if (!FIXUP && status != 0u) flag_group(t.overflow_list, t.overflow_count, t.group);
     store_vis_tile(a, vis, g, h.hit);
 }
 
 }  // namespace
 
-// One tile per one-wave workgroup, dynamic LDS for a.max_depth levels (the launch of sf_trace_dirs_wave). Touches none
-// of the context's statistics.
+// The traversal only reads the light's root image: staged once.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_shadow_wave(FrameArgs a, const float* pos4, ShadowArgs sa,
                                                                       uint8_t* vis, uint32_t groups,
                                                                       uint32_t* overflow_list, uint32_t* overflow_count)
 {
     extern __shared__ float lds[];
-    if (blockIdx.x >= groups) return;
-    stage_root(lds, a.root);
-    trace_shadow_group<false>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, build_column(a.consts), blockIdx.x,
-                              a.max_depth, overflow_list, overflow_count);
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_shadow_group(a, pos4, sa, vis, t); });
 }
 
-// Re-trace of the flagged tiles at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and counters). The
-// traversal only reads the light's root image: staged once.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_shadow_fixup(FrameArgs a, const float* pos4, ShadowArgs sa,
                                                                        uint8_t* vis, const uint32_t* overflow_list,
                                                                        uint32_t* counters, uint32_t parity)
 {
     extern __shared__ float lds[];
-    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
-                                         [&](uint32_t group, const float4 bcol) {
-        trace_shadow_group<true>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, bcol, group, SF_MAX_LEVELS,
-                                 nullptr, nullptr);
-    });
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_shadow_group(a, pos4, sa, vis, t); });
 }
 
 // ------------------------------------------------------------------------------------------
 // Many lights per pixel in one launch (sf_trace_shadows_to). Bit i of mask[p] is what
-// sf_trace_shadow_wave writes for light i at p (1 = 255, 0 = 0), bits n..63 are 0. The lane's position is loaded once;
-// per light (a uniform index, the lights are scalar loads from the argument segment) d, len and bound are formed as in
-// trace_shadow_group, the root image is restaged with the translation 0 - l_i (as trace_ray_group does per origin)
-// and traverse_ray runs in its shadow mode, unchanged. A tile with no surface pixel traces nothing. The launch's
-// levels are one value for all lights; a tile flagged for any light goes onto the overflow list once and is re-traced
-// for all of them.
+// sf_trace_shadow_wave writes for light i at p (1 = 255, 0 = 0), bits n..63 are 0. The pose is the lane's surface point
+// w = o + P, formed once; the entries are the lights (trace_point_entries), the ending the mask's. A tile with no
+// surface pixel traces nothing. The launch's levels are one value for all lights.
 // ------------------------------------------------------------------------------------------
 namespace {
 
-// The part of stage_root's image that depends on the light: words 0..2 the translation, word 3 its squared length
-// (the columns stay). Without a branch on the lane, as stage_root_all_lanes: lane l writes word l & 3. (stage_root
-// itself inside the loop over the lights had its 16 lane compares hoisted into 32 SGPRs: occupancy 7.)
-__device__ __forceinline__ void stage_root_translation(float* __restrict__ Lbase, float tx, float ty, float tz)
-{
-    const uint32_t l = threadIdx.x & 3u;
-    const float tcc = (tx * tx + ty * ty) + tz * tz;
-    Lbase[l] = l == 0u ? tx : l == 1u ? ty : l == 2u ? tz : tcc;   // TraverseLds::root()
-}
-
 template <bool FIXUP>
-__device__ __forceinline__ void trace_shadows_group(const FrameArgs& a, const float4* __restrict__ pos4,
+__device__ __forceinline__ void trace_shadows_group(const FrameArgs& a, const float* __restrict__ pos4,
                                                     const ShadowLights& sl, uint64_t* __restrict__ mask,
-                                                    float* __restrict__ L, const float4 bcol, uint32_t group,
-                                                    uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
+                                                    const LightTile<FIXUP>& t)
 {
-    const DeviceConsts* __restrict__ K = a.consts;
-    const GroupLane g = tile_lane(a, group);
-    const float4 P = pos4[g.ray];
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
     const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
-    const uint32_t n = sl.n;   // (uniform, 1..64)
     uint64_t shadowed = 0ull;   // bit i: light i does not reach the lane's pixel
     uint32_t status = 0u;
     if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss: every light's bit is set)
         const float wx = __fadd_rn(sl.o[0], P.x), wy = __fadd_rn(sl.o[1], P.y), wz = __fadd_rn(sl.o[2], P.z);
-        const uint32_t culls = a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST);
-        lds_fence();
-        stage_root(L, a.root);   // the columns, once per tile; each light restages its translation
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 0u; i < n; ++i) {
-            const float lx = sl.l[i][0], ly = sl.l[i][1], lz = sl.l[i][2];
-            float dx, dy, dz, bound;
-            shadow_ray(wx, wy, wz, lx, ly, lz, sl.keep, K->lut, dx, dy, dz, bound);
-            // finiteness depends on the light: a light that is not finite leaves no lane on, and its bit stays set
-            const bool on = surface && finite3(dx, dy, dz);
-            const uint64_t onm = wave_ballot(on);
-            if (onm == 0ull) continue;   // (uniform)
-            const uint32_t axl = axis_lane(onm, g.mid);
-            const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
-            float r[12];   // (traverse_ray reads the translation only; the columns are in the staged image)
-#pragma unroll
-            for (int k = 0; k < 9; ++k) r[k] = 0.0f;
-            r[9] = __fsub_rn(0.0f, lx);   // (Sphereflake.cpp:83 at the light)
-            r[10] = __fsub_rn(0.0f, ly);
-            r[11] = __fsub_rn(0.0f, lz);
-            lds_fence();
-            stage_root_translation(L, r[9], r[10], r[11]);   // (the light before left its own)
-            HitState h;
-            h.hit = false;
-            int32_t md = -1;
-            uint32_t st = 0u;
-            traverse_ray<false, false, true>(K, r, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az, on, h,
-                                                    md, st, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
-            status |= st;
-            shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
-        }
+        shadowed = trace_point_entries(a, g, surface, wx, wy, wz, sl, t, status);
     }
-    // (uniform) more levels needed for some light: once on the list
-    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);
-    // a tile row is 64 contiguous bytes: one 8-byte vector store per valid lane
-    const uint64_t all = n >= 64u ? ~0ull : (1ull << n) - 1ull;
-    if (g.valid) mask[(size_t)g.y * a.W + g.x] = all & ~shadowed;
+    light_mask_end(a, g, sl.n, shadowed, status, mask, t);
 }
 
 }  // namespace
 
-// One tile per one-wave workgroup, dynamic LDS for a.max_depth levels (the launch of sf_trace_shadow_wave). Touches
-// none of the context's statistics.
+// The group stages the columns itself, and a tile without a surface pixel stages nothing.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_wave(FrameArgs a, const float* pos4, ShadowLights sl,
                                                                        uint64_t* mask, uint32_t groups,
                                                                        uint32_t* overflow_list, uint32_t* overflow_count)
 {
     extern __shared__ float lds[];
-    if (blockIdx.x >= groups) return;
-    trace_shadows_group<false>(a, reinterpret_cast<const float4*>(pos4), sl, mask, lds, build_column(a.consts),
-                               blockIdx.x, a.max_depth, overflow_list, overflow_count);
+    light_wave<RootStage::InGroup>(a, lds, groups, overflow_list, overflow_count,
+                                   [&](const WaveTile& t) { trace_shadows_group(a, pos4, sl, mask, t); });
 }
 
-// Re-trace of the flagged tiles, for every light, at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and
-// counters). The group stages the columns itself, and a tile without a surface pixel stages nothing.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_fixup(FrameArgs a, const float* pos4, ShadowLights sl,
                                                                         uint64_t* mask, const uint32_t* overflow_list,
                                                                         uint32_t* counters, uint32_t parity)
 {
     extern __shared__ float lds[];
-    fixup_groups<RootStage::InGroup, false>(a, lds, overflow_list, counters, parity,
-                                            [&](uint32_t group, const float4 bcol) {
-        trace_shadows_group<true>(a, reinterpret_cast<const float4*>(pos4), sl, mask, lds, bcol, group, SF_MAX_LEVELS,
-                                  nullptr, nullptr);
-    });
+    light_fixup<RootStage::InGroup>(a, lds, overflow_list, counters, parity,
+                                    [&](const FixupTile& t) { trace_shadows_group(a, pos4, sl, mask, t); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4517,14 +4651,12 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_fixup(FrameArg
 namespace {
 
 template <bool FIXUP>
-__device__ __forceinline__ void trace_sun_group(const FrameArgs& a, const float4* __restrict__ pos4, const SunArgs& sa,
-                                                uint8_t* __restrict__ vis, float* __restrict__ L, const float4 bcol,
-                                                uint32_t group, uint32_t levels, uint32_t* overflow_list,
-                                                uint32_t* overflow_count)
+__device__ __forceinline__ void trace_sun_group(const FrameArgs& a, const float* __restrict__ pos4, const SunArgs& sa,
+                                                uint8_t* __restrict__ vis, const LightTile<FIXUP>& t)
 {
     const DeviceConsts* __restrict__ K = a.consts;
-    const GroupLane g = tile_lane(a, group);
-    const float4 P = pos4[g.ray];
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
     const bool surface = !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
     const float wx = __fadd_rn(sa.o[0], P.x), wy = __fadd_rn(sa.o[1], P.y), wz = __fadd_rn(sa.o[2], P.z);
     const float Fx = __fadd_rn(wx, sa.f[0]), Fy = __fadd_rn(wy, sa.f[1]), Fz = __fadd_rn(wz, sa.f[2]);
@@ -4539,262 +4671,164 @@ __device__ __forceinline__ void trace_sun_group(const FrameArgs& a, const float4
     uint32_t status = 0u;
     if (wave_ballot(on) != 0ull) {   // (uniform; else no ray of the group is traced)
         const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;   // (the mixed traversal has no cone and no order)
-        float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
+        float* const cstk = t.L + SF_LDS_WAVE_FLOATS(t.levels + 1u);
         int32_t md = -1;
         lds_fence();   // (the re-trace's earlier tile has read its tables)
-        traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, status, culls, bound);
+        traverse_mixed<true>(K, t.L, cstk, t.bcol, t.levels, dx, dy, dz, rx, ry, rz, on, h, md, status, culls, bound);
     }
-    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);   // (uniform) more levels needed
+    // (uniform) more levels needed
+    if (!FIXUP && status != 0u) flag_group(t.overflow_list, t.overflow_count, t.group);
     store_vis_tile(a, vis, g, h.hit);
 }
 
 }  // namespace
 
-// One tile per one-wave workgroup, dynamic LDS SF_LDS_RAYS_FLOATS(a.max_depth) (the mixed traversal's tables and
-// centre stack). Touches none of the context's statistics.
+// The mixed traversal reads the root image's columns and never writes it: staged once (as in every trace below whose
+// rays have an origin per lane).
 extern "C" __global__ __launch_bounds__(64) void sf_trace_sun_wave(FrameArgs a, const float* pos4, SunArgs sa,
                                                                    uint8_t* vis, uint32_t groups,
                                                                    uint32_t* overflow_list, uint32_t* overflow_count)
 {
     extern __shared__ float lds[];
-    if (blockIdx.x >= groups) return;
-    stage_root(lds, a.root);
-    trace_sun_group<false>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, build_column(a.consts), blockIdx.x,
-                           a.max_depth, overflow_list, overflow_count);
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_sun_group(a, pos4, sa, vis, t); });
 }
 
-// Re-trace of the flagged tiles at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and counters). The mixed
-// traversal reads the root image's columns and never writes it: staged once.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_sun_fixup(FrameArgs a, const float* pos4, SunArgs sa,
                                                                     uint8_t* vis, const uint32_t* overflow_list,
                                                                     uint32_t* counters, uint32_t parity)
 {
     extern __shared__ float lds[];
-    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
-                                         [&](uint32_t group, const float4 bcol) {
-        trace_sun_group<true>(a, reinterpret_cast<const float4*>(pos4), sa, vis, lds, bcol, group, SF_MAX_LEVELS,
-                              nullptr, nullptr);
-    });
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_sun_group(a, pos4, sa, vis, t); });
 }
 
 // ------------------------------------------------------------------------------------------
 // Many sun directions per pixel in one launch (sf_trace_suns_to): a soft sun, a sky dome of parallel
 // rays. Bit i of mask[p] is what sf_trace_sun_wave writes for direction i at p (1 = 255, 0 = 0), bits n..63 are 0. The
-// lane's position is loaded and w = o + P formed once; per direction (a uniform index, the f_i = s_i tau are scalar
-// loads from the argument segment) F, d, bound and the lane's root centre are formed as in trace_sun_group and
-// traverse_mixed runs in its any-hit mode, unchanged, on the axis columns staged once. A tile with no surface pixel
-// traces nothing; a direction that leaves no lane on (zero or not finite) is skipped and keeps its bit. A tile flagged
-// for any direction goes onto the overflow list once and is re-traced for all of them.
+// pose: the lane's position is loaded and w = o + P formed once; per direction F = w + f_i, the f_i = s_i tau scalar
+// loads from the argument segment (trace_sun_group's F). A tile with no surface pixel traces nothing; a direction that
+// is zero or not finite leaves no lane on.
 // ------------------------------------------------------------------------------------------
 namespace {
 
 template <bool FIXUP>
-__device__ __forceinline__ void trace_suns_group(const FrameArgs& a, const float4* __restrict__ pos4,
-                                                 const SunDirs& sd, uint64_t* __restrict__ mask,
-                                                 float* __restrict__ L, const float4 bcol, uint32_t group,
-                                                 uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
+__device__ __forceinline__ void trace_suns_group(const FrameArgs& a, const float* __restrict__ pos4, const SunDirs& sd,
+                                                 uint64_t* __restrict__ mask, const LightTile<FIXUP>& t)
 {
-    const DeviceConsts* __restrict__ K = a.consts;
-    const GroupLane g = tile_lane(a, group);
-    const float4 P = pos4[g.ray];
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
     const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
-    const uint32_t n = sd.n;   // (uniform, 1..64)
     uint64_t shadowed = 0ull;   // bit i: direction i's ray to the lane's pixel is stopped
     uint32_t status = 0u;
     if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss: every direction's bit is set)
         const float wx = __fadd_rn(sd.o[0], P.x), wy = __fadd_rn(sd.o[1], P.y), wz = __fadd_rn(sd.o[2], P.z);
-        const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;   // (the mixed traversal has no cone and no order)
-        float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 0u; i < n; ++i) {
-            const float Fx = __fadd_rn(wx, sd.f[i][0]), Fy = __fadd_rn(wy, sd.f[i][1]), Fz = __fadd_rn(wz, sd.f[i][2]);
-            float dx, dy, dz, bound;
-            shadow_ray(wx, wy, wz, Fx, Fy, Fz, sd.keep, K->lut, dx, dy, dz, bound);
-            // the lane's root centre (Sphereflake.cpp:83 at F)
-            const float rx = __fsub_rn(0.0f, Fx), ry = __fsub_rn(0.0f, Fy), rz = __fsub_rn(0.0f, Fz);
-            // finiteness depends on the direction: one that is zero or not finite leaves no lane on
-            const bool on = surface && finite3(dx, dy, dz);
-            if (wave_ballot(on) == 0ull) continue;   // (uniform)
-            HitState h;
-            h.hit = false;
-            int32_t md = -1;
-            uint32_t st = 0u;
-            lds_fence();   // (the direction before, or the re-trace's earlier tile, has read its tables)
-            traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, st, culls, bound);
-            status |= st;
-            shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
-        }
+        shadowed = trace_parallel_entries(a, sd.n, sd.keep, t, status, [&](uint32_t i) {
+            return RayPose{wx, wy, wz, __fadd_rn(wx, sd.f[i][0]), __fadd_rn(wy, sd.f[i][1]), __fadd_rn(wz, sd.f[i][2]),
+                           surface};
+        });
     }
-    // (uniform) more levels needed for some direction: once on the list
-    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);
-    // a tile row is 64 contiguous bytes: one 8-byte vector store per valid lane
-    const uint64_t all = n >= 64u ? ~0ull : (1ull << n) - 1ull;
-    if (g.valid) mask[(size_t)g.y * a.W + g.x] = all & ~shadowed;
+    light_mask_end(a, g, sd.n, shadowed, status, mask, t);
 }
 
-// ---- the summing traces (sf_trace_suns_sum_to, sf_trace_shadows_sum_to): the loops of
-// trace_suns_group and trace_shadows_group with another ending. Across the traversals a lane carries what it carries
-// there -- its position, the 64-bit `shadowed` word, the surface flag; the normal, the base and the three sums exist
-// only in the ending (light_sum_store), which adds colour_i (lit_i ? lam_i : 0) per channel in index order onto the
-// base and makes one 16-byte vector store. A tile flagged for more levels is re-traced for ALL of the chunk's entries,
-// so its first pass stores nothing (the flag is uniform and known when the loop ends): an accumulating call would
-// otherwise add the chunk twice. The fixup kernel reads the base, sums and stores.
+}  // namespace
 
-// The ending for a lane of a tile that is not flagged. lam(i) is the Lambert term of entry i at the lane's pixel.
-template <class Sum, class Lam>
-__device__ __forceinline__ void light_sum_store(const FrameArgs& a, const GroupLane& g, bool surface, uint64_t shadowed,
-                                                const Sum& ss, float4* __restrict__ out, Lam lam)
+extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_wave(FrameArgs a, const float* pos4, SunDirs sd,
+                                                                    uint64_t* mask, uint32_t groups,
+                                                                    uint32_t* overflow_list, uint32_t* overflow_count)
 {
-    if (!g.valid) return;   // (a partial tile: nothing outside the image)
-    float4* const o = out + ((size_t)g.y * a.W + g.x);
-    if (!surface) {   // a miss of the frame: an accumulating call leaves it, an overwriting one zeroes it
-        if (!ss.accumulate) *o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        return;
-    }
-    float4 S = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (ss.accumulate) S = *o;   // (uniform)
-#pragma clang loop unroll(disable)
-    for (uint32_t i = 0u; i < ss.n; ++i) {
-        const float k = ((shadowed >> i) & 1ull) ? 0.0f : lam(i);
-        S.x = __fadd_rn(S.x, __fmul_rn(ss.c[i][0], k));
-        S.y = __fadd_rn(S.y, __fmul_rn(ss.c[i][1], k));
-        S.z = __fadd_rn(S.z, __fmul_rn(ss.c[i][2], k));
-    }
-    *o = S;   // (.w: the base's)
+    extern __shared__ float lds[];
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_suns_group(a, pos4, sd, mask, t); });
 }
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_fixup(FrameArgs a, const float* pos4, SunDirs sd,
+                                                                     uint64_t* mask, const uint32_t* overflow_list,
+                                                                     uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_suns_group(a, pos4, sd, mask, t); });
+}
+
+// ------------------------------------------------------------------------------------------
+// The summing traces (sf_trace_suns_sum_to, sf_trace_shadows_sum_to): the entries of sf_trace_suns_to
+// and sf_trace_shadows_to under the summing ending, one chunk of the call's entries per launch. The Lambert terms are
+// sf_light_image_suns_px's and sf_light_image_many_px's (sf_internal.h).
+// ------------------------------------------------------------------------------------------
+namespace {
 
 template <bool FIXUP>
-__device__ __forceinline__ void trace_suns_sum_group(const FrameArgs& a, const float4* __restrict__ pos4,
-                                                     const float4* __restrict__ nrm4, const SunSum& ss,
-                                                     float4* __restrict__ out, float* __restrict__ L,
-                                                     const float4 bcol, uint32_t group, uint32_t levels,
-                                                     uint32_t* overflow_list, uint32_t* overflow_count)
+__device__ __forceinline__ void trace_suns_sum_group(const FrameArgs& a, const float* __restrict__ pos4,
+                                                     const float* __restrict__ nrm4, const SunSum& ss,
+                                                     float* __restrict__ out, const LightTile<FIXUP>& t)
 {
-    const DeviceConsts* __restrict__ K = a.consts;
-    const GroupLane g = tile_lane(a, group);
-    const float4 P = pos4[g.ray];
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
     const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
     const uint32_t n = ss.n;   // (uniform, 1..64)
     uint64_t shadowed = 0ull;   // bit i: direction i's ray to the lane's pixel is stopped
     uint32_t status = 0u;
+    // trace_suns_group's entries with trace_parallel_entries' loop written out.
+    // A FIX MADE IN trace_parallel_entries IS MADE HERE TOO.
+    // Why the copy: through the shared loop this kernel's traversal kept its instructions but got other registers and
+    // ran 2.4-3.0 % slower at n = 16..256 (measured).
     if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss)
+        const DeviceConsts* __restrict__ K = a.consts;
         const float wx = __fadd_rn(ss.o[0], P.x), wy = __fadd_rn(ss.o[1], P.y), wz = __fadd_rn(ss.o[2], P.z);
         const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;
-        float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
+        float* const cstk = t.L + SF_LDS_WAVE_FLOATS(t.levels + 1u);
 #pragma clang loop unroll(disable)
-        for (uint32_t i = 0u; i < n; ++i) {   // (trace_suns_group's loop)
+        for (uint32_t i = 0u; i < n; ++i) {
             const float Fx = __fadd_rn(wx, ss.f[i][0]), Fy = __fadd_rn(wy, ss.f[i][1]), Fz = __fadd_rn(wz, ss.f[i][2]);
             float dx, dy, dz, bound;
             shadow_ray(wx, wy, wz, Fx, Fy, Fz, ss.keep, K->lut, dx, dy, dz, bound);
             const float rx = __fsub_rn(0.0f, Fx), ry = __fsub_rn(0.0f, Fy), rz = __fsub_rn(0.0f, Fz);
             const bool on = surface && finite3(dx, dy, dz);
-            if (wave_ballot(on) == 0ull) continue;   // (uniform: the entry traces no ray and is lit)
+            if (wave_ballot(on) == 0ull) continue;
             HitState h;
             h.hit = false;
             int32_t md = -1;
             uint32_t st = 0u;
             lds_fence();
-            traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, st, culls, bound);
+            traverse_mixed<true>(K, t.L, cstk, t.bcol, t.levels, dx, dy, dz, rx, ry, rz, on, h, md, st, culls, bound);
             status |= st;
             shadowed |= h.hit ? (1ull << i) : 0ull;
         }
     }
-    if (!FIXUP && status != 0u) {   // (uniform) more levels needed: the fixup kernel sums and stores this tile
-        flag_group(overflow_list, overflow_count, group);
-        return;
-    }
-    float4 N = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (surface) N = nrm4[g.ray];
-    // sf_light_image_suns_px's lam
-    light_sum_store(a, g, surface, shadowed, ss, out, [&](uint32_t i) {
-        const float sx = ss.s[i][0], sy = ss.s[i][1], sz = ss.s[i][2];
-        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(N.x, sx), __fmul_rn(N.y, sy)), __fmul_rn(N.z, sz));
-        return fmaxf(0.0f, dot);   // (a NaN product gives 0)
+    light_sum_end(a, g, surface, shadowed, status, ss, nrm4, out, t, [&](const float4 N, uint32_t i) {
+        return sf_lambert_sun(N, ss.s[i][0], ss.s[i][1], ss.s[i][2]);
     });
 }
 
 template <bool FIXUP>
-__device__ __forceinline__ void trace_shadows_sum_group(const FrameArgs& a, const float4* __restrict__ pos4,
-                                                        const float4* __restrict__ nrm4, const ShadowSum& ss,
-                                                        float4* __restrict__ out, float* __restrict__ L,
-                                                        const float4 bcol, uint32_t group, uint32_t levels,
-                                                        uint32_t* overflow_list, uint32_t* overflow_count)
+__device__ __forceinline__ void trace_shadows_sum_group(const FrameArgs& a, const float* __restrict__ pos4,
+                                                        const float* __restrict__ nrm4, const ShadowSum& ss,
+                                                        float* __restrict__ out, const LightTile<FIXUP>& t)
 {
-    const DeviceConsts* __restrict__ K = a.consts;
-    const GroupLane g = tile_lane(a, group);
-    const float4 P = pos4[g.ray];
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
     const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
-    const uint32_t n = ss.n;   // (uniform, 1..64)
     const float wx = __fadd_rn(ss.o[0], P.x), wy = __fadd_rn(ss.o[1], P.y), wz = __fadd_rn(ss.o[2], P.z);
     uint64_t shadowed = 0ull;   // bit i: light i does not reach the lane's pixel
     uint32_t status = 0u;
-    if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss)
-        const uint32_t culls = a.flags & (SF_FLAG_NO_CONE_CULL | SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST);
-        lds_fence();
-        stage_root(L, a.root);   // the columns, once per tile; each light restages its translation
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 0u; i < n; ++i) {   // (trace_shadows_group's loop)
-            const float lx = ss.l[i][0], ly = ss.l[i][1], lz = ss.l[i][2];
-            float dx, dy, dz, bound;
-            shadow_ray(wx, wy, wz, lx, ly, lz, ss.keep, K->lut, dx, dy, dz, bound);
-            const bool on = surface && finite3(dx, dy, dz);
-            const uint64_t onm = wave_ballot(on);
-            if (onm == 0ull) continue;   // (uniform: the entry traces no ray and is lit)
-            const uint32_t axl = axis_lane(onm, g.mid);
-            const float ax = readlane_f(dx, axl), ay = readlane_f(dy, axl), az = readlane_f(dz, axl);
-            float r[12];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) r[k] = 0.0f;
-            r[9] = __fsub_rn(0.0f, lx);
-            r[10] = __fsub_rn(0.0f, ly);
-            r[11] = __fsub_rn(0.0f, lz);
-            lds_fence();
-            stage_root_translation(L, r[9], r[10], r[11]);
-            HitState h;
-            h.hit = false;
-            int32_t md = -1;
-            uint32_t st = 0u;
-            traverse_ray<false, false, true>(K, r, L, bcol, levels, on ? dx : ax, on ? dy : ay, on ? dz : az, on, h,
-                                                    md, st, culls, nullptr, axl, nullptr, 0u, 0u, -1, bound);
-            status |= st;
-            shadowed |= h.hit ? (1ull << i) : 0ull;
-        }
-    }
-    if (!FIXUP && status != 0u) {   // (uniform) more levels needed: the fixup kernel sums and stores this tile
-        flag_group(overflow_list, overflow_count, group);
-        return;
-    }
-    float4 N = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (surface) N = nrm4[g.ray];
-    // sf_light_image_many_px's lam, operation for operation
-    light_sum_store(a, g, surface, shadowed, ss, out, [&](uint32_t i) {
-        const float lx = ss.l[i][0], ly = ss.l[i][1], lz = ss.l[i][2];
-        const float dx = __fadd_rn(__fsub_rn(wx, lx), 0.0f);
-        const float dy = __fadd_rn(__fsub_rn(wy, ly), 0.0f);
-        const float dz = __fadd_rn(__fsub_rn(wz, lz), 0.0f);
-        const float len =
-            __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-        const float ex = __fsub_rn(lx, wx), ey = __fsub_rn(ly, wy), ez = __fsub_rn(lz, wz);
-        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(N.x, ex), __fmul_rn(N.y, ey)), __fmul_rn(N.z, ez));
-        return fmaxf(0.0f, dot / len);   // (a NaN quotient gives 0)
+    // (uniform; else the tile is all frame miss)
+    if (wave_ballot(surface) != 0ull) shadowed = trace_point_entries(a, g, surface, wx, wy, wz, ss, t, status);
+    light_sum_end(a, g, surface, shadowed, status, ss, nrm4, out, t, [&](const float4 N, uint32_t i) {
+        return sf_lambert_point(N, wx, wy, wz, ss.l[i][0], ss.l[i][1], ss.l[i][2]);
     });
 }
 
 }  // namespace
 
-// The launches of sf_trace_suns_wave / sf_trace_suns_fixup and of sf_trace_shadows_wave / sf_trace_shadows_fixup, one
-// chunk of the call's entries each. Plain vector stores only; no statistic and none of the renders' state is touched.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_sum_wave(FrameArgs a, const float* pos4,
                                                                         const float* nrm4, SunSum ss, float* out,
                                                                         uint32_t groups, uint32_t* overflow_list,
                                                                         uint32_t* overflow_count)
 {
     extern __shared__ float lds[];
-    if (blockIdx.x >= groups) return;
-    stage_root(lds, a.root);
-    trace_suns_sum_group<false>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ss,
-                                reinterpret_cast<float4*>(out), lds, build_column(a.consts), blockIdx.x, a.max_depth,
-                                overflow_list, overflow_count);
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_suns_sum_group(a, pos4, nrm4, ss, out, t); });
 }
 
 extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_sum_fixup(FrameArgs a, const float* pos4,
@@ -4803,11 +4837,8 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_sum_fixup(FrameAr
                                                                          uint32_t* counters, uint32_t parity)
 {
     extern __shared__ float lds[];
-    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
-                                         [&](uint32_t group, const float4 bcol) {
-        trace_suns_sum_group<true>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ss,
-                                   reinterpret_cast<float4*>(out), lds, bcol, group, SF_MAX_LEVELS, nullptr, nullptr);
-    });
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_suns_sum_group(a, pos4, nrm4, ss, out, t); });
 }
 
 extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_sum_wave(FrameArgs a, const float* pos4,
@@ -4816,10 +4847,8 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_sum_wave(Frame
                                                                            uint32_t* overflow_count)
 {
     extern __shared__ float lds[];
-    if (blockIdx.x >= groups) return;
-    trace_shadows_sum_group<false>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ss,
-                                   reinterpret_cast<float4*>(out), lds, build_column(a.consts), blockIdx.x,
-                                   a.max_depth, overflow_list, overflow_count);
+    light_wave<RootStage::InGroup>(a, lds, groups, overflow_list, overflow_count,
+                                   [&](const WaveTile& t) { trace_shadows_sum_group(a, pos4, nrm4, ss, out, t); });
 }
 
 extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_sum_fixup(FrameArgs a, const float* pos4,
@@ -4828,51 +4857,18 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_shadows_sum_fixup(Fram
                                                                             uint32_t* counters, uint32_t parity)
 {
     extern __shared__ float lds[];
-    fixup_groups<RootStage::InGroup, false>(a, lds, overflow_list, counters, parity,
-                                            [&](uint32_t group, const float4 bcol) {
-        trace_shadows_sum_group<true>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4),
-                                      ss, reinterpret_cast<float4*>(out), lds, bcol, group, SF_MAX_LEVELS, nullptr,
-                                      nullptr);
-    });
-}
-
-// One tile per one-wave workgroup, dynamic LDS SF_LDS_RAYS_FLOATS(a.max_depth) (the launch of sf_trace_sun_wave).
-// Touches none of the context's statistics.
-extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_wave(FrameArgs a, const float* pos4, SunDirs sd,
-                                                                    uint64_t* mask, uint32_t groups,
-                                                                    uint32_t* overflow_list, uint32_t* overflow_count)
-{
-    extern __shared__ float lds[];
-    if (blockIdx.x >= groups) return;
-    stage_root(lds, a.root);
-    trace_suns_group<false>(a, reinterpret_cast<const float4*>(pos4), sd, mask, lds, build_column(a.consts), blockIdx.x,
-                            a.max_depth, overflow_list, overflow_count);
-}
-
-// Re-trace of the flagged tiles, for every direction, at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and
-// counters). The mixed traversal reads the root image's columns and never writes it: staged once.
-extern "C" __global__ __launch_bounds__(64) void sf_trace_suns_fixup(FrameArgs a, const float* pos4, SunDirs sd,
-                                                                     uint64_t* mask, const uint32_t* overflow_list,
-                                                                     uint32_t* counters, uint32_t parity)
-{
-    extern __shared__ float lds[];
-    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
-                                         [&](uint32_t group, const float4 bcol) {
-        trace_suns_group<true>(a, reinterpret_cast<const float4*>(pos4), sd, mask, lds, bcol, group, SF_MAX_LEVELS,
-                               nullptr, nullptr);
-    });
+    light_fixup<RootStage::InGroup>(a, lds, overflow_list, counters, parity,
+                                    [&](const FixupTile& t) { trace_shadows_sum_group(a, pos4, nrm4, ss, out, t); });
 }
 
 // ------------------------------------------------------------------------------------------
 // Ambient occlusion about each pixel's normal in one launch (sf_trace_ao_to / sf_trace_ao_sum_to).
-// trace_suns_group with a direction that depends on the lane: the lane's position AND normal are loaded once, and
-// w = o + P and the frame (T, B) about N (the branch-free frame of Duff et al.: one division per pixel) are formed
-// once; per sample (a uniform index, the local-frame samples h_i are scalar loads from the argument segment)
-// s_i = ((T h.x) + (B h.y)) + (N h.z), f_i = s_i tau, F, d, bound and the lane's root centre are formed as in
-// trace_sun_group and traverse_mixed runs in its any-hit mode, unchanged, on the axis columns staged once. Every
-// operation is its own rounding (sf.h), so a constant normal image gives trace_suns_group's bits for the directions
-// s_i. A tile with no surface pixel traces nothing; a sample that leaves no lane on is skipped and keeps its bit. A
-// tile flagged for any sample goes onto the overflow list once and is re-traced for all of them.
+// trace_suns_group with a direction that depends on the lane. The pose: the lane's position AND normal are loaded
+// once, and w = o + P and the frame (T, B) about N (the branch-free frame of Duff et al.: one division per pixel) are
+// formed once; per sample (a uniform index, the local-frame samples h_i are scalar loads from the argument segment)
+// s_i = ((T h.x) + (B h.y)) + (N h.z), f_i = s_i tau and F = w + f_i. Every operation is its own rounding (sf.h), so
+// a constant normal image gives trace_suns_group's bits for the directions s_i. A tile with no surface pixel traces
+// nothing.
 // ------------------------------------------------------------------------------------------
 namespace {
 
@@ -4890,124 +4886,75 @@ __device__ __forceinline__ void ao_frame(const float4 N, float T[3], float B[3])
     B[2] = -N.y;
 }
 
-// The loop both endings share: bit i of the result is set where sample i's ray to the lane's pixel is stopped.
-// AO is AoArgs or AoSum (o, keep, tau, n, h).
-template <class AO>
-__device__ __forceinline__ uint64_t trace_ao_samples(const FrameArgs& a, const float4 P, const float4 N, bool surface,
-                                                     const AO& ao, float* __restrict__ L, const float4 bcol,
-                                                     uint32_t levels, uint32_t& status)
+// The entries of sf_trace_ao_to and sf_trace_ao_sum_to: AO is AoArgs or AoSum (o, keep, tau, n, h).
+template <bool FIXUP, class AO>
+__device__ __forceinline__ uint64_t trace_ao_entries(const FrameArgs& a, const float4 P, const float4 N, bool surface,
+                                                     const AO& ao, const LightTile<FIXUP>& t, uint32_t& status)
 {
-    const DeviceConsts* __restrict__ K = a.consts;
-    const uint32_t n = ao.n;   // (uniform, 1..64)
-    uint64_t shadowed = 0ull;
     const float wx = __fadd_rn(ao.o[0], P.x), wy = __fadd_rn(ao.o[1], P.y), wz = __fadd_rn(ao.o[2], P.z);
     float T[3], B[3];
     ao_frame(N, T, B);
-    const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;   // (the mixed traversal has no cone and no order)
-    float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
-#pragma clang loop unroll(disable)
-    for (uint32_t i = 0u; i < n; ++i) {
+    // (finiteness depends on the sample and the lane's normal: a NaN, infinite or zero one leaves the lane off)
+    return trace_parallel_entries(a, ao.n, ao.keep, t, status, [&](uint32_t i) {
         const float hx = ao.h[i][0], hy = ao.h[i][1], hz = ao.h[i][2];
         const float sx = __fadd_rn(__fadd_rn(__fmul_rn(T[0], hx), __fmul_rn(B[0], hy)), __fmul_rn(N.x, hz));
         const float sy = __fadd_rn(__fadd_rn(__fmul_rn(T[1], hx), __fmul_rn(B[1], hy)), __fmul_rn(N.y, hz));
         const float sz = __fadd_rn(__fadd_rn(__fmul_rn(T[2], hx), __fmul_rn(B[2], hy)), __fmul_rn(N.z, hz));
-        const float Fx = __fadd_rn(wx, __fmul_rn(sx, ao.tau)), Fy = __fadd_rn(wy, __fmul_rn(sy, ao.tau)),
-                    Fz = __fadd_rn(wz, __fmul_rn(sz, ao.tau));
-        float dx, dy, dz, bound;
-        shadow_ray(wx, wy, wz, Fx, Fy, Fz, ao.keep, K->lut, dx, dy, dz, bound);
-        // the lane's root centre (Sphereflake.cpp:83 at F)
-        const float rx = __fsub_rn(0.0f, Fx), ry = __fsub_rn(0.0f, Fy), rz = __fsub_rn(0.0f, Fz);
-        // finiteness depends on the sample and the lane's normal: a NaN, infinite or zero one leaves the lane off
-        const bool on = surface && finite3(dx, dy, dz);
-        if (wave_ballot(on) == 0ull) continue;   // (uniform)
-        HitState h;
-        h.hit = false;
-        int32_t md = -1;
-        uint32_t st = 0u;
-        lds_fence();   // (the sample before, or the re-trace's earlier tile, has read its tables)
-        traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, st, culls, bound);
-        status |= st;
-        shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
-    }
-    return shadowed;
+        return RayPose{wx, wy, wz, __fadd_rn(wx, __fmul_rn(sx, ao.tau)), __fadd_rn(wy, __fmul_rn(sy, ao.tau)),
+                       __fadd_rn(wz, __fmul_rn(sz, ao.tau)), surface};
+    });
 }
 
 template <bool FIXUP>
-__device__ __forceinline__ void trace_ao_group(const FrameArgs& a, const float4* __restrict__ pos4,
-                                               const float4* __restrict__ nrm4, const AoArgs& ao,
-                                               uint64_t* __restrict__ mask, float* __restrict__ L, const float4 bcol,
-                                               uint32_t group, uint32_t levels, uint32_t* overflow_list,
-                                               uint32_t* overflow_count)
+__device__ __forceinline__ void trace_ao_group(const FrameArgs& a, const float* __restrict__ pos4,
+                                               const float* __restrict__ nrm4, const AoArgs& ao,
+                                               uint64_t* __restrict__ mask, const LightTile<FIXUP>& t)
 {
-    const GroupLane g = tile_lane(a, group);
-    const float4 P = pos4[g.ray];
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
     const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
     uint64_t shadowed = 0ull;   // bit i: sample i's ray to the lane's pixel is stopped
     uint32_t status = 0u;
-    if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss: every sample's bit is set)
-        const float4 N = nrm4[g.ray];   // (g.ray is clamped into the image)
-        shadowed = trace_ao_samples(a, P, N, surface, ao, L, bcol, levels, status);
-    }
-    // (uniform) more levels needed for some sample: once on the list
-    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);
-    // a tile row is 64 contiguous bytes: one 8-byte vector store per valid lane
-    const uint64_t all = ao.n >= 64u ? ~0ull : (1ull << ao.n) - 1ull;
-    if (g.valid) mask[(size_t)g.y * a.W + g.x] = all & ~shadowed;
+    // (uniform; else the tile is all frame miss: every sample's bit is set. g.ray is clamped into the image)
+    if (wave_ballot(surface) != 0ull) shadowed = trace_ao_entries(a, P, px4(nrm4, g.ray), surface, ao, t, status);
+    light_mask_end(a, g, ao.n, shadowed, status, mask, t);
 }
 
-// The summing ending (trace_suns_sum_group's, with lam == 1: the weighting lives in the sample set and the colours).
-// A flagged tile stores nothing in its first pass; the fixup kernel reads the base, sums and stores.
+// The summing ending with lam == 1: the weighting lives in the sample set and the colours.
 template <bool FIXUP>
-__device__ __forceinline__ void trace_ao_sum_group(const FrameArgs& a, const float4* __restrict__ pos4,
-                                                   const float4* __restrict__ nrm4, const AoSum& ao,
-                                                   float4* __restrict__ out, float* __restrict__ L, const float4 bcol,
-                                                   uint32_t group, uint32_t levels, uint32_t* overflow_list,
-                                                   uint32_t* overflow_count)
+__device__ __forceinline__ void trace_ao_sum_group(const FrameArgs& a, const float* __restrict__ pos4,
+                                                   const float* __restrict__ nrm4, const AoSum& ao,
+                                                   float* __restrict__ out, const LightTile<FIXUP>& t)
 {
-    const GroupLane g = tile_lane(a, group);
-    const float4 P = pos4[g.ray];
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
     const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
     uint64_t shadowed = 0ull;
     uint32_t status = 0u;
-    if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss)
-        const float4 N = nrm4[g.ray];
-        shadowed = trace_ao_samples(a, P, N, surface, ao, L, bcol, levels, status);
-    }
-    if (!FIXUP && status != 0u) {   // (uniform) more levels needed: the fixup kernel sums and stores this tile
-        flag_group(overflow_list, overflow_count, group);
-        return;
-    }
-    light_sum_store(a, g, surface, shadowed, ao, out, [](uint32_t) { return 1.0f; });
+    // (uniform; else the tile is all frame miss)
+    if (wave_ballot(surface) != 0ull) shadowed = trace_ao_entries(a, P, px4(nrm4, g.ray), surface, ao, t, status);
+    light_sum_end(a, g, surface, shadowed, status, ao, nrm4, out, t, [](const float4, uint32_t) { return 1.0f; });
 }
 
 }  // namespace
 
-// One tile per one-wave workgroup, dynamic LDS SF_LDS_RAYS_FLOATS(a.max_depth) (the launch of sf_trace_suns_wave).
-// Plain vector stores only; no statistic and none of the renders' state is touched.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_wave(FrameArgs a, const float* pos4, const float* nrm4,
                                                                   AoArgs ao, uint64_t* mask, uint32_t groups,
                                                                   uint32_t* overflow_list, uint32_t* overflow_count)
 {
     extern __shared__ float lds[];
-    if (blockIdx.x >= groups) return;
-    stage_root(lds, a.root);
-    trace_ao_group<false>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ao, mask,
-                          lds, build_column(a.consts), blockIdx.x, a.max_depth, overflow_list, overflow_count);
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_ao_group(a, pos4, nrm4, ao, mask, t); });
 }
 
-// Re-trace of the flagged tiles, for every sample, at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and
-// counters). The mixed traversal reads the root image's columns and never writes it: staged once.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_fixup(FrameArgs a, const float* pos4, const float* nrm4,
                                                                    AoArgs ao, uint64_t* mask,
                                                                    const uint32_t* overflow_list, uint32_t* counters,
                                                                    uint32_t parity)
 {
     extern __shared__ float lds[];
-    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
-                                         [&](uint32_t group, const float4 bcol) {
-        trace_ao_group<true>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ao, mask,
-                             lds, bcol, group, SF_MAX_LEVELS, nullptr, nullptr);
-    });
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_ao_group(a, pos4, nrm4, ao, mask, t); });
 }
 
 extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_sum_wave(FrameArgs a, const float* pos4,
@@ -5016,11 +4963,8 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_sum_wave(FrameArgs 
                                                                       uint32_t* overflow_count)
 {
     extern __shared__ float lds[];
-    if (blockIdx.x >= groups) return;
-    stage_root(lds, a.root);
-    trace_ao_sum_group<false>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ao,
-                              reinterpret_cast<float4*>(out), lds, build_column(a.consts), blockIdx.x, a.max_depth,
-                              overflow_list, overflow_count);
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_ao_sum_group(a, pos4, nrm4, ao, out, t); });
 }
 
 extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_sum_fixup(FrameArgs a, const float* pos4,
@@ -5029,35 +4973,28 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_sum_fixup(FrameArgs
                                                                        uint32_t* counters, uint32_t parity)
 {
     extern __shared__ float lds[];
-    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
-                                         [&](uint32_t group, const float4 bcol) {
-        trace_ao_sum_group<true>(a, reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(nrm4), ao,
-                                 reinterpret_cast<float4*>(out), lds, bcol, group, SF_MAX_LEVELS, nullptr, nullptr);
-    });
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_ao_sum_group(a, pos4, nrm4, ao, out, t); });
 }
 
 // ------------------------------------------------------------------------------------------
 // Light shafts: sun visibility along each pixel's view ray in one launch (sf_trace_shafts_to). Bit i
 // of mask[p] is what sf_trace_sun_wave writes at a pixel whose position is Q_i = E sigma_i (1 = 255, 0 = 0), bits
 // n..63 are 0. The lane's position is loaded and its march end E formed once -- P, or where P == 0 and a direction
-// image was given, dirs[p] far (loaded in those lanes only). Per sample (a uniform index, the sigma_i are scalar loads
-// from the argument segment) Q_i, w = o + Q_i, F = w + f, d, bound and the lane's root centre 0 - F are formed as in
-// trace_sun_group -- all of them per sample: d is nearly -f every time, but its roundings follow w -- and
-// traverse_mixed runs in its any-hit mode, unchanged, on the axis columns staged once. A tile whose E are all zero
-// traces nothing; a sample that leaves no lane on (a zero or non-finite sun, products that all underflow) is skipped
-// and keeps its bit. A tile flagged for any sample goes onto the overflow list once and is re-traced for all of them.
+// image was given, dirs[p] far (loaded in those lanes only). The pose, per sample (a uniform index, the sigma_i are
+// scalar loads from the argument segment): Q_i, w = o + Q_i and F = w + f -- all of them per sample: d is nearly -f
+// every time, but its roundings follow w. A tile whose E are all zero traces nothing; a sample that leaves no lane on
+// (a zero or non-finite sun, products that all underflow) is skipped and keeps its bit.
 // ------------------------------------------------------------------------------------------
 namespace {
 
 template <bool FIXUP>
-__device__ __forceinline__ void trace_shafts_group(const FrameArgs& a, const float4* __restrict__ pos4,
+__device__ __forceinline__ void trace_shafts_group(const FrameArgs& a, const float* __restrict__ pos4,
                                                    const ShaftArgs& sh, uint64_t* __restrict__ mask,
-                                                   float* __restrict__ L, const float4 bcol, uint32_t group,
-                                                   uint32_t levels, uint32_t* overflow_list, uint32_t* overflow_count)
+                                                   const LightTile<FIXUP>& t)
 {
-    const DeviceConsts* __restrict__ K = a.consts;
-    const GroupLane g = tile_lane(a, group);
-    const float4 P = pos4[g.ray];
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
     float Ex = P.x, Ey = P.y, Ez = P.z;
     if (sh.dirs != nullptr && P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) {   // a miss of the frame: marched to far
         const float* __restrict__ dp = sh.dirs + (size_t)g.ray * sh.dirs_stride;
@@ -5066,71 +5003,40 @@ __device__ __forceinline__ void trace_shafts_group(const FrameArgs& a, const flo
         Ez = __fmul_rn(dp[2], sh.far);
     }
     const bool marched = g.valid && !(Ex == 0.0f && Ey == 0.0f && Ez == 0.0f);
-    const uint32_t n = sh.n;   // (uniform, 1..64)
     uint64_t shadowed = 0ull;   // bit i: the sun's ray to the lane's sample i is stopped
     uint32_t status = 0u;
     if (wave_ballot(marched) != 0ull) {   // (uniform; else no pixel of the tile is marched: every sample's bit is set)
-        const uint32_t culls = a.flags & SF_FLAG_NO_OCCL_CULL;   // (the mixed traversal has no cone and no order)
-        float* const cstk = L + SF_LDS_WAVE_FLOATS(levels + 1u);
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 0u; i < n; ++i) {
+        shadowed = trace_parallel_entries(a, sh.n, sh.keep, t, status, [&](uint32_t i) {
             const float sg = sh.sigma[i];
             const float Qx = __fmul_rn(Ex, sg), Qy = __fmul_rn(Ey, sg), Qz = __fmul_rn(Ez, sg);
-            // (a sample at 0 is a frame miss to sf_trace_sun_to: no ray)
-            const bool surface = marched && !(Qx == 0.0f && Qy == 0.0f && Qz == 0.0f);
             const float wx = __fadd_rn(sh.o[0], Qx), wy = __fadd_rn(sh.o[1], Qy), wz = __fadd_rn(sh.o[2], Qz);
-            const float Fx = __fadd_rn(wx, sh.f[0]), Fy = __fadd_rn(wy, sh.f[1]), Fz = __fadd_rn(wz, sh.f[2]);
-            float dx, dy, dz, bound;
-            shadow_ray(wx, wy, wz, Fx, Fy, Fz, sh.keep, K->lut, dx, dy, dz, bound);
-            // the lane's root centre (Sphereflake.cpp:83 at F)
-            const float rx = __fsub_rn(0.0f, Fx), ry = __fsub_rn(0.0f, Fy), rz = __fsub_rn(0.0f, Fz);
-            const bool on = surface && finite3(dx, dy, dz);
-            if (wave_ballot(on) == 0ull) continue;   // (uniform)
-            HitState h;
-            h.hit = false;
-            int32_t md = -1;
-            uint32_t st = 0u;
-            lds_fence();   // (the sample before, or the re-trace's earlier tile, has read its tables)
-            traverse_mixed<true>(K, L, cstk, bcol, levels, dx, dy, dz, rx, ry, rz, on, h, md, st, culls, bound);
-            status |= st;
-            shadowed |= h.hit ? (1ull << i) : 0ull;   // (bits >= 32 are live)
-        }
+            // (a sample at 0 is a frame miss to sf_trace_sun_to: no ray)
+            return RayPose{wx, wy, wz, __fadd_rn(wx, sh.f[0]), __fadd_rn(wy, sh.f[1]), __fadd_rn(wz, sh.f[2]),
+                           marched && !(Qx == 0.0f && Qy == 0.0f && Qz == 0.0f)};
+        });
     }
-    // (uniform) more levels needed for some sample: once on the list
-    if (!FIXUP && status != 0u) flag_group(overflow_list, overflow_count, group);
-    // a tile row is 64 contiguous bytes: one 8-byte vector store per valid lane
-    const uint64_t all = n >= 64u ? ~0ull : (1ull << n) - 1ull;
-    if (g.valid) mask[(size_t)g.y * a.W + g.x] = all & ~shadowed;
+    light_mask_end(a, g, sh.n, shadowed, status, mask, t);
 }
 
 }  // namespace
 
-// One tile per one-wave workgroup, dynamic LDS SF_LDS_RAYS_FLOATS(a.max_depth) (the launch of sf_trace_suns_wave).
-// Touches none of the context's statistics.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_shafts_wave(FrameArgs a, const float* pos4, ShaftArgs sh,
                                                                       uint64_t* mask, uint32_t groups,
                                                                       uint32_t* overflow_list,
                                                                       uint32_t* overflow_count)
 {
     extern __shared__ float lds[];
-    if (blockIdx.x >= groups) return;
-    stage_root(lds, a.root);
-    trace_shafts_group<false>(a, reinterpret_cast<const float4*>(pos4), sh, mask, lds, build_column(a.consts),
-                              blockIdx.x, a.max_depth, overflow_list, overflow_count);
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_shafts_group(a, pos4, sh, mask, t); });
 }
 
-// Re-trace of the flagged tiles, for every sample, at SF_MAX_LEVELS (fixup_groups; sf_trace_dirs_fixup's list and
-// counters). The mixed traversal reads the root image's columns and never writes it: staged once.
 extern "C" __global__ __launch_bounds__(64) void sf_trace_shafts_fixup(FrameArgs a, const float* pos4, ShaftArgs sh,
                                                                        uint64_t* mask, const uint32_t* overflow_list,
                                                                        uint32_t* counters, uint32_t parity)
 {
     extern __shared__ float lds[];
-    fixup_groups<RootStage::Once, false>(a, lds, overflow_list, counters, parity,
-                                         [&](uint32_t group, const float4 bcol) {
-        trace_shafts_group<true>(a, reinterpret_cast<const float4*>(pos4), sh, mask, lds, bcol, group, SF_MAX_LEVELS,
-                                 nullptr, nullptr);
-    });
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_shafts_group(a, pos4, sh, mask, t); });
 }
 
 // ------------------------------------------------------------------------------------------

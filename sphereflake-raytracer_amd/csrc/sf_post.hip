@@ -353,14 +353,7 @@ extern "C" __global__ void __launch_bounds__(256) sf_light_image_px(uint32_t W, 
     if (P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) return;   // a miss of the frame (post_final.glsl:20)
     const float4 n = ld4(nrm4, px);
     const float wx = __fadd_rn(sa.o[0], P.x), wy = __fadd_rn(sa.o[1], P.y), wz = __fadd_rn(sa.o[2], P.z);
-    const float dx = __fadd_rn(__fsub_rn(wx, sa.l[0]), 0.0f);
-    const float dy = __fadd_rn(__fsub_rn(wy, sa.l[1]), 0.0f);
-    const float dz = __fadd_rn(__fsub_rn(wz, sa.l[2]), 0.0f);
-    // (sqrtf and / are correctly rounded under the build's -fhip-fp32-correctly-rounded-divide-sqrt; __fsqrt_rn is not)
-    const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-    const float ex = __fsub_rn(sa.l[0], wx), ey = __fsub_rn(sa.l[1], wy), ez = __fsub_rn(sa.l[2], wz);
-    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(n.x, ex), __fmul_rn(n.y, ey)), __fmul_rn(n.z, ez));
-    const float lam = fmaxf(0.0f, dot / len);   // (a NaN quotient gives 0)
+    const float lam = sf_lambert_point(n, wx, wy, wz, sa.l[0], sa.l[1], sa.l[2]);
     const float k = __fadd_rn(ambient, __fmul_rn(__fsub_rn(1.0f, ambient), vis[px] ? lam : 0.0f));
     uchar4 c = reinterpret_cast<uchar4*>(rgba)[px];
     c.x = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.x, k), 0.5f), 255.0f);
@@ -381,8 +374,7 @@ extern "C" __global__ void __launch_bounds__(256) sf_light_image_sun_px(uint32_t
     const float4 P = ld4(pos4, px);
     if (P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) return;   // a miss of the frame (post_final.glsl:20)
     const float4 n = ld4(nrm4, px);
-    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(n.x, sx), __fmul_rn(n.y, sy)), __fmul_rn(n.z, sz));
-    const float lam = fmaxf(0.0f, dot);   // (a NaN product gives 0)
+    const float lam = sf_lambert_sun(n, sx, sy, sz);
     const float k = __fadd_rn(ambient, __fmul_rn(__fsub_rn(1.0f, ambient), vis[px] ? lam : 0.0f));
     uchar4 c = reinterpret_cast<uchar4*>(rgba)[px];
     c.x = (uint8_t)fminf(__fadd_rn(__fmul_rn((float)c.x, k), 0.5f), 255.0f);
@@ -409,14 +401,7 @@ extern "C" __global__ void __launch_bounds__(256) sf_light_image_many_px(uint32_
     float S = 0.0f;
 #pragma clang loop unroll(disable)
     for (uint32_t i = 0u; i < sl.n; ++i) {
-        const float lx = sl.l[i][0], ly = sl.l[i][1], lz = sl.l[i][2];
-        const float dx = __fadd_rn(__fsub_rn(wx, lx), 0.0f);
-        const float dy = __fadd_rn(__fsub_rn(wy, ly), 0.0f);
-        const float dz = __fadd_rn(__fsub_rn(wz, lz), 0.0f);
-        const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-        const float ex = __fsub_rn(lx, wx), ey = __fsub_rn(ly, wy), ez = __fsub_rn(lz, wz);
-        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(n.x, ex), __fmul_rn(n.y, ey)), __fmul_rn(n.z, ez));
-        const float lam = fmaxf(0.0f, dot / len);   // (a NaN quotient gives 0)
+        const float lam = sf_lambert_point(n, wx, wy, wz, sl.l[i][0], sl.l[i][1], sl.l[i][2]);
         S = __fadd_rn(S, __fmul_rn(sl.w[i], ((m >> i) & 1ull) ? lam : 0.0f));
     }
     const float k = __fadd_rn(ambient, __fmul_rn(__fsub_rn(1.0f, ambient), S));
@@ -444,9 +429,7 @@ extern "C" __global__ void __launch_bounds__(256) sf_light_image_suns_px(uint32_
     float S = 0.0f;
 #pragma clang loop unroll(disable)
     for (uint32_t i = 0u; i < sd.n; ++i) {
-        const float sx = sd.s[i][0], sy = sd.s[i][1], sz = sd.s[i][2];
-        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(n.x, sx), __fmul_rn(n.y, sy)), __fmul_rn(n.z, sz));
-        const float lam = fmaxf(0.0f, dot);   // (a NaN product gives 0)
+        const float lam = sf_lambert_sun(n, sd.s[i][0], sd.s[i][1], sd.s[i][2]);
         S = __fadd_rn(S, __fmul_rn(sd.w[i], ((m >> i) & 1ull) ? lam : 0.0f));
     }
     const float k = __fadd_rn(ambient, __fmul_rn(__fsub_rn(1.0f, ambient), S));

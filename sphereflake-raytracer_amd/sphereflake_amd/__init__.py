@@ -913,15 +913,29 @@ class Sphereflake:
           - a torch CUDA tensor [H, W, 4] (contiguous float32), or a (device address, width, height) tuple: zero
             copy, asynchronous; the result goes to `out`.
         out: a torch CUDA uint8 tensor of H x W elements, or a device address."""
-        return self._trace_vis(lambda W, H: self.shadow_params(light, bias, origin, W, H, max_depth, stream),
-                               "sf_trace_shadow", pos, out)
+        return self._trace_images(lambda W, H: self.shadow_params(light, bias, origin, W, H, max_depth, stream),
+                                  "sf_trace_shadow", pos, out, np.uint8)
 
-    def _trace_vis(self, params, entry, pos, out, dtype=np.uint8):
-        """The `pos` / `out` forms of trace_shadow(), trace_shadows(), trace_sun(), trace_suns() and trace_shafts():
-        params(width, height) makes the call's parameter block, or (block, the host arrays it points into, kept alive
-        until the call has returned); `entry` names the call into the context's own buffer, `entry`_to the one into a
-        caller's; `dtype` is the result's per pixel."""
+    @staticmethod
+    def _image4(a, what):
+        """(device address, width, height) of a contiguous float32 CUDA tensor [H, W, 4] or such a tuple."""
+        if hasattr(a, "data_ptr"):
+            shape = tuple(a.shape)
+            if len(shape) != 3 or shape[-1] != 4 or not (a.is_cuda and a.is_contiguous() and a.element_size() == 4
+                                                         and a.dtype.is_floating_point):
+                raise ValueError(f"{what} must be a contiguous float32 CUDA tensor [H, W, 4]")
+            return a.data_ptr(), shape[1], shape[0]
+        ptr, W, H = (int(x) for x in a)
+        return ptr, W, H
+
+    def _trace_images(self, params, entry, pos, out, dtype, tail=(), normals=False, nrm=None, accumulate=False):
+        """The `pos` / `nrm` / `out` forms of the nine light traces. params(width, height) makes the call's parameter
+        block, or (block, the host arrays it points into, kept alive until the call has returned); `entry` names the
+        call into the context's own buffers, `entry`_to the one into a caller's. The result is `dtype` x `tail` per
+        pixel; `normals`: a normal image `nrm` travels with the position image; `accumulate`: the host form takes its
+        base as `out` and uploads it."""
         to, own = getattr(lib(), entry + "_to"), getattr(lib(), entry)
+        vp = lambda x: ctypes.c_void_p(x) if x else None
 
         def make(W, H):
             p = params(W, H)
@@ -930,44 +944,61 @@ class Sphereflake:
             pos = np.ascontiguousarray(pos, np.float32)
             if pos.ndim != 3 or pos.shape[-1] != 4:
                 raise ValueError("pos must be [H, W, 4]")
-            if out is not None:
-                raise ValueError("a host position image returns a host array: out must be None")
+            images = [pos]
+            if normals:
+                if not isinstance(nrm, np.ndarray):
+                    raise ValueError("a host position image needs a host normal image")
+                nrm = np.ascontiguousarray(nrm, np.float32)
+                if nrm.shape != pos.shape:
+                    raise ValueError("nrm and pos must have the same shape")
+                images.append(nrm)
             H, W = pos.shape[:2]
-            vis = np.empty((H, W), dtype)
+            if accumulate:
+                if not isinstance(out, np.ndarray) or out.shape != (H, W) + tail:
+                    raise ValueError("an accumulating call on host images needs the base as `out` [H, W, 4]")
+                res = np.array(out, dtype, copy=True, order="C")
+            elif out is not None:
+                raise ValueError("a host position image returns a host array: out must be None")
+            else:
+                res = np.empty((H, W) + tail, dtype)
             p, keep = make(W, H)
             if H * W == 0:
-                return vis
-            with _DeviceScratch(self.device, pos.nbytes + vis.nbytes) as d:
-                d.upload(0, pos)
+                return res
+            offs = [k * pos.nbytes for k in range(len(images) + 1)]   # the images, then the result
+            with _DeviceScratch(self.device, offs[-1] + res.nbytes) as d:
+                for a, off in zip(images, offs):
+                    d.upload(off, a)
+                if accumulate:
+                    d.upload(offs[-1], res)
                 with self._mutex:
-                    _check(to(self._ctx, ctypes.byref(p), ctypes.c_void_p(d.ptr), ctypes.c_void_p(d.ptr + pos.nbytes)),
-                           entry + "_to", self._ctx)
+                    _check(to(self._ctx, ctypes.byref(p), *[vp(d.ptr + off) for off in offs]), entry + "_to", self._ctx)
                     # (the scratch is freed on leaving: the trace that reads and writes it must be done)
                     _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
-                d.download(pos.nbytes, vis)
-            return vis
+                d.download(offs[-1], res)
+            del keep
+            return res
         optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
         if pos is None:
-            p, keep = make(0, 0)
-            with self._mutex:
-                if optr:
-                    _check(to(self._ctx, ctypes.byref(p), None, ctypes.c_void_p(optr)), entry + "_to", self._ctx)
-                else:
-                    _check(own(self._ctx, ctypes.byref(p)), entry, self._ctx)
-            return None
-        if hasattr(pos, "data_ptr"):
-            shape = tuple(pos.shape)
-            if len(shape) != 3 or shape[-1] != 4 or not (pos.is_cuda and pos.is_contiguous() and pos.element_size() == 4
-                                                         and pos.dtype.is_floating_point):
-                raise ValueError("pos must be a contiguous float32 CUDA tensor [H, W, 4]")
-            pptr, W, H = pos.data_ptr(), shape[1], shape[0]
+            if nrm is not None:
+                raise ValueError("nrm goes with pos: None selects the context's G-buffer for both")
+            ptrs = [0] * (2 if normals else 1)
         else:
-            pptr, W, H = (int(x) for x in pos)
-        if not optr:
-            raise ValueError("a device position image needs an `out` buffer")
-        p, keep = make(W, H)
+            pptr, W, H = self._image4(pos, "pos")
+            ptrs = [pptr]
+            if normals:
+                if nrm is None or isinstance(nrm, np.ndarray):
+                    raise ValueError("a device position image needs a device normal image")
+                ptrs.append(self._image4(nrm, "nrm")[0] if hasattr(nrm, "data_ptr") or isinstance(nrm, (tuple, list))
+                            else int(nrm))
+            if not optr:
+                raise ValueError("a device position image needs an `out` buffer")
+        p, keep = make(0, 0) if pos is None else make(W, H)
         with self._mutex:
-            _check(to(self._ctx, ctypes.byref(p), ctypes.c_void_p(pptr), ctypes.c_void_p(optr)), entry + "_to", self._ctx)
+            if pos is None and not optr:
+                _check(own(self._ctx, ctypes.byref(p)), entry, self._ctx)
+            else:
+                _check(to(self._ctx, ctypes.byref(p), *[vp(x) for x in ptrs], vp(optr)), entry + "_to", self._ctx)
+        del keep
         return None
 
     def download_shadow(self) -> np.ndarray:
@@ -1030,8 +1061,9 @@ class Sphereflake:
           - a torch CUDA tensor [H, W, 4] (contiguous float32), or a (device address, width, height) tuple: zero
             copy, asynchronous; the result goes to `out`.
         out: a torch CUDA tensor of H x W 8-byte elements, or a device address (8-byte aligned)."""
-        return self._trace_vis(lambda W, H: self.shadows_params(lights, None, bias, origin, W, H, max_depth, stream),
-                               "sf_trace_shadows", pos, out, np.uint64)
+        return self._trace_images(
+            lambda W, H: self.shadows_params(lights, None, bias, origin, W, H, max_depth, stream),
+            "sf_trace_shadows", pos, out, np.uint64)
 
     def download_shadow_masks(self) -> np.ndarray:
         """[H, W] uint64 of the last trace_shadows() into the context's mask buffer (synchronous)."""
@@ -1094,8 +1126,9 @@ class Sphereflake:
         direction from its own surface point. 255 = lit or a miss of the frame, 0 = shadowed; the exact definition is
         in sf.h and sphereflake_amd.lights.sun_model. `pos`, `out` and `origin` as trace_shadow's; the context's
         visibility buffer is the one trace_shadow() writes (download_shadow(), light_image_sun() see it)."""
-        return self._trace_vis(lambda W, H: self.sun_params(direction, distance, bias, origin, W, H, max_depth, stream),
-                               "sf_trace_sun", pos, out)
+        return self._trace_images(
+            lambda W, H: self.sun_params(direction, distance, bias, origin, W, H, max_depth, stream),
+            "sf_trace_sun", pos, out, np.uint8)
 
     def light_image_sun(self, direction, ambient=0.25, pos_ptr=0, nrm_ptr=0, vis_ptr=0, rgba_ptr=0, stream=None):
         """Scale the image of PostProcess() in place by ambient + (1 - ambient) x (lit ? max(0, n . direction) : 0)
@@ -1143,7 +1176,7 @@ class Sphereflake:
         sphereflake_amd.lights.sun_cone samples a sun with an angular size, sky_dirs a sky dome. `pos`, `out` and
         `origin` as trace_shadows'; the context's mask buffer is the one trace_shadows() writes
         (download_shadow_masks(), light_image_suns() see it)."""
-        return self._trace_vis(
+        return self._trace_images(
             lambda W, H: self.suns_params(dirs, None, distance, bias, origin, W, H, max_depth, stream),
             "sf_trace_suns", pos, out, np.uint64)
 
@@ -1223,7 +1256,7 @@ class Sphereflake:
         (3 floats per pixel) or (address, stride). The context's mask buffer is the one trace_shadows() and
         trace_suns() write (download_shadow_masks(), light_image_shafts() see it)."""
         def run(dptr, dstride):
-            return self._trace_vis(
+            return self._trace_images(
                 lambda W, H: self.shafts_params(direction, fractions, None, distance, bias, dptr, dstride, far, origin,
                                                 W, H, max_depth, stream),
                 "sf_trace_shafts", pos, out, np.uint64)
@@ -1300,82 +1333,6 @@ class Sphereflake:
         p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
         return p, (pts, col)
 
-    @staticmethod
-    def _image4(a, what):
-        """(device address, width, height) of a contiguous float32 CUDA tensor [H, W, 4] or such a tuple."""
-        if hasattr(a, "data_ptr"):
-            shape = tuple(a.shape)
-            if len(shape) != 3 or shape[-1] != 4 or not (a.is_cuda and a.is_contiguous() and a.element_size() == 4
-                                                         and a.dtype.is_floating_point):
-                raise ValueError(f"{what} must be a contiguous float32 CUDA tensor [H, W, 4]")
-            return a.data_ptr(), shape[1], shape[0]
-        ptr, W, H = (int(x) for x in a)
-        return ptr, W, H
-
-    def _trace_sum(self, params, entry, pos, nrm, out, accumulate):
-        """The `pos` / `nrm` / `out` forms of trace_suns_sum() and trace_shadows_sum(): params(width, height) makes
-        (block, keepalive); `entry` names the call into the context's own buffers, `entry`_to the one into a
-        caller's."""
-        to, own = getattr(lib(), entry + "_to"), getattr(lib(), entry)
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        if isinstance(pos, np.ndarray):
-            pos = np.ascontiguousarray(pos, np.float32)
-            if pos.ndim != 3 or pos.shape[-1] != 4:
-                raise ValueError("pos must be [H, W, 4]")
-            if not isinstance(nrm, np.ndarray):
-                raise ValueError("a host position image needs a host normal image")
-            nrm = np.ascontiguousarray(nrm, np.float32)
-            if nrm.shape != pos.shape:
-                raise ValueError("nrm and pos must have the same shape")
-            if accumulate:
-                if not isinstance(out, np.ndarray) or out.shape != pos.shape:
-                    raise ValueError("an accumulating call on host images needs the base as `out` [H, W, 4]")
-                buf = np.array(out, np.float32, copy=True, order="C")
-            elif out is not None:
-                raise ValueError("a host position image returns a host array: out must be None")
-            else:
-                buf = np.empty(pos.shape, np.float32)
-            H, W = pos.shape[:2]
-            p, keep = params(W, H)
-            if H * W == 0:
-                return buf
-            with _DeviceScratch(self.device, 3 * pos.nbytes) as d:
-                d.upload(0, pos)
-                d.upload(pos.nbytes, nrm)
-                if accumulate:
-                    d.upload(2 * pos.nbytes, buf)
-                with self._mutex:
-                    _check(to(self._ctx, ctypes.byref(p), vp(d.ptr), vp(d.ptr + pos.nbytes), vp(d.ptr + 2 * pos.nbytes)),
-                           entry + "_to", self._ctx)
-                    # (the scratch is freed on leaving: the trace that reads and writes it must be done)
-                    _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
-                d.download(2 * pos.nbytes, buf)
-            del keep
-            return buf
-        optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
-        if pos is None:
-            if nrm is not None:
-                raise ValueError("nrm goes with pos: None selects the context's G-buffer for both")
-            p, keep = params(0, 0)
-            with self._mutex:
-                if optr:
-                    _check(to(self._ctx, ctypes.byref(p), None, None, vp(optr)), entry + "_to", self._ctx)
-                else:
-                    _check(own(self._ctx, ctypes.byref(p)), entry, self._ctx)
-            del keep
-            return None
-        pptr, W, H = self._image4(pos, "pos")
-        if nrm is None or isinstance(nrm, np.ndarray):
-            raise ValueError("a device position image needs a device normal image")
-        nptr = self._image4(nrm, "nrm")[0] if hasattr(nrm, "data_ptr") or isinstance(nrm, (tuple, list)) else int(nrm)
-        if not optr:
-            raise ValueError("a device position image needs an `out` buffer")
-        p, keep = params(W, H)
-        with self._mutex:
-            _check(to(self._ctx, ctypes.byref(p), vp(pptr), vp(nptr), vp(optr)), entry + "_to", self._ctx)
-        del keep
-        return None
-
     def trace_suns_sum(self, dirs, colours=None, accumulate=False, distance=None, bias=None, pos=None, nrm=None,
                        out=None, origin=None, max_depth=0, stream=None):
         """Add the light of any number (1..65536) of sun directions `dirs` [n, 3] (each TOWARDS the sun, used as given),
@@ -1389,17 +1346,17 @@ class Sphereflake:
             call takes its base as `out`, a numpy array it does not change) -- synchronous;
           - pos, nrm torch CUDA tensors [H, W, 4] (contiguous float32) or (device address, width, height) tuples: zero
             copy, asynchronous; `out` a torch CUDA tensor [H, W, 4] or a device address."""
-        return self._trace_sum(
+        return self._trace_images(
             lambda W, H: self.light_sum_params(dirs, colours, accumulate, distance, bias, origin, W, H, max_depth, stream),
-            "sf_trace_suns_sum", pos, nrm, out, accumulate)
+            "sf_trace_suns_sum", pos, out, np.float32, (4,), normals=True, nrm=nrm, accumulate=accumulate)
 
     def trace_shadows_sum(self, lights, colours=None, accumulate=False, bias=None, pos=None, nrm=None, out=None,
                           origin=None, max_depth=0, stream=None):
         """trace_suns_sum() for point lights `lights` [n, 3] (world): lit_i is trace_shadows()' bit and the Lambert term
         light_image_many()'s."""
-        return self._trace_sum(
+        return self._trace_images(
             lambda W, H: self.light_sum_params(lights, colours, accumulate, None, bias, origin, W, H, max_depth, stream),
-            "sf_trace_shadows_sum", pos, nrm, out, accumulate)
+            "sf_trace_shadows_sum", pos, out, np.float32, (4,), normals=True, nrm=nrm, accumulate=accumulate)
 
     def light_fill(self, rgb, buf_ptr=0, stream=None):
         """Every pixel of the light buffer becomes (r, g, b, 0): the ambient term (sf_light_fill). buf_ptr 0 = the
@@ -1480,59 +1437,9 @@ class Sphereflake:
           - pos, nrm torch CUDA tensors [H, W, 4] (contiguous float32) or (device address, width, height) tuples: zero
             copy, asynchronous; `out` a torch CUDA tensor of H x W 8-byte elements or a device address.
         `origin` is what pos is relative to (None: the context's view origin)."""
-        params = lambda W, H: self.ao_params(samples, None, False, distance, bias, origin, W, H, max_depth, stream)
-        to, own = lib().sf_trace_ao_to, lib().sf_trace_ao
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        if isinstance(pos, np.ndarray):
-            pos = np.ascontiguousarray(pos, np.float32)
-            if pos.ndim != 3 or pos.shape[-1] != 4:
-                raise ValueError("pos must be [H, W, 4]")
-            if not isinstance(nrm, np.ndarray):
-                raise ValueError("a host position image needs a host normal image")
-            nrm = np.ascontiguousarray(nrm, np.float32)
-            if nrm.shape != pos.shape:
-                raise ValueError("nrm and pos must have the same shape")
-            if out is not None:
-                raise ValueError("a host position image returns a host array: out must be None")
-            H, W = pos.shape[:2]
-            mask = np.empty((H, W), np.uint64)
-            p, keep = params(W, H)
-            if H * W == 0:
-                return mask
-            with _DeviceScratch(self.device, 2 * pos.nbytes + mask.nbytes) as d:
-                d.upload(0, pos)
-                d.upload(pos.nbytes, nrm)
-                with self._mutex:
-                    _check(to(self._ctx, ctypes.byref(p), vp(d.ptr), vp(d.ptr + pos.nbytes), vp(d.ptr + 2 * pos.nbytes)),
-                           "sf_trace_ao_to", self._ctx)
-                    # (the scratch is freed on leaving: the trace that reads and writes it must be done)
-                    _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
-                d.download(2 * pos.nbytes, mask)
-            del keep
-            return mask
-        optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
-        if pos is None:
-            if nrm is not None:
-                raise ValueError("nrm goes with pos: None selects the context's G-buffer for both")
-            p, keep = params(0, 0)
-            with self._mutex:
-                if optr:
-                    _check(to(self._ctx, ctypes.byref(p), None, None, vp(optr)), "sf_trace_ao_to", self._ctx)
-                else:
-                    _check(own(self._ctx, ctypes.byref(p)), "sf_trace_ao", self._ctx)
-            del keep
-            return None
-        pptr, W, H = self._image4(pos, "pos")
-        if nrm is None or isinstance(nrm, np.ndarray):
-            raise ValueError("a device position image needs a device normal image")
-        nptr = self._image4(nrm, "nrm")[0] if hasattr(nrm, "data_ptr") or isinstance(nrm, (tuple, list)) else int(nrm)
-        if not optr:
-            raise ValueError("a device position image needs an `out` buffer")
-        p, keep = params(W, H)
-        with self._mutex:
-            _check(to(self._ctx, ctypes.byref(p), vp(pptr), vp(nptr), vp(optr)), "sf_trace_ao_to", self._ctx)
-        del keep
-        return None
+        return self._trace_images(
+            lambda W, H: self.ao_params(samples, None, False, distance, bias, origin, W, H, max_depth, stream),
+            "sf_trace_ao", pos, out, np.uint64, normals=True, nrm=nrm)
 
     def trace_ao_sum(self, samples, colours=None, accumulate=False, distance=4.0, bias=2.0 ** -10, pos=None, nrm=None,
                      out=None, max_depth=0, stream=None, origin=None):
@@ -1541,9 +1448,9 @@ class Sphereflake:
         sample set and the colours (sphereflake_amd.lights.ao_samples, ao_colours, ao_sum_model). colours [n, 3] (None:
         1 / n per component); accumulate, pos, nrm and out as trace_suns_sum()'s. At most 64 samples per call: more are
         further accumulating calls."""
-        return self._trace_sum(
+        return self._trace_images(
             lambda W, H: self.ao_params(samples, colours, accumulate, distance, bias, origin, W, H, max_depth, stream),
-            "sf_trace_ao_sum", pos, nrm, out, accumulate)
+            "sf_trace_ao_sum", pos, out, np.float32, (4,), normals=True, nrm=nrm, accumulate=accumulate)
 
     def Synchronize(self):
         _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
