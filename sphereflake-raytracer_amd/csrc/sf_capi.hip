@@ -17,6 +17,7 @@
 
 #include "sf_build_id.h"   // SF_SOURCE_HASH (generated: build/, scripts/source_hash.py)
 #include "sf_internal.h"
+#include "sf_plan.h"       // the render schedule: band shares, the queue split, the render plan
 #include "sphereflake/sf.h"
 
 extern "C" __global__ void sf_trace_wave1(FrameArgs a, uint32_t* overflow_list, uint32_t* overflow_count);
@@ -256,7 +257,7 @@ struct sf_ctx {
     int64_t rays = 0;
     int last_hip = 0;
     int fixup_blocks = 256;
-    uint32_t waves_per_block = SF_TRACE_WAVES;   // tuning knob: env SF_TRACE_WAVES = 1 | 2 | 4
+    sfplan::Knobs knobs;                         // the schedule's tuning knobs (sf_plan.h), read from the environment
     uint32_t levels_override = 0;                // tuning knob: env SF_LEVELS (LDS levels, 0 = adaptive)
     bool slab_shallow = false;                   // tests only: index slabs as SF_PACKED_INDEX_DIAG (env SF_DIAG_SLAB_SHALLOW)
     int frames_heavy = -1;                       // A/B: sf_render_frames' interleaved head units per frame (env
@@ -265,18 +266,12 @@ struct sf_ctx {
     bool persistent = true;                      // tuning knob: env SF_PERSISTENT=0 -> one workgroup per tile group
     uint32_t flags = 0;                          // SF_FLAG_* A/B switches: env SF_FLAGS
     int cus = 256;
-    uint32_t queues = 8;                         // persistent trace: XCD queue groups, one per XCD (power of 2)
-    uint32_t queues_per_xcd = 4;                 // env SF_QUEUES_PER_XCD = 1 | 2 | 4: tile queues per XCD (full grids)
     uint32_t prio_buckets = 8;                   // top cost buckets (3 octaves) traced at raised wave priority (env SF_PRIO_BUCKETS)
     int occ_key = -1, occ_blocks = 0;            // cached occupancy (waves per block, levels) -> blocks per CU
     int occ_blocks_lean = 0;                     // the same of sf_trace_queue1t, the lean tile loop (1 wave per block)
     int occ_blocks_pair = 0;                     // the same of sf_trace_queue1 / 1c, the pair-unit loop
-    int pair = -1;                               // pair units (env SF_PAIR): 0 never, 1 wherever the lean loop may run,
-                                                 // -1 where the frame has at least as many pairs as the grid has waves
     uint32_t pair_launches = 0;                  // trace launches that took the pair-unit loop (sf_pair_launches)
-    bool lean = true;                            // env SF_LEAN=0: the general tile loop (sf_trace_queue1g) everywhere
-    uint32_t lean_launches = 0;                  // trace launches that took the lean tile loop (sf_lean_launches)
-    uint32_t max_blocks = 0;                     // diagnostics: env SF_MAX_BLOCKS caps the persistent grid
+    uint32_t lean_launches = 0;                  // trace launches that took the lean tile loop or the pair loop (sf_lean_launches)
     int variant = SF_VARIANT_AVX;                // reference path reproduced (sf_set_variant)
     // frame-less progressive mode
     uint32_t* mt_state = nullptr;      // 624 words + next index (std::mt19937 layout)
@@ -366,8 +361,6 @@ struct sf_ctx {
     uint32_t* chunk_off = nullptr;
     uint32_t* order_meta = nullptr;    // [0] work units in tile_order, [1] first split bucket, [2] parts per split tile, [3] first raised-priority bucket
     uint32_t* order_tot = nullptr;     // per cost bucket: tiles of the rebuilding render (sf_order_bucket_scan)
-    uint32_t split_buckets = SF_SPLIT_AUTO;   // env SF_SPLIT_BUCKETS = k: top k buckets (0: never split)
-    uint32_t split_parts = 4;          // env SF_SPLIT_PARTS = 2 (halves) | 4 (quarters); 640x360: 0.122 -> 0.097 ms with quarters
     uint32_t* part_cost = nullptr;     // per tile: slowest part of a split tile (zeroed, reset by the last part)
     uint32_t* part_done = nullptr;     // per tile: parts finished (zeroed, reset by the last part)
     // env SF_SPLIT_PARTS=subtree: split tiles traced as 4 subtree parts (SF_FLAG_SUBTREE) instead of pixel quarters;
@@ -382,26 +375,13 @@ struct sf_ctx {
     // and downloads issued on different streams of one context run in call order, as on one stream.
     hipStream_t last_stream = nullptr; // stream of the latest enqueued work (nullptr: the context stream)
     hipEvent_t join_ev = nullptr;      // the point later calls order after (see ctx_join / StreamMark)
-    // Heavy-first tile order: -1 (default) on whole frames whose tiles fill at most half the persistent grid's
-    // waves (640x360: rebuilt after every 3rd render, costs recorded by every render) and on whole frames of more
-    // than twice its waves (1080p and up: rebuilt after every 64th render (16th until round 5) from that render's costs only, model
-    // splits: no steady-state cost, shorter frame ends); row-major between (1280x720) and on multi-GPU shares, where
-    // with frames in flight the order measured slower (round 3); env SF_ORDER=0 never, SF_ORDER=1 always
-    int order_mode = -1;
-    uint32_t order_every = 0;          // env SF_ORDER_EVERY = k: rebuild the order after every k-th render only
-                                       // (0 = auto: 3 for small frames, 16 for frames over twice the grid, else 1)
-    int order_record_env = -1;         // env SF_ORDER_RECORD=0|1: tile costs recorded only by the render a rebuild
-                                       // reads / by every render (default: only on frames over twice the grid)
-    bool split_env = false;            // SF_SPLIT_BUCKETS given
-    int halves = -1;                   // env SF_HALVES: row-major units as tile halves (SF_FLAG_HALVES); -1 = by policy
     // The frame-less prefetch stream at the device's greatest priority (env SF_PF_PRIO=0: normal): HIP deals streams
     // over GPU_MAX_HW_QUEUES (4) hardware queues, and in a process that made other streams first (the bench) the
     // prefetch stream shared the context stream's queue, serialising the next batch's draws behind this batch's
     // trace: SSE 0.440 -> 0.306, AVX 0.607 -> 0.480 ms per 2^18-packet batch in the bench process; a fresh process
     // measured 0.322 / 0.509 with normal priority (profiles/r4/frameless.txt)
     bool pf_prio = true;
-    bool compact = false;              // env SF_COMPACT=1: the trace kernel with active-ray compaction of sparse nodes
-    bool tie_inline = true;            // env SF_TIE_INLINE=0: ties under the front-first order go to sf_fixup_wave          // env SF_ORDER_RECORD=0: only the render before a rebuild records tile costs
+    bool tie_inline = true;            // env SF_TIE_INLINE=0: ties under the front-first order go to sf_fixup_wave
     uint32_t order_phase = 0;          // renders since the last rebuild
     // Measurement: HIP events around the main trace kernel of each render (sf_set_kernel_timing)
     static constexpr int kTimed = 64;
@@ -662,25 +642,25 @@ int sf_create(int device, uint32_t width, uint32_t height, sf_ctx** out)
     {   // gfx950: 32 CUs per XCD; a compute partition of the chip exposes fewer XCDs (then fewer queues)
         uint32_t x = c->cus >= 32 ? (uint32_t)c->cus / 32u : 1u, q = 1u;
         while (q * 2u <= x && q * 2u <= 8u) q *= 2u;
-        c->queues = q;
+        c->knobs.xcd_groups = q;
         if (const char* ev = std::getenv("SF_NQUEUES")) {
             const int v = std::atoi(ev);
-            if (v == 1 || v == 2 || v == 4 || v == 8) c->queues = (uint32_t)v;
+            if (v == 1 || v == 2 || v == 4 || v == 8) c->knobs.xcd_groups = (uint32_t)v;
         }
         if (const char* ev = std::getenv("SF_QUEUES_PER_XCD")) {
             const int v = std::atoi(ev);
-            if (v == 1 || v == 2 || v == 4) c->queues_per_xcd = (uint32_t)v;
+            if (v == 1 || v == 2 || v == 4) c->knobs.queues_per_xcd = (uint32_t)v;
         }
     }
     if (const char* ev = std::getenv("SF_PERSISTENT")) c->persistent = std::atoi(ev) != 0;
-    if (const char* ev = std::getenv("SF_ORDER")) c->order_mode = std::atoi(ev) != 0 ? 1 : 0;
-    if (const char* ev = std::getenv("SF_COMPACT")) c->compact = std::atoi(ev) != 0;
+    if (const char* ev = std::getenv("SF_ORDER")) c->knobs.order_mode = std::atoi(ev) != 0 ? 1 : 0;
+    if (const char* ev = std::getenv("SF_COMPACT")) c->knobs.compact = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("SF_PF_PRIO")) c->pf_prio = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("SF_TIE_INLINE")) c->tie_inline = std::atoi(ev) != 0;
-    if (const char* ev = std::getenv("SF_LEAN")) c->lean = std::atoi(ev) != 0;
-    if (const char* ev = std::getenv("SF_PAIR")) c->pair = std::atoi(ev) != 0 ? 1 : 0;
-    if (const char* ev = std::getenv("SF_ORDER_RECORD")) c->order_record_env = std::atoi(ev) != 0 ? 1 : 0;
-    if (const char* ev = std::getenv("SF_ORDER_EVERY")) c->order_every = std::atoi(ev) > 1 ? (uint32_t)std::atoi(ev) : 1u;   // (explicit)
+    if (const char* ev = std::getenv("SF_LEAN")) c->knobs.lean = std::atoi(ev) != 0;
+    if (const char* ev = std::getenv("SF_PAIR")) c->knobs.pair = std::atoi(ev) != 0 ? 1 : 0;
+    if (const char* ev = std::getenv("SF_ORDER_RECORD")) c->knobs.order_record = std::atoi(ev) != 0 ? 1 : 0;
+    if (const char* ev = std::getenv("SF_ORDER_EVERY")) c->knobs.order_every = std::atoi(ev) > 1 ? (uint32_t)std::atoi(ev) : 1u;   // (explicit)
     if (const char* ev = std::getenv("SF_PROG_BIN")) c->prog_bin = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("SF_PROG_PREFETCH")) c->prog_prefetch = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("SF_PROG_ADAPT")) c->prog_adapt = std::atoi(ev) != 0;
@@ -691,27 +671,28 @@ int sf_create(int device, uint32_t width, uint32_t height, sf_ctx** out)
         c->mt_seg_max = k < 2 ? 2u : k > (int)kMtSegMax ? kMtSegMax : (uint32_t)k;
     }
     if (const char* ev = std::getenv("SF_SPLIT_BUCKETS"))
-        c->split_buckets = std::strcmp(ev, "model") == 0 ? SF_SPLIT_MODEL
+        c->knobs.split_buckets = std::strcmp(ev, "model") == 0 ? SF_SPLIT_MODEL
                          : std::strcmp(ev, "auto") == 0 ? SF_SPLIT_AUTO : (uint32_t)std::atoi(ev);
-    if (std::getenv("SF_SPLIT_BUCKETS")) c->split_env = true;
-    if (const char* ev = std::getenv("SF_HALVES")) c->halves = std::atoi(ev);
+    if (std::getenv("SF_SPLIT_BUCKETS")) c->knobs.split_env = true;
+    if (const char* ev = std::getenv("SF_HALVES")) c->knobs.halves = std::atoi(ev);
     bool subtree = false;
     if (const char* ev = std::getenv("SF_SPLIT_PARTS")) {
         subtree = std::strcmp(ev, "subtree") == 0;
-        c->split_parts = (subtree || std::atoi(ev) == 4) ? 4u : 2u;
+        c->knobs.split_parts = (subtree || std::atoi(ev) == 4) ? 4u : 2u;
+        c->knobs.subtree = subtree;   // (part_rec is allocated below)
     }
     if (const char* ev = std::getenv("SF_SPLIT_DEPTH")) c->split_depth_env = (uint32_t)std::atoi(ev);
-    if (const char* ev = std::getenv("SF_MAX_BLOCKS")) c->max_blocks = (uint32_t)std::atoi(ev);
+    if (const char* ev = std::getenv("SF_MAX_BLOCKS")) c->knobs.max_blocks = (uint32_t)std::atoi(ev);
     if (const char* ev = std::getenv("SF_PRIO_BUCKETS")) c->prio_buckets = (uint32_t)std::atoi(ev);
     if (const char* ev = std::getenv("SF_FLAGS")) c->flags = (uint32_t)std::strtoul(ev, nullptr, 0);
     const char* const pipe_env = std::getenv("SF_PIPE");
     if (const char* ev = std::getenv("SF_TRACE_WAVES")) {
         const int w = std::atoi(ev);
-        c->waves_per_block = (w == 1 || w == 2 || w == 4) ? (uint32_t)w : SF_TRACE_WAVES;
-    } else if (c->compact || (pipe_env && std::atoi(pipe_env) != 0)) {
+        c->knobs.waves_per_block = (w == 1 || w == 2 || w == 4) ? (uint32_t)w : SF_TRACE_WAVES;
+    } else if (c->knobs.compact || (pipe_env && std::atoi(pipe_env) != 0)) {
         // the compaction variant is a 2-wave kernel; SF_PIPE=1 once chose a latency variant that was one too, and
         // still means two waves per workgroup (SF_PIPE=0: nothing)
-        c->waves_per_block = 2;
+        c->knobs.waves_per_block = 2;
     }
     if (const char* ev = std::getenv("SF_LEVELS")) {
         const int l = std::atoi(ev);
@@ -817,14 +798,7 @@ int sf_get_setup(const sf_ctx* c, float child[9][16], float root[16])
 
 uint32_t sf_slab_rows(uint32_t height, uint32_t band_rows, uint32_t band_count, uint32_t band_index)
 {
-    if (band_rows == 0) band_rows = ((height + 7) / 8) * 8;
-    if (band_count == 0) band_count = 1;
-    uint32_t bands = (height + band_rows - 1) / band_rows, rows = 0;
-    for (uint32_t b = band_index; b < bands; b += band_count) {
-        uint32_t y0 = b * band_rows, y1 = y0 + band_rows < height ? y0 + band_rows : height;
-        rows += y1 - y0;
-    }
-    return rows;
+    return sfplan::band_share(height, band_rows, band_count, band_index).rows;
 }
 
 static FrameArgs frame_args(const sf_ctx* c)
@@ -848,8 +822,8 @@ static FrameArgs frame_args(const sf_ctx* c)
     a.consts = c->consts;
     a.stats = c->stats;
     a.flags = c->flags;
-    a.xcds = c->queues;
-    a.queues = c->queues;   // (x queues per XCD once the persistent grid is known, launch())
+    a.xcds = c->knobs.xcd_groups;
+    a.queues = c->knobs.xcd_groups;   // (the plan's split once the persistent grid is known, plan_frame_args)
     return a;
 }
 
@@ -866,7 +840,7 @@ static int order_rebuild(sf_ctx* c, hipStream_t s, uint32_t ntiles, uint32_t wav
     const uint32_t cap = c->part_rec ? SF_SPLIT_CAP : 0xffffffffu;
     if (fuse) {
         hipLaunchKernelGGL(sf_order_scan, dim3(1), dim3(1024), 0, s, c->chunk_cnt, nc, ntiles, split_buckets,
-                           c->split_parts, spare, waves, c->prio_buckets, c->chunk_off, c->order_meta,
+                           c->knobs.split_parts, spare, waves, c->prio_buckets, c->chunk_off, c->order_meta,
                            (const uint32_t*)c->tile_cost, c->tile_order, cap);
         SF_HIP(c, hipGetLastError());
     } else {   // (round 5: one-wave workgroups only -- see sf_order_bucket_scan)
@@ -875,7 +849,7 @@ static int order_rebuild(sf_ctx* c, hipStream_t s, uint32_t ntiles, uint32_t wav
         SF_HIP(c, hipGetLastError());
         hipLaunchKernelGGL(sf_order_scatter_plan, dim3(nc), dim3(64), 0, s, (const uint32_t*)c->tile_cost, ntiles,
                            c->chunk_cnt, (const uint32_t*)c->chunk_off, (const uint32_t*)c->order_tot, split_buckets,
-                           c->split_parts, spare, waves, c->prio_buckets, cap, c->order_meta, c->tile_order);
+                           c->knobs.split_parts, spare, waves, c->prio_buckets, cap, c->order_meta, c->tile_order);
         SF_HIP(c, hipGetLastError());
     }
     c->order_n = ntiles;
@@ -930,6 +904,93 @@ static uint32_t frame_levels(const sf_ctx* c, bool* bounded_out)
     return levels;
 }
 
+// The persistent trace kernels of one FrameArgs, by sfplan::Kernel (sf_trace_frames1 takes a FrameBatch).
+typedef void (*QueueKernel)(FrameArgs);
+static const QueueKernel kQueueKernels[sfplan::kFrames1] = { sf_trace_queue1,  sf_trace_queue1c, sf_trace_queue1s,
+                                                             sf_trace_queue1t, sf_trace_queue1g, sf_trace_queue2,
+                                                             sf_trace_queue2c, sf_trace_queue4 };
+
+// Blocks per CU of the kernels a persistent launch() of these levels may take (occ_blocks: the general loop of the
+// knobs' waves per block; occ_blocks_lean, occ_blocks_pair), cached by waves per block, levels and compaction.
+static int queue_occupancy(sf_ctx* c, uint32_t levels, size_t lds)
+{
+    const uint32_t wpb = c->knobs.waves_per_block;
+    const int key = (int)(wpb * 64 + levels) | (c->knobs.compact ? 1 << 20 : 0);
+    if (c->occ_key == key) return SF_OK;
+    const sfplan::Kernel general = wpb == 1 ? sfplan::kQueue1g
+                                 : wpb == 2 ? (c->knobs.compact ? sfplan::kQueue2c : sfplan::kQueue2) : sfplan::kQueue4;
+    int nb = 0;
+    auto query = [&](sfplan::Kernel k) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kQueueKernels[k], (int)(64 * wpb), wpb * lds);
+    };
+    SF_HIP(c, query(general));
+    c->occ_blocks = c->occ_blocks_lean = c->occ_blocks_pair = nb < 1 ? 1 : nb;
+    if (wpb == 1) {
+        SF_HIP(c, query(sfplan::kQueue1t));
+        c->occ_blocks_lean = nb < 1 ? 1 : nb;
+        SF_HIP(c, query(sfplan::kQueue1));
+        c->occ_blocks_pair = nb < 1 ? 1 : nb;
+        SF_HIP(c, query(sfplan::kQueue1c));
+        if (nb >= 1 && nb < c->occ_blocks_pair) c->occ_blocks_pair = nb;   // (one grid for both pair kernels)
+    }
+    c->occ_key = key;
+    return SF_OK;
+}
+
+// What launch() and sf_render_frames fill alike: the member's band share and, with a plan (the persistent traces),
+// its queues, flags and the unit order it runs on -- `oc`'s, the context whose order state the plan was made from;
+// `costs`: this frame is the one that records the unit costs the plan asks for.
+static void plan_frame_args(FrameArgs& a, const sf_render_params& p, const sfplan::BandShare& sh,
+                            const sfplan::RenderPlan* pl, const sf_ctx* oc, bool costs)
+{
+    a.tile_rows = sh.tile_rows;
+    a.tiles_per_band = sh.tiles_per_band;
+    a.tpb_magic = 0xffffffffu / sh.tiles_per_band;
+    a.band_count = sh.band_count;
+    a.band_index = p.band_index;
+    a.emit_aux = p.emit_aux ? 1u : 0u;
+    if (!pl) return;
+    a.xcds = pl->xcds;
+    a.queues = pl->queues;
+    a.flags |= pl->flags_add;
+    a.px_magic = pl->px_magic;
+    if (!pl->use_order) return;
+    a.tile_order = pl->have_order ? oc->tile_order : nullptr;   // ordered by ctx_join
+    a.order_meta = oc->order_meta;
+    a.part_cost = oc->part_cost;
+    a.part_done = oc->part_done;
+    if (costs) {
+        a.tile_cost = pl->costs ? oc->tile_cost : nullptr;
+        a.chunk_cnt = pl->rebuild ? oc->chunk_cnt : nullptr;
+    }
+}
+
+extern "C++" {
+// A trace launch inside the context's timing ring (sf_set_kernel_timing): every ev_period-th one runs between two
+// events of the ring's next slot, and its first waves sample the clocks into that slot (*probe: the launch's
+// FrameArgs.clock_probe, set before `enqueue` runs).
+template <class Enqueue>
+static int timed_launch(sf_ctx* c, hipStream_t s, uint64_t** probe, Enqueue enqueue)
+{
+    const bool timed = c->timing && c->ev_phase == 0;
+    if (c->timing) c->ev_phase = (c->ev_phase + 1u) % c->ev_period;
+    if (timed) {
+        SF_HIP(c, hipEventRecord(c->ev[c->ev_next][0], s));
+        *probe = c->clock_buf + (size_t)c->ev_next * SF_CLOCK_WAVES * 4u;
+    }
+    enqueue();
+    SF_HIP(c, hipGetLastError());
+    if (timed) {
+        SF_HIP(c, hipEventRecord(c->ev[c->ev_next][1], s));
+        c->ev_next = (c->ev_next + 1u) % sf_ctx::kTimed;
+        c->ev_count = c->ev_count < (uint32_t)sf_ctx::kTimed ? c->ev_count + 1u : c->ev_count;
+    }
+    return SF_OK;
+}
+}   // extern "C++"
+
+// sf_render / sf_render_to: validate; provision the levels (and, for the persistent trace, query the occupancy);
+// plan the schedule (sf_plan.h); apply it.
 static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm, float* min_t, uint32_t* hidx)
 {
     if (!c) return SF_EINVAL;
@@ -938,40 +999,24 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
     sf_render_params p;
     std::memset(&p, 0, sizeof p);
     if (pp) p = *pp;
-    const uint32_t tiles_y = (c->H + 7) / 8;
-    uint32_t band_rows = p.band_rows ? p.band_rows : tiles_y * 8;
-    uint32_t band_count = p.band_count ? p.band_count : 1;
-    if (band_rows % 8 != 0 || p.band_index >= band_count) return SF_EINVAL;
+    const sfplan::BandShare sh = sfplan::band_share(c->H, p.band_rows, p.band_count, p.band_index);
+    if (sh.band_rows % 8 != 0 || p.band_index >= sh.band_count) return SF_EINVAL;
     if (p.kernel > SF_KERNEL_PER_RAY || p.max_depth > SF_MAX_DEPTH_LIMIT) return SF_EINVAL;
-    const uint32_t tpb = band_rows / 8;
-    const uint32_t bands = (tiles_y + tpb - 1) / tpb;
-    // owned tile rows: full bands for all but possibly the frame's last band
-    uint32_t tile_rows = 0;
-    for (uint32_t b = p.band_index; b < bands; b += band_count) {
-        uint32_t t0 = b * tpb, t1 = t0 + tpb < tiles_y ? t0 + tpb : tiles_y;
-        tile_rows += t1 - t0;
-    }
     hipStream_t s = p.stream ? (hipStream_t)p.stream : c->stream;
     DevGuard g(c->device);
-    if (tile_rows == 0) return SF_OK;
+    if (sh.tile_rows == 0) return SF_OK;
     const bool unknown_before = c->stats_unknown;
     if (int rc = ctx_join(c, s)) return rc;
     StreamMark mark_(c, s);
 
     FrameArgs a = frame_args(c);
     bool unresolved_safe = false;   // this launch adds nothing to the unresolved word (see sf_ctx::stats_unknown)
-    a.tile_rows = tile_rows;
-    a.tiles_per_band = tpb;
-    a.tpb_magic = 0xffffffffu / tpb;
-    a.band_count = band_count;
-    a.band_index = p.band_index;
     a.compact = p.compact ? 1u : 0u;
     if (p.packed > SF_PACKED_INDEX) return SF_EINVAL;
     if (p.packed == SF_PACKED_INDEX && sf_slab_bytes(c) != 4u) return SF_EINVAL;   // (a hit could be too deep)
     a.packed = p.packed;
     if (a.packed == SF_PACKED_INDEX && c->slab_shallow) a.packed = SF_PACKED_INDEX_DIAG;
     if (a.packed && p.kernel == SF_KERNEL_PER_RAY) return SF_EINVAL;   // (the per-ray kernel writes the plain layout)
-    a.emit_aux = p.emit_aux ? 1u : 0u;
     a.pos = pos;
     a.nrm = nrm;
     a.min_t = min_t;
@@ -985,10 +1030,11 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
         a.phase_sums = c->tile_trace + 3 * ntr;
     }
 
-    uint32_t ntiles = a.tiles_x * tile_rows;   // (the persistent trace's units: pair units where it takes them)
-    const uint32_t blocks = (ntiles + SF_WAVES_PER_BLOCK - 1) / SF_WAVES_PER_BLOCK;
+    const uint32_t ntiles = a.tiles_x * sh.tile_rows;
     if (p.kernel == SF_KERNEL_PER_RAY) {
+        plan_frame_args(a, p, sh, nullptr, c, false);
         a.max_depth = 31;
+        const uint32_t blocks = (ntiles + SF_WAVES_PER_BLOCK - 1) / SF_WAVES_PER_BLOCK;
         hipLaunchKernelGGL(sf_trace_ray, dim3(blocks), dim3(256), 0, s, a);
         SF_HIP(c, hipGetLastError());
     } else {
@@ -999,7 +1045,7 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
         a.max_depth = autod ? levels : p.max_depth;
         const size_t lds = (size_t)SF_LDS_WAVE_FLOATS(a.max_depth) * 4;
         uint32_t* cnt = c->ovf_counters + c->parity;
-        const uint32_t wpb = c->waves_per_block;
+        const uint32_t wpb = c->knobs.waves_per_block;
         const dim3 block(64 * wpb);
         // levels proven sufficient on the persistent kernel: only a tie under the front-first child order can flag
         // a tile, and its own wave re-traces it in index order -- no fixup launch after the trace
@@ -1007,171 +1053,36 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
         const bool tie_inline = bounded && c->persistent && front_first && c->tie_inline;
         if (tie_inline) a.flags |= SF_FLAG_TIE_INLINE;
         if (c->persistent) {
-            // The lean tile loop (sf_trace_queue1t) serves a launch that asks for nothing it leaves out: whole-tile units
-            // of one plain frame. What the launch itself says is known here; what the schedule adds (part units, tile
-            // costs) below -- the grid is sized by the occupancy of the kernel the launch takes.
-            const uint32_t lean_off = SF_FLAG_DIAG_HALF | SF_FLAG_DIAG_HALF_SEL | SF_FLAG_DIAG_UNITS |
-                                      SF_FLAG_DIAG_FORCE_RETRACE | SF_FLAG_PRIO_FLAT;
-            const bool plain = c->lean && wpb == 1 && band_count == 1u && !a.compact && !a.packed && !a.emit_aux &&
-                               !a.tile_trace;
-            const bool lean_ok = plain && (a.flags & lean_off) == 0u;
-            const void* kern = wpb == 1 ? (const void*)sf_trace_queue1g
-                             : wpb == 2 ? (c->compact ? (const void*)sf_trace_queue2c : (const void*)sf_trace_queue2)
-                                        : (const void*)sf_trace_queue4;
-            const int key = (int)(wpb * 64 + a.max_depth) | (c->compact ? 1 << 20 : 0);
-            if (c->occ_key != key) {
-                int nb = 0;
-                SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, (int)block.x, wpb * lds));
-                c->occ_blocks = nb < 1 ? 1 : nb;
-                c->occ_blocks_lean = c->occ_blocks;
-                c->occ_blocks_pair = c->occ_blocks;
-                if (wpb == 1) {
-                    SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sf_trace_queue1t, (int)block.x, lds));
-                    c->occ_blocks_lean = nb < 1 ? 1 : nb;
-                    SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sf_trace_queue1, (int)block.x, lds));
-                    c->occ_blocks_pair = nb < 1 ? 1 : nb;
-                    SF_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sf_trace_queue1c, (int)block.x, lds));
-                    if (nb >= 1 && nb < c->occ_blocks_pair) c->occ_blocks_pair = nb;   // (one grid for both pair kernels)
-                }
-                c->occ_key = key;
+            if (int rc = queue_occupancy(c, a.max_depth, lds)) return rc;
+            const uint32_t cus = (uint32_t)c->cus;
+            const sfplan::Launch ask = { a.tiles_x, sh.tile_rows, sh.band_count, a.compact != 0u, a.packed != 0u,
+                                         p.emit_aux != 0, a.tile_trace != nullptr, a.flags, 0u };
+            const sfplan::Grids full = { (uint32_t)c->occ_blocks * cus, (uint32_t)c->occ_blocks_lean * cus,
+                                         (uint32_t)c->occ_blocks_pair * cus };
+            const sfplan::RenderPlan pl = sfplan::render_plan(ask, c->knobs, full, { c->order_n, c->order_pair, c->order_phase });
+            c->order_phase = pl.order_phase;
+            plan_frame_args(a, p, sh, &pl, c, true);
+            if (pl.subtree) {
+                a.part_rec = c->part_rec;
+                a.split_depth = c->split_depth_env ? c->split_depth_env : (levels > 3u ? levels - 3u : 1u);
             }
-            // Pair units (sf_trace_queue1: two adjacent tiles per wave, the traversal's upper levels walked once): a
-            // launch the lean loop could serve -- the pair loop also serves the forced re-trace itself -- of a frame
-            // with more tiles than twice the persistent grid, the pair kernel's and the single-tile lean loop's: there
-            // are then at least as many pairs as waves, and the frame is one today's schedule calls `large` (1080p and
-            // up; 1280x720, 14 400 tiles against 2 x 7 168 and 2 x 8 192 waves, keeps its single-tile path: with one
-            // pair per wave it measured 0.028 -> 0.040 ms). Every schedule quantity below then counts pair units, and
-            // the render that rebuilds the order records unit costs in the pair loop (sf_trace_queue1c): a context
-            // never mixes tile and pair orders.
-            const uint32_t pair_off = lean_off & ~SF_FLAG_DIAG_FORCE_RETRACE;
-            const uint32_t pair_grid = (uint32_t)(c->occ_blocks_pair > c->occ_blocks_lean ? c->occ_blocks_pair
-                                                                                          : c->occ_blocks_lean) * (uint32_t)c->cus;
-            // (a context told to split tiles, SF_SPLIT_BUCKETS, keeps tile units by default: pair units have no parts)
-            const bool pair = plain && (a.flags & pair_off) == 0u && c->halves <= 0 && c->pair != 0 &&
-                              (c->pair > 0 || (ntiles > 2u * pair_grid && !(c->split_env && c->split_buckets != 0u)));
-            if (pair) {
-                const uint32_t pairs_x = (a.tiles_x + 1u) / 2u;
-                ntiles = pairs_x * tile_rows;
-                a.px_magic = 0xffffffffu / pairs_x;
+            if (pl.lean) c->lean_launches += 1u;   // (the pair loop counts as lean too)
+            if (pl.pair) c->pair_launches += 1u;
+            if (int rc = timed_launch(c, s, &a.clock_probe, [&] {
+                    hipLaunchKernelGGL(kQueueKernels[pl.kernel], dim3(pl.grid), block, wpb * lds, s, a);
+                }))
+                return rc;
+            if (pl.rebuild) {   // the next render's unit order, from this render's unit costs
+                if (int rc = order_rebuild(c, s, pl.units, pl.order_waves, pl.split_buckets, pl.pair)) return rc;
             }
-            uint32_t nblk = (uint32_t)(pair ? c->occ_blocks_pair : lean_ok ? c->occ_blocks_lean : c->occ_blocks) * (uint32_t)c->cus;
-            const bool small = ntiles <= 2u * nblk * wpb;   // tiles fill the full persistent grid at most twice
-            // The heavy-first order (and the splits it carries) only where the frame's tiles fill at most half
-            // the grid's waves: there idle slots take the split heaviest tiles and shorten the frame. With 3
-            // frames in flight, frames of more tiles are throughput-bound and the order costs more than it
-            // gains: 1280x720 0.039 -> 0.036 ms, a 1080p member's share over 2 / 4 GPUs 0.045 -> 0.042 /
-            // 0.028 -> 0.026 ms without it, while 640x360 keeps it (0.0203 vs 0.0232 ms on a fixed view).
-            // A member's share of a multi-GPU frame (band_count > 1) stays row-major too: its tiles are every N-th
-            // band row of the frame, and with frames in flight the order measured slower there at every N (1080p
-            // over 8 GPUs: 0.0212 vs 0.0204 ms per frame, `profiles/r3/share2/r3aw.txt`).
-            const bool tiny = 2u * ntiles <= nblk * wpb && band_count == 1u;
-            // Round 4: whole frames of more than twice the grid's waves (1080p and up) take the order too, in a form
-            // that costs the steady state nothing: rebuilt after every 16th render (64th since round 5, below) from that render's tile costs
-            // alone (the renders between record nothing), heavy tiles split by the makespan model. With 3 frames in
-            // flight the steady frame period is unchanged (1080p 0.0787 vs 0.0792 ms, 4K 0.373 vs 0.373), but a
-            // frame whose successors are not yet queued -- the last of a timed loop, a lone frame -- no longer ends
-            // on its heaviest tiles' serial traversal: one frame alone 0.175 -> 0.151-0.164 ms at 1080p, and the
-            // driver's 20-step loop 0.0871 -> 0.0846 ms per frame (mean of 4 interleaved runs a side,
-            // profiles/r4/order_ab.txt). Frames between half and twice the grid (1280x720) measured slower with it
-            // (0.0358 -> 0.0388 ms) and keep the row-major order. End of round 4, with the faster kernel: large
-            // frames take the order WITHOUT splits -- the split parts re-traverse their tile's shared upper levels,
-            // and with frames in flight only the loop's last frame gains from them: the 20-step loop 0.0759-0.0782
-            // -> 0.0748-0.0766 ms, one frame alone 0.133-0.136 -> 0.129-0.139, steady period unchanged (5
-            // interleaved runs a side, profiles/r4/split0_ab.txt).
-            const bool large = !small && band_count == 1u;
-            const bool use_order = c->order_mode > 0 || (c->order_mode < 0 && (tiny || large));
-            const uint32_t split_buckets = (pair || (large && !c->split_env)) ? 0u : c->split_buckets;   // (pairs: no parts)
-            // row-major halves (SF_FLAG_HALVES): every tile as two units of its pixel rows 0-3 / 4-7
-            const bool halves = !use_order && c->halves > 0;
-            if (halves) a.flags |= SF_FLAG_HALVES;
-            // work units: tiles, or up to `split_parts` per tile when the schedule may split tiles
-            const uint32_t units_max = (use_order && split_buckets != 0u) ? c->split_parts * ntiles
-                                                                          : halves ? 2u * ntiles : ntiles;
-            const uint32_t need = (units_max + wpb - 1) / wpb;
-            if (nblk > need) nblk = need;
-            if (c->max_blocks && nblk > c->max_blocks) nblk = c->max_blocks;
-            dim3 grid(nblk);
-            // every queue group needs blocks of its own (the group is blockIdx mod xcds): fewer queues for a
-            // grid of fewer blocks than groups
-            while (a.xcds > 1u && a.xcds > nblk) a.xcds >>= 1;
-            a.queues = a.xcds;
-            // several queues per XCD split each XCD's tickets over as many counters (less contention on
-            // each); every queue needs waves of its own, so only with a full grid (>= 64 waves per queue)
-            if (c->queues_per_xcd > 1u && nblk * wpb >= 64u * a.xcds * c->queues_per_xcd)
-                a.queues = a.xcds * c->queues_per_xcd;
-            // the order is rebuilt after every order_every-th render (and whenever none exists for this frame
-            // size); the renders in between keep the last order and record their tile costs only
-            // Small frames (tiles fill the persistent grid less than twice) are latency-bound: there the stale
-            // order costs the trace nothing measurable while the two order kernels are ~5 us of a ~80 us
-            // frame, so by default they are rebuilt after every 3rd render (640x360 -6 %, 1280x720 -4 %);
-            // full grids are throughput-bound and a stale order costs more than the kernels (1080p).
-            // (large frames: every 64th since round 5 -- the rebuild's scan is one 16-wave workgroup, which waits for
-            // wave slots behind the frames in flight, 64 us median and up to 1.6 ms in the bench, with its slot's next
-            // frame queued behind it: the driver's 20-step loop 0.0727-0.0743 -> 0.0721-0.0722 ms in two 5-run A/Bs;
-            // a one-wave scan, or the rebuild on a stream of its own, measured slower, profiles/r5/order/)
-            const uint32_t every = c->order_every ? c->order_every : (small ? 3u : large ? 64u : 1u);
-            const bool have_order = c->order_n == ntiles && c->order_pair == pair;   // (an order of this launch's units)
-            const bool rebuild = use_order && (!have_order || c->order_phase + 1u >= every);
-            if (use_order) c->order_phase = rebuild ? 0u : c->order_phase + 1u;
-            if (use_order) {
-                // tile costs: recorded by every render, or only by the render whose costs the rebuild reads
-                const bool record = c->order_record_env >= 0 ? c->order_record_env != 0 : !large;
-                a.tile_cost = (rebuild || record) ? c->tile_cost : nullptr;
-                a.chunk_cnt = rebuild ? c->chunk_cnt : nullptr;
-                a.part_cost = c->part_cost;
-                a.part_done = c->part_done;
-                if (c->part_rec && split_buckets != 0u && wpb == 1u) {   // split tiles are traced as subtree parts
-                    a.part_rec = c->part_rec;
-                    a.split_depth = c->split_depth_env ? c->split_depth_env : (levels > 3u ? levels - 3u : 1u);
-                    a.flags |= SF_FLAG_SUBTREE;
-                }
-                a.tile_order = have_order ? c->tile_order : nullptr;   // ordered by ctx_join
-                a.order_meta = c->order_meta;
-            }
-            const bool timed = c->timing && c->ev_phase == 0;
-            if (c->timing) c->ev_phase = (c->ev_phase + 1u) % c->ev_period;
-            if (timed) {
-                SF_HIP(c, hipEventRecord(c->ev[c->ev_next][0], s));
-                a.clock_probe = c->clock_buf + (size_t)c->ev_next * SF_CLOCK_WAVES * 4u;
-            }
-            // lean: no part units in what the launch reads (the order's splits, row-major halves) and no tile costs
-            // recorded (the render a rebuild of the order reads takes the general loop)
-            const bool lean = pair || (lean_ok && !(use_order && split_buckets != 0u) && !halves && !a.tile_cost &&
-                                       !a.chunk_cnt && !(a.flags & (SF_FLAG_SUBTREE | SF_FLAG_HALVES)));
-            if (lean_ok && !lean && c->occ_blocks < c->occ_blocks_lean) {   // (the general loop after all: its own occupancy)
-                const uint32_t cap = (uint32_t)c->occ_blocks * (uint32_t)c->cus;
-                if (grid.x > cap) grid.x = cap;
-                while (a.xcds > 1u && a.xcds > grid.x) a.xcds >>= 1;
-                a.queues = a.xcds;
-                if (c->queues_per_xcd > 1u && grid.x * wpb >= 64u * a.xcds * c->queues_per_xcd)
-                    a.queues = a.xcds * c->queues_per_xcd;
-            }
-            if (lean) c->lean_launches += 1u;
-            if (pair) c->pair_launches += 1u;
-            if (pair && a.tile_cost) hipLaunchKernelGGL(sf_trace_queue1c, grid, block, lds, s, a);
-            else if (pair) hipLaunchKernelGGL(sf_trace_queue1, grid, block, lds, s, a);
-            else if (wpb == 1 && (a.flags & SF_FLAG_SUBTREE)) hipLaunchKernelGGL(sf_trace_queue1s, grid, block, lds, s, a);
-            else if (wpb == 1 && lean) hipLaunchKernelGGL(sf_trace_queue1t, grid, block, lds, s, a);
-            else if (wpb == 1) hipLaunchKernelGGL(sf_trace_queue1g, grid, block, lds, s, a);
-            else if (wpb == 2 && c->compact) hipLaunchKernelGGL(sf_trace_queue2c, grid, block, 2 * lds, s, a);
-            else if (wpb == 2) hipLaunchKernelGGL(sf_trace_queue2, grid, block, 2 * lds, s, a);
-            else hipLaunchKernelGGL(sf_trace_queue4, grid, block, 4 * lds, s, a);
-            SF_HIP(c, hipGetLastError());
-            if (timed) {
-                SF_HIP(c, hipEventRecord(c->ev[c->ev_next][1], s));
-                c->ev_next = (c->ev_next + 1u) % sf_ctx::kTimed;
-                c->ev_count = c->ev_count < (uint32_t)sf_ctx::kTimed ? c->ev_count + 1u : c->ev_count;
-            }
-            if (rebuild) {   // the next render's tile order, from this render's tile costs
-                if (int rc = order_rebuild(c, s, ntiles, nblk * wpb, split_buckets, pair)) return rc;
-            }
-        } else {
+        } else {   // SF_PERSISTENT=0: one workgroup per tile group, no schedule
+            plan_frame_args(a, p, sh, nullptr, c, false);
             const dim3 grid((ntiles + wpb - 1) / wpb);
             if (wpb == 1) hipLaunchKernelGGL(sf_trace_wave1, grid, block, lds, s, a, c->ovf_list, cnt);
             else if (wpb == 2) hipLaunchKernelGGL(sf_trace_wave2, grid, block, 2 * lds, s, a, c->ovf_list, cnt);
             else hipLaunchKernelGGL(sf_trace_wave4, grid, block, 4 * lds, s, a, c->ovf_list, cnt);
+            SF_HIP(c, hipGetLastError());
         }
-        SF_HIP(c, hipGetLastError());
         // Re-trace of overflowed tiles (it also zeroes the next render's overflow counter itself). With the
         // levels proven sufficient (persistent kernel) only an exact tie under the front-first child order can
         // flag a tile -- never seen on the BASELINE views --: its own wave re-traces it (tie_inline), or with
@@ -1191,12 +1102,7 @@ static int launch(sf_ctx* c, const sf_render_params* pp, float* pos, float* nrm,
         // LDS-level hint for later renders: only needed when the geometric bound is unavailable
         if (!bounded) SF_HIP(c, hipMemcpyAsync(c->h_depth, c->stats, 4, hipMemcpyDeviceToHost, s));
     }
-    uint32_t rows = 0;
-    for (uint32_t b = p.band_index; b < bands; b += band_count) {
-        uint32_t y0 = b * band_rows, y1 = y0 + band_rows < c->H ? y0 + band_rows : c->H;
-        rows += y1 - y0;
-    }
-    c->rays += (int64_t)rows * c->W;
+    c->rays += (int64_t)sh.rows * c->W;
     if (unresolved_safe) c->stats_unknown = unknown_before;
     return SF_OK;
 }
@@ -2263,10 +2169,8 @@ int sf_render_frames(sf_ctx* const* cs, uint32_t n, const sf_render_params* pp)
         for (uint32_t j = 0; j < k; ++j)
             if (cs[j] == cs[k]) return SF_EINVAL;   // (two frames into one G-buffer in one launch would race)
     }
-    const uint32_t tiles_y = (c0->H + 7) / 8;
-    const uint32_t band_rows = p.band_rows ? p.band_rows : tiles_y * 8;
-    const uint32_t band_count = p.band_count ? p.band_count : 1;
-    if (band_rows % 8 != 0 || p.band_index >= band_count || p.kernel > SF_KERNEL_PER_RAY) return SF_EINVAL;
+    const sfplan::BandShare sh = sfplan::band_share(c0->H, p.band_rows, p.band_count, p.band_index);
+    if (sh.band_rows % 8 != 0 || p.band_index >= sh.band_count || p.kernel > SF_KERNEL_PER_RAY) return SF_EINVAL;
     // one launch only where each frame alone would take the bounded one-wave persistent trace with nothing after it
     uint32_t levels = 0;
     bool one = n > 1 || c0->frames_one;
@@ -2275,9 +2179,9 @@ int sf_render_frames(sf_ctx* const* cs, uint32_t n, const sf_render_params* pp)
         bool bounded = false;
         const uint32_t l = frame_levels(c, &bounded);
         const bool front_first = (c->flags & (SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST)) == 0u;
-        one = bounded && c->persistent && c->waves_per_block == 1u && !c->compact && !c->part_rec && !c->tile_trace &&
-              !(front_first && !c->tie_inline) && c->flags == c0->flags && c->variant == c0->variant &&
-              !(c->flags & SF_FLAG_DIAG_HALF);
+        one = bounded && c->persistent && c->knobs.waves_per_block == 1u && !c->knobs.compact && !c->part_rec &&
+              !c->tile_trace && !(front_first && !c->tie_inline) && c->flags == c0->flags &&
+              c->variant == c0->variant && !(c->flags & SF_FLAG_DIAG_HALF);
         levels = l > levels ? l : levels;
     }
     if (!one) {   // one launch per frame: the same frames (launch() orders each context's own calls)
@@ -2285,18 +2189,9 @@ int sf_render_frames(sf_ctx* const* cs, uint32_t n, const sf_render_params* pp)
             if (int rc = launch(cs[k], &p, cs[k]->pos, cs[k]->nrm, cs[k]->min_t, cs[k]->hit_index)) return rc;
         return SF_OK;
     }
-    const uint32_t tpb = band_rows / 8;
-    const uint32_t bands = (tiles_y + tpb - 1) / tpb;
-    uint32_t tile_rows = 0, rows = 0;
-    for (uint32_t b = p.band_index; b < bands; b += band_count) {
-        const uint32_t t0 = b * tpb, t1 = t0 + tpb < tiles_y ? t0 + tpb : tiles_y;
-        tile_rows += t1 - t0;
-        const uint32_t y0 = b * band_rows, y1 = y0 + band_rows < c0->H ? y0 + band_rows : c0->H;
-        rows += y1 - y0;
-    }
     hipStream_t s = p.stream ? (hipStream_t)p.stream : c0->stream;
     DevGuard g(c0->device);
-    if (tile_rows == 0) return SF_OK;
+    if (sh.tile_rows == 0) return SF_OK;
     bool unknown_before[SF_BATCH_MAX];
     for (uint32_t k = 0; k < n; ++k) {
         unknown_before[k] = cs[k]->stats_unknown;
@@ -2310,86 +2205,47 @@ int sf_render_frames(sf_ctx* const* cs, uint32_t n, const sf_render_params* pp)
         c0->occ_blocks = nb < 1 ? 1 : nb;
         c0->occ_key = key;
     }
-    uint32_t nblk = (uint32_t)c0->occ_blocks * (uint32_t)c0->cus;
-    const uint32_t ntiles = ((c0->W + 7) / 8) * tile_rows;
-    // c0's order policy, as launch() decides it for one of these frames
-    const bool small = ntiles <= 2u * nblk;
-    const bool tiny = 2u * ntiles <= nblk && band_count == 1u;
-    const bool large = !small && band_count == 1u;
-    const bool use_order = c0->order_mode > 0 || (c0->order_mode < 0 && (tiny || large));
-    const uint32_t split_buckets = (large && !c0->split_env) ? 0u : c0->split_buckets;
-    const uint32_t units_max = (use_order && split_buckets != 0u) ? c0->split_parts * ntiles : ntiles;
-    if ((uint64_t)n * units_max >= 0x20000000ull) return SF_EINVAL;   // (positions below 2^29: FrameBatch.magic)
-    if (nblk > n * units_max) nblk = n * units_max;
-    if (c0->max_blocks && nblk > c0->max_blocks) nblk = c0->max_blocks;
-    uint32_t xcds = c0->queues;
-    while (xcds > 1u && xcds > nblk) xcds >>= 1;
-    uint32_t queues = xcds;
-    if (c0->queues_per_xcd > 1u && nblk >= 64u * xcds * c0->queues_per_xcd) queues = xcds * c0->queues_per_xcd;
-    const uint32_t every = c0->order_every ? c0->order_every : (small ? 3u : large ? 64u : 1u);
-    const bool have_order = c0->order_n == ntiles && !c0->order_pair;   // (a tile order, not sf_render_to's pair units)
-    const bool rebuild = use_order && (!have_order || c0->order_phase + 1u >= every);
-    if (use_order) c0->order_phase = rebuild ? 0u : c0->order_phase + 1u;
-    const bool record = use_order && (c0->order_record_env >= 0 ? c0->order_record_env != 0 : !large);
+    // the schedule c0's order state gives these frames: launch()'s for one of them, on the one kernel
     const bool front_first = (c0->flags & (SF_FLAG_NO_OCCL_CULL | SF_FLAG_NO_FRONT_FIRST)) == 0u;
+    const sfplan::Launch ask = { (c0->W + 7) / 8, sh.tile_rows, sh.band_count, false, false, p.emit_aux != 0, false,
+                                 c0->flags | (front_first ? SF_FLAG_TIE_INLINE : 0u), n };
+    const sfplan::RenderPlan pl = sfplan::render_plan(ask, c0->knobs, { (uint32_t)c0->occ_blocks * (uint32_t)c0->cus, 0u, 0u },
+                                                      { c0->order_n, c0->order_pair, c0->order_phase });
+    if (!pl.ok) return SF_EINVAL;
+    c0->order_phase = pl.order_phase;
     FrameBatch b;
     std::memset(&b, 0, sizeof b);
     b.nframes = n;
     b.magic = (uint32_t)((0x100000000ull + n - 1u) / n);
-    b.units = ntiles;
-    b.heavy = c0->frames_heavy >= 0 ? (uint32_t)c0->frames_heavy : nblk / n;   // every frame's heaviest units among
-                                                                                // the waves' static first units
+    b.units = pl.units;
+    b.heavy = c0->frames_heavy >= 0 ? (uint32_t)c0->frames_heavy : pl.grid / n;   // every frame's heaviest units among
+                                                                                   // the waves' static first units
     for (uint32_t k = 0; k < n; ++k) {
         sf_ctx* c = cs[k];
         FrameArgs a = frame_args(c);
-        a.tile_rows = tile_rows;
-        a.tiles_per_band = tpb;
-        a.tpb_magic = 0xffffffffu / tpb;
-        a.band_count = band_count;
-        a.band_index = p.band_index;
-        a.emit_aux = p.emit_aux ? 1u : 0u;
+        if (front_first) a.flags |= SF_FLAG_TIE_INLINE;
+        // (only frame 0 records unit costs: the order and its histogram are per unit)
+        plan_frame_args(a, p, sh, &pl, c0, k == 0u);
         a.pos = c->pos;
         a.nrm = c->nrm;
         a.min_t = c->min_t;
         a.hit_index = c->hit_index;
         a.max_depth = levels;
-        if (front_first) a.flags |= SF_FLAG_TIE_INLINE;
         a.counters = c0->ovf_counters;   // the launch's queues: c0's, at c0's parity
         a.overflow_list = c0->ovf_list;
         a.parity = c0->parity;
-        a.xcds = xcds;
-        a.queues = queues;
-        if (use_order) {
-            a.tile_order = have_order ? c0->tile_order : nullptr;
-            a.order_meta = c0->order_meta;
-            a.part_cost = c0->part_cost;
-            a.part_done = c0->part_done;
-            if (k == 0u) {   // only frame 0 records tile costs (the order and its histogram are per tile)
-                a.tile_cost = (rebuild || record) ? c0->tile_cost : nullptr;
-                a.chunk_cnt = rebuild ? c0->chunk_cnt : nullptr;
-            }
-        }
         b.f[k] = a;
     }
-    const bool timed = c0->timing && c0->ev_phase == 0;
-    if (c0->timing) c0->ev_phase = (c0->ev_phase + 1u) % c0->ev_period;
-    if (timed) {
-        SF_HIP(c0, hipEventRecord(c0->ev[c0->ev_next][0], s));
-        b.f[0].clock_probe = c0->clock_buf + (size_t)c0->ev_next * SF_CLOCK_WAVES * 4u;
-    }
-    hipLaunchKernelGGL(sf_trace_frames1, dim3(nblk), dim3(64), lds, s, b);
-    SF_HIP(c0, hipGetLastError());
-    if (timed) {
-        SF_HIP(c0, hipEventRecord(c0->ev[c0->ev_next][1], s));
-        c0->ev_next = (c0->ev_next + 1u) % sf_ctx::kTimed;
-        c0->ev_count = c0->ev_count < (uint32_t)sf_ctx::kTimed ? c0->ev_count + 1u : c0->ev_count;
-    }
-    if (rebuild)
-        if (int rc = order_rebuild(c0, s, ntiles, nblk, split_buckets)) return rc;
+    if (int rc = timed_launch(c0, s, &b.f[0].clock_probe, [&] {
+            hipLaunchKernelGGL(sf_trace_frames1, dim3(pl.grid), dim3(64), lds, s, b);
+        }))
+        return rc;
+    if (pl.rebuild)
+        if (int rc = order_rebuild(c0, s, pl.units, pl.order_waves, pl.split_buckets)) return rc;
     c0->parity ^= 1u;
     for (uint32_t k = 0; k < n; ++k) {
         sf_ctx* c = cs[k];
-        c->rays += (int64_t)rows * c->W;
+        c->rays += (int64_t)sh.rows * c->W;
         c->stats_unknown = unknown_before[k];   // (bounded, unpacked: the launch adds nothing to the unresolved word)
         if (s != c->stream) SF_HIP(c, hipEventRecord(c->join_ev, s));   // (StreamMark)
     }
@@ -2399,15 +2255,14 @@ int sf_render_frames(sf_ctx* const* cs, uint32_t n, const sf_render_params* pp)
 // Depth bound of every hit under the context's view (-1: none provable). Every sphere lies inside the root's
 // bounding sphere (radius 2 around the root centre), so a depth-d node can pass the LOD test (t < T_d,
 // Sphereflake.h:146) only if |root centre| - 2 < T_d; a node is self-tested only when its parent passed, so hits
-// lie at most one level below the deepest such d. (The same bound launch() provisions its LDS levels from.)
+// lie at most one level below the deepest such d: the bound launch() provisions its LDS levels from,
+// geometric_levels. (That one answers its default, unproven, where the gap is not positive, and d + 1 otherwise --
+// proven unless it is more levels than the kernels have: a positive gap shows as one or the other.)
 static int hit_depth_bound(const sf_ctx* c)
 {
-    const float rc = std::sqrt(c->root[12] * c->root[12] + c->root[13] * c->root[13] + c->root[14] * c->root[14]);
-    const float gap = (rc - 2.0f) * (1.0f - 1e-3f);
-    if (!(gap > 0.0f)) return -1;
-    uint32_t dmax = 0;
-    while (dmax + 1u < SF_DEPTH_TABLE && c->host_consts.dt.lod[dmax + 1u] > gap) ++dmax;
-    return (int)dmax + 1;
+    bool bounded = false;
+    const uint32_t levels = geometric_levels(c, &bounded);
+    return (bounded || levels > SF_MAX_DEPTH_LIMIT) ? (int)levels : -1;
 }
 
 // True when no depth-SF_INDEX_SLAB_DEPTH node can pass the LOD test for any ray of the view, so every hit lies at depth

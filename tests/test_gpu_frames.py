@@ -173,6 +173,43 @@ def test_frames_random_views_against_oracle():
             f.close()
 
 
+def test_frames_alternate_with_pair_launches(monkeypatch):
+    """The two launch paths alternating on one context's order state under pair units: 40 x 16 (five tile columns:
+    the last pair of a row has no B tile) on the config view, the order rebuilt after every launch. Render() leaves
+    an order of 3 x 2 pairs, the batch finds pair units where it needs tiles and leaves one of 5 x 2 tiles (which
+    also shows that it ran as one launch), Render() finds tiles where it needs pairs. Every frame is the oracle's."""
+    from test_gpu_lean_tile import bits, reference
+    from test_gpu_pair_tile import ENV_KEYS
+    for k in ENV_KEYS | {"SF_ORDER_EVERY"}:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in (("SF_PAIR", "1"), ("SF_ORDER", "1"), ("SF_ORDER_EVERY", "1")):
+        monkeypatch.setenv(k, v)
+    view, (W, H), ref = reference(("config", (40, 16)))
+
+    def check(f, what):
+        pos, nrm, _, _ = f.download()
+        assert np.array_equal(bits(pos), bits(ref["pos4"])), what
+        assert np.array_equal(bits(nrm), bits(ref["nrm4"])), what
+        assert f.stats().max_depth == ref["stats"]["max_depth"], what
+
+    with sf.Sphereflake(W, H) as a, sf.Sphereflake(W, H) as b:
+        a.SetView(*view)
+        b.SetView(*view)
+        units = []
+        a.Render()
+        units.append(sf.lib().sf_order_units(a.ctx))
+        check(a, "launch 1")
+        sf.render_frames([a, b])
+        units.append(sf.lib().sf_order_units(a.ctx))
+        check(a, "batch, frame 0")
+        check(b, "batch, frame 1")
+        a.Render()
+        units.append(sf.lib().sf_order_units(a.ctx))
+        check(a, "launch 2")
+        assert units == [6, 10, 6]
+        assert (a.pair_launches(), b.pair_launches()) == (2, 0)
+
+
 def test_frames_rejects_bad_batches():
     W, H = 64, 64
     flakes = [sf.Sphereflake(W, H) for _ in range(9)]
