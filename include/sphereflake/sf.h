@@ -669,6 +669,82 @@ int sf_trace_ao_sum_to(sf_ctx* ctx, const sf_ao_params* params, const float* pos
    (SF_ESTATE for an accumulating call before anything has written it). */
 int sf_trace_ao_sum(sf_ctx* ctx, const sf_ao_params* params);
 
+/* --- fewer rays per pixel: a per-pixel spin and an edge-aware filter of the light buffer ---- */
+/* sf_trace_ao_to gives every pixel the same sample set, so a small n shows as banding. Interleaved sampling spreads
+   a small n over neighbouring pixels and gathers it back: each pixel of a size x size block turns the shared sample
+   set by its own angle about its normal, so a block sees n size^2 directions, and sf_light_filter_to then averages the
+   block, stopped at normal and plane discontinuities.
+   DEFINITION OF THE SPUN MASK (exact; binary32, round to nearest, every operation rounded on its own, no fused
+   multiply-add). Steps 1-5 of sf_trace_ao_to's definition hold. Between step 2 and step 3, with (c, s) the table entry
+   of pixel (x, y) -- x the column and y the row of the image the call is given (width x height of the params, or the
+   context's frame) -- per component k:
+       T'.k = (T.k c) + (B.k s)        B'.k = (B.k c) - (T.k s)
+   and step 3 uses T' and B'. The frame is turned ONCE PER PIXEL, not once per sample. (c, s) is used as given: it is
+   not normalised, and cos and sin of an angle make the turn a rotation about N.
+   CONSEQUENCES, all bit for bit:
+   - The 1 x 1 table {(1, 0)} gives sf_trace_ao_to's mask and sf_trace_ao_sum_to's sum. T' = T + (B 0) and
+     B' = B - (T 0) differ from T and B in the sign of a zero at most, and no later step sees it: F = w + f and the
+     root centre 0 - F carry no sign of a zero f that matters, and d = (w - F) + 0.0f has none.
+   - A table whose entries are all equal gives the 1 x 1 table's result.
+   - A constant normal N0 with a 1 x 1 table (c, s) gives sf_trace_suns_to's bits for the directions
+     sphereflake_amd/lights.py ao_directions(N0, samples, spin=(c, s)).
+   - A crop of the images whose top-left corner is at multiples of `size` gives the crop of the whole's result. */
+#define SF_AO_SPIN_MAX 8
+typedef struct sf_ao_spin {
+    const float* cs;   /* HOST, size x size x 2 floats, row-major: (c, s) of pixel (x, y) is entry
+                          (y % size) * size + (x % size); used as given, not normalised; every value finite; read
+                          before the call returns */
+    uint32_t size;     /* 1 .. SF_AO_SPIN_MAX */
+} sf_ao_spin;
+/* sf_trace_ao_to, sf_trace_ao, sf_trace_ao_sum_to and sf_trace_ao_sum with the spin: everything after the spin argument
+   is as in the unspun call, and so are the buffers, the ordering, the statistics and the re-trace. The summing calls
+   are sf_trace_ao_sum_to's definition with the spun bit: a call equals its split at any k, a flagged tile stores
+   nothing in its first pass, .w and the frame's misses are handled the same way. Errors: everything the unspun call
+   rejects, and SF_EINVAL for a null spin, a null cs, a size of 0 or above SF_AO_SPIN_MAX, or a table value that is not
+   finite. A failing call writes nothing. */
+int sf_trace_ao_spin_to(sf_ctx* ctx, const sf_ao_params* params, const sf_ao_spin* spin, const float* pos4,
+                        const float* nrm4, uint64_t* mask);
+int sf_trace_ao_spin(sf_ctx* ctx, const sf_ao_params* params, const sf_ao_spin* spin);
+int sf_trace_ao_spin_sum_to(sf_ctx* ctx, const sf_ao_params* params, const sf_ao_spin* spin, const float* pos4,
+                            const float* nrm4, float* out);
+int sf_trace_ao_spin_sum(sf_ctx* ctx, const sf_ao_params* params, const sf_ao_spin* spin);
+
+/* The filter: an R x R box over the light buffer that accepts a neighbour only on the same surface.
+   DEFINITION (exact, as above). For pixel p = (x, y) with P_p = pos4[p].xyz and N_p = nrm4[p].xyz:
+     1. P_p == (0, 0, 0) is a miss of the frame: out[p] = in[p].
+     2. Else the taps q = (x + dx, y + dy) are visited with dy outer and dx inner, both from -floor(R / 2) to
+        R - 1 - floor(R / 2) (-2 .. +1 for R = 4): any such window holds every entry of an R x R spin table once.
+     3. A tap outside the image, or one that is a miss of the frame, is skipped. The tap q == p is always accepted. Any
+        other tap is accepted iff nn >= normal_min, with nn = ((N_p.x N_q.x) + (N_p.y N_q.y)) + (N_p.z N_q.z), and
+        (e e) <= (k2 pp), with D = P_q - P_p per component, e = ((N_p.x D.x) + (N_p.y D.y)) + (N_p.z D.z),
+        pp = ((P_p.x P_p.x) + (P_p.y P_p.y)) + (P_p.z P_p.z) and k2 = plane_max plane_max formed on the host in
+        binary32. A comparison with a NaN is false: that tap is rejected.
+     4. Per channel S starts at 0 and an accepted tap does S = S + in[q].c, in visiting order; a rejected tap leaves S
+        as it is. out[p].xyz = S / (float)count, a correctly rounded division; out[p].w = in[p].w.
+   R = 1 is a copy. The defaults (0.9, 0.02) were picked from three candidates on an 80 x 45 fixture at n = 4; THEY ARE
+   NOT TUNED AT 1920 x 1080. sphereflake_amd/lights.py: light_filter_model. */
+typedef struct sf_light_filter_params {
+    uint32_t size;          /* R, 1 .. SF_AO_SPIN_MAX: the window is R x R pixels (sf_light_filter_defaults: 4) */
+    float normal_min;       /* a tap q is accepted only if N_p . N_q >= normal_min (defaults: 0.9f); not NaN */
+    float plane_max;        /* ... and its distance from p's tangent plane <= plane_max |P_p| (defaults: 0.02f);
+                               finite and >= 0 */
+    uint32_t width, height; /* as sf_sun_params */
+    void* stream;           /* NULL = the context stream */
+} sf_light_filter_params;
+int sf_light_filter_defaults(const sf_ctx* ctx, sf_light_filter_params* params);
+/* pos4, nrm4, in and out are DEVICE images of width * height float4. NULL pos4 / nrm4 / in select the context's
+   G-buffer and light buffer, at the context's size only (SF_ESTATE for a null `in` before anything has written the
+   light buffer). Asynchronous on the stream and ordered with the context's other calls; no statistic is touched.
+   SF_EINVAL for a null out, in == out (the context's light buffer included), a size of 0 or above SF_AO_SPIN_MAX, a NaN
+   normal_min, a plane_max that is negative, infinite or NaN, and sizes as sf_trace_ao_to's. A failing call writes
+   nothing. */
+int sf_light_filter_to(sf_ctx* ctx, const sf_light_filter_params* params, const float* pos4, const float* nrm4,
+                       const float* in, float* out);
+/* The context's G-buffer and light buffer, in place for the caller: filtered into a second buffer the context owns
+   (allocated on first use) and copied back on the stream, so the pointer sf_light_buffer returns never changes.
+   SF_ESTATE before anything has written the light buffer. */
+int sf_light_filter(sf_ctx* ctx, const sf_light_filter_params* params);
+
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the
    work units of all n frames from one set of tile queues -- a wave whose frame runs dry goes on with the next

@@ -360,6 +360,45 @@ public:
         std::lock_guard<FairMutex> lk(m_Mutex);
         Check(sf_trace_ao_sum(m_Ctx, &params));
     }
+    // The same four with a per-pixel spin (new; sf_trace_ao_spin_to and its siblings, sf.h): each pixel of a
+    // spin.size x spin.size block turns the samples by its own table entry about its normal; LightFilter gathers the
+    // block back.
+    void TraceAO(const sf_ao_params& params, const sf_ao_spin& spin, const float* positions4, const float* normals4,
+                 uint64_t* masks)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_ao_spin_to(m_Ctx, &params, &spin, positions4, normals4, masks));
+    }
+    void TraceAO(const sf_ao_params& params, const sf_ao_spin& spin)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_ao_spin(m_Ctx, &params, &spin));
+    }
+    void TraceAOSum(const sf_ao_params& params, const sf_ao_spin& spin, const float* positions4, const float* normals4,
+                    float* light4)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_ao_spin_sum_to(m_Ctx, &params, &spin, positions4, normals4, light4));
+    }
+    void TraceAOSum(const sf_ao_params& params, const sf_ao_spin& spin)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_ao_spin_sum(m_Ctx, &params, &spin));
+    }
+    // The edge-aware box filter of a light buffer (new; sf_light_filter_to, sf.h) into `filtered4`, which is not
+    // `light4`; null input pointers select this object's own frame and light buffer ...
+    void LightFilter(const sf_light_filter_params& params, const float* positions4, const float* normals4,
+                     const float* light4, float* filtered4)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_filter_to(m_Ctx, &params, positions4, normals4, light4, filtered4));
+    }
+    // ... or this object's own light buffer, in place (sf_light_filter)
+    void LightFilter(const sf_light_filter_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_filter(m_Ctx, &params));
+    }
 
     // the device frame, downloaded into the vectors when it is newer than their contents (Refresh)
     const GBuffer& GetGBuffer() const

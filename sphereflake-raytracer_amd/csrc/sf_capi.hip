@@ -115,6 +115,20 @@ extern "C" __global__ void sf_trace_ao_sum_wave(FrameArgs a, const float* pos4, 
 extern "C" __global__ void sf_trace_ao_sum_fixup(FrameArgs a, const float* pos4, const float* nrm4, AoSum ao,
                                                  float* out, const uint32_t* overflow_list, uint32_t* counters,
                                                  uint32_t parity);
+extern "C" __global__ void sf_trace_ao_spin_wave(FrameArgs a, const float* pos4, const float* nrm4, AoArgs ao, AoSpin sp,
+                                                 uint64_t* mask, uint32_t groups, uint32_t* overflow_list,
+                                                 uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_ao_spin_fixup(FrameArgs a, const float* pos4, const float* nrm4, AoArgs ao,
+                                                  AoSpin sp, uint64_t* mask, const uint32_t* overflow_list,
+                                                  uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_trace_ao_spin_sum_wave(FrameArgs a, const float* pos4, const float* nrm4, AoSum ao,
+                                                     AoSpin sp, float* out, uint32_t groups, uint32_t* overflow_list,
+                                                     uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_ao_spin_sum_fixup(FrameArgs a, const float* pos4, const float* nrm4, AoSum ao,
+                                                      AoSpin sp, float* out, const uint32_t* overflow_list,
+                                                      uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_light_filter_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
+                                              const float* in, float* out, uint32_t R, float normal_min, float k2);
 extern "C" __global__ void sf_light_fill_px(uint32_t n, float r, float g, float b, float* buf);
 extern "C" __global__ void sf_light_image_buffer_px(uint32_t W, uint32_t H, const float* pos4, const float* buf,
                                                     uint8_t* rgba);
@@ -400,6 +414,7 @@ struct sf_ctx {
     uint8_t* shadow = nullptr;         // W x H visibility bytes (sf_trace_shadow): lazily allocated
     uint64_t* shadow_masks = nullptr;  // W x H visibility masks (sf_trace_shadows): lazily allocated
     float* light = nullptr;            // W x H float4 light buffer (sf_light_fill, sf_trace_suns_sum): lazily allocated
+    float* light_filtered = nullptr;   // W x H float4: sf_light_filter's target before the copy back, lazily allocated
     int centre_exact = -1;             // sfhost::post_centre_exact(W) && (H), cached
 };
 
@@ -516,6 +531,7 @@ static void free_ctx(sf_ctx* c)
     (void)hipFree(c->shadow);
     (void)hipFree(c->shadow_masks);
     (void)hipFree(c->light);
+    (void)hipFree(c->light_filtered);
     for (int i = 0; i < sf_ctx::kTimed; ++i)
         for (int j = 0; j < 2; ++j)
             if (c->ev[i][j]) (void)hipEventDestroy(c->ev[i][j]);
@@ -2106,6 +2122,161 @@ int sf_trace_ao_sum(sf_ctx* c, const sf_ao_params* p)
                                     [&] { return ao_check(c, p, true, nullptr, true, &im); }))
         return rc;
     return sf_trace_ao_sum_to(c, p, nullptr, nullptr, nullptr);
+}
+
+// The four calls above with a per-pixel spin (kernels sf_trace_ao_spin_wave / _fixup, sf_trace_ao_spin_sum_wave /
+// _fixup): the same checks, buffers and launches, with the table by value beside the samples.
+static_assert(SF_AO_SPIN == SF_AO_SPIN_MAX, "the table in the argument block is the ABI's largest");
+static_assert(sizeof(AoSpin) <= 520, "the spin table's share of the argument segment");
+static_assert(sizeof(FrameArgs) + sizeof(AoSum) + sizeof(AoSpin) + 64 <= 4096, "kernel argument segment");
+
+// the table: size 1..SF_AO_SPIN_MAX, every value finite; copied into the argument block
+static int spin_args(const sf_ao_spin* spin, AoSpin* sp)
+{
+    if (!spin || !spin->cs || spin->size == 0u || spin->size > SF_AO_SPIN_MAX) return SF_EINVAL;
+    std::memset(sp, 0, sizeof *sp);
+    sp->size = spin->size;
+    for (uint32_t e = 0; e < spin->size * spin->size; ++e)
+        for (int k = 0; k < 2; ++k) {
+            if (!std::isfinite(spin->cs[2u * e + k])) return SF_EINVAL;
+            sp->cs[e][k] = spin->cs[2u * e + k];
+        }
+    return SF_OK;
+}
+
+int sf_trace_ao_spin_to(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin, const float* pos4, const float* nrm4,
+                        uint64_t* mask)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!mask) return SF_EINVAL;
+    ShadowImage im;
+    if (int rc = ao_check(c, p, false, pos4, !nrm4, &im)) return rc;
+    AoSpin sp;
+    if (int rc = spin_args(spin, &sp)) return rc;
+    AoArgs ao;
+    ao_args(c, p, &ao);
+    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
+    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_ao_spin_wave, sf_trace_ao_spin_fixup, nrm, ao,
+                              sp, mask);
+}
+
+int sf_trace_ao_spin(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    ShadowImage im;
+    AoSpin sp;
+    if (int rc = own_buffer_checked(c, &c->shadow_masks, 8, false, [&] {
+            const int rc2 = ao_check(c, p, false, nullptr, true, &im);
+            return rc2 ? rc2 : spin_args(spin, &sp);
+        }))
+        return rc;
+    return sf_trace_ao_spin_to(c, p, spin, nullptr, nullptr, c->shadow_masks);
+}
+
+int sf_trace_ao_spin_sum_to(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin, const float* pos4,
+                            const float* nrm4, float* out)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    ShadowImage im;
+    if (int rc = ao_check(c, p, true, pos4, !nrm4 || !out, &im)) return rc;
+    AoSpin sp;
+    if (int rc = spin_args(spin, &sp)) return rc;
+    if (!out && !c->light) return SF_ESTATE;
+    AoSum ao;
+    ao_args(c, p, &ao);
+    ao.accumulate = p->accumulate ? 1u : 0u;
+    entry_values(3u * p->n, p->colours, 1.0f / (float)p->n, &ao.c[0][0]);
+    float* const dst = out ? out : c->light;
+    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
+    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_ao_spin_sum_wave, sf_trace_ao_spin_sum_fixup,
+                              nrm, ao, sp, dst);
+}
+
+int sf_trace_ao_spin_sum(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    ShadowImage im;
+    AoSpin sp;
+    if (int rc = own_buffer_checked(c, &c->light, 16, p->accumulate != 0u, [&] {
+            const int rc2 = ao_check(c, p, true, nullptr, true, &im);
+            return rc2 ? rc2 : spin_args(spin, &sp);
+        }))
+        return rc;
+    return sf_trace_ao_spin_sum_to(c, p, spin, nullptr, nullptr, nullptr);
+}
+
+// The edge-aware box filter of the light buffer (kernel sf_light_filter_px).
+int sf_light_filter_defaults(const sf_ctx* c, sf_light_filter_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->size = 4u;
+    p->normal_min = 0.9f;
+    p->plane_max = 0.02f;
+    return SF_OK;
+}
+
+// The parameters alone: every failure here is SF_EINVAL.
+static int filter_check(const sf_ctx* c, const sf_light_filter_params* p, bool ctx_buffer, uint32_t* W, uint32_t* H)
+{
+    if (p->size == 0u || p->size > SF_AO_SPIN_MAX) return SF_EINVAL;
+    if (p->normal_min != p->normal_min) return SF_EINVAL;
+    if (!(p->plane_max >= 0.0f) || std::isinf(p->plane_max)) return SF_EINVAL;   // (NaN fails the compare)
+    if ((p->width == 0u) != (p->height == 0u)) return SF_EINVAL;
+    *W = p->width ? p->width : c->W;
+    *H = p->height ? p->height : c->H;
+    if (ctx_buffer && (*W != c->W || *H != c->H)) return SF_EINVAL;   // (a context buffer, at its size only)
+    if ((uint64_t)*W * *H > 0x7fffffffull) return SF_EINVAL;   // (pixel indices are 32-bit in the kernel)
+    return SF_OK;
+}
+
+// The launch on the call's stream; `back`: where the result is then copied (the context form), or null.
+static int filter_launch(sf_ctx* c, const sf_light_filter_params* p, uint32_t W, uint32_t H, const float* pos4,
+                         const float* nrm4, const float* in, float* out, float* back)
+{
+    const float k2 = p->plane_max * p->plane_max;   // (one rounding: sf.h's k2)
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    DevGuard g(c->device);
+    if (int rc = ctx_join(c, s)) return rc;
+    StreamMark mark_(c, s);
+    const dim3 grid((W + 31u) / 32u, (H + 7u) / 8u);   // (SF_FILTER_BX x SF_FILTER_BY pixels per block, sf_post.hip)
+    if (grid.x == 0u || grid.y == 0u) return SF_OK;
+    hipLaunchKernelGGL(sf_light_filter_px, grid, dim3(256), 0, s, W, H, pos4, nrm4, in, out, p->size, p->normal_min,
+                       k2);
+    SF_HIP(c, hipGetLastError());
+    if (back) SF_HIP(c, hipMemcpyAsync(back, out, (size_t)W * H * 16, hipMemcpyDeviceToDevice, s));
+    return SF_OK;
+}
+
+int sf_light_filter_to(sf_ctx* c, const sf_light_filter_params* p, const float* pos4, const float* nrm4,
+                       const float* in, float* out)
+{
+    if (!c || !p || !out) return SF_EINVAL;
+    uint32_t W, H;
+    if (int rc = filter_check(c, p, !pos4 || !nrm4 || !in, &W, &H)) return rc;
+    if (!in && !c->light) return SF_ESTATE;
+    const float* const src = in ? in : (const float*)c->light;
+    if (src == out) return SF_EINVAL;
+    return filter_launch(c, p, W, H, pos4 ? pos4 : (const float*)c->pos, nrm4 ? nrm4 : (const float*)c->nrm, src, out,
+                         nullptr);
+}
+
+// In place for the caller: into the context's second buffer, then copied back on the same stream.
+int sf_light_filter(sf_ctx* c, const sf_light_filter_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    uint32_t W, H;
+    if (int rc = filter_check(c, p, true, &W, &H)) return rc;
+    if (!c->light) return SF_ESTATE;
+    if (!c->light_filtered) {
+        DevGuard g(c->device);
+        SF_HIP(c, hipMalloc(&c->light_filtered, (size_t)W * H * 16));
+    }
+    return filter_launch(c, p, W, H, c->pos, c->nrm, c->light, c->light_filtered, c->light);
 }
 
 int sf_light_buffer(sf_ctx* c, float** buf)

@@ -291,6 +291,15 @@ struct AoSum {
     float h[SF_AO_SAMPLES][3];
     float c[SF_AO_SAMPLES][3];        // the samples' colours
 };
+// The per-pixel spin of sf_trace_ao_spin_to and its siblings: the table travels by value beside AoArgs / AoSum (520 B;
+// sf_capi.hip asserts the 4 KB limit with it). A lane indexes it with its own pixel, so these are vector loads from
+// the argument segment, once per tile.
+#define SF_AO_SPIN 8u                 // == SF_AO_SPIN_MAX (sf.h): the table is at most 8 x 8
+struct AoSpin {
+    uint32_t size;                    // 1..SF_AO_SPIN
+    uint32_t pad_;
+    float cs[SF_AO_SPIN * SF_AO_SPIN][2];   // (c, s) of pixel (x, y): entry (y % size) * size + (x % size)
+};
 
 #if defined(__HIPCC__) || defined(__HIP__)
 // The two Lambert terms at a pixel of normal n, shared by the image passes (sf_post.hip) and the summing traces

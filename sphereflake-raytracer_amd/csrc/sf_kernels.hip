@@ -4978,6 +4978,121 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_sum_fixup(FrameArgs
 }
 
 // ------------------------------------------------------------------------------------------
+// Ambient occlusion with a per-pixel spin (sf_trace_ao_spin_to / sf_trace_ao_spin_sum_to): the four
+// kernels above with each lane's frame turned about its normal by its pixel's own (c, s), once per tile, before the
+// sample loop: T' = (T c) + (B s), B' = (B c) - (T s) (sf.h). The lane reads its entry of the table in the argument
+// segment at (g.y % size) * size + (g.x % size): a vector load, since the index is the lane's. The sample loop, the
+// endings and the re-trace are the unspun kernels'. trace_ao_entries is not touched and not shared: a traversal's call
+// site decides its registers and its time (§6.18), so the spun pose is a function of its own.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// The entries of the spun calls: ao_frame, the turn, then trace_ao_entries' pose with T' and B'.
+template <bool FIXUP, class AO>
+__device__ __forceinline__ uint64_t trace_ao_spin_entries(const FrameArgs& a, const GroupLane& g, const float4 P,
+                                                          const float4 N, bool surface, const AO& ao,
+                                                          const AoSpin& sp, const LightTile<FIXUP>& t,
+                                                          uint32_t& status)
+{
+    const float wx = __fadd_rn(ao.o[0], P.x), wy = __fadd_rn(ao.o[1], P.y), wz = __fadd_rn(ao.o[2], P.z);
+    float T0[3], B0[3], T[3], B[3];
+    ao_frame(N, T0, B0);
+    const uint32_t e = (g.y % sp.size) * sp.size + (g.x % sp.size);   // (< size^2 <= 64 for any pixel)
+    const float c = sp.cs[e][0], s = sp.cs[e][1];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        T[k] = __fadd_rn(__fmul_rn(T0[k], c), __fmul_rn(B0[k], s));
+        B[k] = __fsub_rn(__fmul_rn(B0[k], c), __fmul_rn(T0[k], s));
+    }
+    return trace_parallel_entries(a, ao.n, ao.keep, t, status, [&](uint32_t i) {
+        const float hx = ao.h[i][0], hy = ao.h[i][1], hz = ao.h[i][2];
+        const float sx = __fadd_rn(__fadd_rn(__fmul_rn(T[0], hx), __fmul_rn(B[0], hy)), __fmul_rn(N.x, hz));
+        const float sy = __fadd_rn(__fadd_rn(__fmul_rn(T[1], hx), __fmul_rn(B[1], hy)), __fmul_rn(N.y, hz));
+        const float sz = __fadd_rn(__fadd_rn(__fmul_rn(T[2], hx), __fmul_rn(B[2], hy)), __fmul_rn(N.z, hz));
+        return RayPose{wx, wy, wz, __fadd_rn(wx, __fmul_rn(sx, ao.tau)), __fadd_rn(wy, __fmul_rn(sy, ao.tau)),
+                       __fadd_rn(wz, __fmul_rn(sz, ao.tau)), surface};
+    });
+}
+
+template <bool FIXUP>
+__device__ __forceinline__ void trace_ao_spin_group(const FrameArgs& a, const float* __restrict__ pos4,
+                                                    const float* __restrict__ nrm4, const AoArgs& ao,
+                                                    const AoSpin& sp, uint64_t* __restrict__ mask,
+                                                    const LightTile<FIXUP>& t)
+{
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
+    const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    uint64_t shadowed = 0ull;
+    uint32_t status = 0u;
+    // (uniform; else the tile is all frame miss)
+    if (wave_ballot(surface) != 0ull)
+        shadowed = trace_ao_spin_entries(a, g, P, px4(nrm4, g.ray), surface, ao, sp, t, status);
+    light_mask_end(a, g, ao.n, shadowed, status, mask, t);
+}
+
+template <bool FIXUP>
+__device__ __forceinline__ void trace_ao_spin_sum_group(const FrameArgs& a, const float* __restrict__ pos4,
+                                                        const float* __restrict__ nrm4, const AoSum& ao,
+                                                        const AoSpin& sp, float* __restrict__ out,
+                                                        const LightTile<FIXUP>& t)
+{
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
+    const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    uint64_t shadowed = 0ull;
+    uint32_t status = 0u;
+    // (uniform; else the tile is all frame miss)
+    if (wave_ballot(surface) != 0ull)
+        shadowed = trace_ao_spin_entries(a, g, P, px4(nrm4, g.ray), surface, ao, sp, t, status);
+    light_sum_end(a, g, surface, shadowed, status, ao, nrm4, out, t, [](const float4, uint32_t) { return 1.0f; });
+}
+
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_spin_wave(FrameArgs a, const float* pos4,
+                                                                       const float* nrm4, AoArgs ao, AoSpin sp,
+                                                                       uint64_t* mask, uint32_t groups,
+                                                                       uint32_t* overflow_list,
+                                                                       uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_ao_spin_group(a, pos4, nrm4, ao, sp, mask, t); });
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_spin_fixup(FrameArgs a, const float* pos4,
+                                                                        const float* nrm4, AoArgs ao, AoSpin sp,
+                                                                        uint64_t* mask, const uint32_t* overflow_list,
+                                                                        uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_ao_spin_group(a, pos4, nrm4, ao, sp, mask, t); });
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_spin_sum_wave(FrameArgs a, const float* pos4,
+                                                                           const float* nrm4, AoSum ao, AoSpin sp,
+                                                                           float* out, uint32_t groups,
+                                                                           uint32_t* overflow_list,
+                                                                           uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_ao_spin_sum_group(a, pos4, nrm4, ao, sp, out, t); });
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_spin_sum_fixup(FrameArgs a, const float* pos4,
+                                                                            const float* nrm4, AoSum ao, AoSpin sp,
+                                                                            float* out, const uint32_t* overflow_list,
+                                                                            uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_ao_spin_sum_group(a, pos4, nrm4, ao, sp, out, t); });
+}
+
+// ------------------------------------------------------------------------------------------
 // Light shafts: sun visibility along each pixel's view ray in one launch (sf_trace_shafts_to). Bit i
 // of mask[p] is what sf_trace_sun_wave writes at a pixel whose position is Q_i = E sigma_i (1 = 255, 0 = 0), bits
 // n..63 are 0. The lane's position is loaded and its march end E formed once -- P, or where P == 0 and a direction

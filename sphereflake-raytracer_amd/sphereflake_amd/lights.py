@@ -613,12 +613,47 @@ def ao_colours(samples, colour=(1.0, 1.0, 1.0), kind="cosine"):
     return (wgt[:, None] * c).astype(_F)
 
 
-def ao_basis(nrm4):
+AO_SPIN_MAX = 8          # SF_AO_SPIN_MAX: the spin table is at most 8 x 8
+
+
+def ao_spins(size):
+    """The spin table [size, size, 2] float32 of trace_ao(spin=...): entry k = y size + x holds (cos, sin) of the angle
+    2 pi ((7 k mod size^2) + 0.5) / size^2, formed in float64 and rounded. The size^2 angles are evenly spaced over the
+    turn, and 7 k mod size^2 keeps neighbouring pixels' angles apart (7 is coprime to size^2 for every size but 7, where
+    the table repeats 7 angles); any size x size window of pixels holds every entry once."""
+    size = int(size)
+    if not 1 <= size <= AO_SPIN_MAX:
+        raise ValueError(f"size is 1..{AO_SPIN_MAX}")
+    m = size * size
+    k = np.arange(m, dtype=np.int64)
+    ang = 2.0 * np.pi * (((7 * k) % m) + 0.5) / m
+    return np.stack([np.cos(ang), np.sin(ang)], axis=-1).astype(_F).reshape(size, size, 2)
+
+
+def _spin_of(spin, shape):
+    """(c, s) float32, each broadcastable over the normals of `shape` [...]: one pair as given, or a table
+    [size, size, 2] tiled over the image's pixel coordinates -- pixel (x, y) takes entry (y % size, x % size)."""
+    t = np.asarray(spin, _F)
+    if t.shape == (2,):
+        return t[0], t[1]
+    if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[2] != 2 or not 1 <= t.shape[0] <= AO_SPIN_MAX:
+        raise ValueError(f"spin is one (c, s) pair or a table [size, size, 2], size 1..{AO_SPIN_MAX}")
+    if len(shape) != 2:
+        raise ValueError("a spin table needs a normal image [H, W, 3 | 4]")
+    size = t.shape[0]
+    e = t[np.arange(shape[0])[:, None] % size, np.arange(shape[1])[None, :] % size]
+    return e[..., 0, None], e[..., 1, None]
+
+
+def ao_basis(nrm4, spin=None):
     """Step 2 of sf_trace_ao_to's definition: the frame (T, B, N), each [..., 3] float32, about the normals
     nrm4 [..., 3 | 4], used as given (not normalised). The branch-free frame of Duff et al., one rounding per
     operation in the order written: sg = copysign(1, N.z), a = -1 / (sg + N.z), b = (N.x N.y) a,
     T = (1 + sg ((N.x N.x) a), sg b, -sg N.x), B = (b, sg + (N.y N.y) a, -N.y). Orthonormal, to rounding, for a
-    unit N; sg + N.z is never zero."""
+    unit N; sg + N.z is never zero.
+    spin (trace_ao(spin=...), sf_trace_ao_spin_to): one (c, s) pair, or a table [size, size, 2] indexed by the pixel
+    coordinates of the normal image [H, W, 3 | 4]; the frame is then turned about N, per component
+    T' = (T c) + (B s), B' = (B c) - (T s), one rounding per operation. None: not turned, today's bits."""
     N = np.array(np.asarray(nrm4, _F)[..., :3], _F, copy=True)
     x, y, z = N[..., 0], N[..., 1], N[..., 2]
     with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
@@ -627,16 +662,19 @@ def ao_basis(nrm4):
         b = (x * y) * a
         T = np.stack([_F(1.0) + sg * ((x * x) * a), sg * b, -(sg * x)], axis=-1)
         B = np.stack([b, sg + (y * y) * a, -y], axis=-1)
+        if spin is not None:
+            c, s = _spin_of(spin, N.shape[:-1])
+            T, B = (T * c) + (B * s), (B * c) - (T * s)
     assert T.dtype == _F and B.dtype == _F
     return T, B, N
 
 
-def ao_directions(nrm4, samples):
+def ao_directions(nrm4, samples, spin=None):
     """Step 3: the world directions s [n, ..., 3] of the local-frame samples h [n, 3] about the normals
     nrm4 [..., 3 | 4]: per component c, s_i.c = ((T.c h_i.x) + (B.c h_i.y)) + (N.c h_i.z) with (T, B, N) of ao_basis,
     one rounding per operation. For one normal [3 | 4] the result [n, 3] is the `dirs` of trace_suns that trace_ao
-    equals on a constant normal image."""
-    T, B, N = ao_basis(nrm4)
+    equals on a constant normal image. spin: as ao_basis'; with one normal, one (c, s) pair."""
+    T, B, N = ao_basis(nrm4, spin)
     h = np.asarray(samples, _F).reshape(-1, 3)
     _count(h.shape[0], AO_SAMPLES_MAX)
     with np.errstate(invalid="ignore", over="ignore", under="ignore"):
@@ -645,20 +683,20 @@ def ao_directions(nrm4, samples):
     return s
 
 
-def ao_model(pos4, nrm4, origin, samples, distance, bias):
+def ao_model(pos4, nrm4, origin, samples, distance, bias, spin=None):
     """Steps 1-4 of sf_trace_ao_to's definition up to the ray, stacked per sample as suns_model stacks them:
     (F [n, ..., 3], d [n, ..., 3], bound [n, ...], is_surface [...]) for a position image pos4 [..., 3 | 4] relative
     to `origin`, its normal image nrm4 and the samples [n, 3]. With s_i = ao_directions(nrm4, samples)[i] (a
     direction per pixel): w = origin + P, f_i = s_i tau, F_i = w + f_i the ray's origin, d_i = (w - F_i) + 0 its
     unnormalised direction, bound_i = |d_i| (1 - bias). is_surface is False where P == (0, 0, 0): no ray, every bit
-    set."""
+    set. spin: as ao_basis' (sf_trace_ao_spin_to's definition); None is the unspun call."""
     if not 0.0 <= float(bias) < 1.0:
         raise ValueError("bias must be in [0, 1)")
     tau = _F(distance)
     if not (np.isfinite(tau) and tau > 0):
         raise ValueError("distance must be finite and > 0")
     P, w = _world(pos4, origin)
-    s = ao_directions(nrm4, samples)
+    s = ao_directions(nrm4, samples, spin)
     if s.shape[1:] != P.shape:
         raise ValueError("nrm4 and pos4 must have the same height and width")
     with np.errstate(invalid="ignore", over="ignore", under="ignore"):
@@ -699,4 +737,55 @@ def ao_sum_model(base, pos4, masks, colours, accumulate=False):
     assert S.dtype == _F
     surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
     out[..., :3] = np.where(surface[..., None], S, out[..., :3])
+    return out
+
+
+# --- the edge-aware box filter of the light buffer (sf_light_filter_to) ---------------------------------------------
+def light_filter_model(buf, pos4, nrm4, size, normal_min=0.9, plane_max=0.02):
+    """What sf_light_filter_to makes of the light buffer buf [H, W, 4]: a new float32 array, sf.h's definition on the
+    host. A miss pixel (P == 0) is copied. Else the taps q = p + (dx, dy), dy outer and dx inner, both from -(size // 2)
+    to size - 1 - size // 2, are visited in that order; a tap outside the image or a miss is skipped; q == p is
+    accepted; any other tap iff ((N_p.x N_q.x) + (N_p.y N_q.y)) + (N_p.z N_q.z) >= normal_min and e e <= k2 pp with
+    e = ((N_p.x D.x) + (N_p.y D.y)) + (N_p.z D.z), D = P_q - P_p, pp = |P_p|^2 summed in that order and
+    k2 = float32(plane_max) float32(plane_max); a comparison with a NaN rejects. Per channel S = S + buf[q] over the
+    accepted taps in visiting order, out.xyz = S / float32(count), out.w = buf[p].w."""
+    size = int(size)
+    if not 1 <= size <= AO_SPIN_MAX:
+        raise ValueError(f"size is 1..{AO_SPIN_MAX}")
+    nmin, pmax = _F(normal_min), _F(plane_max)
+    if np.isnan(nmin) or not (np.isfinite(pmax) and pmax >= 0):
+        raise ValueError("normal_min must not be NaN; plane_max must be finite and not negative")
+    src = np.asarray(buf, _F)
+    P = np.asarray(pos4, _F)[..., :3]
+    N = np.asarray(nrm4, _F)[..., :3]
+    if src.ndim != 3 or src.shape[-1] != 4 or P.shape != src.shape[:2] + (3,) or N.shape != P.shape:
+        raise ValueError("buf, pos4 and nrm4 must be [H, W, 4] images of one size")
+    H, W = src.shape[:2]
+    k2 = pmax * pmax
+    surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
+    S = np.zeros((H, W, 3), _F)
+    count = np.zeros((H, W), np.int64)
+    lo, hi = -(size // 2), size - 1 - size // 2
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        pp = (P[..., 0] * P[..., 0] + P[..., 1] * P[..., 1]) + P[..., 2] * P[..., 2]
+        limit = k2 * pp
+        for dy in range(lo, hi + 1):
+            for dx in range(lo, hi + 1):
+                # the pixels p whose tap q = p + (dx, dy) lies in the image, and their taps
+                ys, xs = slice(max(0, -dy), min(H, H - dy)), slice(max(0, -dx), min(W, W - dx))
+                yq, xq = slice(max(0, dy), min(H, H + dy)), slice(max(0, dx), min(W, W + dx))
+                Pp, Np, Pq, Nq = P[ys, xs], N[ys, xs], P[yq, xq], N[yq, xq]
+                if dx == 0 and dy == 0:
+                    ok = np.ones(Pp.shape[:2], bool)
+                else:
+                    nn = (Np[..., 0] * Nq[..., 0] + Np[..., 1] * Nq[..., 1]) + Np[..., 2] * Nq[..., 2]
+                    D = Pq - Pp
+                    e = (Np[..., 0] * D[..., 0] + Np[..., 1] * D[..., 1]) + Np[..., 2] * D[..., 2]
+                    ok = surface[yq, xq] & (nn >= nmin) & ((e * e) <= limit[ys, xs])
+                S[ys, xs] = np.where(ok[..., None], S[ys, xs] + src[yq, xq, :3], S[ys, xs])
+                count[ys, xs] += ok
+        mean = S / np.maximum(count, 1).astype(_F)[..., None]
+    assert mean.dtype == _F
+    out = np.array(src, _F, copy=True)
+    out[..., :3] = np.where(surface[..., None], mean, src[..., :3])
     return out

@@ -1,0 +1,208 @@
+"""The per-pixel spin of the ambient-occlusion traces without a GPU: the host models' identities, the table of
+lights.ao_spins, the oracle conditions tests/test_gpu_ao_spin.py relies on, the header, the exports and the struct
+layout. Everything is compared bit for bit."""
+import ctypes
+import pathlib
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import sphereflake_amd as sf
+from sphereflake_amd import lights
+from dirscheck import same_bits
+from oracle import pyoracle
+from rayscheck import frame
+import aocheck as ac
+import aospincheck as sc
+
+F = np.float32
+SYMBOLS = ("sf_trace_ao_spin_to", "sf_trace_ao_spin", "sf_trace_ao_spin_sum_to", "sf_trace_ao_spin_sum")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    sf.build()
+
+
+# ---- the models ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["t1", "t3"])
+def test_no_spin_and_the_identity_table_are_todays_model(name):
+    """spin=None is the code path of before; the 1 x 1 table {(1, 0)} gives the same F, d and bound at every surface
+    pixel, bit for bit (the sign of a zero is lost in F = w + f and d = (w - F) + 0 before anything reads it)."""
+    S = pyoracle.load_setup(name)
+    f = frame(name)
+    h = lights.ao_samples(64)
+    plain = lights.ao_model(f["pos4"], f["nrm4"], S["origin"], h, ac.TAU, ac.B10)
+    none = lights.ao_model(f["pos4"], f["nrm4"], S["origin"], h, ac.TAU, ac.B10, spin=None)
+    ident = lights.ao_model(f["pos4"], f["nrm4"], S["origin"], h, ac.TAU, ac.B10, spin=sc.IDENTITY)
+    pair = lights.ao_model(f["pos4"], f["nrm4"], S["origin"], h, ac.TAU, ac.B10, spin=(1.0, 0.0))
+    surf = plain[3]
+    assert int(surf.sum()) >= 800
+    for other in (none, ident, pair):
+        assert np.array_equal(other[3], surf)
+        for a, b, what in zip(plain[:3], other[:3], ("F", "d", "bound")):
+            assert same_bits(a[:, surf], b[:, surf]), what
+    T0, B0, N0 = lights.ao_basis(f["nrm4"])
+    T1, B1, N1 = lights.ao_basis(f["nrm4"], spin=None)
+    assert same_bits(T0, T1) and same_bits(B0, B1) and same_bits(N0, N1)
+
+
+def test_the_turn_is_the_definition():
+    """T' = (T c) + (B s), B' = (B c) - (T s) per component, each operation rounded on its own; a table is indexed
+    [y % size, x % size]; a uniform table is its one pair."""
+    nrm = frame("t3")["nrm4"]
+    T, B, N = lights.ao_basis(nrm)
+    tab = lights.ao_spins(3)
+    Ts, Bs, Ns = lights.ao_basis(nrm, spin=tab)
+    assert same_bits(N, Ns)
+    H, W = nrm.shape[:2]
+    for y, x in ((0, 0), (1, 2), (17, 30), (44, 79), (20, 41)):
+        c, s = tab[y % 3, x % 3]
+        for k in range(3):
+            assert Ts[y, x, k] == F(F(T[y, x, k] * c) + F(B[y, x, k] * s))
+            assert Bs[y, x, k] == F(F(B[y, x, k] * c) - F(T[y, x, k] * s))
+    uniform = np.empty((4, 4, 2), F)
+    uniform[...] = np.array(sc.PAIR, F)
+    Tu, Bu, _ = lights.ao_basis(nrm, spin=uniform)
+    Tp, Bp, _ = lights.ao_basis(nrm, spin=sc.PAIR)
+    assert same_bits(Tu, Tp) and same_bits(Bu, Bp)
+    # a turned frame stays orthonormal to rounding for a rotation
+    surf = (N * N).sum(-1) > 0.5
+    assert np.abs((Ts * Bs).sum(-1)[surf]).max() < 1e-5 and np.abs((Ts * Ts).sum(-1)[surf] - 1).max() < 1e-5
+    # one normal takes one pair, and the directions are those of the turned frame
+    N0 = np.array(ac.CONSTANT_NORMALS[3], F)
+    D = lights.ao_directions(N0, sc.H8, spin=sc.PAIR)
+    T1, B1, _ = lights.ao_basis(N0, spin=sc.PAIR)
+    for i, h in enumerate(sc.H8):
+        assert same_bits(D[i], ((T1 * h[0]) + (B1 * h[1])) + (N0 * h[2]))
+    assert not same_bits(D, lights.ao_directions(N0, sc.H8))
+    with pytest.raises(ValueError):
+        lights.ao_directions(N0, sc.H8, spin=tab)          # a table needs an image
+    with pytest.raises(ValueError):
+        lights.ao_basis(nrm, spin=np.zeros((9, 9, 2), F))  # larger than SF_AO_SPIN_MAX
+    with pytest.raises(ValueError):
+        lights.ao_basis(nrm, spin=np.zeros((4, 3, 2), F))
+
+
+def test_ao_spins_values():
+    for size in range(1, 9):
+        t = lights.ao_spins(size)
+        assert t.shape == (size, size, 2) and t.dtype == F
+        m = size * size
+        for k in {0, min(1, m - 1), m // 2, m - 1}:
+            ang = 2.0 * np.pi * (((7 * k) % m) + 0.5) / m
+            assert t[k // size, k % size, 0] == F(np.cos(ang)) and t[k // size, k % size, 1] == F(np.sin(ang))
+        assert np.abs((t.astype(np.float64) ** 2).sum(-1) - 1).max() < 1e-6
+        angles = {int(round((np.degrees(np.arctan2(s, c)) % 360) * 1000)) for c, s in t.reshape(-1, 2).astype(np.float64)}
+        assert len(angles) == (7 if size == 7 else m)   # (7 divides 49: the size-7 table repeats seven angles)
+    t4 = lights.ao_spins(4)
+    assert t4[0, 0, 0] == F(np.cos(np.pi / 16)) and t4[0, 1, 0] == F(np.cos(2 * np.pi * 7.5 / 16))
+    assert same_bits(lights.ao_spins(1), np.array([[[np.cos(np.pi), np.sin(np.pi)]]], F))
+    for bad in (0, 9, -1):
+        with pytest.raises(ValueError):
+            lights.ao_spins(bad)
+    assert lights.AO_SPIN_MAX == 8 and sf.SF_AO_SPIN_MAX == 8
+
+
+# ---- the oracle conditions of the GPU tests -------------------------------------------------------------
+@pytest.mark.parametrize("name", ["t1", "t3"])
+def test_oracle_facts_of_the_spun_case(name):
+    """ao_samples(8) under ao_spins(4), tau = 4, bias 2^-10, on the sampled pixels: per table entry at least 20 pixels
+    whose word differs from the unspun word (observed minimum 38 on t1, 53 on t3), and at least 100 lit and 100
+    occluded bits (observed minimum 182): neither an ignored table nor a constant mask can pass."""
+    every = ac.EVERY[name]
+    S4 = lights.ao_spins(4)
+    spun, pick = sc.oracle_mask(name, sc.H8, S4, ac.TAU, ac.B10, "avx", every)
+    plain, pick2 = ac.oracle_mask(name, sc.H8, ac.TAU, ac.B10, "avx", None, every)
+    assert np.array_equal(pick, pick2) and int(pick.sum()) == {"t1": 830, "t3": 1200}[name]
+    ent = sc.entry_of(pick.shape, 4)
+    differ = [int((pick & (ent == k) & (spun != plain)).sum()) for k in range(16)]
+    lit = [sum(int((pick & (ent == k) & ac.bit(spun, i)).sum()) for i in range(8)) for k in range(16)]
+    occ = [sum(int((pick & (ent == k) & ~ac.bit(spun, i)).sum()) for i in range(8)) for k in range(16)]
+    print(name, "differ", min(differ), "lit", min(lit), "occluded", min(occ))
+    assert min(differ) >= 20 and min(lit) >= 100 and min(occ) >= 100
+
+
+# ---- the header, the library, the class -----------------------------------------------------------------
+def test_header_states_the_definition():
+    text = " ".join(pathlib.Path(sf.HEADER_PATH).read_text().split())
+    for sym in SYMBOLS + ("sf_ao_spin",):
+        assert sym in text, sym
+    assert "#define SF_AO_SPIN_MAX 8" in text
+    assert "T'.k = (T.k c) + (B.k s) B'.k = (B.k c) - (T.k s)" in text
+    assert "The frame is turned ONCE PER PIXEL, not once per sample." in text
+    assert "The 1 x 1 table {(1, 0)} gives sf_trace_ao_to's mask and sf_trace_ao_sum_to's sum." in text
+    assert "A table whose entries are all equal gives the 1 x 1 table's result." in text
+    assert "ao_directions(N0, samples, spin=(c, s))" in text
+    assert "top-left corner is at multiples of `size`" in text
+    assert "#define SF_ABI_VERSION 1" in text and sf.lib().sf_abi_version() == 1
+
+
+def test_symbols_are_exported():
+    if shutil.which("nm") is None:
+        pytest.skip("binutils not available")
+    out = subprocess.run(["nm", "-D", "--defined-only", sf.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    have = {l.split()[-1] for l in out.splitlines() if l.strip()}
+    assert set(SYMBOLS) <= have
+    assert set(SYMBOLS) <= set(sf.SIGNATURES)
+
+
+def test_struct_layout_matches_the_header():
+    P = sf.sf_ao_spin
+    assert ctypes.sizeof(P) == 16 and (P.cs.offset, P.size.offset) == (0, 8)
+
+
+def test_error_codes_without_a_device():
+    L = sf.lib()
+    p = sf.sf_ao_params()
+    buf = (ctypes.c_float * 64)()
+    vp = ctypes.cast(buf, ctypes.c_void_p)
+    p.samples, p.n, p.distance = ctypes.cast(buf, ctypes.POINTER(ctypes.c_float)), 1, 4.0
+    sp = sf.sf_ao_spin()
+    sp.cs, sp.size = ctypes.cast(buf, ctypes.POINTER(ctypes.c_float)), 1
+    assert L.sf_trace_ao_spin_to(None, ctypes.byref(p), ctypes.byref(sp), vp, vp, vp) == sf.SF_EINVAL
+    assert L.sf_trace_ao_spin(None, ctypes.byref(p), ctypes.byref(sp)) == sf.SF_EINVAL
+    assert L.sf_trace_ao_spin_sum_to(None, ctypes.byref(p), ctypes.byref(sp), vp, vp, vp) == sf.SF_EINVAL
+    assert L.sf_trace_ao_spin_sum(None, ctypes.byref(p), ctypes.byref(sp)) == sf.SF_EINVAL
+
+
+def test_cpp_members_are_inline_over_the_c_abi(tmp_path):
+    """The TraceAO / TraceAOSum overloads with a spin and LightFilter compile for an application, stay inline, and
+    need only sf_* symbols the library has."""
+    if shutil.which("g++") is None or shutil.which("nm") is None:
+        pytest.skip("binutils / g++ not available")
+    repo = pathlib.Path(__file__).resolve().parent.parent
+    src = tmp_path / "spin.cpp"
+    src.write_text('#include "Sphereflake.hpp"\n'
+                   "using namespace SphereflakeRaytracer;\n"
+                   "void occlude(Sphereflake& s, const float* pdev, const float* ndev, uint64_t* mdev, float* ldev,\n"
+                   "             float* fdev) {\n"
+                   "    static const float h[6] = { 0.0f, 0.0f, 1.0f, 0.6f, 0.0f, 0.8f };\n"
+                   "    static const float cs[8] = { 1.0f, 0.0f, 0.0f, 1.0f, -1.0f, 0.0f, 0.0f, -1.0f };\n"
+                   "    sf_ao_params p;\n"
+                   "    sf_ao_defaults(s.Context(), &p);\n"
+                   "    p.samples = h; p.n = 2;\n"
+                   "    sf_ao_spin spin = { cs, 2 };\n"
+                   "    s.TraceAO(p, spin);\n"
+                   "    s.TraceAOSum(p, spin);\n"
+                   "    sf_light_filter_params f;\n"
+                   "    sf_light_filter_defaults(s.Context(), &f);\n"
+                   "    f.size = 2;\n"
+                   "    s.LightFilter(f);\n"
+                   "    p.width = f.width = 64; p.height = f.height = 36; p.accumulate = 1;\n"
+                   "    s.TraceAO(p, spin, pdev, ndev, mdev);\n"
+                   "    s.TraceAOSum(p, spin, pdev, ndev, ldev);\n"
+                   "    s.LightFilter(f, pdev, ndev, ldev, fdev);\n}\n")
+    obj = tmp_path / "spin.o"
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-c", f"-I{repo / 'include'}",
+                        f"-I{repo / 'sphereflake-raytracer_amd' / 'csrc'}", str(src), "-o", str(obj)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    nm = lambda *a: {l.split()[-1] for l in subprocess.run(["nm", *a], capture_output=True, text=True,
+                                                           check=True).stdout.splitlines() if l.strip()}
+    need, have = nm("-u", str(obj)), nm("-D", "--defined-only", sf.LIB_PATH)
+    assert set(SYMBOLS) | {"sf_light_filter_to", "sf_light_filter"} <= need
+    assert not [n for n in need if "TraceAO" in n or "LightFilter" in n]
+    assert not [n for n in need if (n.startswith("sf_") or "SphereflakeRaytracer" in n) and n not in have]
