@@ -128,6 +128,77 @@ def render(setup: dict, rows=None, threads: int | None = None, lut: np.ndarray |
     return {"pos4": pos, "nrm4": nrm, "minT": mint, "index": idx, "depth": dep, "stats": stats}
 
 
+_root_columns = None
+
+
+def root_columns() -> np.ndarray:
+    """Columns 0..2 of the root transform (the rotation of Sphereflake.cpp:83, the same at every origin), [12],
+    as the reference dumped them (tests/golden/setup_t1.json)."""
+    global _root_columns
+    if _root_columns is None:
+        c = np.ascontiguousarray(load_setup("t1")["root"][:12], np.float32)
+        c.setflags(write=False)
+        _root_columns = c
+    return _root_columns
+
+
+def trace_rays(children, origins, dirs, lod: float = 70.0, threads: int = 8, bounds=None) -> dict:
+    """A batch of rays, ray i from origins[i] ([N, 3], or one origin [3] for all) along dirs[i] ([N, 3], normalised by
+    the oracle as a pixel's direction is): sfo_trace_rays, the loop over sfo_render_rows' 1 x 1 frame in C, split
+    over `threads` in contiguous chunks. Returns what tests/rayscheck.py's oracle_multi returns: pos4 [N, 4],
+    nrm4 [N, 4], minT [N], index [N] and stats (max_depth, closest, hits). The LOD constant is the library's global,
+    set here before the rays are traced.
+    bounds [N] (optional, sfo_trace_rays_near): also near_depth [N] int8, per ray the depth of the deepest node it
+    expands whose bounding-sphere root t is under bounds[i] (-1: none) -- the nodes an any-hit traversal that stops
+    at that bound must still open on a ray nothing stops."""
+    L = lib()
+    L.sfo_set_lod_constant.argtypes = [ctypes.c_float]
+    fp, up = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
+    L.sfo_trace_rays.argtypes = [ctypes.c_uint64, fp, fp, fp, fp, up, fp, up, fp, fp, ctypes.POINTER(ctypes.c_longlong)]
+    L.sfo_trace_rays.restype = ctypes.c_int
+    L.sfo_trace_rays_near.argtypes = L.sfo_trace_rays.argtypes + [fp, ctypes.POINTER(ctypes.c_int8)]
+    L.sfo_trace_rays_near.restype = ctypes.c_int
+    L.sfo_set_lod_constant(ctypes.c_float(lod))
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    n = d.shape[0]
+    o = np.ascontiguousarray(np.broadcast_to(np.asarray(origins, np.float32).reshape(-1, 3), (n, 3)))
+    child = np.ascontiguousarray(children, np.float32).reshape(-1)
+    cols = root_columns()
+    lut = np.ascontiguousarray(load_lut(), dtype=np.uint32)
+    pos, nrm = np.empty((n, 4), np.float32), np.empty((n, 4), np.float32)
+    mint, idx = np.empty(n, np.float32), np.empty(n, np.uint32)
+    if bounds is not None:
+        bnd = np.ascontiguousarray(bounds, np.float32).reshape(-1)
+        assert bnd.shape[0] == n
+        near = np.empty(n, np.int8)
+    chunks = max(1, min(int(threads), n // 512))
+    cuts = [n * k // chunks for k in range(chunks + 1)]
+
+    def work(k):
+        a, b = cuts[k], cuts[k + 1]
+        st = (ctypes.c_longlong * 5)()
+        args = (b - a, _fp(o[a:b]), _fp(d[a:b]), _fp(cols), _fp(child), lut.ctypes.data_as(up),
+                _fp(mint[a:b]), idx[a:b].ctypes.data_as(up), _fp(pos[a:b]), _fp(nrm[a:b]), st)
+        if bounds is None:
+            rc = L.sfo_trace_rays(*args)
+        else:
+            rc = L.sfo_trace_rays_near(*args, _fp(bnd[a:b]), near[a:b].ctypes.data_as(ctypes.POINTER(ctypes.c_int8)))
+        assert rc == 0
+        return list(st)
+
+    if chunks == 1:
+        res = [work(0)]
+    else:
+        with ThreadPoolExecutor(chunks) as ex:
+            res = list(ex.map(work, range(chunks)))
+    closest = np.array([r[4] for r in res], np.uint32).view(np.float32).min() if n else np.finfo(np.float32).max
+    out = {"pos4": pos, "nrm4": nrm, "minT": mint, "index": idx,
+           "stats": {"max_depth": max(r[0] for r in res), "closest": float(closest), "hits": sum(r[1] for r in res)}}
+    if bounds is not None:
+        out["near_depth"] = near
+    return out
+
+
 def rsqrtps(x: float, lut: np.ndarray | None = None) -> float:
     lut = np.ascontiguousarray(load_lut() if lut is None else lut, dtype=np.uint32)
     return lib().sfo_rsqrtps(x, lut.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))

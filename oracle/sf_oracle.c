@@ -106,6 +106,11 @@ typedef struct {
 static float g_lod_constant = 70.0f;
 void sfo_set_lod_constant(float c) { g_lod_constant = c; }
 
+/* A statistic beside max_depth, for sfo_trace_rays_near: the deepest node the calling thread's ray expands whose
+   bounding-sphere root t lies under g_near_bound. It changes nothing that is traced or returned elsewhere. */
+static _Thread_local float g_near_bound = 0.0f;
+static _Thread_local int g_near_depth = -1;
+
 /* Sphereflake::IntersectSphereflake, Sphereflake.h:86-226 (per ray). */
 static void intersect(trav_t* tv, const float D[3], const float* parent, hit_t* h,
                       float parentRadius, int depth, uint64_t node)
@@ -119,6 +124,7 @@ static void intersect(trav_t* tv, const float D[3], const float* parent, hit_t* 
     if (!ray_sphere(D, C, R2b, &t)) return;                       /* :119, :140-144 */
     if (!(sqrtf(t / r) < g_lod_constant || t < 0.0f)) return;    /* :146-153 (SSE :129-136) */
     if (depth > tv->max_depth) tv->max_depth = depth;             /* :157-160 */
+    if (t < g_near_bound && depth > g_near_depth) g_near_depth = depth;
     tv->interior++;
     float scale = (4.0f / 3.0f) * r;                              /* :162 */
     for (int i = 0; i < 9; ++i) {                                 /* :165-172 */
@@ -197,6 +203,73 @@ int sfo_render_rows(uint32_t W, uint32_t H,
     if (stats_out) { stats_out[0] = tv.max_depth; stats_out[1] = hits; stats_out[2] = tv.nodes; stats_out[3] = tv.interior; }
     if (closest_out) *closest_out = closest;
     return 0;
+}
+
+/*
+ * A batch of rays, each with its own origin: ray i is the one pixel of sfo_render_rows' 1 x 1 frame with o = 0 and
+ * tl = tr = bl = dirs3[3 i] (so its ray generation forms D = Normalize(d), and a -0 component of d comes out as +0),
+ * under the root whose columns 0..2 are root_columns[0..11] and whose translation is 0 - origins3[3 i] (what SetView
+ * at that origin gives, Sphereflake.cpp:83). It is a loop over sfo_render_rows itself: there is one code path.
+ * Outputs per ray as sfo_render_rows' (any may be NULL). stats_out[0..3] as there, over the batch;
+ * stats_out[4] = the bit pattern of the smallest minT (FLT_MAX's where nothing is hit).
+ */
+static int trace_rays(uint64_t n, const float* origins3, const float* dirs3, const float root_columns[12],
+                      const float child[9 * 16], const uint32_t* lut,
+                      float* minT, uint32_t* index, float* pos4, float* nrm4, long long* stats_out,
+                      const float* bounds, int8_t* near_depth)
+{
+    static const float zero[3] = { 0.0f, 0.0f, 0.0f };
+    long long tot[4] = { 0, 0, 0, 0 };
+    float closest = FLT_MAX;
+    float root[16];
+    memcpy(root, root_columns, 12 * sizeof(float));
+    root[15] = 1.0f;
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* d = dirs3 + 3 * i;
+        long long st[4];
+        float cl;
+        root[12] = 0.0f - origins3[3 * i];
+        root[13] = 0.0f - origins3[3 * i + 1];
+        root[14] = 0.0f - origins3[3 * i + 2];
+        g_near_bound = bounds ? bounds[i] : 0.0f;
+        g_near_depth = -1;
+        int rc = sfo_render_rows(1, 1, zero, d, d, d, root, child, lut, 0, 1,
+                                 pos4 ? pos4 + 4 * i : 0, nrm4 ? nrm4 + 4 * i : 0, minT ? minT + i : 0,
+                                 index ? index + i : 0, 0, st, &cl);
+        g_near_bound = 0.0f;
+        if (rc) return rc;
+        if (near_depth) near_depth[i] = (int8_t)g_near_depth;
+        if (st[0] > tot[0]) tot[0] = st[0];
+        tot[1] += st[1];
+        tot[2] += st[2];
+        tot[3] += st[3];
+        if (cl < closest) closest = cl;
+    }
+    if (stats_out) {
+        memcpy(stats_out, tot, sizeof tot);
+        stats_out[4] = (long long)f2u(closest);
+    }
+    return 0;
+}
+
+int sfo_trace_rays(uint64_t n, const float* origins3, const float* dirs3, const float root_columns[12],
+                   const float child[9 * 16], const uint32_t* lut,
+                   float* minT, uint32_t* index, float* pos4, float* nrm4, long long* stats_out)
+{
+    return trace_rays(n, origins3, dirs3, root_columns, child, lut, minT, index, pos4, nrm4, stats_out, 0, 0);
+}
+
+/* sfo_trace_rays, and per ray near_depth[i] = the depth of the deepest node the ray expands (bounding sphere and LOD
+ * passed, as max_depth counts them) whose bounding-sphere root t is under bounds[i]; -1 where there is none. An
+ * any-hit traversal that stops at a bound must still open these nodes on a ray that nothing stops before its bound:
+ * every sphere of a subtree lies in the node's bounding ball, so nothing before the ball's entry can be told of it. */
+int sfo_trace_rays_near(uint64_t n, const float* origins3, const float* dirs3, const float root_columns[12],
+                        const float child[9 * 16], const uint32_t* lut,
+                        float* minT, uint32_t* index, float* pos4, float* nrm4, long long* stats_out,
+                        const float* bounds, int8_t* near_depth)
+{
+    return trace_rays(n, origins3, dirs3, root_columns, child, lut, minT, index, pos4, nrm4, stats_out, bounds,
+                      near_depth);
 }
 
 /* Sobol::Sample, Sobol.cpp:41-55, for a caller-supplied direction-number table
