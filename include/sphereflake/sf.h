@@ -745,6 +745,91 @@ int sf_light_filter_to(sf_ctx* ctx, const sf_light_filter_params* params, const 
    SF_ESTATE before anything has written the light buffer. */
 int sf_light_filter(sf_ctx* ctx, const sf_light_filter_params* params);
 
+/* --- the light buffer over several frames: reproject, test, blend ---------------------------- */
+/* A camera that moves every frame starts every light trace from nothing. The flake is static, so the last frame's light
+   buffer can be carried into the new view by geometry alone: a pixel's world point is taken back through the LAST
+   view's ray generation to the pixel of the last frame it falls in, that pixel's light is kept where it lies on the same
+   surface (sf_light_filter_to's test), and the new value is blended in. .w of the light buffer, which the traces and the
+   filter only carry, counts the frames blended into a pixel.
+
+   sf_reproject_matrix: the inverse of a view's ray generation. view is origin o, top-left tl, top-right tr, bottom-left
+   bl (12 floats, as sf_set_view takes them). a = tr - tl, b = bl - tl and c = tl - o are formed in binary32, promoted
+   to double and put as the COLUMNS of a 3 x 3 matrix; m is its inverse, row-major, adjugate over determinant in double,
+   every operation rounded on its own (no fused multiply-add), in this order:
+       bc = (b.y c.z - b.z c.y, b.z c.x - b.x c.z, b.x c.y - b.y c.x)
+       ca = (c.y a.z - c.z a.y, c.z a.x - c.x a.z, c.x a.y - c.y a.x)
+       ab = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x)
+       det = ((a.x bc.x) + (a.y bc.y)) + (a.z bc.z)
+       m[0..2] = bc / det     m[3..5] = ca / det     m[6..8] = ab / det
+   and each entry rounded once to binary32. m (a u + b v + c) = (u, v, 1) to rounding: pixel (x, y) of a W x H frame
+   looks along a u + b v + c with u = x / W and v = y / H, no half-pixel offset (sphereflake_amd/dirs.py pinhole), so
+   for a point at D from the origin, q = m D gives the pixel coordinates (W q.x / q.z, H q.y / q.z) and q.z > 0 in front
+   of the viewer. SF_EINVAL for a null pointer, an input that is not finite, or a determinant that is 0 or not finite;
+   m is then not written. No context, no device. sphereflake_amd/lights.py: reproject_matrix. */
+int sf_reproject_matrix(const float view[12], float m[9]);
+
+/* DEFINITION OF THE ACCUMULATION (exact; binary32, round to nearest, every operation rounded on its own, no fused
+   multiply-add). Inputs: the current frame's position image pos4, normal image nrm4 and light buffer `in`, relative to
+   the origin o (origin / use_origin); the history's position image hist_pos4, normal image hist_nrm4 and light buffer
+   hist, relative to o' = hist_origin, with m = hist_m the sf_reproject_matrix of the history's view, used AS GIVEN.
+   For pixel p = (x, y) with P = pos4[p].xyz and N = nrm4[p].xyz:
+     1. P == (0, 0, 0) is a miss of the frame: out[p] = (in[p].xyz, 0).
+     2. w = o + P per component; D = w - o'; q.k = ((m[3k] D.x) + (m[3k+1] D.y)) + (m[3k+2] D.z) for k = 0, 1, 2.
+     3. u = q.x / q.z and v = q.y / q.z, correctly rounded divisions; fx = (u (float)W) + 0.5f, fy = (v (float)H) + 0.5f;
+        X = floorf(fx), Y = floorf(fy). The tap exists iff q.z > 0, 0 <= X < (float)W and 0 <= Y < (float)H. A
+        comparison with a NaN is false.
+     4. With t = (X, Y), P' = hist_pos4[t].xyz, N' = hist_nrm4[t].xyz and h = hist[t], the tap is accepted iff all of:
+        P' != (0, 0, 0); h.w >= 1; nn >= normal_min, with nn = ((N.x N'.x) + (N.y N'.y)) + (N.z N'.z); and
+        (e e) <= (k2 pp), with E = (o' + P') - w per component, e = ((N.x E.x) + (N.y E.y)) + (N.z E.z),
+        pp = ((P.x P.x) + (P.y P.y)) + (P.z P.z) and k2 = plane_max plane_max formed on the host in binary32.
+     5. Accepted: m = min(h.w + 1.0f, (float)max_history); per channel out.c = h.c + ((in.c - h.c) / m), a correctly
+        rounded division; out.w = m. Otherwise out[p] = (in[p].xyz, 1).
+   CONSEQUENCES:
+   - A history whose .w is 0 everywhere (a fresh sf_light_fill) gives (in.xyz, 1) on every surface pixel: the first
+     frame needs no special case.
+   - With the history's view equal to the current one, t = p for every surface pixel (checked on the fixtures; the
+     largest |fx - x - 0.5| seen is 0.001 at 1920 wide and 0.004 at 3840).
+   - K calls from a still view with max_history >= K leave the running mean of the K inputs, rounded in the order of
+     step 5, and .w = K.
+   - Once .w has reached max_history the blend is an exponential average with weight 1 / max_history.
+   - max_history = 1 gives h + (in - h), WHICH IS NOT `in` TO THE LAST BIT.
+   - Only the term accumulated is carried: what is sharp (suns, shadows, shafts) is added per frame, after this call.
+   The thresholds are sf_light_filter_to's and as little tuned. sphereflake_amd/lights.py: light_accumulate_model. */
+typedef struct sf_light_accumulate_params {
+    uint32_t max_history;   /* 1 .. 65535: the most frames a pixel's value stands for (sf_light_accumulate_defaults: 16) */
+    float normal_min;       /* the tap is accepted only if N . N' >= normal_min (defaults: 0.9f); not NaN */
+    float plane_max;        /* ... and its distance from p's tangent plane <= plane_max |P| (defaults: 0.02f); finite
+                               and >= 0 */
+    float origin[3];        /* as sf_sun_params.origin */
+    uint32_t use_origin;    /* as sf_sun_params.use_origin */
+    float hist_origin[3];   /* o': the origin the history's positions are relative to; finite */
+    float hist_m[9];        /* sf_reproject_matrix of the history's view, used as given; finite */
+    uint32_t width, height; /* as sf_sun_params */
+    void* stream;           /* NULL = the context stream */
+} sf_light_accumulate_params;
+/* Zeroed, then max_history 16, normal_min 0.9f, plane_max 0.02f. */
+int sf_light_accumulate_defaults(const sf_ctx* ctx, sf_light_accumulate_params* params);
+/* All seven images are DEVICE images of width * height float4, none NULL. Asynchronous on the stream and ordered with the
+   context's other calls; no statistic is touched. SF_EINVAL for a null image, an `out` that is one of the inputs, a
+   max_history of 0 or above 65535, a NaN normal_min, a plane_max that is negative, infinite or NaN, a hist_m or
+   hist_origin value that is not finite, and sizes as sf_trace_ao_to's; SF_ENOVIEW for use_origin == 0 before
+   sf_set_view. A failing call writes nothing. */
+int sf_light_accumulate_to(sf_ctx* ctx, const sf_light_accumulate_params* params, const float* pos4, const float* nrm4,
+                           const float* in, const float* hist_pos4, const float* hist_nrm4, const float* hist,
+                           float* out);
+/* The context form: the context's G-buffer, light buffer and current view (sf_set_view's) against a history the context
+   owns -- positions, normals, light, the view they belong to and a valid flag; made on first use, freed by sf_destroy.
+   hist_*, origin and use_origin of the params are ignored, and width / height must be 0 or the context's. The result
+   goes to the second buffer sf_light_filter keeps and is copied back, so the pointer sf_light_buffer returns never
+   changes; positions, normals and the result are then copied into the history and the view recorded: four copies, all
+   on the stream. Without a valid history (the first call, or after sf_light_history_reset) every surface pixel takes the
+   "otherwise" branch of step 5. The history is a copy: a later in-place sf_light_filter, or further summing traces,
+   do not reach it. SF_ENOVIEW before sf_set_view; SF_ESTATE before anything has written the light buffer; SF_EINVAL
+   for a view sf_reproject_matrix rejects. */
+int sf_light_accumulate(sf_ctx* ctx, const sf_light_accumulate_params* params);
+/* Forget the history: the next sf_light_accumulate is a first call. The buffers are kept. */
+int sf_light_history_reset(sf_ctx* ctx);
+
 /* Several frames in ONE persistent launch (round 6): frame k is ctxs[k]'s current view, rendered into ctxs[k]'s
    G-buffer and stats exactly as sf_render(ctxs[k], params) would (bit for bit), but one resident grid takes the
    work units of all n frames from one set of tile queues -- a wave whose frame runs dry goes on with the next

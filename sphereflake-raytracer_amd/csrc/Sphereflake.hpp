@@ -399,6 +399,29 @@ public:
         std::lock_guard<FairMutex> lk(m_Mutex);
         Check(sf_light_filter(m_Ctx, &params));
     }
+    // The light buffer over several frames (new; sf_light_accumulate_to, sf.h): `light4` of the current frame blended
+    // into the history's, where the history's pixel lies on the same surface, into `accumulated4`, which is none of
+    // the inputs; params.hist_origin and params.hist_m (sf_reproject_matrix) are the history's view ...
+    void LightAccumulate(const sf_light_accumulate_params& params, const float* positions4, const float* normals4,
+                         const float* light4, const float* histPositions4, const float* histNormals4,
+                         const float* histLight4, float* accumulated4)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_accumulate_to(m_Ctx, &params, positions4, normals4, light4, histPositions4, histNormals4,
+                                     histLight4, accumulated4));
+    }
+    // ... or this object's own frame and light buffer against the history it keeps (sf_light_accumulate), in place
+    void LightAccumulate(const sf_light_accumulate_params& params)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_accumulate(m_Ctx, &params));
+    }
+    // the next LightAccumulate(params) starts a new history
+    void LightHistoryReset()
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_light_history_reset(m_Ctx));
+    }
 
     // the device frame, downloaded into the vectors when it is newer than their contents (Refresh)
     const GBuffer& GetGBuffer() const

@@ -129,6 +129,9 @@ extern "C" __global__ void sf_trace_ao_spin_sum_fixup(FrameArgs a, const float* 
                                                       uint32_t* counters, uint32_t parity);
 extern "C" __global__ void sf_light_filter_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
                                               const float* in, float* out, uint32_t R, float normal_min, float k2);
+extern "C" __global__ void sf_light_accumulate_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
+                                                  const float* in, const float* hpos4, const float* hnrm4,
+                                                  const float* hist, float* out, LightAccum a);
 extern "C" __global__ void sf_light_fill_px(uint32_t n, float r, float g, float b, float* buf);
 extern "C" __global__ void sf_light_image_buffer_px(uint32_t W, uint32_t H, const float* pos4, const float* buf,
                                                     uint8_t* rgba);
@@ -415,6 +418,14 @@ struct sf_ctx {
     uint64_t* shadow_masks = nullptr;  // W x H visibility masks (sf_trace_shadows): lazily allocated
     float* light = nullptr;            // W x H float4 light buffer (sf_light_fill, sf_trace_suns_sum): lazily allocated
     float* light_filtered = nullptr;   // W x H float4: sf_light_filter's target before the copy back, lazily allocated
+    // sf_light_accumulate's history, W x H float4 each, lazily allocated: the last accumulated frame's positions,
+    // normals and light, with the origin they are relative to and that view's sf_reproject_matrix
+    float* hist_pos = nullptr;
+    float* hist_nrm = nullptr;
+    float* hist_light = nullptr;
+    float hist_o[3] = {};
+    float hist_m[9] = {};
+    bool hist_valid = false;
     int centre_exact = -1;             // sfhost::post_centre_exact(W) && (H), cached
 };
 
@@ -532,6 +543,9 @@ static void free_ctx(sf_ctx* c)
     (void)hipFree(c->shadow_masks);
     (void)hipFree(c->light);
     (void)hipFree(c->light_filtered);
+    (void)hipFree(c->hist_pos);
+    (void)hipFree(c->hist_nrm);
+    (void)hipFree(c->hist_light);
     for (int i = 0; i < sf_ctx::kTimed; ++i)
         for (int j = 0; j < 2; ++j)
             if (c->ev[i][j]) (void)hipEventDestroy(c->ev[i][j]);
@@ -1569,19 +1583,27 @@ static int own_buffer_checked(sf_ctx* c, T** buf, size_t bytes, bool accumulate,
     return SF_OK;
 }
 
-// One thread per pixel of the context's frame: kernel(args...) on `stream` (null: the context's), ordered after the
-// context's earlier work.
+// One thread per pixel of an image of `pixels` pixels: kernel(args...) on `stream` (null: the context's), ordered after
+// the context's earlier work.
 template <class Kernel, class... Args>
-static int pixel_pass(sf_ctx* c, void* stream, Kernel kernel, Args... args)
+static int pixel_pass_of(sf_ctx* c, void* stream, size_t pixels, Kernel kernel, Args... args)
 {
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     DevGuard g(c->device);
     if (int rc = ctx_join(c, s)) return rc;
     StreamMark mark_(c, s);
-    const dim3 grid((unsigned)(((size_t)c->W * c->H + 255u) / 256u));
+    const dim3 grid((unsigned)((pixels + 255u) / 256u));
+    if (grid.x == 0u) return SF_OK;
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...);
     SF_HIP(c, hipGetLastError());
     return SF_OK;
+}
+
+// The same for the context's own frame.
+template <class Kernel, class... Args>
+static int pixel_pass(sf_ctx* c, void* stream, Kernel kernel, Args... args)
+{
+    return pixel_pass_of(c, stream, (size_t)c->W * c->H, kernel, args...);
 }
 
 // The lighting passes that shade by a normal: kernel(W, H, pos4, nrm4, mid..., ambient, rgba), the buffers defaulted to
@@ -2277,6 +2299,153 @@ int sf_light_filter(sf_ctx* c, const sf_light_filter_params* p)
         SF_HIP(c, hipMalloc(&c->light_filtered, (size_t)W * H * 16));
     }
     return filter_launch(c, p, W, H, c->pos, c->nrm, c->light, c->light_filtered, c->light);
+}
+
+// The light buffer over several frames (kernel sf_light_accumulate_px). The inverse of a view's ray
+// generation first: host arithmetic in double, every operation rounded on its own (the build's -ffp-contract=off), in
+// sf.h's order; sphereflake_amd/lights.py reproject_matrix forms the same bits.
+int sf_reproject_matrix(const float view[12], float m[9])
+{
+    if (!view || !m) return SF_EINVAL;
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(view[k])) return SF_EINVAL;
+    const float *o = view, *tl = view + 3, *tr = view + 6, *bl = view + 9;
+    double a[3], b[3], cc[3];
+    for (int k = 0; k < 3; ++k) {
+        const float af = tr[k] - tl[k], bf = bl[k] - tl[k], cf = tl[k] - o[k];   // (binary32, then promoted)
+        a[k] = (double)af;
+        b[k] = (double)bf;
+        cc[k] = (double)cf;
+    }
+    const double bc[3] = { b[1] * cc[2] - b[2] * cc[1], b[2] * cc[0] - b[0] * cc[2], b[0] * cc[1] - b[1] * cc[0] };
+    const double ca[3] = { cc[1] * a[2] - cc[2] * a[1], cc[2] * a[0] - cc[0] * a[2], cc[0] * a[1] - cc[1] * a[0] };
+    const double ab[3] = { a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0] };
+    const double det = (a[0] * bc[0] + a[1] * bc[1]) + a[2] * bc[2];
+    if (det == 0.0 || !std::isfinite(det)) return SF_EINVAL;
+    float r[9];
+    for (int k = 0; k < 3; ++k) {
+        r[k] = (float)(bc[k] / det);
+        r[3 + k] = (float)(ca[k] / det);
+        r[6 + k] = (float)(ab[k] / det);
+    }
+    std::memcpy(m, r, sizeof r);
+    return SF_OK;
+}
+
+int sf_light_accumulate_defaults(const sf_ctx* c, sf_light_accumulate_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->max_history = 16u;
+    p->normal_min = 0.9f;
+    p->plane_max = 0.02f;
+    return SF_OK;
+}
+
+// The parameters alone (the history's view: the _to form only); every failure here is SF_EINVAL.
+static int accumulate_check(const sf_ctx* c, const sf_light_accumulate_params* p, bool ctx_form, uint32_t* W,
+                            uint32_t* H)
+{
+    if (p->max_history == 0u || p->max_history > 65535u) return SF_EINVAL;
+    if (p->normal_min != p->normal_min) return SF_EINVAL;
+    if (!(p->plane_max >= 0.0f) || std::isinf(p->plane_max)) return SF_EINVAL;   // (NaN fails the compare)
+    if (!ctx_form) {
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p->hist_origin[k])) return SF_EINVAL;
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(p->hist_m[k])) return SF_EINVAL;
+    }
+    if ((p->width == 0u) != (p->height == 0u)) return SF_EINVAL;
+    *W = p->width ? p->width : c->W;
+    *H = p->height ? p->height : c->H;
+    if (ctx_form && (*W != c->W || *H != c->H)) return SF_EINVAL;   // (the context's buffers, at its size only)
+    if ((uint64_t)*W * *H > 0x7fffffffull) return SF_EINVAL;   // (pixel indices are 32-bit in the kernel)
+    return SF_OK;
+}
+
+// The kernel's argument block: the thresholds of the params, the two origins and the history view's matrix.
+static LightAccum accumulate_args(const sf_light_accumulate_params* p, const float o[3], const float ho[3],
+                                  const float m[9])
+{
+    LightAccum a;
+    for (int k = 0; k < 3; ++k) {
+        a.o[k] = o[k];
+        a.ho[k] = ho[k];
+    }
+    for (int k = 0; k < 9; ++k) a.m[k] = m[k];
+    a.max_history = (float)p->max_history;
+    a.normal_min = p->normal_min;
+    a.k2 = p->plane_max * p->plane_max;   // (one rounding: sf.h's k2)
+    return a;
+}
+
+int sf_light_accumulate_to(sf_ctx* c, const sf_light_accumulate_params* p, const float* pos4, const float* nrm4,
+                           const float* in, const float* hist_pos4, const float* hist_nrm4, const float* hist,
+                           float* out)
+{
+    if (!c || !p || !pos4 || !nrm4 || !in || !hist_pos4 || !hist_nrm4 || !hist || !out) return SF_EINVAL;
+    uint32_t W, H;
+    if (int rc = accumulate_check(c, p, false, &W, &H)) return rc;
+    for (const float* src : { pos4, nrm4, in, hist_pos4, hist_nrm4, hist })
+        if (src == out) return SF_EINVAL;
+    if (!c->has_view && !p->use_origin) return SF_ENOVIEW;
+    const LightAccum a = accumulate_args(p, p->use_origin ? p->origin : c->o, p->hist_origin, p->hist_m);
+    return pixel_pass_of(c, p->stream, (size_t)W * H, sf_light_accumulate_px, W, H, pos4, nrm4, in, hist_pos4,
+                         hist_nrm4, hist, out, a);
+}
+
+// The context form: into the filter's second buffer, copied back, and the frame kept as the next call's history.
+int sf_light_accumulate(sf_ctx* c, const sf_light_accumulate_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    uint32_t W, H;
+    if (int rc = accumulate_check(c, p, true, &W, &H)) return rc;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!c->light) return SF_ESTATE;
+    float view[12], m[9];
+    std::memcpy(view, c->o, 12);
+    std::memcpy(view + 3, c->tl, 12);
+    std::memcpy(view + 6, c->tr, 12);
+    std::memcpy(view + 9, c->bl, 12);
+    if (int rc = sf_reproject_matrix(view, m)) return rc;
+    const size_t bytes = (size_t)W * H * 16;
+    DevGuard g(c->device);
+    for (float** buf : { &c->light_filtered, &c->hist_pos, &c->hist_nrm, &c->hist_light })
+        if (!*buf) SF_HIP(c, hipMalloc(buf, bytes));
+    hipStream_t s = p->stream ? (hipStream_t)p->stream : c->stream;
+    if (!c->hist_valid) {
+        // no history: one whose every pixel is a miss with .w = 0, seen through the current view -- every tap is
+        // rejected at its first test
+        if (int rc = ctx_join(c, s)) return rc;
+        StreamMark mark_(c, s);
+        SF_HIP(c, hipMemsetAsync(c->hist_pos, 0, bytes, s));
+        SF_HIP(c, hipMemsetAsync(c->hist_nrm, 0, bytes, s));
+        SF_HIP(c, hipMemsetAsync(c->hist_light, 0, bytes, s));
+        std::memcpy(c->hist_o, c->o, sizeof c->hist_o);
+        std::memcpy(c->hist_m, m, sizeof c->hist_m);
+    }
+    const LightAccum a = accumulate_args(p, c->o, c->hist_o, c->hist_m);
+    c->hist_valid = false;   // (until the copies below are queued: a failure between leaves no half-made history)
+    if (int rc = pixel_pass_of(c, s, (size_t)W * H, sf_light_accumulate_px, W, H, (const float*)c->pos,
+                               (const float*)c->nrm, (const float*)c->light, (const float*)c->hist_pos,
+                               (const float*)c->hist_nrm, (const float*)c->hist_light, c->light_filtered, a))
+        return rc;
+    StreamMark mark_(c, s);
+    SF_HIP(c, hipMemcpyAsync(c->light, c->light_filtered, bytes, hipMemcpyDeviceToDevice, s));
+    SF_HIP(c, hipMemcpyAsync(c->hist_pos, c->pos, bytes, hipMemcpyDeviceToDevice, s));
+    SF_HIP(c, hipMemcpyAsync(c->hist_nrm, c->nrm, bytes, hipMemcpyDeviceToDevice, s));
+    SF_HIP(c, hipMemcpyAsync(c->hist_light, c->light_filtered, bytes, hipMemcpyDeviceToDevice, s));
+    std::memcpy(c->hist_o, c->o, sizeof c->hist_o);
+    std::memcpy(c->hist_m, m, sizeof c->hist_m);
+    c->hist_valid = true;
+    return SF_OK;
+}
+
+int sf_light_history_reset(sf_ctx* c)
+{
+    if (!c) return SF_EINVAL;
+    c->hist_valid = false;
+    return SF_OK;
 }
 
 int sf_light_buffer(sf_ctx* c, float** buf)

@@ -300,6 +300,16 @@ struct AoSpin {
     uint32_t pad_;
     float cs[SF_AO_SPIN * SF_AO_SPIN][2];   // (c, s) of pixel (x, y): entry (y % size) * size + (x % size)
 };
+// What sf_light_accumulate_px takes beside its images (sf_light_accumulate_to, sf.h): wave-uniform, scalar loads from
+// the argument segment.
+struct LightAccum {
+    float o[3];                       // the origin the current positions are relative to
+    float ho[3];                      // o': the origin the history's positions are relative to
+    float m[9];                       // the history view's sf_reproject_matrix, row-major
+    float max_history;                // (float)max_history, 1 .. 65535: exact
+    float normal_min;
+    float k2;                         // plane_max plane_max, formed on the host
+};
 
 #if defined(__HIPCC__) || defined(__HIP__)
 // The two Lambert terms at a pixel of normal n, shared by the image passes (sf_post.hip) and the summing traces

@@ -579,3 +579,58 @@ extern "C" __global__ void __launch_bounds__(256) sf_light_filter_px(uint32_t W,
     const float n = (float)count;   // (>= 1: the pixel itself)
     reinterpret_cast<float4*>(out)[px] = make_float4(__fdiv_rn(Sx, n), __fdiv_rn(Sy, n), __fdiv_rn(Sz, n), own.w);
 }
+
+// Temporal accumulation of the light buffer (sf_light_accumulate_to, sf.h): one thread per pixel. It
+// loads its own position, normal and light value (three coalesced float4), takes its world point back through the
+// history view's inverse ray generation (LightAccum::m, sf_reproject_matrix) to the one pixel of the history it falls
+// in, and reads that pixel's position, normal and light (one gathered tap of three float4; for a small camera move
+// neighbouring lanes read neighbouring taps). Where the tap lies on the pixel's own surface -- sf_light_filter_px's
+// test, with the history's positions brought to the same origin -- the history is blended with the new value by
+// 1 / min(h.w + 1, max_history), else the new value starts a history of its own (.w = 1). A tap is indexed only
+// after 0 <= X < W and 0 <= Y < H held as float compares (false for a NaN), so no address leaves the images. Every
+// operation rounded on its own, in sf.h's order: the bits are the contract (sphereflake_amd/lights.py
+// light_accumulate_model restates them; tests/test_gpu_light_accumulate.py).
+extern "C" __global__ void __launch_bounds__(256) sf_light_accumulate_px(uint32_t W, uint32_t H, const float* pos4,
+                                                                      const float* nrm4, const float* in,
+                                                                      const float* hpos4, const float* hnrm4,
+                                                                      const float* hist, float* out, LightAccum a)
+{
+    const uint32_t px = blockIdx.x * 256u + threadIdx.x;
+    if (px >= W * H) return;
+    const float4 P = ld4(pos4, px);
+    const float4 N = ld4(nrm4, px);
+    const float4 V = ld4(in, px);
+    if (P.x == 0.0f && P.y == 0.0f && P.z == 0.0f) {   // a miss of the frame
+        reinterpret_cast<float4*>(out)[px] = make_float4(V.x, V.y, V.z, 0.0f);
+        return;
+    }
+    const float wx = __fadd_rn(a.o[0], P.x), wy = __fadd_rn(a.o[1], P.y), wz = __fadd_rn(a.o[2], P.z);
+    const float Dx = __fsub_rn(wx, a.ho[0]), Dy = __fsub_rn(wy, a.ho[1]), Dz = __fsub_rn(wz, a.ho[2]);
+    const float qx = __fadd_rn(__fadd_rn(__fmul_rn(a.m[0], Dx), __fmul_rn(a.m[1], Dy)), __fmul_rn(a.m[2], Dz));
+    const float qy = __fadd_rn(__fadd_rn(__fmul_rn(a.m[3], Dx), __fmul_rn(a.m[4], Dy)), __fmul_rn(a.m[5], Dz));
+    const float qz = __fadd_rn(__fadd_rn(__fmul_rn(a.m[6], Dx), __fmul_rn(a.m[7], Dy)), __fmul_rn(a.m[8], Dz));
+    const float fW = (float)W, fH = (float)H;
+    const float X = floorf(__fadd_rn(__fmul_rn(__fdiv_rn(qx, qz), fW), 0.5f));
+    const float Y = floorf(__fadd_rn(__fmul_rn(__fdiv_rn(qy, qz), fH), 0.5f));
+    float4 r = make_float4(V.x, V.y, V.z, 1.0f);   // no history kept: the new value alone
+    if (qz > 0.0f && X >= 0.0f && X < fW && Y >= 0.0f && Y < fH) {   // (a NaN fails a compare: no tap)
+        const uint32_t t = (uint32_t)Y * W + (uint32_t)X;
+        const float4 Pq = ld4(hpos4, t);
+        const float4 Nq = ld4(hnrm4, t);
+        const float4 h = ld4(hist, t);
+        const float nn = __fadd_rn(__fadd_rn(__fmul_rn(N.x, Nq.x), __fmul_rn(N.y, Nq.y)), __fmul_rn(N.z, Nq.z));
+        const float Ex = __fsub_rn(__fadd_rn(a.ho[0], Pq.x), wx), Ey = __fsub_rn(__fadd_rn(a.ho[1], Pq.y), wy),
+                    Ez = __fsub_rn(__fadd_rn(a.ho[2], Pq.z), wz);
+        const float e = __fadd_rn(__fadd_rn(__fmul_rn(N.x, Ex), __fmul_rn(N.y, Ey)), __fmul_rn(N.z, Ez));
+        const float pp = __fadd_rn(__fadd_rn(__fmul_rn(P.x, P.x), __fmul_rn(P.y, P.y)), __fmul_rn(P.z, P.z));
+        const bool surface = !(Pq.x == 0.0f && Pq.y == 0.0f && Pq.z == 0.0f);
+        if (surface && h.w >= 1.0f && nn >= a.normal_min && __fmul_rn(e, e) <= __fmul_rn(a.k2, pp)) {
+            const float m = fminf(__fadd_rn(h.w, 1.0f), a.max_history);
+            r.x = __fadd_rn(h.x, __fdiv_rn(__fsub_rn(V.x, h.x), m));
+            r.y = __fadd_rn(h.y, __fdiv_rn(__fsub_rn(V.y, h.y), m));
+            r.z = __fadd_rn(h.z, __fdiv_rn(__fsub_rn(V.z, h.z), m));
+            r.w = m;
+        }
+    }
+    reinterpret_cast<float4*>(out)[px] = r;
+}

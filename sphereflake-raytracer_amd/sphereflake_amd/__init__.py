@@ -144,6 +144,13 @@ class sf_light_filter_params(ctypes.Structure):
                 ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
 
 
+class sf_light_accumulate_params(ctypes.Structure):
+    _fields_ = [("max_history", ctypes.c_uint32), ("normal_min", ctypes.c_float), ("plane_max", ctypes.c_float),
+                ("origin", ctypes.c_float * 3), ("use_origin", ctypes.c_uint32), ("hist_origin", ctypes.c_float * 3),
+                ("hist_m", ctypes.c_float * 9), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("stream", ctypes.c_void_p)]
+
+
 class sf_stats(ctypes.Structure):
     _fields_ = [("max_depth", ctypes.c_int32), ("closest", ctypes.c_float),
                 ("rays", ctypes.c_int64), ("overflow_tiles", ctypes.c_int64)]
@@ -240,6 +247,11 @@ SIGNATURES = {
     "sf_light_filter_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_filter_params), ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_light_filter": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_filter_params)]),
+    "sf_reproject_matrix": (ctypes.c_int, [_F, _F]),
+    "sf_light_accumulate_defaults": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_accumulate_params)]),
+    "sf_light_accumulate_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_accumulate_params)] + [ctypes.c_void_p] * 7),
+    "sf_light_accumulate": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_accumulate_params)]),
+    "sf_light_history_reset": (ctypes.c_int, [_CTX]),
     "sf_light_fill": (ctypes.c_int, [_CTX, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]),
     "sf_light_buffer": (ctypes.c_int, [_CTX, ctypes.POINTER(ctypes.c_void_p)]),
     "sf_download_light": (ctypes.c_int, [_CTX, ctypes.c_void_p]),
@@ -445,6 +457,16 @@ def root_transform(origin) -> np.ndarray:
     o = _f32(origin, 3)
     out = np.zeros(16, np.float32)
     _check(lib().sf_root_transform(_fp(o), _fp(out)), "sf_root_transform")
+    return out
+
+
+def reproject_matrix(view) -> np.ndarray:
+    """sf_reproject_matrix: the inverse [9] (row-major 3 x 3) of the ray generation of the view (origin, top-left,
+    top-right, bottom-left), 12 floats. sphereflake_amd.lights.reproject_matrix states the same arithmetic in numpy."""
+    v = _f32(np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in view])
+             if isinstance(view, (tuple, list)) else view, 12)
+    out = np.zeros(9, np.float32)
+    _check(lib().sf_reproject_matrix(_fp(v), _fp(out)), "sf_reproject_matrix")
     return out
 
 
@@ -1551,6 +1573,109 @@ class Sphereflake:
         return self._trace_images(lambda W, H: self.light_filter_params(size, normal_min, plane_max, W, H, stream),
                                   "sf_light_filter", pos, out, np.float32, (4,), normals=True, nrm=nrm, buf=buf,
                                   has_buf=True)
+
+    # the light buffer over several frames (sf_light_accumulate_to / sf_light_accumulate / sf_light_history_reset) ------
+    def light_accumulate_params(self, max_history=16, normal_min=None, plane_max=None, origin=None, hist_view=None,
+                                width=0, height=0, stream=None):
+        """sf_light_accumulate_defaults, overridden; normal_min and plane_max None keep the library's defaults
+        (0.9, 0.02). hist_view: the history's view (origin, top-left, top-right, bottom-left), 12 floats -- its origin
+        becomes hist_origin and its reproject_matrix() hist_m; None leaves both zero (the context form ignores them)."""
+        p = sf_light_accumulate_params()
+        _check(lib().sf_light_accumulate_defaults(self._ctx, ctypes.byref(p)), "sf_light_accumulate_defaults")
+        p.max_history = int(max_history)
+        if normal_min is not None:
+            p.normal_min = float(normal_min)
+        if plane_max is not None:
+            p.plane_max = float(plane_max)
+        if origin is not None:
+            p.origin[:] = [float(x) for x in _f32(origin, 3)]
+            p.use_origin = 1
+        if hist_view is not None:
+            v = _f32(np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in hist_view]), 12)
+            p.hist_origin[:] = [float(x) for x in v[:3]]
+            p.hist_m[:] = [float(x) for x in reproject_matrix(v)]
+        p.width, p.height, p.stream = int(width), int(height), stream
+        return p
+
+    def light_accumulate(self, max_history=16, normal_min=0.9, plane_max=0.02, pos=None, nrm=None, buf=None,
+                         hist_pos=None, hist_nrm=None, hist=None, hist_view=None, out=None, origin=None, stream=None):
+        """Blend a light buffer into the last frame's, reprojected (sf_light_accumulate_to; sf.h,
+        sphereflake_amd.lights.light_accumulate_model): each surface pixel's world point is taken back through
+        `hist_view` to the pixel of the history it falls in; where that pixel lies on the same surface -- normals within
+        normal_min, positions within plane_max |P| of the tangent plane, a history count .w >= 1 -- the result is
+        h + (new - h) / min(h.w + 1, max_history) with that as its .w, else the new value with .w = 1. A miss of the
+        frame keeps the new value with .w = 0.
+          - no images: the context form (sf_light_accumulate). The context's G-buffer, light buffer and current view
+            against the history the context keeps, in place (the address light_buffer() returns does not change); the
+            frame then becomes the history of the next call -- asynchronous;
+          - pos, nrm, buf, hist_pos, hist_nrm, hist numpy arrays [H, W, 4]: uploaded, accumulated, and a numpy
+            [H, W, 4] float32 returned -- synchronous;
+          - the six torch CUDA tensors [H, W, 4] (contiguous float32), (device address, width, height) tuples or, after
+            `pos`, plain device addresses: zero copy, asynchronous; `out` a torch CUDA tensor [H, W, 4] or a device
+            address, none of the inputs.
+        hist_view is the history's (origin, top-left, top-right, bottom-left); `origin` is what pos is relative to (None:
+        the context's view origin)."""
+        images = (pos, nrm, buf, hist_pos, hist_nrm, hist)
+        names = ("pos", "nrm", "buf", "hist_pos", "hist_nrm", "hist")
+        if all(a is None for a in images):
+            if out is not None or hist_view is not None:
+                raise ValueError("the context form takes no images, no hist_view and no out")
+            p = self.light_accumulate_params(max_history, normal_min, plane_max, None, None, 0, 0, stream)
+            with self._mutex:
+                _check(lib().sf_light_accumulate(self._ctx, ctypes.byref(p)), "sf_light_accumulate", self._ctx)
+            return None
+        if any(a is None for a in images) or hist_view is None:
+            raise ValueError("pos, nrm, buf, hist_pos, hist_nrm, hist and hist_view go together")
+        vp = lambda x: ctypes.c_void_p(x) if x else None
+        if isinstance(pos, np.ndarray):
+            if not all(isinstance(a, np.ndarray) for a in images):
+                raise ValueError("a host position image needs host images throughout")
+            if out is not None:
+                raise ValueError("host images return a host array: out must be None")
+            host = [np.ascontiguousarray(a, np.float32) for a in images]
+            if host[0].ndim != 3 or host[0].shape[-1] != 4 or any(a.shape != host[0].shape for a in host):
+                raise ValueError("the six images must be [H, W, 4] of one size")
+            H, W = host[0].shape[:2]
+            p = self.light_accumulate_params(max_history, normal_min, plane_max, origin, hist_view, W, H, stream)
+            res = np.empty((H, W, 4), np.float32)
+            if H * W == 0:
+                return res
+            offs = [k * res.nbytes for k in range(7)]   # the images, then the result
+            with _DeviceScratch(self.device, 7 * res.nbytes) as d:
+                for a, off in zip(host, offs):
+                    d.upload(off, a)
+                with self._mutex:
+                    _check(lib().sf_light_accumulate_to(self._ctx, ctypes.byref(p), *[vp(d.ptr + off) for off in offs]),
+                           "sf_light_accumulate_to", self._ctx)
+                    # (the scratch is freed on leaving: the pass that reads and writes it must be done)
+                    _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
+                d.download(offs[-1], res)
+            return res
+        if any(isinstance(a, np.ndarray) for a in images):
+            raise ValueError("a device position image needs device images throughout")
+        pptr, W, H = self._image4(pos, "pos")
+        ptrs = [pptr]
+        for a, what in zip(images[1:], names[1:]):
+            if hasattr(a, "data_ptr") or isinstance(a, (tuple, list)):
+                ptr, w, h = self._image4(a, what)
+                if (w, h) != (W, H):
+                    raise ValueError(f"{what} and pos must have the same size")
+                ptrs.append(ptr)
+            else:
+                ptrs.append(int(a))
+        optr = 0 if out is None else out.data_ptr() if hasattr(out, "data_ptr") else int(out)
+        if not optr:
+            raise ValueError("device images need an `out` buffer")
+        p = self.light_accumulate_params(max_history, normal_min, plane_max, origin, hist_view, W, H, stream)
+        with self._mutex:
+            _check(lib().sf_light_accumulate_to(self._ctx, ctypes.byref(p), *[vp(x) for x in ptrs], vp(optr)),
+                   "sf_light_accumulate_to", self._ctx)
+        return None
+
+    def light_history_reset(self):
+        """Forget the context form's history: the next light_accumulate() is a first call (sf_light_history_reset)."""
+        with self._mutex:
+            _check(lib().sf_light_history_reset(self._ctx), "sf_light_history_reset", self._ctx)
 
     def Synchronize(self):
         _check(lib().sf_synchronize(self._ctx), "sf_synchronize", self._ctx)
