@@ -745,6 +745,88 @@ int sf_light_filter_to(sf_ctx* ctx, const sf_light_filter_params* params, const 
    SF_ESTATE before anything has written the light buffer. */
 int sf_light_filter(sf_ctx* ctx, const sf_light_filter_params* params);
 
+/* --- sky reflections: a lobe of rays about each pixel's mirror direction ----------------------- */
+/* Every term above is diffuse: nothing depends on where the viewer stands. Here the axis the samples are turned about
+   is the MIRROR DIRECTION of the pixel's view vector about its normal, formed on the device, and the summing call
+   weighs each open ray by the sky's colour IN THAT RAY'S OWN WORLD DIRECTION. The rays are posed as AO's are -- from a
+   point tau up the direction, down to the surface point, as an any-hit query -- so no ray starts on the flake, and
+   the answer is "is this direction open to the sky?": a sky reflection with self-occlusion.
+   DEFINITION OF THE MASK (exact; binary32, round to nearest, every operation rounded on its own, no fused
+   multiply-add). Inputs: sf_trace_ao_to's (position image, normal image, origin o, n <= SF_AO_SAMPLES_MAX local-frame
+   samples h_i used as given, tau, bias, the shadow LOD constant, optionally sf_trace_ao_spin_to's table) and an eye.
+   For pixel p with P = pos4[p].xyz and N = nrm4[p].xyz (as given, not normalised):
+     1. P == (0, 0, 0) is a miss of the frame: no ray is traced and every bit i < n is set.
+     2. The view vector V: with use_eye == 0, V = P (the positions are relative to the viewer); otherwise
+        V = (o + P) - eye per component. THESE ARE DIFFERENT BITS, even for eye == o: (o + P) - o is not P in binary32
+        (on the 80 x 45 fixture it changes 3022 of 3600 axes in their last bits).
+     3. The mirror axis A: nv = ((N.x V.x) + (N.y V.y)) + (N.z V.z); k = nv + nv; R.c = V.c - (k N.c);
+        rr = ((R.x R.x) + (R.y R.y)) + (R.z R.z); len = sqrtf(rr), correctly rounded; A.c = R.c / len, a correctly
+        rounded division.
+     4. Steps 2-5 of sf_trace_ao_to's definition follow with A in place of N: the frame of Duff et al. about A; where a
+        spin is given, the turn of sf_trace_ao_spin_to by the pixel's table entry; s_i.c = ((T.c h_i.x) + (B.c h_i.y))
+        + (A.c h_i.z); f_i = s_i tau; F, d and bound as sf_trace_ao_to forms them; bit i is 0 iff min_t < bound; a d or
+        an F that is not finite sets the bit without a ray -- a NaN normal and a zero-length R are such cases; bits
+        n..63 are 0.
+   DEFINITION OF THE SUM. Steps 1-4 of the DEFINITION OF THE SUM of sf_trace_suns_sum_to hold for the base, the misses
+   of the frame, .w and the order. The term of entry i takes the sky's colour along s_i:
+       u_i = ((s_i.x up.x) + (s_i.y up.y)) + (s_i.z up.z)
+       t_i = min(max(u_i, 0), 1), and +0 where u_i is -0 or NaN
+       E_i.c = horizon.c + ((zenith.c - horizon.c) t_i)
+       S.c = S.c + (colours[i].c (open_i ? E_i.c : 0.0f))
+   `up` is used as given, not normalised. open_i is bit i of the mask defined above. A closed direction adds
+   colours[i].c 0.0f: the flake's own reflection is black.
+   CONSEQUENCES, all bit for bit:
+   - The mask equals sf_trace_ao_spin_to's mask (sf_trace_ao_to's without a spin) on a normal image that holds A
+     (sphereflake_amd/lights.py: mirror_axes makes that image on the host).
+   - With zenith == horizon == (1, 1, 1) the sum equals sf_trace_ao_spin_sum_to's (sf_trace_ao_sum_to's) on that
+     image: E is exactly 1, and a closed entry adds colours 0, as there.
+   - h = (0, 0, 1) gives s = A exactly, with or without a spin.
+   - A call equals its split into an overwriting call with the first k entries and an accumulating call with the
+     rest, for every k.
+   - A flagged tile stores nothing in its first pass.
+   - A crop of the images whose top-left corner is at multiples of the spin's `size` gives the crop of the whole's
+     result.
+   - tau >= 4 keeps every ray's origin outside the flake's radius-2 ball for |h| = 1 (|A| is 1 to rounding).
+   WHAT THIS IS NOT: the flake does not reflect itself, there is no Fresnel term, and sf_light_image_buffer still
+   multiplies the image by the buffer: c (diffuse + specular).
+   sphereflake_amd/lights.py states all of it on the host (mirror_axes, mirror_model, sky_gradient, mirror_sum_model,
+   lobe_samples). */
+typedef struct sf_mirror_params {
+    const float* samples;     /* as sf_ao_params.samples: the lobe about the mirror axis (z along it) */
+    const float* colours;     /* as sf_ao_params.colours; the summing call only */
+    uint32_t n;               /* 1 .. SF_AO_SAMPLES_MAX */
+    uint32_t accumulate;      /* the summing call only: 0 = overwrite the output, 1 = add to what it holds */
+    float distance;           /* tau, finite and > 0 (sf_mirror_defaults: 4) */
+    float bias;               /* as sf_sun_params.bias */
+    float origin[3];          /* as sf_sun_params.origin */
+    uint32_t use_origin;      /* as sf_sun_params.use_origin */
+    uint32_t width, height;   /* as sf_sun_params */
+    uint32_t max_depth;       /* 0 = 12, as sf_sun_params.max_depth */
+    void* stream;             /* NULL = the context stream */
+    float eye[3];             /* the viewer, world space; read where use_eye != 0, then finite */
+    uint32_t use_eye;         /* 0 = the view vector is P itself; 1 = (o + P) - eye */
+    float zenith[3];          /* the sky's colour where s . up >= 1; each finite and >= 0; the summing call only */
+    float horizon[3];         /* ... and where s . up <= 0 */
+    float up[3];              /* used as given, not normalised; finite; the summing call only */
+} sf_mirror_params;
+
+/* Zeroed (n = 0, samples NULL: the caller sets both; overwriting; use_eye 0), distance 4, the default bias of
+   sf_shadow_defaults, zenith = horizon = (1, 1, 1), up = (0, 0, 1). */
+int sf_mirror_defaults(const sf_ctx* ctx, sf_mirror_params* params);
+/* The four calls. spin NULL means unspun; otherwise as sf_trace_ao_spin_to's. The buffers (NULL pos4 / nrm4 select the
+   context's G-buffer; the context's mask buffer and light buffer), the stream ordering, the statistics (none touched)
+   and the re-trace accounting (a flagged tile is re-traced once for all samples and counts in overflow_tiles) are the
+   spun AO calls'. Errors: everything sf_trace_ao_spin_to / sf_trace_ao_spin_sum_to rejects, with a NULL spin allowed;
+   SF_EINVAL as well for an eye component that is not finite under use_eye, and, in the summing calls, a zenith or
+   horizon component that is negative, infinite or NaN or an up component that is not finite. A failing call writes
+   nothing. */
+int sf_trace_mirror_to(sf_ctx* ctx, const sf_mirror_params* params, const sf_ao_spin* spin, const float* pos4,
+                       const float* nrm4, uint64_t* mask);
+int sf_trace_mirror(sf_ctx* ctx, const sf_mirror_params* params, const sf_ao_spin* spin);
+int sf_trace_mirror_sum_to(sf_ctx* ctx, const sf_mirror_params* params, const sf_ao_spin* spin, const float* pos4,
+                           const float* nrm4, float* out);
+int sf_trace_mirror_sum(sf_ctx* ctx, const sf_mirror_params* params, const sf_ao_spin* spin);
+
 /* --- the light buffer over several frames: reproject, test, blend ---------------------------- */
 /* A camera that moves every frame starts every light trace from nothing. The flake is static, so the last frame's light
    buffer can be carried into the new view by geometry alone: a pixel's world point is taken back through the LAST

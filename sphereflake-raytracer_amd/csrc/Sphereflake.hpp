@@ -385,6 +385,31 @@ public:
         std::lock_guard<FairMutex> lk(m_Mutex);
         Check(sf_trace_ao_spin_sum(m_Ctx, &params, &spin));
     }
+    // Sky reflections (new; sf_trace_mirror_to and its siblings, sf.h): the samples turned about each pixel's mirror
+    // direction instead of its normal, into a mask per pixel, or ADDED into a light buffer with the sky's colour along
+    // each open ray; a null spin is the unspun call, null image pointers select this object's own frame and buffers.
+    void TraceMirror(const sf_mirror_params& params, const sf_ao_spin* spin, const float* positions4,
+                     const float* normals4, uint64_t* masks)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_mirror_to(m_Ctx, &params, spin, positions4, normals4, masks));
+    }
+    void TraceMirror(const sf_mirror_params& params, const sf_ao_spin* spin = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_mirror(m_Ctx, &params, spin));
+    }
+    void TraceMirrorSum(const sf_mirror_params& params, const sf_ao_spin* spin, const float* positions4,
+                        const float* normals4, float* light4)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_mirror_sum_to(m_Ctx, &params, spin, positions4, normals4, light4));
+    }
+    void TraceMirrorSum(const sf_mirror_params& params, const sf_ao_spin* spin = nullptr)
+    {
+        std::lock_guard<FairMutex> lk(m_Mutex);
+        Check(sf_trace_mirror_sum(m_Ctx, &params, spin));
+    }
     // The edge-aware box filter of a light buffer (new; sf_light_filter_to, sf.h) into `filtered4`, which is not
     // `light4`; null input pointers select this object's own frame and light buffer ...
     void LightFilter(const sf_light_filter_params& params, const float* positions4, const float* normals4,

@@ -127,6 +127,18 @@ extern "C" __global__ void sf_trace_ao_spin_sum_wave(FrameArgs a, const float* p
 extern "C" __global__ void sf_trace_ao_spin_sum_fixup(FrameArgs a, const float* pos4, const float* nrm4, AoSum ao,
                                                       AoSpin sp, float* out, const uint32_t* overflow_list,
                                                       uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_trace_mirror_wave(FrameArgs a, const float* pos4, const float* nrm4, MirrorArgs mr,
+                                                AoSpin sp, uint64_t* mask, uint32_t groups, uint32_t* overflow_list,
+                                                uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_mirror_fixup(FrameArgs a, const float* pos4, const float* nrm4, MirrorArgs mr,
+                                                 AoSpin sp, uint64_t* mask, const uint32_t* overflow_list,
+                                                 uint32_t* counters, uint32_t parity);
+extern "C" __global__ void sf_trace_mirror_sum_wave(FrameArgs a, const float* pos4, const float* nrm4, MirrorSum mr,
+                                                    AoSpin sp, float* out, uint32_t groups, uint32_t* overflow_list,
+                                                    uint32_t* overflow_count);
+extern "C" __global__ void sf_trace_mirror_sum_fixup(FrameArgs a, const float* pos4, const float* nrm4, MirrorSum mr,
+                                                     AoSpin sp, float* out, const uint32_t* overflow_list,
+                                                     uint32_t* counters, uint32_t parity);
 extern "C" __global__ void sf_light_filter_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
                                               const float* in, float* out, uint32_t R, float normal_min, float k2);
 extern "C" __global__ void sf_light_accumulate_px(uint32_t W, uint32_t H, const float* pos4, const float* nrm4,
@@ -2229,6 +2241,140 @@ int sf_trace_ao_spin_sum(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spi
         }))
         return rc;
     return sf_trace_ao_spin_sum_to(c, p, spin, nullptr, nullptr, nullptr);
+}
+
+// Sky reflections (kernels sf_trace_mirror_wave / _fixup, sf_trace_mirror_sum_wave / _fixup): the
+// spun AO calls' checks, buffers and launches with the eye and the sky's gradient beside the samples. One kernel set:
+// a null spin travels as the 1 x 1 table {(1, 0)}, which is the unspun definition bit for bit (sf.h).
+static_assert(sizeof(FrameArgs) + sizeof(MirrorArgs) + sizeof(AoSpin) + 64 <= 4096, "kernel argument segment");
+static_assert(sizeof(FrameArgs) + sizeof(MirrorSum) + sizeof(AoSpin) + 64 <= 4096, "kernel argument segment");
+
+int sf_mirror_defaults(const sf_ctx* c, sf_mirror_params* p)
+{
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->distance = 4.0f;
+    p->bias = kShadowBias;
+    for (int k = 0; k < 3; ++k) p->zenith[k] = p->horizon[k] = 1.0f;
+    p->up[2] = 1.0f;
+    return SF_OK;
+}
+
+// the fields the mirror parameters share with AO's, for ao_check and ao_args
+static sf_ao_params mirror_ao_params(const sf_mirror_params* p)
+{
+    sf_ao_params q;
+    std::memset(&q, 0, sizeof q);
+    q.samples = p->samples;
+    q.colours = p->colours;
+    q.n = p->n;
+    q.accumulate = p->accumulate;
+    q.distance = p->distance;
+    q.bias = p->bias;
+    for (int k = 0; k < 3; ++k) q.origin[k] = p->origin[k];
+    q.use_origin = p->use_origin;
+    q.width = p->width;
+    q.height = p->height;
+    q.max_depth = p->max_depth;
+    q.stream = p->stream;
+    return q;
+}
+
+// Everything the calls check, in one place: AO's list, the eye, the gradient (the summing calls only), the table (a
+// null spin: the identity), which is copied into the argument block. Every failure of the mirror's own is SF_EINVAL.
+static int mirror_check(const sf_ctx* c, const sf_mirror_params* p, const sf_ao_spin* spin, bool sum,
+                        const float* pos4, bool ctx_buffer, ShadowImage* im, AoSpin* sp)
+{
+    const sf_ao_params q = mirror_ao_params(p);
+    if (int rc = ao_check(c, &q, sum, pos4, ctx_buffer, im)) return rc;
+    if (p->use_eye)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p->eye[k])) return SF_EINVAL;
+    if (sum)
+        for (int k = 0; k < 3; ++k)
+            if (!light_component(p->zenith[k]) || !light_component(p->horizon[k]) || !std::isfinite(p->up[k]))
+                return SF_EINVAL;
+    if (spin) return spin_args(spin, sp);
+    std::memset(sp, 0, sizeof *sp);
+    sp->size = 1u;
+    sp->cs[0][0] = 1.0f;
+    return SF_OK;
+}
+
+extern "C++" {
+// what MirrorArgs and MirrorSum share, from the parameters
+template <class MR>
+static void mirror_args(const sf_ctx* c, const sf_mirror_params* p, MR* mr)
+{
+    const sf_ao_params q = mirror_ao_params(p);
+    ao_args(c, &q, mr);
+    mr->use_eye = p->use_eye ? 1u : 0u;
+    for (int k = 0; k < 3; ++k) mr->eye[k] = p->use_eye ? p->eye[k] : 0.0f;
+}
+}  // extern "C++"
+
+int sf_trace_mirror_to(sf_ctx* c, const sf_mirror_params* p, const sf_ao_spin* spin, const float* pos4,
+                       const float* nrm4, uint64_t* mask)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    if (!mask) return SF_EINVAL;
+    ShadowImage im;
+    AoSpin sp;
+    if (int rc = mirror_check(c, p, spin, false, pos4, !nrm4, &im, &sp)) return rc;
+    MirrorArgs mr;
+    mirror_args(c, p, &mr);
+    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
+    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_mirror_wave, sf_trace_mirror_fixup, nrm, mr, sp,
+                              mask);
+}
+
+int sf_trace_mirror(sf_ctx* c, const sf_mirror_params* p, const sf_ao_spin* spin)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    ShadowImage im;
+    AoSpin sp;
+    if (int rc = own_buffer_checked(c, &c->shadow_masks, 8, false,
+                                    [&] { return mirror_check(c, p, spin, false, nullptr, true, &im, &sp); }))
+        return rc;
+    return sf_trace_mirror_to(c, p, spin, nullptr, nullptr, c->shadow_masks);
+}
+
+int sf_trace_mirror_sum_to(sf_ctx* c, const sf_mirror_params* p, const sf_ao_spin* spin, const float* pos4,
+                           const float* nrm4, float* out)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    ShadowImage im;
+    AoSpin sp;
+    if (int rc = mirror_check(c, p, spin, true, pos4, !nrm4 || !out, &im, &sp)) return rc;
+    if (!out && !c->light) return SF_ESTATE;
+    MirrorSum mr;
+    mirror_args(c, p, &mr);
+    mr.accumulate = p->accumulate ? 1u : 0u;
+    for (int k = 0; k < 3; ++k) {
+        mr.up[k] = p->up[k];
+        mr.horizon[k] = p->horizon[k];
+        mr.span[k] = p->zenith[k] - p->horizon[k];   // (one rounding: zenith.c - horizon.c of the definition)
+    }
+    entry_values(3u * p->n, p->colours, 1.0f / (float)p->n, &mr.c[0][0]);
+    float* const dst = out ? out : c->light;
+    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
+    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_mirror_sum_wave, sf_trace_mirror_sum_fixup, nrm,
+                              mr, sp, dst);
+}
+
+int sf_trace_mirror_sum(sf_ctx* c, const sf_mirror_params* p, const sf_ao_spin* spin)
+{
+    if (!c || !p) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    ShadowImage im;
+    AoSpin sp;
+    if (int rc = own_buffer_checked(c, &c->light, 16, p->accumulate != 0u,
+                                    [&] { return mirror_check(c, p, spin, true, nullptr, true, &im, &sp); }))
+        return rc;
+    return sf_trace_mirror_sum_to(c, p, spin, nullptr, nullptr, nullptr);
 }
 
 // The edge-aware box filter of the light buffer (kernel sf_light_filter_px).

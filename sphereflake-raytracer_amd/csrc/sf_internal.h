@@ -300,6 +300,32 @@ struct AoSpin {
     uint32_t pad_;
     float cs[SF_AO_SPIN * SF_AO_SPIN][2];   // (c, s) of pixel (x, y): entry (y % size) * size + (x % size)
 };
+// Sky reflections (sf_trace_mirror_to, sf_trace_mirror_sum_to): AoArgs / AoSum with the eye of the view vector, and for
+// the sum the sky's gradient (808 B / 1616 B; the spin table travels beside them: sf_capi.hip asserts the 4 KB limit).
+// All of it is wave-uniform: scalar loads.
+struct MirrorArgs {
+    float o[3];
+    float keep;
+    float tau;
+    uint32_t n;
+    float eye[3];                     // the viewer (world), read where use_eye != 0
+    uint32_t use_eye;                 // 0: V = P, else V = (o + P) - eye
+    float h[SF_AO_SAMPLES][3];
+};
+struct MirrorSum {
+    float o[3];
+    float keep;
+    float tau;
+    uint32_t n;
+    float eye[3];
+    uint32_t use_eye;
+    uint32_t accumulate;              // 0: the base is 0, 1: the base is what the output holds
+    float up[3];                      // as given, not normalised
+    float horizon[3];
+    float span[3];                    // zenith - horizon per component, formed on the host (one rounding)
+    float h[SF_AO_SAMPLES][3];
+    float c[SF_AO_SAMPLES][3];        // the samples' colours
+};
 // What sf_light_accumulate_px takes beside its images (sf_light_accumulate_to, sf.h): wave-uniform, scalar loads from
 // the argument segment.
 struct LightAccum {

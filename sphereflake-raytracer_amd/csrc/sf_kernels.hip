@@ -5093,6 +5093,207 @@ extern "C" __global__ __launch_bounds__(64) void sf_trace_ao_spin_sum_fixup(Fram
 }
 
 // ------------------------------------------------------------------------------------------
+// Sky reflections: a lobe of rays about each pixel's mirror direction (sf_trace_mirror_to / sf_trace_mirror_sum_to,
+// DESIGN.md §6.21). The spun AO kernels with another axis: the lane forms the mirror direction A of its view vector
+// about its normal (sf.h's steps 2 and 3: one square root and three divisions per pixel), then the frame about A and
+// the turn by its table entry, once per tile; the sample loop is trace_ao_entries' with A where N was. Across the
+// traversals the lane keeps w, T, B and A -- what the spun AO lane keeps with N -- and N is dead once A is formed. The
+// unspun call travels as the 1 x 1 table {(1, 0)}: bit-identical (sf.h), one kernel set. The mask ending is the
+// shared one; the summing ending is new: entry i's factor is the sky's RGB colour in the direction s_i of the lane's
+// own ray, formed from the SAME T, B and A the pose keeps, through the same device function (mirror_dir) -- the same
+// bits. (Forming the frame a second time from P and N for the ending was tried first: the compiler then kept P, N and
+// both frames live, 63 / 71 VGPRs and occupancy 7 in the fixup kernel; kept once it is 51 / 60 and occupancy 8.)
+// The pose is a function of its own, as trace_ao_spin_entries is (§6.18).
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// What a lane keeps across the traversals: w = o + P and the turned frame (T, B, A) about its mirror axis.
+struct MirrorPose {
+    float w[3], T[3], B[3];
+    float4 A;
+};
+
+// The pose of sf.h's steps 2-4: the mirror axis, ao_frame about it, the turn. MR is MirrorArgs or MirrorSum.
+template <class MR>
+__device__ __forceinline__ MirrorPose mirror_pose(const GroupLane& g, const float4 P, const float4 N, const MR& mr,
+                                                  const AoSpin& sp)
+{
+    MirrorPose m;
+    m.w[0] = __fadd_rn(mr.o[0], P.x);
+    m.w[1] = __fadd_rn(mr.o[1], P.y);
+    m.w[2] = __fadd_rn(mr.o[2], P.z);
+    // V: the position as given (relative to the viewer), or the world point less the eye -- other roundings
+    const float vx = mr.use_eye ? __fsub_rn(m.w[0], mr.eye[0]) : P.x;   // (uniform)
+    const float vy = mr.use_eye ? __fsub_rn(m.w[1], mr.eye[1]) : P.y;
+    const float vz = mr.use_eye ? __fsub_rn(m.w[2], mr.eye[2]) : P.z;
+    const float nv = __fadd_rn(__fadd_rn(__fmul_rn(N.x, vx), __fmul_rn(N.y, vy)), __fmul_rn(N.z, vz));
+    const float k = __fadd_rn(nv, nv);
+    const float rx = __fsub_rn(vx, __fmul_rn(k, N.x));
+    const float ry = __fsub_rn(vy, __fmul_rn(k, N.y));
+    const float rz = __fsub_rn(vz, __fmul_rn(k, N.z));
+    // (__builtin_sqrtf: the correctly rounded square root, as in shadow_ray)
+    const float len = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(rx, rx), __fmul_rn(ry, ry)), __fmul_rn(rz, rz)));
+    m.A = make_float4(__fdiv_rn(rx, len), __fdiv_rn(ry, len), __fdiv_rn(rz, len), 0.0f);
+    float T0[3], B0[3];
+    ao_frame(m.A, T0, B0);
+    const uint32_t e = (g.y % sp.size) * sp.size + (g.x % sp.size);   // (< size^2 <= 64 for any pixel)
+    const float c = sp.cs[e][0], s = sp.cs[e][1];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        m.T[q] = __fadd_rn(__fmul_rn(T0[q], c), __fmul_rn(B0[q], s));
+        m.B[q] = __fsub_rn(__fmul_rn(B0[q], c), __fmul_rn(T0[q], s));
+    }
+    return m;
+}
+
+// s_i of step 3 of sf_trace_ao_to's definition about A.
+__device__ __forceinline__ void mirror_dir(const MirrorPose& m, float hx, float hy, float hz, float& sx, float& sy,
+                                           float& sz)
+{
+    sx = __fadd_rn(__fadd_rn(__fmul_rn(m.T[0], hx), __fmul_rn(m.B[0], hy)), __fmul_rn(m.A.x, hz));
+    sy = __fadd_rn(__fadd_rn(__fmul_rn(m.T[1], hx), __fmul_rn(m.B[1], hy)), __fmul_rn(m.A.y, hz));
+    sz = __fadd_rn(__fadd_rn(__fmul_rn(m.T[2], hx), __fmul_rn(m.B[2], hy)), __fmul_rn(m.A.z, hz));
+}
+
+// The entries of the mirror calls: trace_ao_entries' sample loop on the pose.
+template <bool FIXUP, class MR>
+__device__ __forceinline__ uint64_t trace_mirror_entries(const FrameArgs& a, bool surface, const MR& mr,
+                                                         const MirrorPose& m, const LightTile<FIXUP>& t,
+                                                         uint32_t& status)
+{
+    // (a NaN normal or a zero-length R makes A, every s_i and every F not finite: the lane stays off)
+    return trace_parallel_entries(a, mr.n, mr.keep, t, status, [&](uint32_t i) {
+        float sx, sy, sz;
+        mirror_dir(m, mr.h[i][0], mr.h[i][1], mr.h[i][2], sx, sy, sz);
+        return RayPose{m.w[0], m.w[1], m.w[2], __fadd_rn(m.w[0], __fmul_rn(sx, mr.tau)),
+                       __fadd_rn(m.w[1], __fmul_rn(sy, mr.tau)), __fadd_rn(m.w[2], __fmul_rn(sz, mr.tau)), surface};
+    });
+}
+
+// The summing ending with an RGB factor per entry: light_sum_end's steps (the flagged tile that stores nothing, the
+// miss of the frame, the base, the index order, .w), with S.c = S.c + (colours[i].c (open_i ? E.c : 0)) where fac(i, E)
+// gives entry i's factor at the lane's pixel.
+template <bool FIXUP, class Sum, class Fac>
+__device__ __forceinline__ void light_sum_rgb_end(const FrameArgs& a, const GroupLane& g, bool surface,
+                                                  uint64_t shadowed, uint32_t status, const Sum& ss,
+                                                  float* __restrict__ out, const LightTile<FIXUP>& t, Fac fac)
+{
+    if (!FIXUP && status != 0u) {
+        flag_group(t.overflow_list, t.overflow_count, t.group);
+        return;
+    }
+    if (!g.valid) return;   // (a partial tile: nothing outside the image)
+    float4* const o = reinterpret_cast<float4*>(out) + ((size_t)g.y * a.W + g.x);
+    if (!surface) {   // a miss of the frame: an accumulating call leaves it, an overwriting one zeroes it
+        if (!ss.accumulate) *o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    float4 S = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (ss.accumulate) S = *o;   // (uniform)
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0u; i < ss.n; ++i) {
+        float E[3];
+        fac(i, E);
+        const bool open = ((shadowed >> i) & 1ull) == 0ull;
+        S.x = __fadd_rn(S.x, __fmul_rn(ss.c[i][0], open ? E[0] : 0.0f));
+        S.y = __fadd_rn(S.y, __fmul_rn(ss.c[i][1], open ? E[1] : 0.0f));
+        S.z = __fadd_rn(S.z, __fmul_rn(ss.c[i][2], open ? E[2] : 0.0f));
+    }
+    *o = S;   // (.w: the base's)
+}
+
+template <bool FIXUP>
+__device__ __forceinline__ void trace_mirror_group(const FrameArgs& a, const float* __restrict__ pos4,
+                                                   const float* __restrict__ nrm4, const MirrorArgs& mr,
+                                                   const AoSpin& sp, uint64_t* __restrict__ mask,
+                                                   const LightTile<FIXUP>& t)
+{
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
+    const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    uint64_t shadowed = 0ull;   // bit i: sample i's ray to the lane's pixel is stopped
+    uint32_t status = 0u;
+    // (uniform; else the tile is all frame miss: every sample's bit is set)
+    if (wave_ballot(surface) != 0ull) {
+        const MirrorPose m = mirror_pose(g, P, px4(nrm4, g.ray), mr, sp);
+        shadowed = trace_mirror_entries(a, surface, mr, m, t, status);
+    }
+    light_mask_end(a, g, mr.n, shadowed, status, mask, t);
+}
+
+// The sky's colour along s_i: t = min(max(s_i . up, 0), 1), +0 where the product is -0 or NaN;
+// E = horizon + (span t), span = zenith - horizon formed by the host (one rounding).
+template <bool FIXUP>
+__device__ __forceinline__ void trace_mirror_sum_group(const FrameArgs& a, const float* __restrict__ pos4,
+                                                       const float* __restrict__ nrm4, const MirrorSum& mr,
+                                                       const AoSpin& sp, float* __restrict__ out,
+                                                       const LightTile<FIXUP>& t)
+{
+    const GroupLane g = tile_lane(a, t.group);
+    const float4 P = px4(pos4, g.ray);
+    const bool surface = g.valid && !(P.x == 0.0f && P.y == 0.0f && P.z == 0.0f);
+    uint64_t shadowed = 0ull;
+    uint32_t status = 0u;
+    MirrorPose m = {};
+    if (wave_ballot(surface) != 0ull) {   // (uniform; else the tile is all frame miss)
+        m = mirror_pose(g, P, px4(nrm4, g.ray), mr, sp);
+        shadowed = trace_mirror_entries(a, surface, mr, m, t, status);
+    }
+    light_sum_rgb_end(a, g, surface, shadowed, status, mr, out, t, [&](uint32_t i, float E[3]) {
+        float sx, sy, sz;
+        mirror_dir(m, mr.h[i][0], mr.h[i][1], mr.h[i][2], sx, sy, sz);
+        const float u = __fadd_rn(__fadd_rn(__fmul_rn(sx, mr.up[0]), __fmul_rn(sy, mr.up[1])), __fmul_rn(sz, mr.up[2]));
+        const float tt = u > 0.0f ? (u < 1.0f ? u : 1.0f) : 0.0f;   // (a NaN fails the compare)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) E[q] = __fadd_rn(mr.horizon[q], __fmul_rn(mr.span[q], tt));
+    });
+}
+
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_mirror_wave(FrameArgs a, const float* pos4,
+                                                                      const float* nrm4, MirrorArgs mr, AoSpin sp,
+                                                                      uint64_t* mask, uint32_t groups,
+                                                                      uint32_t* overflow_list,
+                                                                      uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_mirror_group(a, pos4, nrm4, mr, sp, mask, t); });
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_mirror_fixup(FrameArgs a, const float* pos4,
+                                                                       const float* nrm4, MirrorArgs mr, AoSpin sp,
+                                                                       uint64_t* mask, const uint32_t* overflow_list,
+                                                                       uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_mirror_group(a, pos4, nrm4, mr, sp, mask, t); });
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_mirror_sum_wave(FrameArgs a, const float* pos4,
+                                                                          const float* nrm4, MirrorSum mr, AoSpin sp,
+                                                                          float* out, uint32_t groups,
+                                                                          uint32_t* overflow_list,
+                                                                          uint32_t* overflow_count)
+{
+    extern __shared__ float lds[];
+    light_wave<RootStage::Once>(a, lds, groups, overflow_list, overflow_count,
+                                [&](const WaveTile& t) { trace_mirror_sum_group(a, pos4, nrm4, mr, sp, out, t); });
+}
+
+extern "C" __global__ __launch_bounds__(64) void sf_trace_mirror_sum_fixup(FrameArgs a, const float* pos4,
+                                                                           const float* nrm4, MirrorSum mr, AoSpin sp,
+                                                                           float* out, const uint32_t* overflow_list,
+                                                                           uint32_t* counters, uint32_t parity)
+{
+    extern __shared__ float lds[];
+    light_fixup<RootStage::Once>(a, lds, overflow_list, counters, parity,
+                                 [&](const FixupTile& t) { trace_mirror_sum_group(a, pos4, nrm4, mr, sp, out, t); });
+}
+
+// ------------------------------------------------------------------------------------------
 // Light shafts: sun visibility along each pixel's view ray in one launch (sf_trace_shafts_to). Bit i
 // of mask[p] is what sf_trace_sun_wave writes at a pixel whose position is Q_i = E sigma_i (1 = 255, 0 = 0), bits
 // n..63 are 0. The lane's position is loaded and its march end E formed once -- P, or where P == 0 and a direction

@@ -139,6 +139,12 @@ class sf_ao_spin(ctypes.Structure):
     _fields_ = [("cs", ctypes.POINTER(ctypes.c_float)), ("size", ctypes.c_uint32)]
 
 
+class sf_mirror_params(ctypes.Structure):
+    _fields_ = sf_ao_params._fields_ + [("eye", ctypes.c_float * 3), ("use_eye", ctypes.c_uint32),
+                                        ("zenith", ctypes.c_float * 3), ("horizon", ctypes.c_float * 3),
+                                        ("up", ctypes.c_float * 3)]
+
+
 class sf_light_filter_params(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("normal_min", ctypes.c_float), ("plane_max", ctypes.c_float),
                 ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
@@ -243,6 +249,13 @@ SIGNATURES = {
     "sf_trace_ao_spin_sum_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_ao_params), ctypes.POINTER(sf_ao_spin),
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_trace_ao_spin_sum": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_ao_params), ctypes.POINTER(sf_ao_spin)]),
+    "sf_mirror_defaults": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_mirror_params)]),
+    "sf_trace_mirror_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_mirror_params), ctypes.POINTER(sf_ao_spin),
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_mirror": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_mirror_params), ctypes.POINTER(sf_ao_spin)]),
+    "sf_trace_mirror_sum_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_mirror_params), ctypes.POINTER(sf_ao_spin),
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_trace_mirror_sum": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_mirror_params), ctypes.POINTER(sf_ao_spin)]),
     "sf_light_filter_defaults": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_filter_params)]),
     "sf_light_filter_to": (ctypes.c_int, [_CTX, ctypes.POINTER(sf_light_filter_params), ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -1545,6 +1558,66 @@ class Sphereflake:
             lead=lead)
         del keep
         return res
+
+    # sky reflections about each pixel's mirror direction (sf_trace_mirror_to / sf_trace_mirror_sum_to and their
+    # context forms)
+    def mirror_params(self, samples, colours=None, accumulate=False, distance=None, bias=None, origin=None, eye=None,
+                      zenith=None, horizon=None, up=None, width=0, height=0, max_depth=0, stream=None):
+        """sf_mirror_defaults, overridden: (params, keepalive). samples, colours, accumulate, distance, bias and origin
+        as ao_params'; eye None: the view vector is the position itself (positions relative to the viewer), else the
+        world point less `eye`; zenith, horizon, up None keep the library's defaults ((1, 1, 1), (1, 1, 1), (0, 0, 1))."""
+        q, keep = self.ao_params(samples, colours, accumulate, distance, bias, origin, width, height, max_depth, stream)
+        p = sf_mirror_params()
+        _check(lib().sf_mirror_defaults(self._ctx, ctypes.byref(p)), "sf_mirror_defaults")
+        for name, _ in sf_ao_params._fields_:   # (sf_ao_defaults' distance and bias are sf_mirror_defaults')
+            setattr(p, name, getattr(q, name))
+        if eye is not None:
+            p.eye[:] = [float(x) for x in _f32(eye, 3)]
+            p.use_eye = 1
+        for field, v in (("zenith", zenith), ("horizon", horizon), ("up", up)):
+            if v is not None:
+                getattr(p, field)[:] = [float(x) for x in _f32(v, 3)]
+        return p, keep
+
+    def trace_mirror(self, samples, distance=4.0, bias=2.0 ** -10, pos=None, nrm=None, out=None, max_depth=0,
+                     stream=None, origin=None, spin=None, eye=None):
+        """trace_ao() about each pixel's MIRROR DIRECTION instead of its normal: the view vector V (the position itself,
+        or with `eye` the world point less the eye) is mirrored about the normal on the device, A = normalise(V - 2 (N . V)
+        N), and the `samples` [n, 3] -- a lobe about +z, sphereflake_amd.lights.lobe_samples -- are turned about A and
+        traced as trace_ao() traces them: a uint64 per pixel, bit i = 1 where sample i's direction is open to the sky
+        (sf_trace_mirror_to, sf.h; sphereflake_amd.lights.mirror_axes, mirror_model). pos, nrm, out, origin and spin as
+        trace_ao()'s. The flake does not reflect itself: a closed direction is just closed."""
+        lead, keep = self._mirror_spin(spin)
+        res = self._trace_images(
+            lambda W, H: self.mirror_params(samples, None, False, distance, bias, origin, eye, None, None, None, W, H,
+                                            max_depth, stream),
+            "sf_trace_mirror", pos, out, np.uint64, normals=True, nrm=nrm, lead=lead)
+        del keep
+        return res
+
+    def trace_mirror_sum(self, samples, colours=None, zenith=(1.0, 1.0, 1.0), horizon=(1.0, 1.0, 1.0),
+                         up=(0.0, 0.0, 1.0), accumulate=False, distance=4.0, bias=2.0 ** -10, pos=None, nrm=None,
+                         out=None, max_depth=0, stream=None, origin=None, spin=None, eye=None):
+        """trace_mirror() summed into a float4 light buffer: per surface pixel and channel, in index order,
+        S += colour_i x (open_i ? E_i : 0) with E_i the sky's colour in the world direction s_i of THAT PIXEL'S ray:
+        E_i = horizon + (zenith - horizon) clamp(s_i . up, 0, 1) (sf_trace_mirror_sum_to, sf.h;
+        sphereflake_amd.lights.sky_gradient, mirror_sum_model). colours [n, 3] (None: 1 / n per component); accumulate,
+        pos, nrm and out as trace_ao_sum()'s. Add it AFTER light_filter(): the mirror direction turns with the normal
+        far faster than occlusion does. There is no Fresnel term, and light_image_buffer() still multiplies the image
+        by the buffer."""
+        lead, keep = self._mirror_spin(spin)
+        res = self._trace_images(
+            lambda W, H: self.mirror_params(samples, colours, accumulate, distance, bias, origin, eye, zenith, horizon,
+                                            up, W, H, max_depth, stream),
+            "sf_trace_mirror_sum", pos, out, np.float32, (4,), normals=True, nrm=nrm, accumulate=accumulate, lead=lead)
+        del keep
+        return res
+
+    @classmethod
+    def _mirror_spin(cls, spin):
+        """(lead arguments, keepalive) of a trace_mirror call: the spin is always passed, None as a null pointer."""
+        _, lead, keep = cls._spin(spin)
+        return (lead if lead else (None,)), keep
 
     def light_filter_params(self, size=4, normal_min=None, plane_max=None, width=0, height=0, stream=None):
         """sf_light_filter_defaults, overridden; normal_min and plane_max None keep the library's defaults (0.9, 0.02)."""

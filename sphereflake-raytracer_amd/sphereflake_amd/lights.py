@@ -22,7 +22,9 @@ image once per call. Ambient occlusion (``Sphereflake.trace_ao`` / ``trace_ao_su
 ao_directions, ao_model, ao_sum_model) traces a hemisphere of such sun rays about each pixel's own normal; a per-pixel
 spin and an edge-aware filter (ao_spins, light_filter_model) make four such rays stand for sixty-four, and temporal
 accumulation (``Sphereflake.light_accumulate``: reproject_matrix, light_accumulate_model, ao_phase) carries the light
-buffer from one frame of a moving camera to the next.
+buffer from one frame of a moving camera to the next. Sky reflections (``Sphereflake.trace_mirror`` /
+``trace_mirror_sum``: lobe_samples, mirror_axes, mirror_model, sky_gradient, mirror_sum_model) turn a lobe of such rays
+about each pixel's mirror direction and weigh every open one by the sky's colour along it.
 """
 from __future__ import annotations
 
@@ -756,6 +758,115 @@ def ao_sum_model(base, pos4, masks, colours, accumulate=False):
         bit = ((mask >> np.uint64(i)) & np.uint64(1)) != 0
         k = np.where(bit, _F(1.0), _F(0.0)).astype(_F)
         S = S + col[i] * k[..., None]
+    assert S.dtype == _F
+    surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
+    out[..., :3] = np.where(surface[..., None], S, out[..., :3])
+    return out
+
+
+# --- sky reflections about each pixel's mirror direction (sf_trace_mirror_to, sf_trace_mirror_sum_to) ---------------
+def lobe_samples(n, exponent):
+    """n local-frame unit samples h [n, 3] of a Phong lobe about +z (density proportional to h.z ^ exponent), the
+    `samples` of trace_mirror: ao_samples' golden-angle spiral with another height. With u_i = (i + 0.5) / n and
+    theta_i = i pi (3 - sqrt 5): h.z = (1 - u_i) ^ (1 / (exponent + 1)), radius sqrt(1 - h.z^2),
+    h = (radius cos(theta_i), radius sin(theta_i), h.z); made in float64 and rounded to float32. exponent 1 is
+    ao_samples(n)'s cosine distribution; a large exponent narrows the lobe towards the mirror direction."""
+    n = _count(n, AO_SAMPLES_MAX)
+    e = float(exponent)
+    if not (np.isfinite(e) and e >= 0.0):
+        raise ValueError("exponent must be finite and not negative")
+    i = np.arange(n, dtype=np.float64)
+    u = (i + 0.5) / n
+    th = i * _GOLDEN
+    z = (1.0 - u) ** (1.0 / (e + 1.0))
+    r = np.sqrt(1.0 - z * z)
+    return np.stack([r * np.cos(th), r * np.sin(th), z], axis=-1).astype(_F)
+
+
+def mirror_axes(pos4, nrm4, origin=None, eye=None):
+    """Steps 2 and 3 of sf_trace_mirror_to's definition: the image [..., 4] float32 with the mirror axis A in xyz and
+    .w = 0 -- the normal image on which trace_ao equals trace_mirror. eye None: V = P, the positions as given
+    (`origin` is not read); else V = (origin + P) - eye per component, other bits even for eye == origin. Then, one
+    rounding per operation: nv = ((N.x V.x) + (N.y V.y)) + (N.z V.z), k = nv + nv, R = V - (k N),
+    len = sqrt(((R.x R.x) + (R.y R.y)) + (R.z R.z)), A = R / len. A miss of the frame (P == 0 with eye None) gives
+    NaN: nothing reads it."""
+    P = np.asarray(pos4, _F)[..., :3]
+    N = np.asarray(nrm4, _F)[..., :3]
+    if P.shape != N.shape:
+        raise ValueError("nrm4 and pos4 must have the same height and width")
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
+        if eye is None:
+            V = P
+        else:
+            if origin is None:
+                raise ValueError("an eye needs the origin the positions are relative to")
+            V = (np.asarray(origin, _F).reshape(3) + P) - np.asarray(eye, _F).reshape(3)
+        nv = (N[..., 0] * V[..., 0] + N[..., 1] * V[..., 1]) + N[..., 2] * V[..., 2]
+        k = nv + nv
+        R = V - k[..., None] * N
+        A = R / _length(R)[..., None]
+    assert A.dtype == _F
+    out = np.zeros(A.shape[:-1] + (4,), _F)
+    out[..., :3] = A
+    return out
+
+
+def mirror_model(pos4, nrm4, origin, samples, distance, bias, spin=None, eye=None):
+    """Steps 1-4 of sf_trace_mirror_to's definition up to the ray: ao_model on the mirror axes --
+    (F [n, ..., 3], d [n, ..., 3], bound [n, ...], is_surface [...])."""
+    return ao_model(pos4, mirror_axes(pos4, nrm4, origin, eye), origin, samples, distance, bias, spin=spin)
+
+
+def sky_gradient(dirs, zenith=(0.25, 0.45, 1.0), horizon=(1.0, 0.8, 0.6), up=(0.0, 0.0, 1.0)):
+    """E [..., 3] float32 of sf_trace_mirror_sum_to's definition for the directions dirs [..., 3], one rounding per
+    operation: u = ((s.x up.x) + (s.y up.y)) + (s.z up.z), t = min(max(u, 0), 1) and +0 where u is -0 or NaN,
+    E.c = horizon.c + ((zenith.c - horizon.c) t). `up` is used as given, not normalised. NOT sky_colours, which works
+    in float64, normalises and pre-divides by n."""
+    s = np.asarray(dirs, _F)
+    z = np.asarray(zenith, _F).reshape(3)
+    h = np.asarray(horizon, _F).reshape(3)
+    w = np.asarray(up, _F).reshape(3)
+    if not ((np.isfinite(z) & (z >= 0)).all() and (np.isfinite(h) & (h >= 0)).all()):
+        raise ValueError("colour components must be finite and not negative")
+    if not np.isfinite(w).all():
+        raise ValueError("up must be finite")
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        u = (s[..., 0] * w[0] + s[..., 1] * w[1]) + s[..., 2] * w[2]
+        t = np.where(u > 0, np.where(u < 1, u, _F(1.0)), _F(0.0)).astype(_F)
+        E = h + (z - h) * t[..., None]
+    assert E.dtype == _F
+    return E
+
+
+def mirror_sum_model(base, pos4, nrm4, origin, masks, samples, colours, zenith=(1.0, 1.0, 1.0),
+                     horizon=(1.0, 1.0, 1.0), up=(0.0, 0.0, 1.0), accumulate=False, spin=None, eye=None):
+    """What trace_mirror_sum leaves in the light buffer: a new float32 array [..., 4]. ao_sum_model with the factor of
+    entry i the sky's colour along that pixel's own ray: S = S + colours[i] (bit i ? E_i : 0) per channel, in index
+    order, with E_i = sky_gradient(s_i) and s_i = ao_directions(mirror_axes(...), samples, spin)[i]. masks [...] are
+    the uint64 words of trace_mirror for the same samples, spin and eye."""
+    col = np.asarray(colours, _F).reshape(-1, 3)
+    n = _count(col.shape[0], AO_SAMPLES_MAX)
+    if not (np.isfinite(col) & (col >= 0)).all():
+        raise ValueError("every colour component must be finite and not negative")
+    P = np.asarray(pos4, _F)[..., :3]
+    mask = np.asarray(masks, np.uint64)
+    s = ao_directions(mirror_axes(pos4, nrm4, origin, eye), samples, spin)
+    if s.shape[0] != n:
+        raise ValueError("one colour per sample")
+    if accumulate:
+        if base is None:
+            raise ValueError("an accumulating call needs its base")
+        out = np.array(base, _F, copy=True)
+    else:
+        out = np.zeros(P.shape[:-1] + (4,), _F)
+    if out.shape != P.shape[:-1] + (4,) or mask.shape != P.shape[:-1]:
+        raise ValueError("base must be [..., 4] and masks [...] over the images' pixels")
+    S = out[..., :3].copy()
+    for i in range(n):
+        bit = ((mask >> np.uint64(i)) & np.uint64(1)) != 0
+        E = sky_gradient(s[i], zenith, horizon, up)
+        with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+            S = S + col[i] * np.where(bit[..., None], E, _F(0.0)).astype(_F)
     assert S.dtype == _F
     surface = ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
     out[..., :3] = np.where(surface[..., None], S, out[..., :3])
