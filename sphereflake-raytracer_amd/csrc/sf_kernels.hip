@@ -43,6 +43,7 @@
 #include <stdint.h>
 
 #include "sf_internal.h"
+#include "sf_rootforms.h"
 
 #pragma clang fp contract(off)
 
@@ -343,18 +344,12 @@ __device__ __forceinline__ void sel_in_place(uint32_t& dst, uint32_t src, uint64
 // Near root with sqrt_rn(x) for x = R2 - d2 >= 2^-96 (finite): the hardware estimate and its +-1 ulp correction
 // by two fma residuals -- the sequence the compiler emits for a correctly rounded sqrtf, without the scaling of
 // tiny arguments and the zero/inf class fix-up that x >= 2^-96 never needs, so bit for bit its result there.
+// The correction and the choice between the two roots as arithmetic, without a compare -> select pair and its wait
+// states (sf_rootforms.h, with the proofs): eight VALU instructions behind the v_sqrt where the selects took twelve
+// and three s_nop.
 __device__ __forceinline__ float near_root_big(float tca, float x)
 {
-    const float s0 = __builtin_amdgcn_sqrtf(x);
-    const float sdn = __uint_as_float(__float_as_uint(s0) - 1u);
-    const float sup = __uint_as_float(__float_as_uint(s0) + 1u);
-    const float rdn = __builtin_fmaf(-sdn, s0, x);
-    const float rup = __builtin_fmaf(-sup, s0, x);
-    float thc = rdn <= 0.0f ? sdn : s0;
-    thc = rup > 0.0f ? sup : thc;
-    const float t0 = tca + thc;
-    const float t1 = tca - thc;
-    return (t0 <= t1) ? t0 : t1;
+    return near_root_of(tca, sqrt_fix(__builtin_amdgcn_sqrtf(x), x));
 }
 
 // Exact near root for the rare undecided lanes of the LOD bracket. Inlined: its uniform branch stays a
