@@ -1476,6 +1476,15 @@ static void shadow_origin(const sf_ctx* c, uint32_t use_origin, const float orig
     *keep = 1.0f - bias;
 }
 
+// What every trace checks before anything else: the context and the parameters, the view, and, where the result goes
+// to the caller's buffer only, that buffer.
+static int trace_preamble(const sf_ctx* c, bool params, bool out = true)
+{
+    if (!c || !params) return SF_EINVAL;
+    if (!c->has_view) return SF_ENOVIEW;
+    return out ? SF_OK : SF_EINVAL;
+}
+
 // a colour component: finite and not negative (NaN fails the compare)
 static bool light_component(float v) { return v >= 0.0f && !std::isinf(v); }
 
@@ -1595,6 +1604,37 @@ static int own_buffer_checked(sf_ctx* c, T** buf, size_t bytes, bool accumulate,
     return SF_OK;
 }
 
+// The own-buffer form of a trace whose `_to` form does all its checks: the context's G-buffer into c->*buf.
+template <class P, class T>
+static int trace_own(sf_ctx* c, const P* p, T* sf_ctx::*buf, int (*to)(sf_ctx*, const P*, const float*, T*))
+{
+    if (!c || !p) return SF_EINVAL;
+    if (int rc = own_result_buffer(c, p->width, p->height, &(c->*buf))) return rc;
+    return to(c, p, nullptr, c->*buf);
+}
+
+// The context's own buffer c->*buf (`bytes` per pixel) to the host, after everything queued on the context.
+template <class T>
+static int download_own(sf_ctx* c, T* sf_ctx::*buf, size_t bytes, T* host)
+{
+    if (!c || !host) return SF_EINVAL;
+    if (!(c->*buf)) return SF_ESTATE;
+    if (int rc = sf_synchronize(c)) return rc;
+    DevGuard g(c->device);
+    SF_HIP(c, hipMemcpy(host, c->*buf, (size_t)c->W * c->H * bytes, hipMemcpyDeviceToHost));
+    return SF_OK;
+}
+
+// Its device pointer: null before the first use, which is SF_ESTATE where the buffer is `required`.
+template <class T>
+static int own_buffer_pointer(sf_ctx* c, T* sf_ctx::*buf, bool required, T** out)
+{
+    if (!c || !out) return SF_EINVAL;
+    if (required && !(c->*buf)) return SF_ESTATE;
+    *out = c->*buf;
+    return SF_OK;
+}
+
 // One thread per pixel of an image of `pixels` pixels: kernel(args...) on `stream` (null: the context's), ordered after
 // the context's earlier work.
 template <class Kernel, class... Args>
@@ -1653,9 +1693,7 @@ static ShadowArgs shadow_args(const sf_ctx* c, const sf_shadow_params* p)
 
 int sf_trace_shadow_to(sf_ctx* c, const sf_shadow_params* p, const float* pos4, uint8_t* vis)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if (!vis) return SF_EINVAL;
+    if (int rc = trace_preamble(c, p != nullptr, vis != nullptr)) return rc;
     ShadowImage im;
     if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
     const ShadowArgs sa = shadow_args(c, p);
@@ -1668,28 +1706,12 @@ int sf_trace_shadow_to(sf_ctx* c, const sf_shadow_params* p, const float* pos4, 
 
 int sf_trace_shadow(sf_ctx* c, const sf_shadow_params* p)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow)) return rc;
-    return sf_trace_shadow_to(c, p, nullptr, c->shadow);
+    return trace_own(c, p, &sf_ctx::shadow, sf_trace_shadow_to);
 }
 
-int sf_download_shadow(sf_ctx* c, uint8_t* vis)
-{
-    if (!c || !vis) return SF_EINVAL;
-    if (!c->shadow) return SF_ESTATE;
-    int rc = sf_synchronize(c);
-    if (rc != SF_OK) return rc;
-    DevGuard g(c->device);
-    SF_HIP(c, hipMemcpy(vis, c->shadow, (size_t)c->W * c->H, hipMemcpyDeviceToHost));
-    return SF_OK;
-}
+int sf_download_shadow(sf_ctx* c, uint8_t* vis) { return download_own(c, &sf_ctx::shadow, 1, vis); }
 
-int sf_shadow_buffer(sf_ctx* c, uint8_t** vis)
-{
-    if (!c || !vis) return SF_EINVAL;
-    *vis = c->shadow;
-    return SF_OK;
-}
+int sf_shadow_buffer(sf_ctx* c, uint8_t** vis) { return own_buffer_pointer(c, &sf_ctx::shadow, false, vis); }
 
 int sf_light_image(sf_ctx* c, const sf_shadow_params* p, float ambient, const float* pos4, const float* nrm4,
                    const uint8_t* vis, uint8_t* rgba)
@@ -1726,9 +1748,7 @@ static const float kNoCentre[3] = { 0.0f, 0.0f, 0.0f };   // (the kernel stages 
 
 int sf_trace_shadows_to(sf_ctx* c, const sf_shadows_params* p, const float* pos4, uint64_t* mask)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if (!mask) return SF_EINVAL;
+    if (int rc = trace_preamble(c, p != nullptr, mask != nullptr)) return rc;
     if (int rc = entries_check(p->n, SF_SHADOW_LIGHTS_MAX, p->lights, nullptr, 0u, false)) return rc;
     ShadowImage im;
     if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
@@ -1740,27 +1760,14 @@ int sf_trace_shadows_to(sf_ctx* c, const sf_shadows_params* p, const float* pos4
 
 int sf_trace_shadows(sf_ctx* c, const sf_shadows_params* p)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow_masks)) return rc;
-    return sf_trace_shadows_to(c, p, nullptr, c->shadow_masks);
+    return trace_own(c, p, &sf_ctx::shadow_masks, sf_trace_shadows_to);
 }
 
-int sf_download_shadow_masks(sf_ctx* c, uint64_t* mask)
-{
-    if (!c || !mask) return SF_EINVAL;
-    if (!c->shadow_masks) return SF_ESTATE;
-    int rc = sf_synchronize(c);
-    if (rc != SF_OK) return rc;
-    DevGuard g(c->device);
-    SF_HIP(c, hipMemcpy(mask, c->shadow_masks, (size_t)c->W * c->H * 8, hipMemcpyDeviceToHost));
-    return SF_OK;
-}
+int sf_download_shadow_masks(sf_ctx* c, uint64_t* mask) { return download_own(c, &sf_ctx::shadow_masks, 8, mask); }
 
 int sf_shadow_mask_buffer(sf_ctx* c, uint64_t** mask)
 {
-    if (!c || !mask) return SF_EINVAL;
-    *mask = c->shadow_masks;
-    return SF_OK;
+    return own_buffer_pointer(c, &sf_ctx::shadow_masks, false, mask);
 }
 
 int sf_light_image_many(sf_ctx* c, const sf_shadows_params* p, float ambient, const float* pos4, const float* nrm4,
@@ -1807,9 +1814,7 @@ int sf_sun_defaults(const sf_ctx* c, sf_sun_params* p)
 
 int sf_trace_sun_to(sf_ctx* c, const sf_sun_params* p, const float* pos4, uint8_t* vis)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if (!vis) return SF_EINVAL;
+    if (int rc = trace_preamble(c, p != nullptr, vis != nullptr)) return rc;
     if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
     ShadowImage im;   // (its checks fail with SF_EINVAL as the distance does: their order cannot be told)
     if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, &im)) return rc;
@@ -1819,12 +1824,7 @@ int sf_trace_sun_to(sf_ctx* c, const sf_sun_params* p, const float* pos4, uint8_
     return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_sun_wave, sf_trace_sun_fixup, sa, vis);
 }
 
-int sf_trace_sun(sf_ctx* c, const sf_sun_params* p)
-{
-    if (!c || !p) return SF_EINVAL;
-    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow)) return rc;
-    return sf_trace_sun_to(c, p, nullptr, c->shadow);
-}
+int sf_trace_sun(sf_ctx* c, const sf_sun_params* p) { return trace_own(c, p, &sf_ctx::shadow, sf_trace_sun_to); }
 
 int sf_light_image_sun(sf_ctx* c, const sf_sun_params* p, float ambient, const float* pos4, const float* nrm4,
                        const uint8_t* vis, uint8_t* rgba)
@@ -1859,9 +1859,7 @@ static void suns_args(const sf_ctx* c, const sf_suns_params* p, SunDirs* sd)
 
 int sf_trace_suns_to(sf_ctx* c, const sf_suns_params* p, const float* pos4, uint64_t* mask)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if (!mask) return SF_EINVAL;
+    if (int rc = trace_preamble(c, p != nullptr, mask != nullptr)) return rc;
     if (int rc = entries_check(p->n, SF_SUN_DIRS_MAX, p->dirs, nullptr, 0u, false)) return rc;
     if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
     ShadowImage im;
@@ -1873,9 +1871,7 @@ int sf_trace_suns_to(sf_ctx* c, const sf_suns_params* p, const float* pos4, uint
 
 int sf_trace_suns(sf_ctx* c, const sf_suns_params* p)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow_masks)) return rc;
-    return sf_trace_suns_to(c, p, nullptr, c->shadow_masks);
+    return trace_own(c, p, &sf_ctx::shadow_masks, sf_trace_suns_to);
 }
 
 int sf_light_image_suns(sf_ctx* c, const sf_suns_params* p, float ambient, const float* pos4, const float* nrm4,
@@ -1934,9 +1930,7 @@ static void shafts_args(const sf_ctx* c, const sf_shafts_params* p, ShaftArgs* s
 
 int sf_trace_shafts_to(sf_ctx* c, const sf_shafts_params* p, const float* pos4, uint64_t* mask)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if (!mask) return SF_EINVAL;
+    if (int rc = trace_preamble(c, p != nullptr, mask != nullptr)) return rc;
     if (int rc = shafts_check(p, false)) return rc;
     if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
     ShadowImage im;
@@ -1948,9 +1942,7 @@ int sf_trace_shafts_to(sf_ctx* c, const sf_shafts_params* p, const float* pos4, 
 
 int sf_trace_shafts(sf_ctx* c, const sf_shafts_params* p)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (int rc = own_result_buffer(c, p->width, p->height, &c->shadow_masks)) return rc;
-    return sf_trace_shafts_to(c, p, nullptr, c->shadow_masks);
+    return trace_own(c, p, &sf_ctx::shadow_masks, sf_trace_shafts_to);
 }
 
 // The buffers defaulted to the context's (as light_image_pass, without a normal image or an ambient term).
@@ -2001,8 +1993,7 @@ static int light_sum_check(const sf_ctx* c, const sf_light_sum_params* p, bool s
 static int trace_sum_to(sf_ctx* c, const sf_light_sum_params* p, bool suns, const float* pos4, const float* nrm4,
                         float* out)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
+    if (int rc = trace_preamble(c, p != nullptr)) return rc;
     ShadowImage im;
     if (int rc = light_sum_check(c, p, suns, pos4, !nrm4 || !out, &im)) return rc;
     if (!out && !c->light) return SF_ESTATE;
@@ -2041,8 +2032,7 @@ static int trace_sum_to(sf_ctx* c, const sf_light_sum_params* p, bool suns, cons
 // needs it written.
 static int trace_sum_own(sf_ctx* c, const sf_light_sum_params* p, bool suns)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
+    if (int rc = trace_preamble(c, p != nullptr)) return rc;
     ShadowImage im;
     if (int rc = own_buffer_checked(c, &c->light, 16, p->accumulate != 0u,
                                     [&] { return light_sum_check(c, p, suns, nullptr, true, &im); }))
@@ -2064,13 +2054,31 @@ int sf_trace_shadows_sum_to(sf_ctx* c, const sf_light_sum_params* p, const float
 
 int sf_trace_shadows_sum(sf_ctx* c, const sf_light_sum_params* p) { return trace_sum_own(c, p, false); }
 
-// Ambient occlusion about each pixel's normal (kernels sf_trace_ao_wave / _fixup, sf_trace_ao_sum_wave / _fixup,
-// DESIGN.md §6.17). The launches of sf_trace_suns_to and sf_trace_suns_sum_to with the local-frame samples by value in
-// the argument segment and the normal image beside the position image; the mask buffer is sf_trace_shadows', the
-// light buffer sf_trace_suns_sum's. The argument block stays under the 4 KB kernel-argument limit:
+// The lobe traces: rays about a direction of each pixel's own, laid out from local-frame samples that travel by value in
+// the argument segment, with the normal image beside the position image. Ambient
+// occlusion about the normal (kernels sf_trace_ao_wave / _fixup, sf_trace_ao_sum_wave / _fixup), the same with a
+// per-pixel spin (sf_trace_ao_spin_wave / _fixup, sf_trace_ao_spin_sum_wave / _fixup: the table by value beside the
+// samples) and sky reflections about the mirror direction (sf_trace_mirror_wave / _fixup, sf_trace_mirror_sum_wave /
+// _fixup: the eye and the sky's gradient beside the samples; a null spin travels as the 1 x 1 table {(1, 0)}, which is
+// the unspun definition bit for bit, sf.h). The launches are sf_trace_suns_to's and sf_trace_suns_sum_to's; the mask
+// buffer is sf_trace_shadows', the light buffer sf_trace_suns_sum's. Twelve entry points, one host path: lobe_to and
+// lobe_own over a LobeCall. The argument blocks stay what the kernels were compiled for, under the 4 KB limit:
 static_assert(SF_AO_SAMPLES == SF_AO_SAMPLES_MAX, "one mask bit per sample");
+static_assert(SF_AO_SPIN == SF_AO_SPIN_MAX, "the table in the argument block is the ABI's largest");
+static_assert(sizeof(AoSpin) <= 520, "the spin table's share of the argument segment");
 static_assert(sizeof(FrameArgs) + sizeof(AoArgs) + 64 <= 4096, "kernel argument segment");
-static_assert(sizeof(FrameArgs) + sizeof(AoSum) + 64 <= 4096, "kernel argument segment");
+static_assert(sizeof(FrameArgs) + sizeof(AoSum) + sizeof(AoSpin) + 64 <= 4096, "kernel argument segment");
+static_assert(sizeof(FrameArgs) + sizeof(MirrorArgs) + sizeof(AoSpin) + 64 <= 4096, "kernel argument segment");
+static_assert(sizeof(FrameArgs) + sizeof(MirrorSum) + sizeof(AoSpin) + 64 <= 4096, "kernel argument segment");
+static_assert(sizeof(AoArgs) == 792 && offsetof(AoArgs, tau) == 16 && offsetof(AoArgs, h) == 24, "AoArgs");
+static_assert(sizeof(AoSum) == 1564 && offsetof(AoSum, accumulate) == 24 && offsetof(AoSum, h) == 28 &&
+                  offsetof(AoSum, c) == 796, "AoSum");
+static_assert(sizeof(AoSpin) == 520 && offsetof(AoSpin, cs) == 8, "AoSpin");
+static_assert(sizeof(MirrorArgs) == 808 && offsetof(MirrorArgs, eye) == 24 && offsetof(MirrorArgs, use_eye) == 36 &&
+                  offsetof(MirrorArgs, h) == 40, "MirrorArgs");
+static_assert(sizeof(MirrorSum) == 1616 && offsetof(MirrorSum, accumulate) == 40 && offsetof(MirrorSum, up) == 44 &&
+                  offsetof(MirrorSum, horizon) == 56 && offsetof(MirrorSum, span) == 68 &&
+                  offsetof(MirrorSum, h) == 80 && offsetof(MirrorSum, c) == 848, "MirrorSum");
 
 int sf_ao_defaults(const sf_ctx* c, sf_ao_params* p)
 {
@@ -2081,88 +2089,64 @@ int sf_ao_defaults(const sf_ctx* c, sf_ao_params* p)
     return SF_OK;
 }
 
-// Everything the calls check, in one place (the colours: the summing calls only); the images' sizes come back in `im`.
-static int ao_check(const sf_ctx* c, const sf_ao_params* p, bool sum, const float* pos4, bool ctx_buffer,
-                    ShadowImage* im)
+int sf_mirror_defaults(const sf_ctx* c, sf_mirror_params* p)
 {
-    if (int rc = entries_check(p->n, SF_AO_SAMPLES_MAX, p->samples, sum ? p->colours : nullptr, 3u * p->n, true))
-        return rc;
-    if (!(p->distance > 0.0f) || std::isinf(p->distance)) return SF_EINVAL;   // (NaN fails the compare)
-    if (int rc = shadow_image(c, p->bias, p->max_depth, p->width, p->height, pos4, im)) return rc;
-    if (ctx_buffer && (im->W != c->W || im->H != c->H)) return SF_EINVAL;   // (a context buffer, at its size only)
+    if (!c || !p) return SF_EINVAL;
+    std::memset(p, 0, sizeof *p);
+    p->distance = 4.0f;
+    p->bias = kShadowBias;
+    for (int k = 0; k < 3; ++k) p->zenith[k] = p->horizon[k] = 1.0f;
+    p->up[2] = 1.0f;
     return SF_OK;
 }
 
-extern "C++" {
-// what AoArgs and AoSum share, from the parameters
-template <class AO>
-static void ao_args(const sf_ctx* c, const sf_ao_params* p, AO* ao)
-{
-    entry_args(c, p->use_origin, p->origin, p->bias, p->n, ao);
-    ao->tau = p->distance;
-    entry_triples(p->n, p->samples, ao->h);
-}
-}  // extern "C++"
+// A call, by what the twelve differ in.
+enum SpinRule {
+    kNoSpin,           // plain AO: the kernels take no table
+    kSpinRequired,     // spun AO: a null table is SF_EINVAL
+    kSpinOrIdentity    // the mirror: a null table is the 1 x 1 identity
+};
+struct LobeCall {
+    bool given;                       // the caller's parameters were not null
+    sf_ao_params p;                   // the fields all twelve share (the mirror's, copied in)
+    const sf_mirror_params* mirror;   // the mirror's own fields, or null
+    const sf_ao_spin* spin;
+    SpinRule rule;
+    bool sum;                         // colours into a light buffer, else one mask bit per sample
+};
 
-int sf_trace_ao_to(sf_ctx* c, const sf_ao_params* p, const float* pos4, const float* nrm4, uint64_t* mask)
+static LobeCall ao_call(const sf_ao_params* p, const sf_ao_spin* spin, SpinRule rule, bool sum)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if (!mask) return SF_EINVAL;
-    ShadowImage im;
-    if (int rc = ao_check(c, p, false, pos4, !nrm4, &im)) return rc;
-    AoArgs ao;
-    ao_args(c, p, &ao);
-    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
-    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_ao_wave, sf_trace_ao_fixup, nrm, ao, mask);
-}
-
-int sf_trace_ao(sf_ctx* c, const sf_ao_params* p)
-{
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    ShadowImage im;
-    if (int rc = own_buffer_checked(c, &c->shadow_masks, 8, false,
-                                    [&] { return ao_check(c, p, false, nullptr, true, &im); }))
-        return rc;
-    return sf_trace_ao_to(c, p, nullptr, nullptr, c->shadow_masks);
+    LobeCall k;
+    std::memset(&k, 0, sizeof k);
+    k.given = p != nullptr;
+    if (p) k.p = *p;
+    k.spin = spin;
+    k.rule = rule;
+    k.sum = sum;
+    return k;
 }
 
-int sf_trace_ao_sum_to(sf_ctx* c, const sf_ao_params* p, const float* pos4, const float* nrm4, float* out)
+static LobeCall mirror_call(const sf_mirror_params* p, const sf_ao_spin* spin, bool sum)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    ShadowImage im;
-    if (int rc = ao_check(c, p, true, pos4, !nrm4 || !out, &im)) return rc;
-    if (!out && !c->light) return SF_ESTATE;
-    AoSum ao;
-    ao_args(c, p, &ao);
-    ao.accumulate = p->accumulate ? 1u : 0u;
-    entry_values(3u * p->n, p->colours, 1.0f / (float)p->n, &ao.c[0][0]);
-    float* const dst = out ? out : c->light;
-    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
-    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_ao_sum_wave, sf_trace_ao_sum_fixup, nrm, ao,
-                              dst);
+    LobeCall k = ao_call(nullptr, spin, kSpinOrIdentity, sum);
+    if (!p) return k;
+    k.given = true;
+    k.mirror = p;
+    k.p.samples = p->samples;
+    k.p.colours = p->colours;
+    k.p.n = p->n;
+    k.p.accumulate = p->accumulate;
+    k.p.distance = p->distance;
+    k.p.bias = p->bias;
+    for (int i = 0; i < 3; ++i) k.p.origin[i] = p->origin[i];
+    k.p.use_origin = p->use_origin;
+    k.p.width = p->width;
+    k.p.height = p->height;
+    k.p.max_depth = p->max_depth;
+    k.p.stream = p->stream;
+    return k;
 }
-
-// The context's G-buffer into the context's light buffer: an overwriting call makes the buffer, an accumulating one
-// needs it written (trace_sum_own).
-int sf_trace_ao_sum(sf_ctx* c, const sf_ao_params* p)
-{
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    ShadowImage im;
-    if (int rc = own_buffer_checked(c, &c->light, 16, p->accumulate != 0u,
-                                    [&] { return ao_check(c, p, true, nullptr, true, &im); }))
-        return rc;
-    return sf_trace_ao_sum_to(c, p, nullptr, nullptr, nullptr);
-}
-
-// The four calls above with a per-pixel spin (kernels sf_trace_ao_spin_wave / _fixup, sf_trace_ao_spin_sum_wave /
-// _fixup): the same checks, buffers and launches, with the table by value beside the samples.
-static_assert(SF_AO_SPIN == SF_AO_SPIN_MAX, "the table in the argument block is the ABI's largest");
-static_assert(sizeof(AoSpin) <= 520, "the spin table's share of the argument segment");
-static_assert(sizeof(FrameArgs) + sizeof(AoSum) + sizeof(AoSpin) + 64 <= 4096, "kernel argument segment");
 
 // the table: size 1..SF_AO_SPIN_MAX, every value finite; copied into the argument block
 static int spin_args(const sf_ao_spin* spin, AoSpin* sp)
@@ -2178,123 +2162,29 @@ static int spin_args(const sf_ao_spin* spin, AoSpin* sp)
     return SF_OK;
 }
 
-int sf_trace_ao_spin_to(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin, const float* pos4, const float* nrm4,
-                        uint64_t* mask)
+// Everything a call checks, in this order: the list (the colours: the summing calls only), the distance, the image,
+// a context buffer at the context's size only, the eye, the gradient (the summing calls only), then the table, which
+// is copied into the argument block. The images' sizes come back in `im`.
+static int lobe_check(const sf_ctx* c, const LobeCall& k, const float* pos4, bool ctx_buffer, ShadowImage* im,
+                      AoSpin* sp)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if (!mask) return SF_EINVAL;
-    ShadowImage im;
-    if (int rc = ao_check(c, p, false, pos4, !nrm4, &im)) return rc;
-    AoSpin sp;
-    if (int rc = spin_args(spin, &sp)) return rc;
-    AoArgs ao;
-    ao_args(c, p, &ao);
-    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
-    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_ao_spin_wave, sf_trace_ao_spin_fixup, nrm, ao,
-                              sp, mask);
-}
-
-int sf_trace_ao_spin(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin)
-{
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    ShadowImage im;
-    AoSpin sp;
-    if (int rc = own_buffer_checked(c, &c->shadow_masks, 8, false, [&] {
-            const int rc2 = ao_check(c, p, false, nullptr, true, &im);
-            return rc2 ? rc2 : spin_args(spin, &sp);
-        }))
+    const sf_ao_params& p = k.p;
+    if (int rc = entries_check(p.n, SF_AO_SAMPLES_MAX, p.samples, k.sum ? p.colours : nullptr, 3u * p.n, true))
         return rc;
-    return sf_trace_ao_spin_to(c, p, spin, nullptr, nullptr, c->shadow_masks);
-}
-
-int sf_trace_ao_spin_sum_to(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin, const float* pos4,
-                            const float* nrm4, float* out)
-{
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    ShadowImage im;
-    if (int rc = ao_check(c, p, true, pos4, !nrm4 || !out, &im)) return rc;
-    AoSpin sp;
-    if (int rc = spin_args(spin, &sp)) return rc;
-    if (!out && !c->light) return SF_ESTATE;
-    AoSum ao;
-    ao_args(c, p, &ao);
-    ao.accumulate = p->accumulate ? 1u : 0u;
-    entry_values(3u * p->n, p->colours, 1.0f / (float)p->n, &ao.c[0][0]);
-    float* const dst = out ? out : c->light;
-    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
-    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_ao_spin_sum_wave, sf_trace_ao_spin_sum_fixup,
-                              nrm, ao, sp, dst);
-}
-
-int sf_trace_ao_spin_sum(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin)
-{
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    ShadowImage im;
-    AoSpin sp;
-    if (int rc = own_buffer_checked(c, &c->light, 16, p->accumulate != 0u, [&] {
-            const int rc2 = ao_check(c, p, true, nullptr, true, &im);
-            return rc2 ? rc2 : spin_args(spin, &sp);
-        }))
-        return rc;
-    return sf_trace_ao_spin_sum_to(c, p, spin, nullptr, nullptr, nullptr);
-}
-
-// Sky reflections (kernels sf_trace_mirror_wave / _fixup, sf_trace_mirror_sum_wave / _fixup): the
-// spun AO calls' checks, buffers and launches with the eye and the sky's gradient beside the samples. One kernel set:
-// a null spin travels as the 1 x 1 table {(1, 0)}, which is the unspun definition bit for bit (sf.h).
-static_assert(sizeof(FrameArgs) + sizeof(MirrorArgs) + sizeof(AoSpin) + 64 <= 4096, "kernel argument segment");
-static_assert(sizeof(FrameArgs) + sizeof(MirrorSum) + sizeof(AoSpin) + 64 <= 4096, "kernel argument segment");
-
-int sf_mirror_defaults(const sf_ctx* c, sf_mirror_params* p)
-{
-    if (!c || !p) return SF_EINVAL;
-    std::memset(p, 0, sizeof *p);
-    p->distance = 4.0f;
-    p->bias = kShadowBias;
-    for (int k = 0; k < 3; ++k) p->zenith[k] = p->horizon[k] = 1.0f;
-    p->up[2] = 1.0f;
-    return SF_OK;
-}
-
-// the fields the mirror parameters share with AO's, for ao_check and ao_args
-static sf_ao_params mirror_ao_params(const sf_mirror_params* p)
-{
-    sf_ao_params q;
-    std::memset(&q, 0, sizeof q);
-    q.samples = p->samples;
-    q.colours = p->colours;
-    q.n = p->n;
-    q.accumulate = p->accumulate;
-    q.distance = p->distance;
-    q.bias = p->bias;
-    for (int k = 0; k < 3; ++k) q.origin[k] = p->origin[k];
-    q.use_origin = p->use_origin;
-    q.width = p->width;
-    q.height = p->height;
-    q.max_depth = p->max_depth;
-    q.stream = p->stream;
-    return q;
-}
-
-// Everything the calls check, in one place: AO's list, the eye, the gradient (the summing calls only), the table (a
-// null spin: the identity), which is copied into the argument block. Every failure of the mirror's own is SF_EINVAL.
-static int mirror_check(const sf_ctx* c, const sf_mirror_params* p, const sf_ao_spin* spin, bool sum,
-                        const float* pos4, bool ctx_buffer, ShadowImage* im, AoSpin* sp)
-{
-    const sf_ao_params q = mirror_ao_params(p);
-    if (int rc = ao_check(c, &q, sum, pos4, ctx_buffer, im)) return rc;
-    if (p->use_eye)
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(p->eye[k])) return SF_EINVAL;
-    if (sum)
-        for (int k = 0; k < 3; ++k)
-            if (!light_component(p->zenith[k]) || !light_component(p->horizon[k]) || !std::isfinite(p->up[k]))
-                return SF_EINVAL;
-    if (spin) return spin_args(spin, sp);
+    if (!(p.distance > 0.0f) || std::isinf(p.distance)) return SF_EINVAL;   // (NaN fails the compare)
+    if (int rc = shadow_image(c, p.bias, p.max_depth, p.width, p.height, pos4, im)) return rc;
+    if (ctx_buffer && (im->W != c->W || im->H != c->H)) return SF_EINVAL;
+    if (const sf_mirror_params* const m = k.mirror) {
+        if (m->use_eye)
+            for (int i = 0; i < 3; ++i)
+                if (!std::isfinite(m->eye[i])) return SF_EINVAL;
+        if (k.sum)
+            for (int i = 0; i < 3; ++i)
+                if (!light_component(m->zenith[i]) || !light_component(m->horizon[i]) || !std::isfinite(m->up[i]))
+                    return SF_EINVAL;
+    }
+    if (k.rule == kNoSpin) return SF_OK;
+    if (k.spin || k.rule == kSpinRequired) return spin_args(k.spin, sp);
     std::memset(sp, 0, sizeof *sp);
     sp->size = 1u;
     sp->cs[0][0] = 1.0f;
@@ -2302,79 +2192,152 @@ static int mirror_check(const sf_ctx* c, const sf_mirror_params* p, const sf_ao_
 }
 
 extern "C++" {
-// what MirrorArgs and MirrorSum share, from the parameters
-template <class MR>
-static void mirror_args(const sf_ctx* c, const sf_mirror_params* p, MR* mr)
+// What the four argument blocks share, what the two summing ones add, and what the mirror's two add.
+template <class Args>
+static void lobe_args(const sf_ctx* c, const sf_ao_params& p, Args* x)
 {
-    const sf_ao_params q = mirror_ao_params(p);
-    ao_args(c, &q, mr);
-    mr->use_eye = p->use_eye ? 1u : 0u;
-    for (int k = 0; k < 3; ++k) mr->eye[k] = p->use_eye ? p->eye[k] : 0.0f;
+    entry_args(c, p.use_origin, p.origin, p.bias, p.n, x);
+    x->tau = p.distance;
+    entry_triples(p.n, p.samples, x->h);
+}
+
+template <class Sum>
+static void lobe_sum_args(const sf_ao_params& p, Sum* x)
+{
+    x->accumulate = p.accumulate ? 1u : 0u;
+    entry_values(3u * p.n, p.colours, 1.0f / (float)p.n, &x->c[0][0]);
+}
+
+template <class Mirror>
+static void lobe_eye_args(const sf_mirror_params* m, Mirror* x)
+{
+    x->use_eye = m->use_eye ? 1u : 0u;
+    for (int i = 0; i < 3; ++i) x->eye[i] = m->use_eye ? m->eye[i] : 0.0f;
 }
 }  // extern "C++"
+
+// The `_to` forms: null images are the context's (at its size only), a summing call's null out its light buffer.
+static int lobe_to(sf_ctx* c, const LobeCall& k, const float* pos4, const float* nrm4, void* out)
+{
+    if (int rc = trace_preamble(c, k.given, k.sum || out != nullptr)) return rc;
+    ShadowImage im;
+    AoSpin sp;
+    if (int rc = lobe_check(c, k, pos4, !nrm4 || !out, &im, &sp)) return rc;
+    if (!out && !c->light) return SF_ESTATE;
+    const sf_ao_params& p = k.p;
+    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
+    if (!k.sum) {
+        uint64_t* const mask = (uint64_t*)out;
+        if (k.mirror) {
+            MirrorArgs mr;
+            lobe_args(c, p, &mr);
+            lobe_eye_args(k.mirror, &mr);
+            return mixed_origin_trace(c, p.stream, im, p.max_depth, sf_trace_mirror_wave, sf_trace_mirror_fixup, nrm,
+                                      mr, sp, mask);
+        }
+        AoArgs ao;
+        lobe_args(c, p, &ao);
+        if (k.rule == kNoSpin)
+            return mixed_origin_trace(c, p.stream, im, p.max_depth, sf_trace_ao_wave, sf_trace_ao_fixup, nrm, ao, mask);
+        return mixed_origin_trace(c, p.stream, im, p.max_depth, sf_trace_ao_spin_wave, sf_trace_ao_spin_fixup, nrm, ao,
+                                  sp, mask);
+    }
+    float* const dst = out ? (float*)out : c->light;
+    if (const sf_mirror_params* const m = k.mirror) {
+        MirrorSum mr;
+        lobe_args(c, p, &mr);
+        lobe_eye_args(m, &mr);
+        lobe_sum_args(p, &mr);
+        for (int i = 0; i < 3; ++i) {
+            mr.up[i] = m->up[i];
+            mr.horizon[i] = m->horizon[i];
+            mr.span[i] = m->zenith[i] - m->horizon[i];   // (one rounding: zenith.c - horizon.c of the definition)
+        }
+        return mixed_origin_trace(c, p.stream, im, p.max_depth, sf_trace_mirror_sum_wave, sf_trace_mirror_sum_fixup,
+                                  nrm, mr, sp, dst);
+    }
+    AoSum ao;
+    lobe_args(c, p, &ao);
+    lobe_sum_args(p, &ao);
+    if (k.rule == kNoSpin)
+        return mixed_origin_trace(c, p.stream, im, p.max_depth, sf_trace_ao_sum_wave, sf_trace_ao_sum_fixup, nrm, ao,
+                                  dst);
+    return mixed_origin_trace(c, p.stream, im, p.max_depth, sf_trace_ao_spin_sum_wave, sf_trace_ao_spin_sum_fixup, nrm,
+                              ao, sp, dst);
+}
+
+// The own-buffer forms: the context's G-buffer into its mask buffer, or into its light buffer, which an overwriting
+// call makes and an accumulating one needs written (trace_sum_own).
+static int lobe_own(sf_ctx* c, const LobeCall& k)
+{
+    if (int rc = trace_preamble(c, k.given)) return rc;
+    ShadowImage im;
+    AoSpin sp;
+    const auto check = [&] { return lobe_check(c, k, nullptr, true, &im, &sp); };
+    if (k.sum) {
+        if (int rc = own_buffer_checked(c, &c->light, 16, k.p.accumulate != 0u, check)) return rc;
+        return lobe_to(c, k, nullptr, nullptr, nullptr);
+    }
+    if (int rc = own_buffer_checked(c, &c->shadow_masks, 8, false, check)) return rc;
+    return lobe_to(c, k, nullptr, nullptr, c->shadow_masks);
+}
+
+int sf_trace_ao_to(sf_ctx* c, const sf_ao_params* p, const float* pos4, const float* nrm4, uint64_t* mask)
+{
+    return lobe_to(c, ao_call(p, nullptr, kNoSpin, false), pos4, nrm4, mask);
+}
+
+int sf_trace_ao(sf_ctx* c, const sf_ao_params* p) { return lobe_own(c, ao_call(p, nullptr, kNoSpin, false)); }
+
+int sf_trace_ao_sum_to(sf_ctx* c, const sf_ao_params* p, const float* pos4, const float* nrm4, float* out)
+{
+    return lobe_to(c, ao_call(p, nullptr, kNoSpin, true), pos4, nrm4, out);
+}
+
+int sf_trace_ao_sum(sf_ctx* c, const sf_ao_params* p) { return lobe_own(c, ao_call(p, nullptr, kNoSpin, true)); }
+
+int sf_trace_ao_spin_to(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin, const float* pos4, const float* nrm4,
+                        uint64_t* mask)
+{
+    return lobe_to(c, ao_call(p, spin, kSpinRequired, false), pos4, nrm4, mask);
+}
+
+int sf_trace_ao_spin(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin)
+{
+    return lobe_own(c, ao_call(p, spin, kSpinRequired, false));
+}
+
+int sf_trace_ao_spin_sum_to(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin, const float* pos4,
+                            const float* nrm4, float* out)
+{
+    return lobe_to(c, ao_call(p, spin, kSpinRequired, true), pos4, nrm4, out);
+}
+
+int sf_trace_ao_spin_sum(sf_ctx* c, const sf_ao_params* p, const sf_ao_spin* spin)
+{
+    return lobe_own(c, ao_call(p, spin, kSpinRequired, true));
+}
 
 int sf_trace_mirror_to(sf_ctx* c, const sf_mirror_params* p, const sf_ao_spin* spin, const float* pos4,
                        const float* nrm4, uint64_t* mask)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    if (!mask) return SF_EINVAL;
-    ShadowImage im;
-    AoSpin sp;
-    if (int rc = mirror_check(c, p, spin, false, pos4, !nrm4, &im, &sp)) return rc;
-    MirrorArgs mr;
-    mirror_args(c, p, &mr);
-    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
-    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_mirror_wave, sf_trace_mirror_fixup, nrm, mr, sp,
-                              mask);
+    return lobe_to(c, mirror_call(p, spin, false), pos4, nrm4, mask);
 }
 
 int sf_trace_mirror(sf_ctx* c, const sf_mirror_params* p, const sf_ao_spin* spin)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    ShadowImage im;
-    AoSpin sp;
-    if (int rc = own_buffer_checked(c, &c->shadow_masks, 8, false,
-                                    [&] { return mirror_check(c, p, spin, false, nullptr, true, &im, &sp); }))
-        return rc;
-    return sf_trace_mirror_to(c, p, spin, nullptr, nullptr, c->shadow_masks);
+    return lobe_own(c, mirror_call(p, spin, false));
 }
 
 int sf_trace_mirror_sum_to(sf_ctx* c, const sf_mirror_params* p, const sf_ao_spin* spin, const float* pos4,
                            const float* nrm4, float* out)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    ShadowImage im;
-    AoSpin sp;
-    if (int rc = mirror_check(c, p, spin, true, pos4, !nrm4 || !out, &im, &sp)) return rc;
-    if (!out && !c->light) return SF_ESTATE;
-    MirrorSum mr;
-    mirror_args(c, p, &mr);
-    mr.accumulate = p->accumulate ? 1u : 0u;
-    for (int k = 0; k < 3; ++k) {
-        mr.up[k] = p->up[k];
-        mr.horizon[k] = p->horizon[k];
-        mr.span[k] = p->zenith[k] - p->horizon[k];   // (one rounding: zenith.c - horizon.c of the definition)
-    }
-    entry_values(3u * p->n, p->colours, 1.0f / (float)p->n, &mr.c[0][0]);
-    float* const dst = out ? out : c->light;
-    const float* const nrm = nrm4 ? nrm4 : (const float*)c->nrm;
-    return mixed_origin_trace(c, p->stream, im, p->max_depth, sf_trace_mirror_sum_wave, sf_trace_mirror_sum_fixup, nrm,
-                              mr, sp, dst);
+    return lobe_to(c, mirror_call(p, spin, true), pos4, nrm4, out);
 }
 
 int sf_trace_mirror_sum(sf_ctx* c, const sf_mirror_params* p, const sf_ao_spin* spin)
 {
-    if (!c || !p) return SF_EINVAL;
-    if (!c->has_view) return SF_ENOVIEW;
-    ShadowImage im;
-    AoSpin sp;
-    if (int rc = own_buffer_checked(c, &c->light, 16, p->accumulate != 0u,
-                                    [&] { return mirror_check(c, p, spin, true, nullptr, true, &im, &sp); }))
-        return rc;
-    return sf_trace_mirror_sum_to(c, p, spin, nullptr, nullptr, nullptr);
+    return lobe_own(c, mirror_call(p, spin, true));
 }
 
 // The edge-aware box filter of the light buffer (kernel sf_light_filter_px).
@@ -2594,24 +2557,9 @@ int sf_light_history_reset(sf_ctx* c)
     return SF_OK;
 }
 
-int sf_light_buffer(sf_ctx* c, float** buf)
-{
-    if (!c || !buf) return SF_EINVAL;
-    if (!c->light) return SF_ESTATE;
-    *buf = c->light;
-    return SF_OK;
-}
+int sf_light_buffer(sf_ctx* c, float** buf) { return own_buffer_pointer(c, &sf_ctx::light, true, buf); }
 
-int sf_download_light(sf_ctx* c, float* buf4)
-{
-    if (!c || !buf4) return SF_EINVAL;
-    if (!c->light) return SF_ESTATE;
-    int rc = sf_synchronize(c);
-    if (rc != SF_OK) return rc;
-    DevGuard g(c->device);
-    SF_HIP(c, hipMemcpy(buf4, c->light, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost));
-    return SF_OK;
-}
+int sf_download_light(sf_ctx* c, float* buf4) { return download_own(c, &sf_ctx::light, 16, buf4); }
 
 // One thread per pixel of the context's frame; a null buf is the context's buffer, made here if need be.
 int sf_light_fill(sf_ctx* c, const float rgb[3], float* buf, void* stream)

@@ -360,6 +360,12 @@ SIGNATURES = {
 SF_ECOMM = -8
 SF_DIST_ID_BYTES = 128
 
+# the sf_*_defaults of the light traces' parameter blocks (Sphereflake._defaults)
+_DEFAULTS = {sf_shadow_params: "sf_shadow_defaults", sf_shadows_params: "sf_shadows_defaults",
+             sf_sun_params: "sf_sun_defaults", sf_suns_params: "sf_suns_defaults",
+             sf_shafts_params: "sf_shafts_defaults", sf_light_sum_params: "sf_light_sum_defaults",
+             sf_ao_params: "sf_ao_defaults", sf_mirror_params: "sf_mirror_defaults"}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -444,6 +450,38 @@ def _fp(a: np.ndarray):
 
 
 _F3 = ctypes.c_float * 3
+
+
+# What the parameter builders of the light traces share (Sphereflake.shadow_params ... mirror_params).
+def _entries(a, per, limit, what) -> np.ndarray:
+    """The list of a parameter block: [n, per] float32 ([n] where per is 1), n in 1..limit."""
+    a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1 if per == 1 else (-1, per)))
+    if not 1 <= a.shape[0] <= limit:
+        raise ValueError(f"1..{limit} {what} per call, not {a.shape[0]}")
+    return a
+
+
+def _entry_values(values, n, per, message):
+    """The weights [n] or colours [n, 3] beside a list of n entries, or None."""
+    if values is None:
+        return None
+    v = np.ascontiguousarray(np.asarray(values, np.float32).reshape(-1 if per == 1 else (-1, per)))
+    if v.shape[0] != n:
+        raise ValueError(message)
+    return v
+
+
+def _params_tail(p, distance, bias, origin, width, height, max_depth, stream):
+    """The fields every block ends with; distance and bias None keep what sf_*_defaults set, origin None the view's."""
+    if distance is not None:
+        p.distance = float(distance)
+    if bias is not None:
+        p.bias = float(bias)
+    if origin is not None:
+        p.origin[:] = [float(x) for x in _f32(origin, 3)]
+        p.use_origin = 1
+    p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
+    return p
 
 
 def _vec3(v):
@@ -945,19 +983,54 @@ class Sphereflake:
                    "sf_probe_rays", self._ctx)
         return mint, idx, pos, nrm
 
+    # what the light traces' builders, image passes and own buffers share ----------
+    def _defaults(self, block):
+        """A parameter block after its sf_*_defaults (_DEFAULTS names it)."""
+        p = block()
+        _check(getattr(lib(), _DEFAULTS[block])(self._ctx, ctypes.byref(p)), _DEFAULTS[block])
+        return p
+
+    def _list_params(self, block, field, entries, per, limit, what, vfield, values, vper, message):
+        """(block, keepalive) of a trace of a list: `block` after its defaults with p.n and p.`field` set from `entries`
+        (_entries) and, where `values` are given, p.`vfield` from them (_entry_values)."""
+        e = _entries(entries, per, limit, what)
+        p = self._defaults(block)
+        setattr(p, field, _fp(e))
+        v = _entry_values(values, e.shape[0], vper, message)
+        if v is not None:
+            setattr(p, vfield, _fp(v))
+        p.n = e.shape[0]
+        return p, (e, v)
+
+    def _light_image(self, entry, p, lead, ptrs, keep=None):
+        """The light_image* calls: entry(ctx, p, *lead, *ptrs), device addresses with 0 as null. `keep`: the host
+        arrays p points into, held by this frame until the call has returned."""
+        with self._mutex:
+            _check(getattr(lib(), entry)(self._ctx, ctypes.byref(p), *lead,
+                                         *(ctypes.c_void_p(x) if x else None for x in ptrs)), entry, self._ctx)
+
+    def _own_pointer(self, entry) -> int:
+        """The device address of one of the context's own result buffers (0 where there is none yet)."""
+        ptr = ctypes.c_void_p()
+        rc = getattr(lib(), entry)(self._ctx, ctypes.byref(ptr))
+        if rc == SF_ESTATE:
+            return 0
+        _check(rc, entry)
+        return ptr.value or 0
+
+    def _own_download(self, entry, dtype, tail=()) -> np.ndarray:
+        """[H, W] + tail elements of one of the context's own result buffers (synchronous)."""
+        a = np.empty((self.height, self.width) + tail, dtype)
+        with self._mutex:
+            _check(getattr(lib(), entry)(self._ctx, a.ctypes.data_as(ctypes.c_void_p)), entry, self._ctx)
+        return a
+
     # shadows from a point light (sf_trace_shadow_to / sf_trace_shadow / sf_light_image) ----------
     def shadow_params(self, light, bias=None, origin=None, width=0, height=0, max_depth=0, stream=None):
         """sf_shadow_defaults, overridden: bias None keeps the library's default."""
-        p = sf_shadow_params()
-        _check(lib().sf_shadow_defaults(self._ctx, ctypes.byref(p)), "sf_shadow_defaults")
+        p = self._defaults(sf_shadow_params)
         p.light[:] = [float(x) for x in _f32(light, 3)]
-        if bias is not None:
-            p.bias = float(bias)
-        if origin is not None:
-            p.origin[:] = [float(x) for x in _f32(origin, 3)]
-            p.use_origin = 1
-        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
-        return p
+        return _params_tail(p, None, bias, origin, width, height, max_depth, stream)
 
     def trace_shadow(self, light, bias=None, pos=None, out=None, origin=None, max_depth=0, stream=None):
         """Which pixels of a position image does a point light at `light` (world) reach? 255 = lit or a miss of the
@@ -1083,53 +1156,26 @@ class Sphereflake:
 
     def download_shadow(self) -> np.ndarray:
         """[H, W] uint8 of the last trace_shadow() into the context's visibility buffer (synchronous)."""
-        vis = np.empty((self.height, self.width), np.uint8)
-        with self._mutex:
-            _check(lib().sf_download_shadow(self._ctx, vis.ctypes.data_as(ctypes.c_void_p)), "sf_download_shadow",
-                   self._ctx)
-        return vis
+        return self._own_download("sf_download_shadow", np.uint8)
 
     def shadow_buffer(self) -> int:
         """Device address of the context's visibility buffer (0 before any trace_shadow() into it)."""
-        ptr = ctypes.c_void_p()
-        _check(lib().sf_shadow_buffer(self._ctx, ctypes.byref(ptr)), "sf_shadow_buffer")
-        return ptr.value or 0
+        return self._own_pointer("sf_shadow_buffer")
 
     def light_image(self, light, ambient=0.25, origin=None, pos_ptr=0, nrm_ptr=0, vis_ptr=0, rgba_ptr=0, stream=None):
         """Scale the image of PostProcess() in place by ambient + (1 - ambient) x (lit ? Lambert term : 0)
         (sf_light_image; sphereflake_amd.lights.light_model). Pointers are device addresses, 0 = the context's
         G-buffer, visibility buffer (trace_shadow()) and image. Asynchronous."""
         p = self.shadow_params(light, None, origin, 0, 0, 0, stream)
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        with self._mutex:
-            _check(lib().sf_light_image(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
-                                        vp(vis_ptr), vp(rgba_ptr)), "sf_light_image", self._ctx)
+        self._light_image("sf_light_image", p, (float(ambient),), (pos_ptr, nrm_ptr, vis_ptr, rgba_ptr))
 
     # many lights per pixel in one launch (sf_trace_shadows_to / sf_trace_shadows / sf_light_image_many) ----------
     def shadows_params(self, lights, weights=None, bias=None, origin=None, width=0, height=0, max_depth=0, stream=None):
         """sf_shadows_defaults, overridden: (params, keepalive). lights [n, 3], weights [n] or None; the host arrays
         the params point into are in `keepalive` and must outlive the call they are passed to."""
-        L = np.ascontiguousarray(np.asarray(lights, np.float32).reshape(-1, 3))
-        n = L.shape[0]
-        if not 1 <= n <= SF_SHADOW_LIGHTS_MAX:
-            raise ValueError(f"1..{SF_SHADOW_LIGHTS_MAX} lights per call, not {n}")
-        p = sf_shadows_params()
-        _check(lib().sf_shadows_defaults(self._ctx, ctypes.byref(p)), "sf_shadows_defaults")
-        p.lights = L.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        wts = None
-        if weights is not None:
-            wts = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
-            if wts.shape[0] != n:
-                raise ValueError("one weight per light")
-            p.weights = wts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        p.n = n
-        if bias is not None:
-            p.bias = float(bias)
-        if origin is not None:
-            p.origin[:] = [float(x) for x in _f32(origin, 3)]
-            p.use_origin = 1
-        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
-        return p, (L, wts)
+        p, keep = self._list_params(sf_shadows_params, "lights", lights, 3, SF_SHADOW_LIGHTS_MAX, "lights",
+                                    "weights", weights, 1, "one weight per light")
+        return _params_tail(p, None, bias, origin, width, height, max_depth, stream), keep
 
     def trace_shadows(self, lights, bias=None, pos=None, out=None, max_depth=0, origin=None, stream=None):
         """Which of up to 64 point lights `lights` [n, 3] (world) reach each pixel of a position image, in one launch:
@@ -1147,17 +1193,11 @@ class Sphereflake:
 
     def download_shadow_masks(self) -> np.ndarray:
         """[H, W] uint64 of the last trace_shadows() into the context's mask buffer (synchronous)."""
-        mask = np.empty((self.height, self.width), np.uint64)
-        with self._mutex:
-            _check(lib().sf_download_shadow_masks(self._ctx, mask.ctypes.data_as(ctypes.c_void_p)),
-                   "sf_download_shadow_masks", self._ctx)
-        return mask
+        return self._own_download("sf_download_shadow_masks", np.uint64)
 
     def shadow_mask_buffer(self) -> int:
         """Device address of the context's mask buffer (0 before any trace_shadows() into it)."""
-        ptr = ctypes.c_void_p()
-        _check(lib().sf_shadow_mask_buffer(self._ctx, ctypes.byref(ptr)), "sf_shadow_mask_buffer")
-        return ptr.value or 0
+        return self._own_pointer("sf_shadow_mask_buffer")
 
     def light_image_many(self, lights, weights=None, ambient=0.25, origin=None, pos_ptr=0, nrm_ptr=0, mask_ptr=0,
                          rgba_ptr=0, stream=None):
@@ -1166,11 +1206,7 @@ class Sphereflake:
         Pointers are device addresses, 0 = the context's G-buffer, mask buffer (trace_shadows()) and image.
         Asynchronous."""
         p, keep = self.shadows_params(lights, weights, None, origin, 0, 0, 0, stream)
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        with self._mutex:
-            _check(lib().sf_light_image_many(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
-                                             vp(mask_ptr), vp(rgba_ptr)), "sf_light_image_many", self._ctx)
-        del keep
+        self._light_image("sf_light_image_many", p, (float(ambient),), (pos_ptr, nrm_ptr, mask_ptr, rgba_ptr), keep)
 
     # the shadow traces' level of detail, shadows from a directional light (sf_set_shadow_lod, sf_trace_sun_to) -------
     def set_shadow_lod(self, lod_constant):
@@ -1187,18 +1223,9 @@ class Sphereflake:
 
     def sun_params(self, direction, distance=None, bias=None, origin=None, width=0, height=0, max_depth=0, stream=None):
         """sf_sun_defaults, overridden: distance and bias None keep the library's defaults (4, 2^-10)."""
-        p = sf_sun_params()
-        _check(lib().sf_sun_defaults(self._ctx, ctypes.byref(p)), "sf_sun_defaults")
+        p = self._defaults(sf_sun_params)
         p.dir[:] = [float(x) for x in _f32(direction, 3)]
-        if distance is not None:
-            p.distance = float(distance)
-        if bias is not None:
-            p.bias = float(bias)
-        if origin is not None:
-            p.origin[:] = [float(x) for x in _f32(origin, 3)]
-            p.use_origin = 1
-        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
-        return p
+        return _params_tail(p, distance, bias, origin, width, height, max_depth, stream)
 
     def trace_sun(self, direction, distance=None, bias=None, pos=None, out=None, origin=None, max_depth=0, stream=None):
         """Which pixels of a position image does a directional light reach? `direction` points TOWARDS the sun (world,
@@ -1214,10 +1241,7 @@ class Sphereflake:
         """Scale the image of PostProcess() in place by ambient + (1 - ambient) x (lit ? max(0, n . direction) : 0)
         (sf_light_image_sun; sphereflake_amd.lights.light_model_sun). Pointers as light_image's. Asynchronous."""
         p = self.sun_params(direction, None, None, None, 0, 0, 0, stream)
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        with self._mutex:
-            _check(lib().sf_light_image_sun(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
-                                            vp(vis_ptr), vp(rgba_ptr)), "sf_light_image_sun", self._ctx)
+        self._light_image("sf_light_image_sun", p, (float(ambient),), (pos_ptr, nrm_ptr, vis_ptr, rgba_ptr))
 
     # many sun directions per pixel in one launch (sf_trace_suns_to / sf_trace_suns / sf_light_image_suns) ----------
     def suns_params(self, dirs, weights=None, distance=None, bias=None, origin=None, width=0, height=0, max_depth=0,
@@ -1225,29 +1249,9 @@ class Sphereflake:
         """sf_suns_defaults, overridden: (params, keepalive). dirs [n, 3], weights [n] or None; distance and bias None
         keep the library's defaults (4, 2^-10). The host arrays the params point into are in `keepalive` and must
         outlive the call they are passed to."""
-        D = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
-        n = D.shape[0]
-        if not 1 <= n <= SF_SUN_DIRS_MAX:
-            raise ValueError(f"1..{SF_SUN_DIRS_MAX} directions per call, not {n}")
-        p = sf_suns_params()
-        _check(lib().sf_suns_defaults(self._ctx, ctypes.byref(p)), "sf_suns_defaults")
-        p.dirs = D.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        wts = None
-        if weights is not None:
-            wts = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
-            if wts.shape[0] != n:
-                raise ValueError("one weight per direction")
-            p.weights = wts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        p.n = n
-        if distance is not None:
-            p.distance = float(distance)
-        if bias is not None:
-            p.bias = float(bias)
-        if origin is not None:
-            p.origin[:] = [float(x) for x in _f32(origin, 3)]
-            p.use_origin = 1
-        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
-        return p, (D, wts)
+        p, keep = self._list_params(sf_suns_params, "dirs", dirs, 3, SF_SUN_DIRS_MAX, "directions",
+                                    "weights", weights, 1, "one weight per direction")
+        return _params_tail(p, distance, bias, origin, width, height, max_depth, stream), keep
 
     def trace_suns(self, dirs, distance=None, bias=None, pos=None, out=None, origin=None, max_depth=0, stream=None):
         """Which of up to 64 sun directions `dirs` [n, 3] (each TOWARDS the sun, world, used as given) reach each pixel
@@ -1267,11 +1271,7 @@ class Sphereflake:
         each. Pointers are device addresses, 0 = the context's G-buffer, mask buffer (trace_suns()) and image.
         Asynchronous."""
         p, keep = self.suns_params(dirs, weights, None, None, None, 0, 0, 0, stream)
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        with self._mutex:
-            _check(lib().sf_light_image_suns(self._ctx, ctypes.byref(p), float(ambient), vp(pos_ptr), vp(nrm_ptr),
-                                             vp(mask_ptr), vp(rgba_ptr)), "sf_light_image_suns", self._ctx)
-        del keep
+        self._light_image("sf_light_image_suns", p, (float(ambient),), (pos_ptr, nrm_ptr, mask_ptr, rgba_ptr), keep)
 
     # light shafts: sun visibility along each pixel's view ray (sf_trace_shafts_to / sf_trace_shafts /
     # sf_light_image_shafts) -------------------------------------------------------------------------------------------
@@ -1280,32 +1280,16 @@ class Sphereflake:
         """sf_shafts_defaults, overridden: (params, keepalive). fractions [n], weights [n] or None; distance and bias
         None keep the library's defaults (4, 2^-10); dirs_ptr is a device address (0 = none) of dirs_stride floats per
         pixel. The host arrays the params point into are in `keepalive` and must outlive the call they are passed to."""
-        F = np.ascontiguousarray(np.asarray(fractions, np.float32).reshape(-1))
-        n = F.shape[0]
-        if not 1 <= n <= SF_SHAFT_SAMPLES_MAX:
-            raise ValueError(f"1..{SF_SHAFT_SAMPLES_MAX} samples per call, not {n}")
-        p = sf_shafts_params()
-        _check(lib().sf_shafts_defaults(self._ctx, ctypes.byref(p)), "sf_shafts_defaults")
-        p.dir[:] = [float(x) for x in _f32(direction, 3)]
-        p.fractions = F.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        wts = None
-        if weights is not None:
-            wts = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
-            if wts.shape[0] != n:
-                raise ValueError("one weight per sample")
-            p.weights = wts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        p.n = n
-        if distance is not None:
-            p.distance = float(distance)
-        if bias is not None:
-            p.bias = float(bias)
+        F = _entries(fractions, 1, SF_SHAFT_SAMPLES_MAX, "samples")
+        p = self._defaults(sf_shafts_params)
+        p.dir[:] = [float(x) for x in _f32(direction, 3)]   # (before the weights, so _list_params does not fit)
+        p.fractions, p.n = _fp(F), F.shape[0]
+        wts = _entry_values(weights, F.shape[0], 1, "one weight per sample")
+        if wts is not None:
+            p.weights = _fp(wts)
         p.dirs = ctypes.cast(ctypes.c_void_p(int(dirs_ptr) or None), ctypes.POINTER(ctypes.c_float))
         p.dirs_stride, p.far = int(dirs_stride), float(far)
-        if origin is not None:
-            p.origin[:] = [float(x) for x in _f32(origin, 3)]
-            p.use_origin = 1
-        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
-        return p, (F, wts)
+        return _params_tail(p, distance, bias, origin, width, height, max_depth, stream), (F, wts)
 
     @staticmethod
     def _dirs_image(dirs):
@@ -1376,11 +1360,7 @@ class Sphereflake:
         p, keep = self.shafts_params((0.0, 0.0, 1.0), fractions, weights, None, None, dptr, dstride, far, None, 0, 0, 0,
                                      stream)
         col = (ctypes.c_float * 3)(*[float(x) for x in _f32(colour, 3)])
-        vp = lambda x: ctypes.c_void_p(x) if x else None
-        with self._mutex:
-            _check(lib().sf_light_image_shafts(self._ctx, ctypes.byref(p), float(gain), col, vp(pos_ptr), vp(mask_ptr),
-                                               vp(rgba_ptr)), "sf_light_image_shafts", self._ctx)
-        del keep
+        self._light_image("sf_light_image_shafts", p, (float(gain), col), (pos_ptr, mask_ptr, rgba_ptr), keep)
 
     # the colour light buffer: sum any number of suns and lights while tracing (sf_trace_suns_sum_to /
     # sf_trace_shadows_sum_to / sf_light_fill / sf_light_image_buffer) ------------------------------------------------
@@ -1389,29 +1369,10 @@ class Sphereflake:
         """sf_light_sum_defaults, overridden: (params, keepalive). points [n, 3] (sun directions or light positions),
         colours [n, 3] or None (1 / n per component); distance and bias None keep the library's defaults (4, 2^-10).
         The host arrays the params point into are in `keepalive` and must outlive the call they are passed to."""
-        pts = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
-        n = pts.shape[0]
-        if not 1 <= n <= SF_LIGHT_SUM_MAX:
-            raise ValueError(f"1..{SF_LIGHT_SUM_MAX} entries per call, not {n}")
-        p = sf_light_sum_params()
-        _check(lib().sf_light_sum_defaults(self._ctx, ctypes.byref(p)), "sf_light_sum_defaults")
-        p.points = pts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        col = None
-        if colours is not None:
-            col = np.ascontiguousarray(np.asarray(colours, np.float32).reshape(-1, 3))
-            if col.shape[0] != n:
-                raise ValueError("one colour per entry")
-            p.colours = col.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        p.n, p.accumulate = n, 1 if accumulate else 0
-        if distance is not None:
-            p.distance = float(distance)
-        if bias is not None:
-            p.bias = float(bias)
-        if origin is not None:
-            p.origin[:] = [float(x) for x in _f32(origin, 3)]
-            p.use_origin = 1
-        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
-        return p, (pts, col)
+        p, keep = self._list_params(sf_light_sum_params, "points", points, 3, SF_LIGHT_SUM_MAX, "entries",
+                                    "colours", colours, 3, "one colour per entry")
+        p.accumulate = 1 if accumulate else 0
+        return _params_tail(p, distance, bias, origin, width, height, max_depth, stream), keep
 
     def trace_suns_sum(self, dirs, colours=None, accumulate=False, distance=None, bias=None, pos=None, nrm=None,
                        out=None, origin=None, max_depth=0, stream=None):
@@ -1448,20 +1409,11 @@ class Sphereflake:
 
     def light_buffer(self) -> int:
         """Device address of the context's light buffer (0 before anything has written it)."""
-        ptr = ctypes.c_void_p()
-        rc = lib().sf_light_buffer(self._ctx, ctypes.byref(ptr))
-        if rc == SF_ESTATE:
-            return 0
-        _check(rc, "sf_light_buffer")
-        return ptr.value or 0
+        return self._own_pointer("sf_light_buffer")
 
     def download_light(self) -> np.ndarray:
         """[H, W, 4] float32 of the context's light buffer (synchronous)."""
-        buf = np.empty((self.height, self.width, 4), np.float32)
-        with self._mutex:
-            _check(lib().sf_download_light(self._ctx, buf.ctypes.data_as(ctypes.c_void_p)), "sf_download_light",
-                   self._ctx)
-        return buf
+        return self._own_download("sf_download_light", np.float32, (4,))
 
     def light_image_buffer(self, pos_ptr=0, buf_ptr=0, rgba_ptr=0, stream=None):
         """Scale the image of PostProcess() in place, per channel, by the light buffer (sf_light_image_buffer;
@@ -1479,29 +1431,10 @@ class Sphereflake:
         [n, 3] or None (1 / n per component; the summing call only); distance and bias None keep the library's
         defaults (4, 2^-10). The host arrays the params point into are in `keepalive` and must outlive the call they are
         passed to."""
-        h = np.ascontiguousarray(np.asarray(samples, np.float32).reshape(-1, 3))
-        n = h.shape[0]
-        if not 1 <= n <= SF_AO_SAMPLES_MAX:
-            raise ValueError(f"1..{SF_AO_SAMPLES_MAX} samples per call, not {n}")
-        p = sf_ao_params()
-        _check(lib().sf_ao_defaults(self._ctx, ctypes.byref(p)), "sf_ao_defaults")
-        p.samples = h.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        col = None
-        if colours is not None:
-            col = np.ascontiguousarray(np.asarray(colours, np.float32).reshape(-1, 3))
-            if col.shape[0] != n:
-                raise ValueError("one colour per sample")
-            p.colours = col.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        p.n, p.accumulate = n, 1 if accumulate else 0
-        if distance is not None:
-            p.distance = float(distance)
-        if bias is not None:
-            p.bias = float(bias)
-        if origin is not None:
-            p.origin[:] = [float(x) for x in _f32(origin, 3)]
-            p.use_origin = 1
-        p.width, p.height, p.max_depth, p.stream = int(width), int(height), int(max_depth), stream
-        return p, (h, col)
+        p, keep = self._list_params(sf_ao_params, "samples", samples, 3, SF_AO_SAMPLES_MAX, "samples",
+                                    "colours", colours, 3, "one colour per sample")
+        p.accumulate = 1 if accumulate else 0
+        return _params_tail(p, distance, bias, origin, width, height, max_depth, stream), keep
 
     @staticmethod
     def _spin(spin):
@@ -1567,8 +1500,7 @@ class Sphereflake:
         as ao_params'; eye None: the view vector is the position itself (positions relative to the viewer), else the
         world point less `eye`; zenith, horizon, up None keep the library's defaults ((1, 1, 1), (1, 1, 1), (0, 0, 1))."""
         q, keep = self.ao_params(samples, colours, accumulate, distance, bias, origin, width, height, max_depth, stream)
-        p = sf_mirror_params()
-        _check(lib().sf_mirror_defaults(self._ctx, ctypes.byref(p)), "sf_mirror_defaults")
+        p = self._defaults(sf_mirror_params)
         for name, _ in sf_ao_params._fields_:   # (sf_ao_defaults' distance and bias are sf_mirror_defaults')
             setattr(p, name, getattr(q, name))
         if eye is not None:

@@ -10,6 +10,7 @@ import functools
 import numpy as np
 
 from sphereflake_amd import lights
+from maskcheck import bit  # noqa: F401
 from oracle import pyoracle
 from rayscheck import LOD, frame, oracle_multi
 import suncheck as su
@@ -23,10 +24,11 @@ SKY_EVERY = 8                # t1 under ao_samples(64): every 8th surface pixel 
 CONSTANT_NORMALS = ((0.0, 0.0, 1.0), (0.0, 0.0, -1.0), (1.0, 0.0, 0.0), (0.6, -0.64, 0.48))
 
 
-def rays_for(children, pos4, nrm4, origin, samples, tau, lod, every=1):
+def rays_for(children, pos4, nrm4, origin, samples, tau, lod, every=1, spin=None):
     """(min_t [n, ...], traced mask [...], deepest node) of the oracle: the closest hit of the ray of every sample at
-    every `every`-th surface pixel in row-major order (FLT_MAX elsewhere)."""
-    Fo, d, _, surf = lights.ao_model(pos4, nrm4, origin, samples, tau, 0.0)
+    every `every`-th surface pixel in row-major order (FLT_MAX elsewhere). spin: the frames turned by the table
+    (tests/aospincheck.py); None is the unspun call itself."""
+    Fo, d, _, surf = lights.ao_model(pos4, nrm4, origin, samples, tau, 0.0, spin=spin)
     n = Fo.shape[0]
     pick = np.zeros(surf.shape, bool).reshape(-1)
     pick[np.nonzero(surf.reshape(-1))[0][::every]] = True
@@ -40,11 +42,11 @@ def rays_for(children, pos4, nrm4, origin, samples, tau, lod, every=1):
     return mints, pick, deepest
 
 
-def mask_of(pos4, nrm4, origin, samples, tau, bias, mints, pick):
+def mask_of(pos4, nrm4, origin, samples, tau, bias, mints, pick, spin=None):
     """The mask words from the oracle's min_t: bit i is 0 where a traced surface pixel has min_t < bound_i, else 1;
     bits n..63 are 0. A surface pixel that was not traced has all its low n bits set and means nothing: compare where
-    `compared(pos4, pick)` holds."""
-    _, _, bound, surf = lights.ao_model(pos4, nrm4, origin, samples, tau, bias)
+    `compared(pos4, pick)` holds. spin: as rays_for's."""
+    _, _, bound, surf = lights.ao_model(pos4, nrm4, origin, samples, tau, bias, spin=spin)
     mask = np.zeros(surf.shape, np.uint64)
     with np.errstate(invalid="ignore"):
         for i in range(bound.shape[0]):
@@ -83,10 +85,6 @@ def oracle_mask(name, samples, tau=TAU, bias=B10, variant="avx", lod=None, every
     f = frame(name, variant)
     mints, pick, _ = frame_rays(name, samples, tau, variant, lod, every)
     return mask_of(f["pos4"], f["nrm4"], S["origin"], samples, tau, bias, mints, pick), pick
-
-
-def bit(mask, i):
-    return ((np.asarray(mask, np.uint64) >> np.uint64(i)) & np.uint64(1)) != 0
 
 
 def counts(mask, n, where):

@@ -10,9 +10,11 @@ import numpy as np
 
 import sphereflake_amd as sf
 from sphereflake_amd import lights
+from maskcheck import assert_mask, assert_shape_of_mask, bit, low, surface_of  # noqa: F401
 from oracle import pyoracle
-from rayscheck import LOD, frame, oracle_multi
-from aocheck import B10, CONSTANT_NORMALS, EVERY, FLT_MAX, TAU, bit, compared, counts, mixed  # noqa: F401
+from rayscheck import LOD, frame
+import aocheck as ac
+from aocheck import B10, CONSTANT_NORMALS, EVERY, FLT_MAX, TAU, compared, counts, mixed  # noqa: F401
 
 F = np.float32
 IDENTITY = np.array([[[1.0, 0.0]]], F)   # the 1 x 1 table that turns nothing
@@ -24,29 +26,12 @@ THRESHOLDS = ((0.9, 0.02), (0.8, 0.05), (0.95, 0.01))   # the defaults and the t
 
 def rays_for(children, pos4, nrm4, origin, samples, spin, tau, lod, every=1):
     """aocheck.rays_for with the frame turned by `spin`: (min_t [n, ...], traced mask [...], deepest node)."""
-    Fo, d, _, surf = lights.ao_model(pos4, nrm4, origin, samples, tau, 0.0, spin=spin)
-    n = Fo.shape[0]
-    pick = np.zeros(surf.shape, bool).reshape(-1)
-    pick[np.nonzero(surf.reshape(-1))[0][::every]] = True
-    pick = pick.reshape(surf.shape)
-    mints = np.full((n,) + surf.shape, FLT_MAX, F)
-    deepest = 0
-    if pick.any():
-        r = oracle_multi(children, Fo[:, pick].reshape(-1, 3), d[:, pick].reshape(-1, 3), 1, lod=lod)
-        mints[:, pick] = r["minT"].reshape(n, -1)
-        deepest = r["stats"]["max_depth"]
-    return mints, pick, deepest
+    return ac.rays_for(children, pos4, nrm4, origin, samples, tau, lod, every, spin=spin)
 
 
 def mask_of(pos4, nrm4, origin, samples, spin, tau, bias, mints, pick):
     """aocheck.mask_of with the spun bounds."""
-    _, _, bound, surf = lights.ao_model(pos4, nrm4, origin, samples, tau, bias, spin=spin)
-    mask = np.zeros(surf.shape, np.uint64)
-    with np.errstate(invalid="ignore"):
-        for i in range(bound.shape[0]):
-            lit = ~(surf & pick & (mints[i] < bound[i]))
-            mask |= lit.astype(np.uint64) << np.uint64(i)
-    return mask
+    return ac.mask_of(pos4, nrm4, origin, samples, tau, bias, mints, pick, spin=spin)
 
 
 @functools.lru_cache(maxsize=None)
@@ -90,27 +75,6 @@ def flake(name, variant="avx"):
     return s
 
 
-def low(n):
-    return np.uint64((1 << n) - 1)
-
-
-def assert_mask(got, want, what, where=None):
-    assert got.dtype == np.uint64 and got.shape == want.shape, what
-    differ = got != want
-    if where is not None:
-        differ &= where
-    bad = np.argwhere(differ)
-    assert bad.size == 0, f"{what}: {len(bad)} pixels differ, first {bad[:4]}: " \
-                          f"{[hex(int(got[tuple(b)])) for b in bad[:4]]} != {[hex(int(want[tuple(b)])) for b in bad[:4]]}"
-
-
-def assert_shape_of_mask(got, n, pos, what):
-    """Bits n..63 are zero everywhere, and a miss of the frame has exactly its low n bits set."""
-    if n < 64:
-        assert (got >> np.uint64(n) == 0).all(), what
-    assert (got[~surface_of(pos)] == low(n)).all(), what
-
-
 def constant_image(shape, N0):
     nrm = np.empty(tuple(shape) + (4,), F)
     nrm[...] = np.array(tuple(N0) + (0.0,), F)
@@ -120,11 +84,6 @@ def constant_image(shape, N0):
 def entry_of(shape, size):
     """The table entry y % size * size + x % size of every pixel of an image [H, W]."""
     return (np.arange(shape[0])[:, None] % size) * size + (np.arange(shape[1])[None, :] % size)
-
-
-def surface_of(pos4):
-    P = np.asarray(pos4)[..., :3]
-    return ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
 
 
 def open_fraction(buf):

@@ -1,6 +1,8 @@
 """Shared pieces of the colour-light-buffer tests (tests/test_light_sum_host.py, tests/test_gpu_light_sum.py)."""
 import numpy as np
 
+from maskcheck import surface_of  # noqa: F401
+
 F = np.float32
 
 # distinct RGB colours for the 8-direction cones and the named lights
@@ -39,10 +41,6 @@ def base_image(shape):
     b = np.empty(tuple(shape) + (4,), F)
     b[...] = np.asarray(BASE, F)
     return b
-
-
-def surface_of(pos):
-    return ~((pos[..., 0] == 0) & (pos[..., 1] == 0) & (pos[..., 2] == 0))
 
 
 def assert_same(got, want, what, where=None):

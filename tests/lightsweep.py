@@ -40,6 +40,7 @@ import numpy as np
 
 from sphereflake_amd import dirs as sfdirs
 from sphereflake_amd import lights
+from maskcheck import bit, low, surface_of  # noqa: F401
 from oracle import pyoracle
 from sweepviews import LOD, SEEDS, sweep_reference, sweep_view  # noqa: F401
 
@@ -180,19 +181,6 @@ def deepest(seed, variant, trace):
 def deepest_needed(seed, variant, trace):
     """The deepest node a lit ray of the trace expands before its bound, at bias 2^-10 (sweep_rays)."""
     return sweep_rays(seed, variant)[trace][2]
-
-
-def surface_of(pos4):
-    P = np.asarray(pos4)[..., :3]
-    return ~((P[..., 0] == 0) & (P[..., 1] == 0) & (P[..., 2] == 0))
-
-
-def bit(mask, i):
-    return ((np.asarray(mask, np.uint64) >> np.uint64(i)) & np.uint64(1)) != 0
-
-
-def low(n):
-    return np.uint64((1 << n) - 1)
 
 
 def both_outcomes(mask, i, where, share=0.10):

@@ -12,6 +12,7 @@ import functools
 import numpy as np
 
 from sphereflake_amd import lights
+from maskcheck import bit, low, surface_of  # noqa: F401
 from oracle import pyoracle
 from rayscheck import LOD, frame, pinhole
 import suncheck as su
@@ -41,10 +42,6 @@ def unit_dirs(name):
 def dirs_of(name):
     """The direction image of the fixture's case, or None where its misses are not marched."""
     return unit_dirs(name) if CASES[name][2] > 0 else None
-
-
-def surface_of(pos):
-    return ~((pos[..., 0] == 0) & (pos[..., 1] == 0) & (pos[..., 2] == 0))
 
 
 def samples(name, fractions, variant="avx"):
@@ -96,14 +93,6 @@ def oracle_mask(name, fractions, bias, variant="avx", every=1, part="surface"):
     return mask_of(samples(name, F, variant), S["origin"], sun(name), CASES[name][1], bias, mints, pick), pick
 
 
-def bit(mask, i):
-    return ((np.asarray(mask, np.uint64) >> np.uint64(i)) & np.uint64(1)) != 0
-
-
 def outcomes(mask, pick, i):
     """(shadowed, lit) counts of bit i among the traced pixels."""
     return int((pick & ~bit(mask, i)).sum()), int((pick & bit(mask, i)).sum())
-
-
-def low(n):
-    return np.uint64((1 << n) - 1) if n < 64 else np.uint64(0xffffffffffffffff)

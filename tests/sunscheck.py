@@ -9,6 +9,7 @@ import functools
 import numpy as np
 
 from sphereflake_amd import lights
+from maskcheck import bit  # noqa: F401
 from oracle import pyoracle
 from rayscheck import LOD, frame
 import suncheck as su
@@ -70,10 +71,6 @@ def oracle_mask(name, dirs, tau=su.TAU, bias=su.B10, variant="avx", lod=None, ev
     S = pyoracle.load_setup(name)
     mints, pick, _ = frame_rays(name, dirs, tau, variant, lod, every)
     return mask_of(frame(name, variant)["pos4"], S["origin"], dirs, tau, bias, mints, pick), pick
-
-
-def bit(mask, i):
-    return ((np.asarray(mask, np.uint64) >> np.uint64(i)) & np.uint64(1)) != 0
 
 
 def mixed(mask, n, where):

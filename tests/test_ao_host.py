@@ -4,13 +4,13 @@ GPU tests stand on, the header and the library's exports, and the error codes th
 import ctypes
 import pathlib
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sphereflake_amd as sf
 from sphereflake_amd import lights
+from abicheck import compile_class_user, defined_symbols, undefined_symbols
 from dirscheck import same_bits
 from oracle import pyoracle
 from rayscheck import frame
@@ -296,8 +296,7 @@ def test_header_states_the_definition():
 def test_symbols_are_exported():
     if shutil.which("nm") is None:
         pytest.skip("binutils not available")
-    out = subprocess.run(["nm", "-D", "--defined-only", sf.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    have = {l.split()[-1] for l in out.splitlines() if l.strip()}
+    have = defined_symbols(sf.LIB_PATH)
     assert set(SYMBOLS) <= have
     assert set(SYMBOLS) <= set(sf.SIGNATURES)
 
@@ -329,28 +328,20 @@ def test_cpp_members_are_inline_over_the_c_abi(tmp_path):
     library has."""
     if shutil.which("g++") is None or shutil.which("nm") is None:
         pytest.skip("binutils / g++ not available")
-    repo = pathlib.Path(__file__).resolve().parent.parent
-    src = tmp_path / "ao.cpp"
-    src.write_text('#include "Sphereflake.hpp"\n'
-                   "using namespace SphereflakeRaytracer;\n"
-                   "void occlude(Sphereflake& s, const float* pdev, const float* ndev, uint64_t* mdev, float* ldev) {\n"
-                   "    static const float h[6] = { 0.0f, 0.0f, 1.0f, 0.6f, 0.0f, 0.8f };\n"
-                   "    sf_ao_params p;\n"
-                   "    sf_ao_defaults(s.Context(), &p);\n"
-                   "    p.samples = h; p.n = 2;\n"
-                   "    s.TraceAO(p);\n"
-                   "    s.TraceAOSum(p);\n"
-                   "    p.width = 64; p.height = 36; p.accumulate = 1;\n"
-                   "    s.TraceAO(p, pdev, ndev, mdev);\n"
-                   "    s.TraceAOSum(p, pdev, ndev, ldev);\n}\n")
-    obj = tmp_path / "ao.o"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-c", f"-I{repo / 'include'}",
-                        f"-I{repo / 'sphereflake-raytracer_amd' / 'csrc'}", str(src), "-o", str(obj)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    nm = lambda *a: {l.split()[-1] for l in subprocess.run(["nm", *a], capture_output=True, text=True,
-                                                           check=True).stdout.splitlines() if l.strip()}
-    need, have = nm("-u", str(obj)), nm("-D", "--defined-only", sf.LIB_PATH)
+    source = ('#include "Sphereflake.hpp"\n'
+              "using namespace SphereflakeRaytracer;\n"
+              "void occlude(Sphereflake& s, const float* pdev, const float* ndev, uint64_t* mdev, float* ldev) {\n"
+              "    static const float h[6] = { 0.0f, 0.0f, 1.0f, 0.6f, 0.0f, 0.8f };\n"
+              "    sf_ao_params p;\n"
+              "    sf_ao_defaults(s.Context(), &p);\n"
+              "    p.samples = h; p.n = 2;\n"
+              "    s.TraceAO(p);\n"
+              "    s.TraceAOSum(p);\n"
+              "    p.width = 64; p.height = 36; p.accumulate = 1;\n"
+              "    s.TraceAO(p, pdev, ndev, mdev);\n"
+              "    s.TraceAOSum(p, pdev, ndev, ldev);\n}\n")
+    obj = compile_class_user(tmp_path, "ao", source)
+    need, have = undefined_symbols(obj), defined_symbols(sf.LIB_PATH)
     assert {"sf_trace_ao_to", "sf_trace_ao", "sf_trace_ao_sum_to", "sf_trace_ao_sum"} <= need
     assert not [n for n in need if "TraceAO" in n]
     assert not [n for n in need if (n.startswith("sf_") or "SphereflakeRaytracer" in n) and n not in have]

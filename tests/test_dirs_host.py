@@ -1,15 +1,14 @@
 """Host side of direction tracing (sf_trace_dirs_to): the direction generators of sphereflake_amd.dirs against
 the oracle and against their own geometry, and the entry points' null-context answers. No GPU needed."""
 import ctypes
-import pathlib
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sphereflake_amd as sf
 from sphereflake_amd import dirs
+from abicheck import compile_class_user, defined_symbols, undefined_symbols
 from dirscheck import oracle_rays, same_bits
 from oracle import pyoracle
 
@@ -92,26 +91,18 @@ def test_cpp_members_are_inline_over_the_c_abi(tmp_path):
     class member to keep in step with the application's vector types), and need only sf_* symbols the library has."""
     if shutil.which("g++") is None or shutil.which("nm") is None:
         pytest.skip("binutils / g++ not available")
-    repo = pathlib.Path(__file__).resolve().parent.parent
-    src = tmp_path / "probe.cpp"
-    src.write_text('#include "Sphereflake.hpp"\n'
-                   "using namespace SphereflakeRaytracer;\n"
-                   "float brake(Sphereflake& s, const float* axes6, const float* ddev, float* pdev, sf_vec4* pos) {\n"
-                   "    float t[6]; uint32_t idx[6];\n"
-                   "    s.ProbeDirections(axes6, 6, t, idx, pos);\n"
-                   "    sf_dirs_params p = {}; p.width = 64; p.height = 1; p.stride = 3;\n"
-                   "    s.TraceDirections(p, ddev, pdev, nullptr);\n"
-                   "    p.width = (uint32_t)s.Width(); p.height = (uint32_t)s.Height();\n"
-                   "    s.TraceDirections(p, ddev);\n"
-                   "    return t[0];\n}\n")
-    obj = tmp_path / "probe.o"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-c", f"-I{repo / 'include'}",
-                        f"-I{repo / 'sphereflake-raytracer_amd' / 'csrc'}", str(src), "-o", str(obj)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    nm = lambda *a: {l.split()[-1] for l in subprocess.run(["nm", *a], capture_output=True, text=True,
-                                                           check=True).stdout.splitlines() if l.strip()}
-    need, have = nm("-u", str(obj)), nm("-D", "--defined-only", sf.LIB_PATH)
+    source = ('#include "Sphereflake.hpp"\n'
+              "using namespace SphereflakeRaytracer;\n"
+              "float brake(Sphereflake& s, const float* axes6, const float* ddev, float* pdev, sf_vec4* pos) {\n"
+              "    float t[6]; uint32_t idx[6];\n"
+              "    s.ProbeDirections(axes6, 6, t, idx, pos);\n"
+              "    sf_dirs_params p = {}; p.width = 64; p.height = 1; p.stride = 3;\n"
+              "    s.TraceDirections(p, ddev, pdev, nullptr);\n"
+              "    p.width = (uint32_t)s.Width(); p.height = (uint32_t)s.Height();\n"
+              "    s.TraceDirections(p, ddev);\n"
+              "    return t[0];\n}\n")
+    obj = compile_class_user(tmp_path, "probe", source)
+    need, have = undefined_symbols(obj), defined_symbols(sf.LIB_PATH)
     assert {"sf_probe_dirs", "sf_trace_dirs_to", "sf_trace_dirs"} <= need
     assert not [n for n in need if "TraceDirections" in n or "ProbeDirections" in n]
     assert not [n for n in need if (n.startswith("sf_") or "SphereflakeRaytracer" in n) and n not in have]

@@ -11,7 +11,8 @@ import pytest
 import sphereflake_amd as sf
 from sphereflake_amd import lights
 from dirscheck import same_bits
-from lightsumcheck import BASE, CONE_COLOURS, assert_same, base_image, colours, surface_of
+from lightsumcheck import BASE, CONE_COLOURS, assert_same, base_image, colours
+from maskcheck import assert_mask, assert_shape_of_mask, low, surface_of
 from oracle import pyoracle
 from rayscheck import frame
 import aocheck as ac
@@ -38,27 +39,6 @@ def flake(name, variant="avx"):
     s.SetVariant(variant)
     s.SetView(S["origin"], S["tl"], S["tr"], S["bl"])
     return s
-
-
-def low(n):
-    return np.uint64((1 << n) - 1)
-
-
-def assert_mask(got, want, what, where=None):
-    assert got.dtype == np.uint64 and got.shape == want.shape, what
-    differ = got != want
-    if where is not None:
-        differ &= where
-    bad = np.argwhere(differ)
-    assert bad.size == 0, f"{what}: {len(bad)} pixels differ, first {bad[:4]}: " \
-                          f"{[hex(int(got[tuple(b)])) for b in bad[:4]]} != {[hex(int(want[tuple(b)])) for b in bad[:4]]}"
-
-
-def assert_shape_of_mask(got, n, pos, what):
-    """Bits n..63 are zero everywhere, and a miss of the frame has exactly its low n bits set."""
-    if n < 64:
-        assert (got >> np.uint64(n) == 0).all(), what
-    assert (got[~surface_of(pos)] == low(n)).all(), what
 
 
 def constant_image(shape, N0):

@@ -10,6 +10,7 @@ import pytest
 import sphereflake_amd as sf
 from sphereflake_amd import lights
 from dirscheck import same_bits
+from maskcheck import assert_mask
 from oracle import pyoracle
 from rayscheck import frame
 import shadowcheck as sc
@@ -51,13 +52,6 @@ def oracle_mask(name, names, bias, variant="avx"):
 
 def surface_of(name, variant="avx"):
     return frame(name, variant)["minT"] < np.finfo(np.float32).max
-
-
-def assert_mask(got, want, what):
-    assert got.dtype == np.uint64 and got.shape == want.shape, what
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{what}: {len(bad)} pixels differ, first {bad[:4]}: " \
-                          f"{[hex(int(got[tuple(b)])) for b in bad[:4]]} != {[hex(int(want[tuple(b)])) for b in bad[:4]]}"
 
 
 def popcount(a):

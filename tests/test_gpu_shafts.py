@@ -11,6 +11,7 @@ import pytest
 import sphereflake_amd as sf
 from sphereflake_amd import lights
 from dirscheck import same_bits
+from maskcheck import assert_mask
 from oracle import pyoracle
 from rayscheck import frame
 import shaftscheck as sc
@@ -42,16 +43,6 @@ def shafts(s, name, fractions, pos, bias=su.B10, **kw):
     kw.setdefault("dirs", sc.dirs_of(name))
     kw.setdefault("far", sc.CASES[name][2])
     return s.trace_shafts(sc.sun(name), fractions, sc.CASES[name][1], bias=bias, pos=pos, **kw)
-
-
-def assert_mask(got, want, what, where=None):
-    assert got.dtype == np.uint64 and got.shape == want.shape, what
-    differ = got != want
-    if where is not None:
-        differ &= where
-    bad = np.argwhere(differ)
-    assert bad.size == 0, f"{what}: {len(bad)} pixels differ, first {bad[:4]}: " \
-                          f"{[hex(int(got[tuple(b)])) for b in bad[:4]]} != {[hex(int(want[tuple(b)])) for b in bad[:4]]}"
 
 
 def assert_high_bits_clear(got, n, what):

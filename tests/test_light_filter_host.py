@@ -4,13 +4,13 @@ struct layout."""
 import ctypes
 import pathlib
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sphereflake_amd as sf
 from sphereflake_amd import lights
+from abicheck import defined_symbols
 from dirscheck import same_bits
 from rayscheck import frame
 import aospincheck as sc
@@ -180,8 +180,7 @@ def test_header_states_the_definition():
 def test_symbols_are_exported():
     if shutil.which("nm") is None:
         pytest.skip("binutils not available")
-    out = subprocess.run(["nm", "-D", "--defined-only", sf.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    have = {l.split()[-1] for l in out.splitlines() if l.strip()}
+    have = defined_symbols(sf.LIB_PATH)
     assert set(SYMBOLS) <= have and set(SYMBOLS) <= set(sf.SIGNATURES)
 
 

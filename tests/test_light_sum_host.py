@@ -4,13 +4,13 @@ exports. The GPU side is tests/test_gpu_light_sum.py."""
 import ctypes
 import pathlib
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sphereflake_amd as sf
 from sphereflake_amd import lights
+from abicheck import compile_class_user, defined_symbols, undefined_symbols
 from dirscheck import same_bits
 from oracle import pyoracle
 from rayscheck import frame
@@ -199,8 +199,7 @@ def test_header_and_abi():
     for sym in SYMBOLS:
         assert getattr(L, sym) is not None, sym
     if shutil.which("nm") is not None:
-        out = subprocess.run(["nm", "-D", "--defined-only", sf.LIB_PATH], capture_output=True, text=True, check=True).stdout
-        assert set(SYMBOLS) <= {l.split()[-1] for l in out.splitlines() if l.strip()}
+        assert set(SYMBOLS) <= defined_symbols(sf.LIB_PATH)
 
 
 def test_struct_layout_matches_the_header():
@@ -233,31 +232,23 @@ def test_cpp_members_are_inline_over_the_c_abi(tmp_path):
     inline, and need only sf_* symbols the library has."""
     if shutil.which("g++") is None or shutil.which("nm") is None:
         pytest.skip("binutils / g++ not available")
-    repo = pathlib.Path(__file__).resolve().parent.parent
-    src = tmp_path / "sum.cpp"
-    src.write_text('#include "Sphereflake.hpp"\n'
-                   "using namespace SphereflakeRaytracer;\n"
-                   "void light(Sphereflake& s, const float* pdev, const float* ndev, float* ldev) {\n"
-                   "    static const float dirs[6] = { 0.6f, 0.0f, 0.8f, 0.0f, 0.6f, 0.8f };\n"
-                   "    static const float amb[3] = { 0.1f, 0.1f, 0.2f };\n"
-                   "    sf_light_sum_params p;\n"
-                   "    sf_light_sum_defaults(s.Context(), &p);\n"
-                   "    p.points = dirs; p.n = 2; p.accumulate = 1;\n"
-                   "    s.LightFill(amb);\n"
-                   "    s.TraceSunsSum(p);\n"
-                   "    s.TraceShadowsSum(p);\n"
-                   "    s.LightImageBuffer();\n"
-                   "    p.width = 64; p.height = 36;\n"
-                   "    s.TraceSunsSum(p, pdev, ndev, ldev);\n"
-                   "    s.TraceShadowsSum(p, pdev, ndev, ldev);\n}\n")
-    obj = tmp_path / "sum.o"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-c", f"-I{repo / 'include'}",
-                        f"-I{repo / 'sphereflake-raytracer_amd' / 'csrc'}", str(src), "-o", str(obj)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    nm = lambda *a: {l.split()[-1] for l in subprocess.run(["nm", *a], capture_output=True, text=True,
-                                                           check=True).stdout.splitlines() if l.strip()}
-    need, have = nm("-u", str(obj)), nm("-D", "--defined-only", sf.LIB_PATH)
+    source = ('#include "Sphereflake.hpp"\n'
+              "using namespace SphereflakeRaytracer;\n"
+              "void light(Sphereflake& s, const float* pdev, const float* ndev, float* ldev) {\n"
+              "    static const float dirs[6] = { 0.6f, 0.0f, 0.8f, 0.0f, 0.6f, 0.8f };\n"
+              "    static const float amb[3] = { 0.1f, 0.1f, 0.2f };\n"
+              "    sf_light_sum_params p;\n"
+              "    sf_light_sum_defaults(s.Context(), &p);\n"
+              "    p.points = dirs; p.n = 2; p.accumulate = 1;\n"
+              "    s.LightFill(amb);\n"
+              "    s.TraceSunsSum(p);\n"
+              "    s.TraceShadowsSum(p);\n"
+              "    s.LightImageBuffer();\n"
+              "    p.width = 64; p.height = 36;\n"
+              "    s.TraceSunsSum(p, pdev, ndev, ldev);\n"
+              "    s.TraceShadowsSum(p, pdev, ndev, ldev);\n}\n")
+    obj = compile_class_user(tmp_path, "sum", source)
+    need, have = undefined_symbols(obj), defined_symbols(sf.LIB_PATH)
     assert {"sf_trace_suns_sum_to", "sf_trace_suns_sum", "sf_trace_shadows_sum_to", "sf_trace_shadows_sum",
             "sf_light_fill", "sf_light_image_buffer"} <= need
     assert not [n for n in need if "Sum" in n or "LightFill" in n or "LightImageBuffer" in n]

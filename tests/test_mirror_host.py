@@ -5,13 +5,13 @@ that is a bit pattern is compared bit for bit."""
 import ctypes
 import pathlib
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sphereflake_amd as sf
 from sphereflake_amd import lights
+from abicheck import compile_class_user, defined_symbols, undefined_symbols
 from dirscheck import same_bits
 from oracle import pyoracle
 from rayscheck import frame
@@ -293,8 +293,7 @@ def test_header_states_the_definition():
 def test_symbols_are_exported():
     if shutil.which("nm") is None:
         pytest.skip("binutils not available")
-    out = subprocess.run(["nm", "-D", "--defined-only", sf.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    have = {l.split()[-1] for l in out.splitlines() if l.strip()}
+    have = defined_symbols(sf.LIB_PATH)
     assert set(SYMBOLS) <= have
     assert set(SYMBOLS) <= set(sf.SIGNATURES)
     for k in ("wave", "fixup", "sum_wave", "sum_fixup"):
@@ -331,34 +330,26 @@ def test_cpp_members_are_inline_over_the_c_abi(tmp_path):
     the library has."""
     if shutil.which("g++") is None or shutil.which("nm") is None:
         pytest.skip("binutils / g++ not available")
-    repo = pathlib.Path(__file__).resolve().parent.parent
-    src = tmp_path / "mirror.cpp"
-    src.write_text('#include "Sphereflake.hpp"\n'
-                   "using namespace SphereflakeRaytracer;\n"
-                   "void reflect(Sphereflake& s, const float* pdev, const float* ndev, uint64_t* mdev, float* ldev) {\n"
-                   "    static const float h[6] = { 0.0f, 0.0f, 1.0f, 0.6f, 0.0f, 0.8f };\n"
-                   "    static const float cs[8] = { 1.0f, 0.0f, 0.0f, 1.0f, -1.0f, 0.0f, 0.0f, -1.0f };\n"
-                   "    sf_mirror_params p;\n"
-                   "    sf_mirror_defaults(s.Context(), &p);\n"
-                   "    p.samples = h; p.n = 2;\n"
-                   "    p.zenith[0] = 0.25f; p.eye[2] = 3.0f; p.use_eye = 1;\n"
-                   "    sf_ao_spin spin = { cs, 2 };\n"
-                   "    s.TraceMirror(p);\n"
-                   "    s.TraceMirror(p, &spin);\n"
-                   "    s.TraceMirrorSum(p);\n"
-                   "    p.accumulate = 1;\n"
-                   "    s.TraceMirrorSum(p, &spin);\n"
-                   "    p.width = 64; p.height = 36;\n"
-                   "    s.TraceMirror(p, &spin, pdev, ndev, mdev);\n"
-                   "    s.TraceMirrorSum(p, nullptr, pdev, ndev, ldev);\n}\n")
-    obj = tmp_path / "mirror.o"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-c", f"-I{repo / 'include'}",
-                        f"-I{repo / 'sphereflake-raytracer_amd' / 'csrc'}", str(src), "-o", str(obj)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    nm = lambda *a: {l.split()[-1] for l in subprocess.run(["nm", *a], capture_output=True, text=True,
-                                                           check=True).stdout.splitlines() if l.strip()}
-    need, have = nm("-u", str(obj)), nm("-D", "--defined-only", sf.LIB_PATH)
+    source = ('#include "Sphereflake.hpp"\n'
+              "using namespace SphereflakeRaytracer;\n"
+              "void reflect(Sphereflake& s, const float* pdev, const float* ndev, uint64_t* mdev, float* ldev) {\n"
+              "    static const float h[6] = { 0.0f, 0.0f, 1.0f, 0.6f, 0.0f, 0.8f };\n"
+              "    static const float cs[8] = { 1.0f, 0.0f, 0.0f, 1.0f, -1.0f, 0.0f, 0.0f, -1.0f };\n"
+              "    sf_mirror_params p;\n"
+              "    sf_mirror_defaults(s.Context(), &p);\n"
+              "    p.samples = h; p.n = 2;\n"
+              "    p.zenith[0] = 0.25f; p.eye[2] = 3.0f; p.use_eye = 1;\n"
+              "    sf_ao_spin spin = { cs, 2 };\n"
+              "    s.TraceMirror(p);\n"
+              "    s.TraceMirror(p, &spin);\n"
+              "    s.TraceMirrorSum(p);\n"
+              "    p.accumulate = 1;\n"
+              "    s.TraceMirrorSum(p, &spin);\n"
+              "    p.width = 64; p.height = 36;\n"
+              "    s.TraceMirror(p, &spin, pdev, ndev, mdev);\n"
+              "    s.TraceMirrorSum(p, nullptr, pdev, ndev, ldev);\n}\n")
+    obj = compile_class_user(tmp_path, "mirror", source)
+    need, have = undefined_symbols(obj), defined_symbols(sf.LIB_PATH)
     assert set(SYMBOLS) <= need
     assert not [n for n in need if "TraceMirror" in n]
     assert not [n for n in need if (n.startswith("sf_") or "SphereflakeRaytracer" in n) and n not in have]

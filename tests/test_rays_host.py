@@ -2,15 +2,14 @@
 root transform's columns), the seeded ray sets of the GPU tests on the oracle, the generators of
 sphereflake_amd.rays, and the entry points' null-context answers. No GPU needed."""
 import ctypes
-import pathlib
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sphereflake_amd as sf
 from sphereflake_amd import dirs, rays
+from abicheck import compile_class_user, defined_symbols, undefined_symbols
 from dirscheck import FLT_MAX, same_bits
 from oracle import pyoracle
 import rayscheck
@@ -129,26 +128,18 @@ def test_cpp_members_are_inline_over_the_c_abi(tmp_path):
     and need only sf_* symbols the library has."""
     if shutil.which("g++") is None or shutil.which("nm") is None:
         pytest.skip("binutils / g++ not available")
-    repo = pathlib.Path(__file__).resolve().parent.parent
-    src = tmp_path / "probe.cpp"
-    src.write_text('#include "Sphereflake.hpp"\n'
-                   "using namespace SphereflakeRaytracer;\n"
-                   "float brake(Sphereflake& s, const float* org, const float* axes, const float* odev,\n"
-                   "            const float* ddev, float* pdev, sf_vec4* pos) {\n"
-                   "    float t[36]; uint32_t idx[36];\n"
-                   "    s.ProbeRays(org, axes, 36, 6, t, idx, pos);\n"
-                   "    sf_rays_params p = {}; p.width = 64; p.height = 1; p.dir_stride = 3; p.origin_stride = 4;\n"
-                   "    p.rays_per_origin = 8;\n"
-                   "    s.TraceRays(p, odev, ddev, pdev, nullptr);\n"
-                   "    return t[0];\n}\n")
-    obj = tmp_path / "probe.o"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-c", f"-I{repo / 'include'}",
-                        f"-I{repo / 'sphereflake-raytracer_amd' / 'csrc'}", str(src), "-o", str(obj)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    nm = lambda *a: {l.split()[-1] for l in subprocess.run(["nm", *a], capture_output=True, text=True,
-                                                           check=True).stdout.splitlines() if l.strip()}
-    need, have = nm("-u", str(obj)), nm("-D", "--defined-only", sf.LIB_PATH)
+    source = ('#include "Sphereflake.hpp"\n'
+              "using namespace SphereflakeRaytracer;\n"
+              "float brake(Sphereflake& s, const float* org, const float* axes, const float* odev,\n"
+              "            const float* ddev, float* pdev, sf_vec4* pos) {\n"
+              "    float t[36]; uint32_t idx[36];\n"
+              "    s.ProbeRays(org, axes, 36, 6, t, idx, pos);\n"
+              "    sf_rays_params p = {}; p.width = 64; p.height = 1; p.dir_stride = 3; p.origin_stride = 4;\n"
+              "    p.rays_per_origin = 8;\n"
+              "    s.TraceRays(p, odev, ddev, pdev, nullptr);\n"
+              "    return t[0];\n}\n")
+    obj = compile_class_user(tmp_path, "probe", source)
+    need, have = undefined_symbols(obj), defined_symbols(sf.LIB_PATH)
     assert {"sf_probe_rays", "sf_trace_rays_to"} <= need
     assert not [n for n in need if "TraceRays" in n or "ProbeRays" in n]
     assert not [n for n in need if (n.startswith("sf_") or "SphereflakeRaytracer" in n) and n not in have]

@@ -4,13 +4,13 @@ header, the error codes that need no device, the light generators and the host s
 import ctypes
 import pathlib
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sphereflake_amd as sf
 from sphereflake_amd import lights
+from abicheck import compile_class_user, defined_symbols, undefined_symbols
 from oracle import pyoracle
 from rayscheck import frame
 import shadowcheck as sc
@@ -23,8 +23,7 @@ SYMBOLS = ("sf_shadows_defaults", "sf_trace_shadows_to", "sf_trace_shadows", "sf
 def test_symbols_are_exported():
     if shutil.which("nm") is None:
         pytest.skip("binutils not available")
-    out = subprocess.run(["nm", "-D", "--defined-only", sf.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    have = {l.split()[-1] for l in out.splitlines() if l.strip()}
+    have = defined_symbols(sf.LIB_PATH)
     assert set(SYMBOLS) <= have
     assert set(SYMBOLS) <= set(sf.SIGNATURES)
 
@@ -161,27 +160,19 @@ def test_cpp_members_are_inline_over_the_c_abi(tmp_path):
     the library has."""
     if shutil.which("g++") is None or shutil.which("nm") is None:
         pytest.skip("binutils / g++ not available")
-    repo = pathlib.Path(__file__).resolve().parent.parent
-    src = tmp_path / "shadows.cpp"
-    src.write_text('#include "Sphereflake.hpp"\n'
-                   "using namespace SphereflakeRaytracer;\n"
-                   "void light(Sphereflake& s, const float* pdev, uint64_t* mdev) {\n"
-                   "    static const float l[6] = { -1.5f, -2.5f, 2.0f, 0.0f, 0.0f, 6.0f };\n"
-                   "    sf_shadows_params p;\n"
-                   "    sf_shadows_defaults(s.Context(), &p);\n"
-                   "    p.lights = l; p.n = 2;\n"
-                   "    s.TraceShadows(p);\n"
-                   "    s.LightImageMany(p, 0.25f);\n"
-                   "    p.width = 64; p.height = 36;\n"
-                   "    s.TraceShadows(p, pdev, mdev);\n}\n")
-    obj = tmp_path / "shadows.o"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-c", f"-I{repo / 'include'}",
-                        f"-I{repo / 'sphereflake-raytracer_amd' / 'csrc'}", str(src), "-o", str(obj)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    nm = lambda *a: {l.split()[-1] for l in subprocess.run(["nm", *a], capture_output=True, text=True,
-                                                           check=True).stdout.splitlines() if l.strip()}
-    need, have = nm("-u", str(obj)), nm("-D", "--defined-only", sf.LIB_PATH)
+    source = ('#include "Sphereflake.hpp"\n'
+              "using namespace SphereflakeRaytracer;\n"
+              "void light(Sphereflake& s, const float* pdev, uint64_t* mdev) {\n"
+              "    static const float l[6] = { -1.5f, -2.5f, 2.0f, 0.0f, 0.0f, 6.0f };\n"
+              "    sf_shadows_params p;\n"
+              "    sf_shadows_defaults(s.Context(), &p);\n"
+              "    p.lights = l; p.n = 2;\n"
+              "    s.TraceShadows(p);\n"
+              "    s.LightImageMany(p, 0.25f);\n"
+              "    p.width = 64; p.height = 36;\n"
+              "    s.TraceShadows(p, pdev, mdev);\n}\n")
+    obj = compile_class_user(tmp_path, "shadows", source)
+    need, have = undefined_symbols(obj), defined_symbols(sf.LIB_PATH)
     assert {"sf_trace_shadows_to", "sf_trace_shadows", "sf_light_image_many"} <= need
     assert not [n for n in need if "TraceShadows" in n or "LightImageMany" in n]
     assert not [n for n in need if (n.startswith("sf_") or "SphereflakeRaytracer" in n) and n not in have]

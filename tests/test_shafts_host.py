@@ -4,13 +4,13 @@ header and the library's exports, and the error codes that need no device. No GP
 import ctypes
 import pathlib
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sphereflake_amd as sf
 from sphereflake_amd import lights
+from abicheck import compile_class_user, defined_symbols, undefined_symbols
 from dirscheck import same_bits
 from oracle import pyoracle
 from rayscheck import frame
@@ -246,8 +246,7 @@ def test_symbols_are_exported():
         assert sym in sf.SIGNATURES and getattr(L, sym) is not None, sym
     if shutil.which("nm") is None:
         return
-    out = subprocess.run(["nm", "-D", "--defined-only", sf.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    have = {l.split()[-1] for l in out.splitlines() if l.strip()}
+    have = defined_symbols(sf.LIB_PATH)
     assert set(SYMBOLS) <= have
 
 
@@ -278,29 +277,21 @@ def test_cpp_members_are_inline_over_the_c_abi(tmp_path):
     the library has."""
     if shutil.which("g++") is None or shutil.which("nm") is None:
         pytest.skip("binutils / g++ not available")
-    repo = pathlib.Path(__file__).resolve().parent.parent
-    src = tmp_path / "shafts.cpp"
-    src.write_text('#include "Sphereflake.hpp"\n'
-                   "using namespace SphereflakeRaytracer;\n"
-                   "void light(Sphereflake& s, const float* pdev, const float* ddev, uint64_t* mdev) {\n"
-                   "    static const float fractions[2] = { 0.25f, 0.75f };\n"
-                   "    static const float colour[3] = { 255.0f, 240.0f, 200.0f };\n"
-                   "    sf_shafts_params p;\n"
-                   "    sf_shafts_defaults(s.Context(), &p);\n"
-                   "    p.fractions = fractions; p.n = 2;\n"
-                   "    p.dirs = ddev; p.dirs_stride = 3; p.far = 13.0f;\n"
-                   "    s.TraceShafts(p);\n"
-                   "    s.LightImageShafts(p, 0.05f, colour);\n"
-                   "    p.width = 64; p.height = 36;\n"
-                   "    s.TraceShafts(p, pdev, mdev);\n}\n")
-    obj = tmp_path / "shafts.o"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-c", f"-I{repo / 'include'}",
-                        f"-I{repo / 'sphereflake-raytracer_amd' / 'csrc'}", str(src), "-o", str(obj)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    nm = lambda *a: {l.split()[-1] for l in subprocess.run(["nm", *a], capture_output=True, text=True,
-                                                           check=True).stdout.splitlines() if l.strip()}
-    need, have = nm("-u", str(obj)), nm("-D", "--defined-only", sf.LIB_PATH)
+    source = ('#include "Sphereflake.hpp"\n'
+              "using namespace SphereflakeRaytracer;\n"
+              "void light(Sphereflake& s, const float* pdev, const float* ddev, uint64_t* mdev) {\n"
+              "    static const float fractions[2] = { 0.25f, 0.75f };\n"
+              "    static const float colour[3] = { 255.0f, 240.0f, 200.0f };\n"
+              "    sf_shafts_params p;\n"
+              "    sf_shafts_defaults(s.Context(), &p);\n"
+              "    p.fractions = fractions; p.n = 2;\n"
+              "    p.dirs = ddev; p.dirs_stride = 3; p.far = 13.0f;\n"
+              "    s.TraceShafts(p);\n"
+              "    s.LightImageShafts(p, 0.05f, colour);\n"
+              "    p.width = 64; p.height = 36;\n"
+              "    s.TraceShafts(p, pdev, mdev);\n}\n")
+    obj = compile_class_user(tmp_path, "shafts", source)
+    need, have = undefined_symbols(obj), defined_symbols(sf.LIB_PATH)
     assert {"sf_trace_shafts_to", "sf_trace_shafts", "sf_light_image_shafts"} <= need
     assert not [n for n in need if "TraceShafts" in n or "LightImageShafts" in n]
     assert not [n for n in need if (n.startswith("sf_") or "SphereflakeRaytracer" in n) and n not in have]

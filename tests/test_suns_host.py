@@ -5,13 +5,13 @@ need no device. No GPU needed."""
 import ctypes
 import pathlib
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sphereflake_amd as sf
 from sphereflake_amd import lights
+from abicheck import compile_class_user, defined_symbols, undefined_symbols
 from dirscheck import same_bits
 import suncheck as su
 import sunscheck as ss
@@ -192,8 +192,7 @@ def test_header_declares_the_entries():
 def test_symbols_are_exported():
     if shutil.which("nm") is None:
         pytest.skip("binutils not available")
-    out = subprocess.run(["nm", "-D", "--defined-only", sf.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    have = {l.split()[-1] for l in out.splitlines() if l.strip()}
+    have = defined_symbols(sf.LIB_PATH)
     assert set(SYMBOLS) <= have
     assert set(SYMBOLS) <= set(sf.SIGNATURES)
 
@@ -224,27 +223,19 @@ def test_cpp_members_are_inline_over_the_c_abi(tmp_path):
     library has."""
     if shutil.which("g++") is None or shutil.which("nm") is None:
         pytest.skip("binutils / g++ not available")
-    repo = pathlib.Path(__file__).resolve().parent.parent
-    src = tmp_path / "suns.cpp"
-    src.write_text('#include "Sphereflake.hpp"\n'
-                   "using namespace SphereflakeRaytracer;\n"
-                   "void light(Sphereflake& s, const float* pdev, uint64_t* mdev) {\n"
-                   "    static const float dirs[6] = { 0.6f, 0.0f, 0.8f, 0.0f, 0.6f, 0.8f };\n"
-                   "    sf_suns_params p;\n"
-                   "    sf_suns_defaults(s.Context(), &p);\n"
-                   "    p.dirs = dirs; p.n = 2;\n"
-                   "    s.TraceSuns(p);\n"
-                   "    s.LightImageSuns(p, 0.25f);\n"
-                   "    p.width = 64; p.height = 36;\n"
-                   "    s.TraceSuns(p, pdev, mdev);\n}\n")
-    obj = tmp_path / "suns.o"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-c", f"-I{repo / 'include'}",
-                        f"-I{repo / 'sphereflake-raytracer_amd' / 'csrc'}", str(src), "-o", str(obj)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    nm = lambda *a: {l.split()[-1] for l in subprocess.run(["nm", *a], capture_output=True, text=True,
-                                                           check=True).stdout.splitlines() if l.strip()}
-    need, have = nm("-u", str(obj)), nm("-D", "--defined-only", sf.LIB_PATH)
+    source = ('#include "Sphereflake.hpp"\n'
+              "using namespace SphereflakeRaytracer;\n"
+              "void light(Sphereflake& s, const float* pdev, uint64_t* mdev) {\n"
+              "    static const float dirs[6] = { 0.6f, 0.0f, 0.8f, 0.0f, 0.6f, 0.8f };\n"
+              "    sf_suns_params p;\n"
+              "    sf_suns_defaults(s.Context(), &p);\n"
+              "    p.dirs = dirs; p.n = 2;\n"
+              "    s.TraceSuns(p);\n"
+              "    s.LightImageSuns(p, 0.25f);\n"
+              "    p.width = 64; p.height = 36;\n"
+              "    s.TraceSuns(p, pdev, mdev);\n}\n")
+    obj = compile_class_user(tmp_path, "suns", source)
+    need, have = undefined_symbols(obj), defined_symbols(sf.LIB_PATH)
     assert {"sf_trace_suns_to", "sf_trace_suns", "sf_light_image_suns"} <= need
     assert not [n for n in need if "TraceSuns" in n or "LightImageSuns" in n]
     assert not [n for n in need if (n.startswith("sf_") or "SphereflakeRaytracer" in n) and n not in have]
